@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the likelihood engine on synthetic pileups of the BASELINE.json configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6] [--cells B] [--fast] [--only]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6] [--cells B] [--fast] [--only] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one resident batch: K1 singlet accumulation (cmd_cram_demuxlet.cpp:412-461), then —
@@ -28,6 +28,12 @@ N > 1: BASELINE.json configs[3] = cfg4 (100k barcodes x 100k SNPs x 64 samples, 
 into N contiguous equal ranges (barcodes are independent, cmd_cram_demuxlet.cpp:576; dense pileup = equal work), rank r
 generates and owns range r, and every step ends with THE one collective of the job: the RCCL gather of the fixed-size
 per-barcode records to rank 0.  Rank 0 prints ONE JSON line.
+
+`--dump-outputs DIR`: after the timed steps of the main record, what its last step computed is written as DIR/<name>.npy (float64),
+the arrays a caller of the timed path receives: N = 1 the engine's llks, llk0s and — doublet configs — l00, grid (llksAB) and one
+array per field of the per-barcode summary (dmx_engine_get_singlet / _get_doublet); N > 1 the records rank 0 gathered (llks, llk0s,
+sing, l00, summary fields).  At most 64 MB in all: beyond that, a fixed seeded sample of barcodes (barcode_index.npy says which).
+The inputs depend on the arguments only, so two builds can be compared array for array.
 """
 from __future__ import annotations
 
@@ -102,6 +108,99 @@ def cpu_sample_cells(dp, cfg, target_s):
     ns_per_pair = 6.0 * (V + 1) + (19.0 * (V * V * A + A) if cfg["doublet"] else 0.0)
     pairs_per_cell = max(1.0, dp.n_pairs / max(dp.n_cells, 1))
     return int(max(1, min(dp.n_cells, round(target_s / (1e-9 * ns_per_pair * pairs_per_cell)))))
+
+
+DUMP_BYTES = 64 << 20         # --dump-outputs: at most this much on disk in all,
+NPY_HEADER_BYTES = 4096       # ... counting this much per file for its .npy header (numpy writes 128 bytes for these arrays)
+DUMP_SEED = 0xD3A0D           # ... and the seed of its barcode sample when the whole output is larger
+
+
+def summary_fields(summary_dtype):
+    """The fields of the per-barcode summary record (capi.SUMMARY_DTYPE) that --dump-outputs writes: all but the padding."""
+    return [k for k in summary_dtype.names if k != "reserved"]
+
+
+def dump_columns(V, A, doublet, summary_dtype, grid=False, sing=False):
+    """What --dump-outputs writes: file name -> float64 values per barcode.  One process writes the grid (llksAB), N ranks the gathered
+    records, which carry sing and no grid."""
+    cols = {"barcode_index": 1, "llks": V, "llk0s": 1}
+    if doublet:
+        if sing:
+            cols["sing"] = V
+        cols["l00"] = A
+        if grid:
+            cols["grid"] = V * V * A
+        cols.update({f"summary_{k}": 1 for k in summary_fields(summary_dtype)})
+    return cols
+
+
+def dump_sample(n, cols, budget=DUMP_BYTES):
+    """Barcodes whose outputs --dump-outputs writes: all n when the files of `cols` (dump_columns) fit the budget, else a fixed seeded sample
+    (sorted) of as many as fit."""
+    k = max(0, min(n, (budget - NPY_HEADER_BYTES * len(cols)) // (8 * sum(cols.values()))))
+    if k == n:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def summary_columns(summ):
+    """The per-barcode summary records (capi.SUMMARY_DTYPE) as one float64 array per field (summary_fields)."""
+    return {f"summary_{k}": summ[k].astype(np.float64) for k in summary_fields(summ.dtype)}
+
+
+def write_dump(out_dir, arrays, cols):
+    """arrays: name -> array of the sampled barcodes (barcode_index among them), exactly the files of `cols` that dump_sample sized the
+    sample for — checked before anything is written.  Written as float64 .npy files; returns the record's entry (bytes = on disk)."""
+    n = len(arrays["barcode_index"])
+    assert set(arrays) == set(cols), sorted(set(arrays) ^ set(cols))
+    for name, a in arrays.items():
+        assert np.size(a) == n * cols[name], (name, np.shape(a), cols[name])
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a, dtype=np.float64))
+        total += (d / f"{name}.npy").stat().st_size
+    assert total <= DUMP_BYTES, total
+    return {"dir": str(d), "arrays": sorted(arrays), "barcodes": n, "bytes": total}
+
+
+def dump_engine_outputs(cx, eng, cfg, out_dir):
+    """--dump-outputs, one process: what dmx_engine_get_singlet / dmx_engine_get_doublet would hand a caller now (right after the last
+    timed step), for the barcodes of dump_sample."""
+    torch, st, capi = cx.torch, cx.synth_torch, cx.engine.capi
+    B, V, A = eng.B, cfg["V"], len(cfg["alphas"])
+    cols = dump_columns(V, A, cfg["doublet"], capi.SUMMARY_DTYPE, grid=True)
+    idx = dump_sample(B, cols)
+    sel = torch.from_numpy(idx).to(cx.dev)
+    v = eng.device_view()
+    arrays = {"barcode_index": idx,
+              "llks": st.tensor_from_ptr(v.llks, (B, V), torch.float64, cx.dev)[sel].cpu().numpy(),
+              "llk0s": st.tensor_from_ptr(v.llk0s, (B,), torch.float64, cx.dev)[sel].cpu().numpy()}
+    if cfg["doublet"]:
+        words = capi.SUMMARY_DTYPE.itemsize // 8
+        arrays["l00"] = st.tensor_from_ptr(v.llks00, (B, A), torch.float64, cx.dev)[sel].cpu().numpy()
+        arrays["grid"] = eng.get_cell_grids(idx.astype(np.int32))
+        sm = st.tensor_from_ptr(v.summary, (B, words), torch.float64, cx.dev)[sel].cpu().numpy()
+        arrays.update(summary_columns(np.ascontiguousarray(sm).view(capi.SUMMARY_DTYPE).reshape(-1)))
+    return write_dump(out_dir, arrays, cols)
+
+
+def dump_gathered_outputs(cx, gathered, counts, cfg, out_dir):
+    """--dump-outputs, N ranks: the per-barcode records rank 0 gathered in the last timed step (record_matrix's columns), all ranks' barcodes
+    in barcode order, for the barcodes of dump_sample."""
+    V, A = cfg["V"], len(cfg["alphas"])
+    sd = cx.engine.capi.SUMMARY_DTYPE
+    cols = dump_columns(V, A, cfg["doublet"], sd, sing=True)
+    rec = cx.torch.cat([gathered[r][:counts[r]] for r in range(len(counts))], dim=0)
+    idx = dump_sample(rec.shape[0], cols)
+    m = rec[cx.torch.from_numpy(idx).to(rec.device)].cpu().numpy()
+    arrays = {"barcode_index": idx, "llks": m[:, :V], "llk0s": m[:, V]}
+    if cfg["doublet"]:
+        arrays["sing"] = m[:, V + 1:2 * V + 1]
+        arrays["l00"] = m[:, 2 * V + 1:2 * V + 1 + A]
+        arrays.update(summary_columns(np.ascontiguousarray(m[:, 2 * V + 1 + A:]).view(sd).reshape(-1)))
+    return write_dump(out_dir, arrays, cols)
 
 
 def engine_rows(cx, eng, cfg, n):
@@ -415,8 +514,9 @@ class Ctx:
     pass
 
 
-def run_config(cx, cfgno, cfg, mode, steps, warmup, with_cpu, with_log, with_e2e=False, parity_s=0.0, defer_cpu=False):
-    """Generate the workload of one configuration on this rank's GPU, time `steps` passes, return the record (rank 0)."""
+def run_config(cx, cfgno, cfg, mode, steps, warmup, with_cpu, with_log, with_e2e=False, parity_s=0.0, defer_cpu=False, dump_dir=None):
+    """Generate the workload of one configuration on this rank's GPU, time `steps` passes, return the record (rank 0).  dump_dir: write the
+    last timed step's outputs there (--dump-outputs)."""
     torch, dist, engine, synth, synth_torch = cx.torch, cx.dist, cx.engine, cx.synth, cx.synth_torch
     dev, world, rank, local = cx.dev, cx.world, cx.rank, cx.local
     fast = mode == "fast"
@@ -513,6 +613,10 @@ def run_config(cx, cfgno, cfg, mode, steps, warmup, with_cpu, with_log, with_e2e
     rows = None
     if rank == 0 and (with_cpu or parity_s > 0):
         rows = engine_rows(cx, eng, cfg, cpu_sample_cells(dp, cfg, 12.0 if with_cpu else parity_s))
+    dumped = None
+    if rank == 0 and dump_dir:
+        dumped = (dump_gathered_outputs(cx, gathered, counts, cfg, dump_dir) if cx.use_dist else
+                  dump_engine_outputs(cx, eng, cfg, dump_dir))
 
     # per-kernel times: the engine brackets every launch of K1, K2, K3 and K3b with HIP events on the stream it launches on
     # (dmx_engine_mean_kernel_times: mean over the TIMED launches, at most the last 16); torch's events on the same stream give
@@ -621,6 +725,8 @@ def run_config(cx, cfgno, cfg, mode, steps, warmup, with_cpu, with_log, with_e2e
                           "kernel_ms_alone": alone,
                           "peak_tflops": FP64_VALU_PEAK_TFLOPS},
         }
+        if dumped:
+            out["dump_outputs"] = dumped
         if world > 1 or cx.use_dist:
             out["ranks_seen"] = dist.get_world_size()
             out["per_rank_ms_per_step"] = per_rank_ms
@@ -869,9 +975,13 @@ def main():
     ap.add_argument("--fast", action="store_true", help="DMX_MODE_FAST for the main record (opt-in, not the headline)")
     ap.add_argument("--alphas", default="", help="override the alpha grid, comma separated (experiments; not the headline)")
     ap.add_argument("--e2e-write-pair", action="store_true", help="with --config/--cells: add the dmx_demuxlet_run --write-pair leg of this workload to the full record")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the main record's last timed step's outputs to DIR/<name>.npy (float64, <= 64 MB; see the docstring)")
     args = ap.parse_args()
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be >= 1")
 
     # --gpus decides the number of ranks.  No launcher in the environment and N > 1: become the launcher (never returns).
     # Under a launcher: its WORLD_SIZE must be what --gpus says.
@@ -962,7 +1072,7 @@ def main():
         out = run_config(cx, cfgno, cfg, "fast" if args.fast else "strict", args.steps, args.warmup,
                          with_cpu=not args.no_cpu_baseline, with_log=single,
                          with_e2e=(single and default_run and not args.only) or (single and args.e2e_write_pair and "e2e4wp"),
-                         defer_cpu=cx.use_dist)
+                         defer_cpu=cx.use_dist, dump_dir=args.dump_outputs or None)
         keys = ("value", "unit", "n_gpus", "ms_per_step", "steps", "warmup", "config", "roofline", "roofline_valu", "fp64_valu", "pair_evals_per_s",
                 "ranks_seen", "per_rank_ms_per_step", "gather_ms", "parity_check")
         if single and default_run and not args.only:

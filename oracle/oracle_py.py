@@ -18,13 +18,15 @@ HERE = Path(__file__).resolve().parent
 LIB_PATH = HERE / "_build" / "liboracle.so"
 REF_HARNESS = HERE / "_ref" / "ref_slice_harness"
 REF_UNITS = HERE / "_ref" / "libref_units.so"
+REF_PARAMS = HERE / "_ref" / "ref_params_driver"
 
 
 def build(force: bool = False) -> None:
     """Compile the oracle (gcc) and, when /root/reference is present, the reference harness."""
     if force or not LIB_PATH.exists() or LIB_PATH.stat().st_mtime < (HERE / "dmx_oracle.c").stat().st_mtime:
         subprocess.check_call(["make", "-s", "-C", str(HERE), "oracle"])
-    if Path("/root/reference").is_dir() and (force or not REF_HARNESS.exists() or not REF_UNITS.exists()):
+    # os.path.isdir, not Path.is_dir: an unreadable parent directory (any user but its owner) means "absent", not an error
+    if os.path.isdir("/root/reference") and (force or not all(p.exists() for p in (REF_HARNESS, REF_UNITS, REF_PARAMS))):
         subprocess.check_call(["make", "-s", "-C", str(HERE), "ref"])
 
 

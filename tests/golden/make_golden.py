@@ -6,7 +6,9 @@ Run here (needs /root/reference):   python tests/golden/make_golden.py
      compiled from /root/reference, recipe oracle/Makefile) and oracle/_ref/libref_units.so,
   2. draws seeded synthetic problems (demuxlet_amd/synth.py) and feeds them to the harness as a text spec,
   3. stores, per case, ONLY data: the inputs (events, float32 genotype matrix, parameters) and the reference's outputs
-     (the four text files as bytes + raw binary64 arrays llks, llk0s, llksAB, llks00 + per-cell counters).
+     (the four text files as bytes + raw binary64 arrays llks, llk0s, llksAB, llks00 + per-cell counters),
+  4. stores what the reference's option parser (oracle/_ref/ref_params_driver) prints for the argument lists of
+     tests/test_cli_cpu.py in ref_params.json.
 No reference source text is stored. The fixtures travel to the GPU box; /root/reference does not.
 """
 import ctypes as C
@@ -152,6 +154,27 @@ def phred_and_store_fixture():
     print("ref_units: phred tables + UMI-store trace ->", (OUT / "ref_units.npz").stat().st_size // 1024, "KiB")
 
 
+def ref_params_fixture():
+    """Row f4: stdout, stderr and exit status of the reference's option parser (oracle/_ref/ref_params_driver) for every argument list
+    of tests/test_cli_cpu.py::PARSER_ARGS, run on that test's two input files.  The directory the reference was compiled in (its
+    __FILE__ in error messages) is cut from the text: it belongs to the build, not to the program."""
+    import json
+    import re
+    import subprocess
+    sys.path.insert(0, str(ROOT / "tests"))
+    import test_cli_cpu as T
+    out = []
+    with tempfile.TemporaryDirectory() as tmp:
+        T.parser_inputs(Path(tmp))
+        for args in T.PARSER_ARGS:
+            a = T.ref_parser_args(args)
+            r = subprocess.run([str(O.REF_PARAMS)] + a, capture_output=True, text=True, cwd=tmp)
+            out.append(dict(args=a, returncode=r.returncode, stdout=r.stdout,
+                            stderr=re.sub(r"\[E:[^\]:]*/params\.cpp:", "[E:params.cpp:", r.stderr)))
+    (OUT / "ref_params.json").write_text(json.dumps(out, indent=1) + "\n")
+    print("ref_params:", len(out), "parser runs ->", (OUT / "ref_params.json").stat().st_size // 1024, "KiB")
+
+
 def main():
     O.build()
     if not O.have_ref():
@@ -187,6 +210,7 @@ def main():
             save_case(name, pb, tmp)
     if not only:
         phred_and_store_fixture()
+        ref_params_fixture()
 
 
 if __name__ == "__main__":

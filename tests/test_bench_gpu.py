@@ -114,3 +114,46 @@ def test_bench_gpus_n_without_a_launcher():
         assert r.returncode == 0, r.stderr[-2000:]
         d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
         assert d["n_gpus"] == 2 and d["ranks_seen"] == 2 and d["config"]["barcodes_per_gpu"] == 96
+
+
+def _dump(tmp, name, *extra, env=None):
+    import os
+    import numpy as np
+    out = tmp / name
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--warmup", "1", "--only", "--no-cpu-baseline", "--dump-outputs", str(out),
+                        *extra], capture_output=True, text=True, cwd=ROOT, timeout=900, env=dict(os.environ, **(env or {})))
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
+    files = sorted(out.glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    arrays = {f.stem: np.load(f) for f in files}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    return d, arrays
+
+
+def test_bench_dump_outputs_of_the_timed_steps(tmp_path):
+    """--dump-outputs DIR: the main record's last timed step's outputs (what dmx_engine_get_singlet / _get_doublet hand a caller), float64,
+    identical from run to run with the same arguments (the inputs are seeded); --steps sets the number of timed steps."""
+    import numpy as np
+    from demuxlet_amd import capi
+    d, a = _dump(tmp_path, "a", "--config", "3", "--cells", "40", "--steps", "3")
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    B, V, A = 40, 32, 2
+    fields = {f"summary_{k}" for k in capi.SUMMARY_DTYPE.names if k != "reserved"}
+    assert set(a) == {"barcode_index", "llks", "llk0s", "l00", "grid"} | fields
+    assert np.array_equal(a["barcode_index"], np.arange(B)) and a["llks"].shape == (B, V) and a["llk0s"].shape == (B,)
+    assert a["l00"].shape == (B, A) and a["grid"].shape == (B, V, V, A) and all(a[f].shape == (B,) for f in fields)
+    assert np.isfinite(a["llks"]).all() and np.isfinite(a["grid"]).all() and (a["summary_n_pairs"] > 0).all()
+    _, b = _dump(tmp_path, "b", "--config", "3", "--cells", "40", "--steps", "2")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_bench_dump_outputs_of_the_sharded_path(tmp_path):
+    """The N>1 path's dump (the records rank 0 gathered) on a 1-rank group: the same rows as the one-process run's dump of that workload."""
+    import numpy as np
+    _, one = _dump(tmp_path, "one", "--config", "4", "--cells", "96", "--steps", "2")
+    _, dist = _dump(tmp_path, "dist", "--config", "4", "--cells", "96", "--steps", "2", env={"DMX_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29534"})
+    assert set(dist) == set(one) - {"grid"} | {"sing"} and dist["sing"].shape == (96, 64)
+    for k in set(one) - {"grid"}:
+        assert np.array_equal(one[k], dist[k]), k

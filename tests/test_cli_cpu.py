@@ -348,7 +348,9 @@ def test_help_and_status_text_are_the_reference_layout(cli, tmp_path):
     assert r.returncode != 0 and r.stderr.index("Run with --help") < r.stderr.index("Command line parameter --bogus (#3) not recognized")
 
 
-REF_PARAMS = ROOT / "oracle" / "_ref" / "ref_params_driver"
+# what the reference's parser printed for each PARSER_ARGS entry: tests/golden/make_golden.py (ref_params_fixture) ran oracle/_ref/ref_params_driver
+# on them and stored stdout, stderr and the exit status
+REF_PARAMS_GOLDEN = ROOT / "tests" / "golden" / "ref_params.json"
 
 
 def _strip_own_group(text):
@@ -368,7 +370,7 @@ def _strip_own_group(text):
     return "\n".join(out)
 
 
-@pytest.mark.parametrize("args", [
+PARSER_ARGS = [
     ["--help"],
     ["--sam", "r.sam", "--vcf", "v.vcf", "--field", "GT", "--out", "o", "--pileup-only"],
     ["--sam", "r.sam", "--vcf", "v.vcf", "--field", "GT", "--geno-error", "0.001", "--sm", "smA", "--sm", "smC", "--out", "o", "--alpha", "0", "--alpha",
@@ -377,28 +379,42 @@ def _strip_own_group(text):
      "--min-callrate", "0.95", "--doublet-prior", "0.0625", "--cap-BQ", "30", "--min-BQ", "20", "--min-MQ", "30", "--min-TD", "5", "--excl-flag", "1796",
      "--min-total", "100", "--min-uniq", "50", "--sam-verbose", "5000", "--vcf-verbose", "7", "--geno-error", "0.00001", "--pileup-only"],
     ["--sam", "r.sam", "--bogus"], ["--sam", "a", "--sam", "b"], ["--min-mac", "x1"], ["--min-mac", "x1", "--write-pair", "3", "--write-pair"],
-    ["--alpha", "zero", "--geno-error", "1e-3", "--geno-error", "2", "-x", "--out"], ["--sm"], ["--min-snp"]])
+    ["--alpha", "zero", "--geno-error", "1e-3", "--geno-error", "2", "-x", "--out"], ["--sm"], ["--min-snp"]]
+
+
+def parser_inputs(d):
+    """The two input files every PARSER_ARGS run sees in its working directory (the reference's run and ours alike)."""
+    (d / "r.sam").write_text("@HD\tVN:1.5\tSO:coordinate\n@SQ\tSN:1\tLN:1000\n")
+    (d / "v.vcf").write_text("##fileformat=VCFv4.2\n##contig=<ID=1,length=1000>\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsmA\tsmC\n")
+
+
+def ref_parser_args(args):
+    return [a for a in args if a != "--pileup-only"]
+
+
+@pytest.mark.parametrize("args", PARSER_ARGS)
 def test_help_status_and_errors_equal_the_reference_parser(cli, tmp_path, args):
     """f4 pinned by the reference itself: params.cpp + Error.cpp compiled alone (oracle/Makefile: ref_params_driver) and driven by the
-    reference's own option table (cmd_cram_demuxlet.cpp:9-76) print the --help text, the status echo and the option errors; the
-    `demuxlet` binary must print the same characters — apart from its one extra option group — and exit the same way."""
-    if not REF_PARAMS.exists():
-        pytest.skip("oracle/_ref/ref_params_driver not built (needs /root/reference)")
-    (tmp_path / "r.sam").write_text("@HD\tVN:1.5\tSO:coordinate\n@SQ\tSN:1\tLN:1000\n")
-    (tmp_path / "v.vcf").write_text("##fileformat=VCFv4.2\n##contig=<ID=1,length=1000>\n#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\tsmA\tsmC\n")
-    ref_args = [a for a in args if a != "--pileup-only"]
-    want = subprocess.run([str(REF_PARAMS)] + ref_args, capture_output=True, text=True, cwd=tmp_path)
+    reference's own option table (cmd_cram_demuxlet.cpp:9-76) print the --help text, the status echo and the option errors (stored in
+    tests/golden/ref_params.json); the `demuxlet` binary must print the same characters — apart from its one extra option group — and exit
+    the same way."""
+    import json
+    parser_inputs(tmp_path)
+    ref_args = ref_parser_args(args)
+    want = [r for r in json.loads(REF_PARAMS_GOLDEN.read_text()) if r["args"] == ref_args]
+    assert len(want) == 1, ref_args
+    want = want[0]
     got = subprocess.run([cli] + args, capture_output=True, text=True, cwd=tmp_path)
-    w = want.stderr
+    w = want["stderr"]
     g = _strip_own_group(got.stderr)
     if "--help" in args:
-        assert got.returncode == 1 and got.stdout == want.stdout == ""
+        assert got.returncode == 1 and got.stdout == want["stdout"] == ""
         assert g == w
         return
     # the status echo is the first thing either program prints; ours goes on with the scan's own messages
     head = w[:w.index("Run with --help for more detailed help messages of each argument.\n\n") + len("Run with --help for more detailed help messages of each argument.\n\n")]
     assert g.startswith(head), (g[:600], head[:600])
-    if want.returncode != 0:                                # option errors: same wording, same place (after the echo), failure status
+    if want["returncode"] != 0:                             # option errors: same wording, same place (after the echo), failure status
         assert got.returncode != 0
         import re
         tail = w[len(head):]
