@@ -34,6 +34,7 @@ SYMBOLS = [
     "dmx_demuxlet_run", "dmx_debug_device_log", "dmx_debug_device_log2", "dmx_debug_device_div", "dmx_debug_log_rate", "dmx_engine_get_sing", "dmx_engine_get_cell_grids", "dmx_write_doublet_summary", "dmx_debug_log_dd",
     "dmx_resolve_tie_order", "dmx_engine_mean_kernel_times", "dmx_store_add_batch", "dmx_write_doublet_summary_grids", "dmx_engine_kernel_names", "dmx_debug_device_log2_lite", "dmx_debug_device_log2_lite32",
     "dmx_engine_format_pair", "dmx_pair_text_get_info", "dmx_pair_text_read", "dmx_pair_text_free",
+    "dmx_engine_refine_genotypes", "dmx_engine_get_refined", "dmx_engine_refined_device_ptr", "dmx_engine_refine_info",
 ]
 
 
@@ -52,6 +53,17 @@ class PairRequest(C.Structure):       # dmx_pair_request
 class PairTextInfo(C.Structure):      # dmx_pair_text_info
     _fields_ = [("n_bytes", C.c_int64), ("n_out", C.c_int32), ("n_patches", C.c_int32), ("cell_off", C.POINTER(C.c_int64)), ("cell_flag", C.POINTER(C.c_uint8)),
                 ("patches", C.POINTER(PairPatch)), ("format_ms", C.c_double)]
+
+
+class RefineRequest(C.Structure):     # dmx_refine_request
+    _fields_ = [("n_cells", C.c_int32), ("assign_memory", C.c_int32), ("assign", C.c_void_p), ("n_snps", C.c_int32), ("reserved0", C.c_int32),
+                ("prior", C.c_void_p), ("floor", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class RefineInfo(C.Structure):        # dmx_refine_info
+    _fields_ = [("blocks_ms", C.c_double), ("partial_ms", C.c_double), ("finish_ms", C.c_double), ("partial_bytes", C.c_int64),
+                ("n_chunks", C.c_int32), ("n_waves", C.c_int32), ("chunk_cells", C.c_int32), ("slab_snps", C.c_int32), ("n_assigned", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
 
 
 class DmxError(RuntimeError):
@@ -179,6 +191,8 @@ def load() -> C.CDLL:
         "dmx_write_doublet_summary_grids": [vp, vp, vp, vp, C.c_char_p],
         "dmx_engine_kernel_names": [vp, vp],
         "dmx_engine_format_pair": [vp, vp, vp], "dmx_pair_text_get_info": [vp, vp], "dmx_pair_text_read": [vp, C.c_int64, C.c_int64, vp],
+        "dmx_engine_refine_genotypes": [vp, vp], "dmx_engine_get_refined": [vp, vp, vp, vp, vp, vp], "dmx_engine_refined_device_ptr": [vp, vp],
+        "dmx_engine_refine_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

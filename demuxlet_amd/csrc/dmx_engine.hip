@@ -1916,7 +1916,8 @@ __global__ __launch_bounds__(kThreads, MINW) void k_singlet_clsw(PileupView pv, 
 
 // Where every cell stands at the boundaries of the SNP blocks [b << shift, (b + 1) << shift): blk[cell][b] = {index of its first
 // pair with SNP id >= b << shift, first read byte of that pair}, b = 0..nblk (the last entry is the cell's end).  One wavefront per
-// cell, one pass over its pair headers; built once per staged pileup.
+// cell, one pass over its pair headers; built once per staged pileup (K1's blocked walk: sparse pileups; the genotype refinement: either
+// layout — pair t of a dense pileup's cell is SNP t).
 __global__ __launch_bounds__(kThreads) void k_snp_blocks(PileupView pv, int nrd_width, int shift, int32_t nblk, int64_t* __restrict__ blk) {
   const int lane = threadIdx.x & 63;
   const int32_t cell = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
@@ -1929,7 +1930,7 @@ __global__ __launch_bounds__(kThreads) void k_snp_blocks(PileupView pv, int nrd_
     const int64_t p = p0 + lane;
     const bool v = p < p_end;
     const uint32_t n = v ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
-    const int32_t b = v ? (pv.pair_snp[p] >> shift) : 0x7FFFFFFF;
+    const int32_t b = v ? ((pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg)) >> shift) : 0x7FFFFFFF;
     const uint32_t incl = seg_scan_incl<64>(n);
     const int64_t off = rd_base + (int64_t)(incl - n);
     int32_t bp = __shfl_up(b, 1);
@@ -1940,6 +1941,118 @@ __global__ __launch_bounds__(kThreads) void k_snp_blocks(PileupView pv, int nrd_
     b_prev = __shfl(b, last);
   }
   for (int32_t bb = b_prev + 1 + lane; bb <= nblk; bb += 64) { out[2 * bb] = p_end; out[2 * bb + 1] = rd_base; }
+}
+
+// ---- genotype refinement (dmx_engine_refine_genotypes) ----------------------------------------------------------
+// LL[i][v][g] = sum of log(GL_{b,i}[g]) over the barcodes b assigned to sample v that have a pair at SNP i, with the pair counts and the
+// stored reads of allele 0 / 1.  Sum order (the contract): a sample's assigned barcodes in ascending cell id, cut into chunks of
+// kRefChunk; inside a chunk the terms are added in barcode order (k_refine_partial), then the chunk partials in ascending chunk order
+// (k_refine_fold).  No floating-point atomics anywhere: the result does not depend on launch geometry, waves or what ran before.
+constexpr int kRefChunk = 64;                    // C: assigned barcodes per chunk
+constexpr int kRefSlabShift = 9, kRefSlab = 1 << kRefSlabShift;   // SNPs per slab: one workgroup's LDS accumulators
+struct RefPartial { double ll[3]; int32_t n_cell, n_ref, n_alt, pad; };
+
+// One wavefront per (chunk, SNP slab): the chunk's barcodes one after another; per barcode, the lanes take its pairs inside the slab
+// (k_snp_blocks' table gives the first pair and read byte, so no barcode prefix is walked twice), a wavefront scan of pair_nrd gives
+// the read offsets as in K1, the GL comes from K1's shared device path (gl_seed's tables, gl_finish's recurrence for deeper pairs) and
+// each lane adds its three logs and counts into the slab's LDS accumulator of its SNP.  A barcode has at most one pair per SNP, so
+// lanes never collide, and the LDS executes one wavefront's instructions in program order, so barcode b + 1 adds after barcode b.
+__global__ __launch_bounds__(64) void k_refine_partial(PileupView pv, int nrd_width, const double* __restrict__ tabs, const int64_t* __restrict__ blk,
+                                                       int32_t nblk, const int32_t* __restrict__ members, const int32_t* __restrict__ chunk_beg,
+                                                       int32_t c0, RefPartial* __restrict__ partial) {
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_ll[3][kRefSlab];
+  __shared__ int32_t s_n[3][kRefSlab];
+  const int lane = threadIdx.x;
+  const int32_t slab = blockIdx.x, chunk = c0 + (int32_t)blockIdx.y;
+  const int32_t s0 = slab << kRefSlabShift;
+  for (int i = lane; i < DMX_LOG_TABLE_DOUBLES; i += 64) s_log[i] = tabs[kLut + i];
+  for (int i = lane; i < kRefSlab; i += 64) {
+#pragma unroll
+    for (int g = 0; g < 3; ++g) { s_ll[g][i] = 0.0; s_n[g][i] = 0; }
+  }
+  __syncthreads();
+  const DmxLogPins lk = dmx_log_pins();
+  const int32_t m_end = chunk_beg[chunk + 1];
+  for (int32_t m = chunk_beg[chunk]; m < m_end; ++m) {
+    const int32_t cell = members[m];
+    const int64_t* bt = blk + ((size_t)cell * (nblk + 1) + slab) * 2;
+    const int64_t p_end = bt[2], cell_p0 = pv.cell_pair_off[cell];
+    int64_t rd_base = bt[1];
+    for (int64_t p0 = bt[0]; p0 < p_end; p0 += 64) {
+      const int64_t p = p0 + lane;
+      const bool v = p < p_end;
+      const uint32_t n = v ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+      const int32_t snp = v ? (pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - cell_p0)) : 0;
+      const uint32_t incl = seg_scan_incl<64>(n);
+      const int64_t off = rd_base + (int64_t)(incl - n);
+      rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      const int k = snp - s0;                          // inside the slab by construction (pairs in ascending SNP order); checked all the same
+      if (v && (unsigned)k < (unsigned)kRefSlab) {
+        const uint32_t rd4 = load_rd4(pv, off, n);
+        const GlSeed sd = gl_seed(tabs, n, rd4);
+        double G0, G1, G2;
+        gl_finish(sd, n, rd4, pv.reads, off, tabs, G0, G1, G2);
+        uint32_t alt = 0;
+        for (uint32_t r = 0; r < n && r < 4; ++r) alt += (rd4 >> (8 * r + 7)) & 1u;
+        for (uint32_t r = 4; r < n; ++r) alt += (uint32_t)pv.reads[off + r] >> 7;
+        s_ll[0][k] += dmx_log_fast_pinned(G0, s_log, lk);    // GL >= 1e-6 / (1 + 3e-6): a normal positive argument
+        s_ll[1][k] += dmx_log_fast_pinned(G1, s_log, lk);
+        s_ll[2][k] += dmx_log_fast_pinned(G2, s_log, lk);
+        s_n[0][k] += 1; s_n[1][k] += (int32_t)(n - alt); s_n[2][k] += (int32_t)alt;
+      }
+      DMX_WAVE_LDS_ORDER();
+    }
+  }
+  RefPartial* out = partial + (size_t)blockIdx.y * pv.S + s0;
+  const int lim = min(kRefSlab, pv.S - s0);
+  for (int i = lane; i < lim; i += 64) {
+    RefPartial r;
+    r.ll[0] = s_ll[0][i]; r.ll[1] = s_ll[1][i]; r.ll[2] = s_ll[2][i];
+    r.n_cell = s_n[0][i]; r.n_ref = s_n[1][i]; r.n_alt = s_n[2][i]; r.pad = 0;
+    out[i] = r;
+  }
+}
+
+// One lane per (SNP i, sample v), i fastest (the partial rows of a chunk are read contiguously): adds the sample's chunks [c0, c1) of this
+// wave of partials, in ascending chunk order, onto the running sums (zeroed before the first wave).
+__global__ __launch_bounds__(256) void k_refine_fold(const RefPartial* __restrict__ partial, int32_t S, int32_t V, const int32_t* __restrict__ samp_chunk,
+                                                     int32_t c0, int32_t c1, double* __restrict__ ll, int32_t* __restrict__ cnt) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)S * V) return;
+  const int32_t v = (int32_t)(t / S), i = (int32_t)(t % S);
+  const int32_t cb = max(samp_chunk[v], c0), ce = min(samp_chunk[v + 1], c1);
+  if (cb >= ce) return;
+  const size_t o = (size_t)i * V + v, SV = (size_t)S * V;
+  double a0 = ll[o * 3], a1 = ll[o * 3 + 1], a2 = ll[o * 3 + 2];
+  int32_t n0 = cnt[o], n1 = cnt[SV + o], n2 = cnt[2 * SV + o];
+  for (int32_t c = cb; c < ce; ++c) {
+    const RefPartial& r = partial[(size_t)(c - c0) * S + i];
+    a0 += r.ll[0]; a1 += r.ll[1]; a2 += r.ll[2];
+    n0 += r.n_cell; n1 += r.n_ref; n2 += r.n_alt;
+  }
+  ll[o * 3] = a0; ll[o * 3 + 1] = a1; ll[o * 3 + 2] = a2;
+  cnt[o] = n0; cnt[SV + o] = n1; cnt[2 * SV + o] = n2;
+}
+
+// gp'[i][v][g] = q[g] exp(LL[g] - max LL) / sum, q[g] = prior[i][v][g] + floor, in float64, rounded to float32; rows no pair covers keep the prior's bits.
+__global__ __launch_bounds__(256) void k_refine_finish(const double* __restrict__ ll, const int32_t* __restrict__ n_cell, const float* __restrict__ prior,
+                                                       int64_t n_rows, double floor_, float* __restrict__ gp) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= n_rows) return;
+  if (n_cell[o] == 0) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(prior) + o * 3;
+    uint32_t* dst = reinterpret_cast<uint32_t*>(gp) + o * 3;
+    dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
+    return;
+  }
+  const double l0 = ll[o * 3], l1 = ll[o * 3 + 1], l2 = ll[o * 3 + 2];
+  const double mx = fmax(fmax(l0, l1), l2);
+  const double w0 = ((double)prior[o * 3] + floor_) * exp(l0 - mx);
+  const double w1 = ((double)prior[o * 3 + 1] + floor_) * exp(l1 - mx);
+  const double w2 = ((double)prior[o * 3 + 2] + floor_) * exp(l2 - mx);
+  const double sum = w0 + w1 + w2;
+  gp[o * 3] = (float)(w0 / sum); gp[o * 3 + 1] = (float)(w1 / sum); gp[o * 3 + 2] = (float)(w2 / sum);
 }
 
 // SNP-minor copies for dense pileups: gT[r][s] = g[s][r] (r = k*3+l, float32 as stored) and g0T[l][s] = gp0s[s][l].
@@ -6239,6 +6352,18 @@ struct dmx_engine {
   // what the last run launched (dmx_engine_kernel_names): host function pointers of the K1 / K2 / K3b kernels, and where K1 ran
   const void *k1_fn = nullptr, *k2_fn = nullptr, *k3b_fn = nullptr; int32_t k1_placement = 0;
   bool k2_sym = false;                                               // launch_doublet picked a k_doublet_sym form (FAST, soft fields, grid {0, 0.5})
+  // genotype refinement (dmx_engine_refine_genotypes): its own slab table of the staged pileup (K1's d_blk is not touched), the chunk plan,
+  // the partials of one wave, the results; two gp' buffers, so that a refinement never overwrites the matrix the engine was handed by pointer
+  int64_t* d_rblk = nullptr; size_t rblk_cap = 0; bool rblk_valid = false; int32_t rblk_S = 0;
+  int32_t* d_rplan = nullptr; size_t rplan_cap = 0; std::vector<int32_t> h_rplan;
+  void* d_rpart = nullptr; size_t rpart_cap = 0;
+  float* d_rprior = nullptr; size_t rprior_cap = 0;
+  double* d_rll = nullptr; size_t rll_cap = 0;
+  int32_t* d_rcnt = nullptr; size_t rcnt_cap = 0;
+  float* d_rgp[2] = {nullptr, nullptr}; size_t rgp_cap[2] = {0, 0}; int rgp_cur = -1;
+  int32_t ref_S = 0; bool have_refined = false;
+  hipEvent_t rev[4] = {};
+  dmx_refine_info ref_info{};
 };
 
 namespace {
@@ -6377,6 +6502,9 @@ extern "C" int dmx_engine_destroy(dmx_engine* e) {
   if (e->d_oth) (void)hipFree(e->d_oth);
   if (e->d_snprec) (void)hipFree(e->d_snprec);
   if (e->d_ctab) (void)hipFree(e->d_ctab);
+  for (void* p : {(void*)e->d_rblk, (void*)e->d_rplan, e->d_rpart, (void*)e->d_rprior, (void*)e->d_rll, (void*)e->d_rcnt, (void*)e->d_rgp[0], (void*)e->d_rgp[1]})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t& ev : e->rev) if (ev) (void)hipEventDestroy(ev);
   for (int i = 0; i < 2; ++i) { if (e->h_stage[i]) (void)hipHostFree(e->h_stage[i]); if (e->ev_stage[i]) (void)hipEventDestroy(e->ev_stage[i]); }
   for (hipEvent_t& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& r : e->ring_s) for (hipEvent_t& ev : r) if (ev) (void)hipEventDestroy(ev);
@@ -6834,6 +6962,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
     }
   }
   e->have_sing = e->have_grid = false;
+  e->rblk_valid = false; e->have_refined = false;
   e->have_pileup = true;
   e->k1_fn = e->k2_fn = e->k3b_fn = nullptr; e->k1_placement = 0;      // nothing has run on this pileup yet
   return DMX_OK;
@@ -7764,6 +7893,147 @@ extern "C" int dmx_engine_kernel_names(dmx_engine* e, dmx_kernel_names* out) {
   std::memset(out, 0, sizeof *out);
   kernel_name(e->k1_fn, out->singlet); kernel_name(e->k2_fn, out->doublet); kernel_name(e->k3b_fn, out->certify);
   out->k1_placement = e->k1_placement;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Genotype refinement from called singlets.  The chunk plan is a counting sort of `assign` on the host (B ints);
+// everything that touches the pileup runs on the device: k_snp_blocks (slab table, once per staged pileup), then per wave of chunks
+// k_refine_partial + k_refine_fold, then k_refine_finish.
+extern "C" int dmx_engine_refine_genotypes(dmx_engine* e, const dmx_refine_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_refine_genotypes: no pileup staged (dmx_engine_set_pileup first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_refine_genotypes: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if ((B > 0 && !rq->assign) || (S > 0 && !rq->prior)) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: missing assign / prior");
+  if (rq->assign_memory != DMX_MEM_HOST && rq->assign_memory != DMX_MEM_DEVICE)
+    return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: assign_memory %d", rq->assign_memory);
+  if (!(rq->floor >= 0.0) || !std::isfinite(rq->floor)) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: floor %g", rq->floor);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->rev[0]) for (hipEvent_t& ev : e->rev) HIP_TRY(hipEventCreate(&ev));
+
+  // ---- chunk plan: samp_chunk[V + 1] | chunk_beg[n_chunks + 1] | members[n_assigned] (cell ids by sample, ascending within a sample)
+  std::vector<int32_t> a((size_t)B);
+  if (B > 0) {
+    if (rq->assign_memory == DMX_MEM_DEVICE) {
+      HIP_TRY(hipMemcpyAsync(a.data(), rq->assign, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+      std::memcpy(a.data(), rq->assign, sizeof(int32_t) * (size_t)B);
+    }
+  }
+  std::vector<int64_t> cnt((size_t)V + 1, 0);
+  for (int32_t b = 0; b < B; ++b) {
+    if (a[(size_t)b] < -1 || a[(size_t)b] >= V) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: assign[%d] = %d is not in [-1, %d)", b, a[(size_t)b], V);
+    if (a[(size_t)b] >= 0) ++cnt[(size_t)a[(size_t)b] + 1];
+  }
+  for (int32_t v = 0; v < V; ++v) cnt[(size_t)v + 1] += cnt[(size_t)v];          // -> first member of each sample
+  const int64_t n_asg = cnt[(size_t)V];
+  std::vector<int32_t>& plan = e->h_rplan;
+  plan.assign((size_t)V + 1, 0);
+  for (int32_t v = 0; v < V; ++v) plan[(size_t)v + 1] = plan[(size_t)v] + (int32_t)((cnt[(size_t)v + 1] - cnt[(size_t)v] + kRefChunk - 1) / kRefChunk);
+  const int32_t nch = plan[(size_t)V];
+  for (int32_t v = 0; v < V; ++v)
+    for (int32_t c = plan[(size_t)v]; c < plan[(size_t)v + 1]; ++c) plan.push_back((int32_t)(cnt[(size_t)v] + (int64_t)(c - plan[(size_t)v]) * kRefChunk));
+  plan.push_back((int32_t)n_asg);
+  const size_t o_beg = (size_t)V + 1, o_mem = o_beg + (size_t)nch + 1;
+  plan.resize(o_mem + (size_t)n_asg);
+  for (int32_t b = 0; b < B; ++b) if (a[(size_t)b] >= 0) plan[o_mem + (size_t)cnt[(size_t)a[(size_t)b]]++] = b;   // stable: ascending cell id
+
+  const size_t rows = (size_t)S * V;
+  if (int rc = ensure_dev((void**)&e->d_rplan, &e->rplan_cap, sizeof(int32_t) * plan.size())) return rc;
+  if (int rc = ensure_dev((void**)&e->d_rprior, &e->rprior_cap, sizeof(float) * rows * 3)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_rll, &e->rll_cap, sizeof(double) * rows * 3)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_rcnt, &e->rcnt_cap, sizeof(int32_t) * rows * 3)) return rc;
+  const int nxt = e->d_g == e->d_rgp[0] ? 1 : 0;                      // never the buffer the engine's genotype matrix is
+  if (int rc = ensure_dev((void**)&e->d_rgp[nxt], &e->rgp_cap[nxt], sizeof(float) * rows * 3)) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_rplan, plan.data(), sizeof(int32_t) * plan.size(), hipMemcpyHostToDevice, e->stream));
+  if (rows) HIP_TRY(hipMemcpyAsync(e->d_rprior, rq->prior, sizeof(float) * rows * 3, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_rll, 0, sizeof(double) * rows * 3, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_rcnt, 0, sizeof(int32_t) * rows * 3, e->stream));
+
+  // ---- slab table of the staged pileup (either layout): where every barcode stands at each slab boundary
+  const int32_t nblk = (int32_t)(((int64_t)S + kRefSlab - 1) >> kRefSlabShift);
+  const bool build_blk = !e->rblk_valid || e->rblk_S != S;
+  HIP_TRY(hipEventRecord(e->rev[0], e->stream));
+  if (build_blk && B > 0) {
+    if (int rc = ensure_dev((void**)&e->d_rblk, &e->rblk_cap, sizeof(int64_t) * 2 * (size_t)B * ((size_t)nblk + 1))) return rc;
+    hipLaunchKernelGGL(k_snp_blocks, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, kRefSlabShift, nblk, e->d_rblk);
+    HIP_TRY(hipGetLastError());
+  }
+  e->rblk_valid = true; e->rblk_S = S;
+  HIP_TRY(hipEventRecord(e->rev[1], e->stream));
+
+  // ---- partials, in waves of chunks that fit the budget (4 GiB, or a sixth of the free memory); the fold keeps the chunk order across waves
+  const size_t per_chunk = sizeof(RefPartial) * (size_t)S;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = std::min<size_t>((size_t)4 << 30, free_b / 6);
+  const int32_t cpw = (int32_t)std::max<size_t>(1, std::min<size_t>({per_chunk ? budget / per_chunk : (size_t)65535, (size_t)65535, (size_t)std::max(nch, 1)}));
+  int32_t n_waves = 0;
+  if (nch > 0 && S > 0) {
+    if (int rc = ensure_dev(&e->d_rpart, &e->rpart_cap, per_chunk * (size_t)cpw)) return rc;
+    const int32_t* d_samp = e->d_rplan;
+    const int32_t* d_beg = e->d_rplan + o_beg;
+    const int32_t* d_mem = e->d_rplan + o_mem;
+    for (int32_t c0 = 0; c0 < nch; c0 += cpw, ++n_waves) {
+      const int32_t nc = std::min(cpw, nch - c0);
+      hipLaunchKernelGGL(k_refine_partial, dim3((unsigned)nblk, (unsigned)nc), dim3(64), 0, e->stream, e->pv, e->nrd_width, (const double*)e->d_lut,
+                         (const int64_t*)e->d_rblk, nblk, d_mem, d_beg, c0, (RefPartial*)e->d_rpart);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_refine_fold, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream, (const RefPartial*)e->d_rpart, S, V, d_samp, c0,
+                         c0 + nc, e->d_rll, e->d_rcnt);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  HIP_TRY(hipEventRecord(e->rev[2], e->stream));
+  if (rows) {
+    hipLaunchKernelGGL(k_refine_finish, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_rll, (const int32_t*)e->d_rcnt,
+                       (const float*)e->d_rprior, (int64_t)rows, rq->floor, e->d_rgp[nxt]);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(e->rev[3], e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's prior may go away after return
+  float ms[3] = {0.f, 0.f, 0.f};
+  for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&ms[i], e->rev[i], e->rev[i + 1]));
+  dmx_refine_info& inf = e->ref_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.blocks_ms = build_blk ? ms[0] : 0.0; inf.partial_ms = ms[1]; inf.finish_ms = ms[2];
+  inf.partial_bytes = nch > 0 ? (int64_t)(per_chunk * (size_t)cpw) : 0;
+  inf.n_chunks = nch; inf.n_waves = n_waves; inf.chunk_cells = kRefChunk; inf.slab_snps = kRefSlab; inf.n_assigned = (int32_t)n_asg;
+  e->rgp_cur = nxt; e->ref_S = S; e->have_refined = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_refined(dmx_engine* e, double* llk, int32_t* n_cell, int32_t* n_ref, int32_t* n_alt, float* gp) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_refined: null engine");
+  if (!e->have_refined) return set_error(DMX_ERR_STATE, "dmx_engine_get_refined: no refinement on the staged pileup (dmx_engine_refine_genotypes first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t rows = (size_t)e->ref_S * e->V;
+  if (!rows) return DMX_OK;
+  if (llk) HIP_TRY(hipMemcpy(llk, e->d_rll, sizeof(double) * rows * 3, hipMemcpyDeviceToHost));
+  if (n_cell) HIP_TRY(hipMemcpy(n_cell, e->d_rcnt, sizeof(int32_t) * rows, hipMemcpyDeviceToHost));
+  if (n_ref) HIP_TRY(hipMemcpy(n_ref, e->d_rcnt + rows, sizeof(int32_t) * rows, hipMemcpyDeviceToHost));
+  if (n_alt) HIP_TRY(hipMemcpy(n_alt, e->d_rcnt + 2 * rows, sizeof(int32_t) * rows, hipMemcpyDeviceToHost));
+  if (gp) HIP_TRY(hipMemcpy(gp, e->d_rgp[e->rgp_cur], sizeof(float) * rows * 3, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_refined_device_ptr(dmx_engine* e, const float** out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_refined_device_ptr: null argument");
+  if (!e->have_refined) return set_error(DMX_ERR_STATE, "dmx_engine_refined_device_ptr: no refinement on the staged pileup (dmx_engine_refine_genotypes first)");
+  *out = e->d_rgp[e->rgp_cur];
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_refine_info(dmx_engine* e, dmx_refine_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_refine_info: null argument");
+  if (!e->have_refined) return set_error(DMX_ERR_STATE, "dmx_engine_refine_info: no refinement on the staged pileup (dmx_engine_refine_genotypes first)");
+  *out = e->ref_info;
   return DMX_OK;
 }
 

@@ -266,6 +266,39 @@ class Engine:
         finally:
             self._L.dmx_pair_text_free(h)
 
+    def refine_genotypes(self, assign, prior: np.ndarray, floor: float = 1e-3):
+        """dmx_engine_refine_genotypes over the staged pileup: pooled per-sample genotype likelihoods of the barcodes assign[b] = sample
+        (-1 = not used) and the refined matrix.  `assign` is a host array, or a device pointer (int) to B int32.  Returns
+        (LL[S][V][3] f64, n_cell[S][V], n_ref[S][V], n_alt[S][V] i32, gp'[S][V][3] f32)."""
+        prior = np.ascontiguousarray(prior, dtype=np.float32)
+        if prior.ndim != 3 or prior.shape[1] != self.V or prior.shape[2] != 3:
+            raise ValueError(f"prior must be [S][{self.V}][3]")
+        if isinstance(assign, int):
+            a, mem, ptr = None, capi.DMX_MEM_DEVICE, assign
+        else:
+            a = np.ascontiguousarray(assign, dtype=np.int32)
+            mem, ptr = capi.DMX_MEM_HOST, (a.ctypes.data if a.size else None)
+        S = prior.shape[0]
+        rq = capi.RefineRequest(self.B, mem, ptr, S, 0, prior.ctypes.data if prior.size else None, float(floor))
+        check(self._L.dmx_engine_refine_genotypes(self._h, C.byref(rq)))
+        ll = np.zeros((S, self.V, 3))
+        n_cell, n_ref, n_alt = (np.zeros((S, self.V), dtype=np.int32) for _ in range(3))
+        gp = np.zeros((S, self.V, 3), dtype=np.float32)
+        check(self._L.dmx_engine_get_refined(self._h, ll.ctypes.data, n_cell.ctypes.data, n_ref.ctypes.data, n_alt.ctypes.data, gp.ctypes.data))
+        return ll, n_cell, n_ref, n_alt, gp
+
+    def refined_device_ptr(self) -> int:
+        """Device pointer of the last refined matrix gp' [S][V][3] f32 (for set_genotypes_device)."""
+        p = C.c_void_p()
+        check(self._L.dmx_engine_refined_device_ptr(self._h, C.byref(p)))
+        return int(p.value)
+
+    def refine_info(self) -> dict:
+        """HIP-event times (ms) and sizes of the last refinement (dmx_engine_refine_info)."""
+        r = capi.RefineInfo()
+        check(self._L.dmx_engine_refine_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.RefineInfo._fields_ if n != "reserved"}
+
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()
         check(self._L.dmx_engine_device_view(self._h, C.byref(v)))

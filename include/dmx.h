@@ -27,7 +27,9 @@ extern "C" {
                                trailing `cell_grid` member; a by-pointer input struct without a size member cannot grow (a caller compiled against ABI 5
                                passes a shorter object), so ABI 7 WITHDRAWS that member — the struct has its ABI 5 layout again and the grids travel as an
                                argument of the new entry point.  Additions only otherwise: callers of ABI <= 5 run unchanged.
-                               8: dmx_engine_format_pair / dmx_pair_text_* (`.pair` rows formatted on the device).  Additions only. */
+                               8: dmx_engine_format_pair / dmx_pair_text_* (`.pair` rows formatted on the device); later, still ABI 8:
+                               dmx_engine_refine_genotypes / _get_refined / _refined_device_ptr / _refine_info (genotype refinement from
+                               called singlets).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -256,6 +258,44 @@ int dmx_engine_kernel_names(dmx_engine*, dmx_kernel_names* out);
 /* Algorithmic HBM bytes one launch of each kernel must move for the staged problem. */
 typedef struct { double singlet_bytes, doublet_bytes, reduce_bytes; } dmx_kernel_bytes;
 int dmx_engine_algorithmic_bytes(dmx_engine*, dmx_kernel_bytes* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Genotype refinement from called singlets (no counterpart in the reference).  For an assignment of barcodes to
+ * samples (assign[b] = 0..V-1, or -1 = not used), over the staged pileup and phred tables, for every SNP i and sample v:
+ *   LL[i][v][g]  = sum of log(GL_{b,i}[g]) over the barcodes b assigned to v that have a pair at SNP i — GL the reference's per-pair vector
+ *                  after the +1e-6 renormalisation (cmd_cram_demuxlet.cpp:426-452); pairs whose stored reads are all allele 2 count too;
+ *   n_cell[i][v] = the number of those pairs;  n_ref / n_alt[i][v] = their stored reads of allele 0 / 1;
+ *   gp'[i][v][g] = q[g] exp(LL[g] - max LL) / sum over g of the same, q[g] = prior[i][v][g] + floor, in float64, rounded to float32;
+ *                  a row with n_cell = 0 is prior's row, bit for bit (no floor).
+ * Sum order: a sample's assigned barcodes in ascending cell id are cut into chunks of 64; inside a chunk the terms are added in barcode
+ * order, then the chunk sums in ascending chunk order.  No floating-point atomics: the same inputs give the same bits, whatever ran before.
+ * The call runs on the engine's stream and synchronises it before returning (the prior may be freed then).  It leaves every other result
+ * of the engine as it was. */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t assign_memory;       /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `assign` lives */
+  const int32_t* assign;       /* [n_cells] */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t reserved0;
+  const float* prior;          /* [n_snps][V][3] float32, HOST (normally the matrix the engine was given) */
+  double  floor;               /* >= 0; 1e-3 is the usual value */
+  int32_t reserved[4];         /* 0 */
+} dmx_refine_request;
+typedef struct {
+  double  blocks_ms;           /* HIP-event times: the slab table (k_snp_blocks; 0 when the staged pileup's table already existed), */
+  double  partial_ms;          /* k_refine_partial + k_refine_fold over all waves, */
+  double  finish_ms;           /* k_refine_finish */
+  int64_t partial_bytes;       /* device bytes of one wave of chunk partials */
+  int32_t n_chunks, n_waves, chunk_cells, slab_snps, n_assigned;
+  int32_t reserved[3];
+} dmx_refine_info;
+int dmx_engine_refine_genotypes(dmx_engine*, const dmx_refine_request*);
+/* Device->host copies of the last refinement (any pointer may be NULL): llk[S][V][3] f64, n_cell / n_ref / n_alt [S][V] i32, gp[S][V][3] f32. */
+int dmx_engine_get_refined(dmx_engine*, double* llk, int32_t* n_cell, int32_t* n_ref, int32_t* n_alt, float* gp);
+/* The device pointer of the last gp' (for dmx_engine_set_genotypes(..., DMX_MEM_DEVICE) without a round trip).  Valid until the engine is
+ * destroyed; a later refinement writes its gp' to the OTHER of two buffers when this one is the engine's genotype matrix, else may reuse it. */
+int dmx_engine_refined_device_ptr(dmx_engine*, const float** out);
+int dmx_engine_refine_info(dmx_engine*, dmx_refine_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * a6,a10..a14  finaliser and writers — replaces cmd_cram_demuxlet.cpp:465-527 (.single), :713-875 (.sing2/.pair/.best).
