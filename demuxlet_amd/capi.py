@@ -35,6 +35,8 @@ SYMBOLS = [
     "dmx_resolve_tie_order", "dmx_engine_mean_kernel_times", "dmx_store_add_batch", "dmx_write_doublet_summary_grids", "dmx_engine_kernel_names", "dmx_debug_device_log2_lite", "dmx_debug_device_log2_lite32",
     "dmx_engine_format_pair", "dmx_pair_text_get_info", "dmx_pair_text_read", "dmx_pair_text_free",
     "dmx_engine_refine_genotypes", "dmx_engine_get_refined", "dmx_engine_refined_device_ptr", "dmx_engine_refine_info",
+    "dmx_engine_cluster_stage", "dmx_engine_cluster_mstep", "dmx_engine_cluster_estep", "dmx_engine_get_cluster", "dmx_engine_get_cluster_stage",
+    "dmx_engine_cluster_device_ptr", "dmx_engine_cluster_info",
 ]
 
 
@@ -64,6 +66,25 @@ class RefineInfo(C.Structure):        # dmx_refine_info
     _fields_ = [("blocks_ms", C.c_double), ("partial_ms", C.c_double), ("finish_ms", C.c_double), ("partial_bytes", C.c_int64),
                 ("n_chunks", C.c_int32), ("n_waves", C.c_int32), ("chunk_cells", C.c_int32), ("slab_snps", C.c_int32), ("n_assigned", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
+
+
+DMX_CLUSTER_LAST_ESTEP = 2
+
+
+class ClusterMstepRequest(C.Structure):   # dmx_cluster_mstep_request
+    _fields_ = [("n_cells", C.c_int32), ("n_snps", C.c_int32), ("n_cols", C.c_int32), ("weights_memory", C.c_int32), ("weights", C.c_void_p),
+                ("prior", C.c_void_p), ("floor", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterEstepRequest(C.Structure):   # dmx_cluster_estep_request
+    _fields_ = [("n_restarts", C.c_int32), ("n_clusters", C.c_int32), ("log_pi", C.c_void_p), ("temperature", C.c_double), ("mask", C.c_void_p),
+                ("ll", C.c_void_p), ("col_sum", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterInfo(C.Structure):           # dmx_cluster_info
+    _fields_ = [("stage_ms", C.c_double), ("mstep_ms", C.c_double), ("estep_ms", C.c_double), ("cache_bytes", C.c_int64), ("scratch_bytes", C.c_int64),
+                ("n_pairs", C.c_int64), ("n_cells", C.c_int32), ("n_snps", C.c_int32), ("sorted", C.c_int32), ("n_cols", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
 
 
 class DmxError(RuntimeError):
@@ -193,6 +214,9 @@ def load() -> C.CDLL:
         "dmx_engine_format_pair": [vp, vp, vp], "dmx_pair_text_get_info": [vp, vp], "dmx_pair_text_read": [vp, C.c_int64, C.c_int64, vp],
         "dmx_engine_refine_genotypes": [vp, vp], "dmx_engine_get_refined": [vp, vp, vp, vp, vp, vp], "dmx_engine_refined_device_ptr": [vp, vp],
         "dmx_engine_refine_info": [vp, vp],
+        "dmx_engine_cluster_stage": [vp], "dmx_engine_cluster_mstep": [vp, vp], "dmx_engine_cluster_estep": [vp, vp],
+        "dmx_engine_get_cluster": [vp, vp, vp, vp, vp], "dmx_engine_get_cluster_stage": [vp, vp, vp, vp, vp], "dmx_engine_cluster_device_ptr": [vp, vp],
+        "dmx_engine_cluster_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

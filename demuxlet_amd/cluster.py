@@ -1,0 +1,283 @@
+"""Genotype-free demultiplexing: EM clustering of barcodes into K donors from the reads alone, then doublet calls between the clusters.
+
+The model is a mixture of K donors whose genotypes are unknown.  Each restart r of R runs its own EM over K columns of one engine of
+V = R * K columns:
+  E-step   K1 (Engine.run_singlet) scores every barcode against every column of the current cluster genotypes; cluster_estep turns
+           llks + log pi into per-(barcode, column) weights on the device and returns the per-restart log-likelihood and column sums.
+  M-step   cluster_mstep pools the per-pair log genotype likelihoods with those weights into a posterior gp' = (q + floor) x likelihood,
+           q the per-SNP Hardy-Weinberg prior from the pooled allele counts; gp' stays on the device and becomes K1's matrix.
+The restart with the highest log-likelihood gives the K genotype columns (sample ids CLUST0 .. CLUST{K-1}); the unchanged
+`demuxlet_run` writes <prefix>.best/.single/.sing2 from them (doublets come out of its grid), and each round r >= 1 refines the
+clusters' genotypes from the previous round's singlets only (the refinement of section 12, prior q) and runs again to <prefix>.r<r>.*.
+
+    python -m demuxlet_amd.cluster --pileup <x>.pileup.txt --n-clusters K --out <prefix> [--restarts R] [--seed S] [--max-iter N]
+        [--tol T] [--floor F] [--min-snp M] [--alpha A ...] [--rounds N] [--match] [--fast] [--gpu G]
+
+reads the dump that `demuxlet --pileup-only` writes; its genotype matrix is ignored unless --match is given."""
+from __future__ import annotations
+
+import argparse
+import sys
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import capi, engine, refine
+
+MAX_COLUMNS = 4094          # dmx_engine_create's widest panel: R * K columns in one engine
+# Restarts: EM from a random hard assignment often settles where one cluster holds two donors and another donor is split.  The true
+# solution's log-likelihood is clearly higher, so more restarts help; measured on synthetic pools of 4 000 barcodes x ~1 000 covered
+# SNPs (tests/test_gpu_cluster.py): 3 of 6 single restarts found the donors at K = 4, 0 of 6 at K = 8; the best of 16 did at both.
+PI_FLOOR = 1e-6             # smallest mixing weight a cluster keeps between iterations
+EM_HEADER = "ITER\tRESTART\tLLK\tPI\n"
+MATCH_HEADER = "CLUST\tSM_ID\tN.CELL\tSUM.LLK\tBEST\n"
+
+
+def cluster_ids(k: int) -> List[str]:
+    return [f"CLUST{j}" for j in range(k)]
+
+
+def check_args(n_clusters: int, restarts: int, max_iter: int, tol: float, floor: float, n_cells: int, n_pairs: int) -> None:
+    """The error paths of cluster_run, before any device work."""
+    if n_clusters < 2:
+        raise ValueError(f"--n-clusters {n_clusters}: clustering needs at least 2 clusters")
+    if restarts < 1:
+        raise ValueError(f"--restarts {restarts}: at least 1")
+    if n_clusters * restarts > MAX_COLUMNS:
+        raise ValueError(f"{restarts} restarts x {n_clusters} clusters = {n_clusters * restarts} columns; one engine holds at most {MAX_COLUMNS}")
+    if max_iter < 1:
+        raise ValueError(f"--max-iter {max_iter}: at least 1")
+    if not (tol >= 0.0) or not (floor >= 0.0):
+        raise ValueError("--tol and --floor must be >= 0")
+    if n_cells < n_clusters or n_pairs == 0:
+        raise ValueError(f"empty pileup: {n_cells} barcodes, {n_pairs} covered (barcode, SNP) pairs for {n_clusters} clusters")
+
+
+def hwe_prior(n_ref: np.ndarray, n_alt: np.ndarray) -> np.ndarray:
+    """q[S][3] float32 = Hardy-Weinberg genotype frequencies of p = (n_alt + 1) / (n_ref + n_alt + 2), the pooled ALT frequency."""
+    p = (np.asarray(n_alt, dtype=np.float64) + 1.0) / (np.asarray(n_ref, dtype=np.float64) + np.asarray(n_alt, dtype=np.float64) + 2.0)
+    return np.stack([(1.0 - p) ** 2, 2.0 * p * (1.0 - p), p * p], axis=1).astype(np.float32)
+
+
+def initial_labels(seed: int, restarts: int, n_cells: int, n_clusters: int) -> np.ndarray:
+    """labels[R][B]: each restart's random hard assignment, from one seeded numpy Generator."""
+    rng = np.random.default_rng(seed)
+    return np.stack([rng.integers(0, n_clusters, size=n_cells) for _ in range(restarts)]).astype(np.int32)
+
+
+def one_hot_weights(labels: np.ndarray, n_clusters: int, mask: Optional[np.ndarray] = None) -> np.ndarray:
+    """w[B][R * K] float64: 1 at column r * K + labels[r][b], 0 elsewhere and for barcodes outside the mask."""
+    R, B = labels.shape
+    w = np.zeros((B, R * n_clusters))
+    for r in range(R):
+        w[np.arange(B), r * n_clusters + labels[r]] = 1.0
+    if mask is not None:
+        w[~np.asarray(mask, dtype=bool)] = 0.0
+    return w
+
+
+def update_log_pi(col_sum: np.ndarray, restarts: int, n_clusters: int) -> np.ndarray:
+    """log pi[R][K] from the E-step's column sums: pi = sum / mass, at least PI_FLOOR, renormalised."""
+    cs = np.asarray(col_sum, dtype=np.float64).reshape(restarts, n_clusters)
+    mass = cs.sum(axis=1, keepdims=True)
+    pi = np.where(mass > 0, cs / np.where(mass > 0, mass, 1.0), 1.0 / n_clusters)
+    pi = np.maximum(pi, PI_FLOOR)
+    pi /= pi.sum(axis=1, keepdims=True)
+    return np.log(pi)
+
+
+def converged(prev: Optional[np.ndarray], cur: np.ndarray, tol: float) -> bool:
+    """Every restart's |dLL| < tol * |LL|."""
+    if prev is None:
+        return False
+    return bool(np.all(np.abs(cur - prev) < tol * np.abs(cur)))
+
+
+def best_restart(ll: np.ndarray) -> int:
+    """The restart with the highest log-likelihood; on a tie the lowest index."""
+    ll = np.asarray(ll, dtype=np.float64)
+    return int(np.flatnonzero(ll == ll.max())[0])
+
+
+def write_em_tsv(path: str, rows: Sequence[Tuple[int, int, float, Sequence[float]]]) -> None:
+    """<prefix>.em.tsv: one row per (iteration, restart): ITER RESTART LLK PI (the mixing weights the E-step used, comma-joined)."""
+    with open(path, "w") as f:
+        f.write(EM_HEADER)
+        for it, r, ll, pi in rows:
+            f.write(f"{it}\t{r}\t{ll:.6f}\t" + ",".join(f"{x:.6g}" for x in pi) + "\n")
+
+
+def match_table(llks: np.ndarray, called: np.ndarray, n_clusters: int) -> Tuple[np.ndarray, np.ndarray]:
+    """For every cluster k and sample v: the number of barcodes called SNG-CLUSTk (called[b] = k, -1 = not a singlet) and the sum of
+    their llks[b][v].  Returns (n_cell[K], sum_llk[K][V])."""
+    called = np.asarray(called)
+    n = np.bincount(called[called >= 0], minlength=n_clusters)[:n_clusters]
+    s = np.zeros((n_clusters, llks.shape[1]))
+    for k in range(n_clusters):
+        s[k] = llks[called == k].sum(axis=0)
+    return n, s
+
+
+def write_match_tsv(path: str, n_cell: np.ndarray, sum_llk: np.ndarray, sample_ids: Sequence[str]) -> None:
+    """<prefix>.match.tsv: one row per (cluster, genotyped sample); BEST = 1 on the sample with the highest SUM.LLK of a cluster with
+    called singlets (the first on a tie)."""
+    with open(path, "w") as f:
+        f.write(MATCH_HEADER)
+        for k in range(sum_llk.shape[0]):
+            best = int(np.argmax(sum_llk[k])) if n_cell[k] > 0 else -1
+            for v, sm in enumerate(sample_ids):
+                f.write(f"CLUST{k}\t{sm}\t{int(n_cell[k])}\t{sum_llk[k, v]:.5f}\t{int(v == best)}\n")
+
+
+def match_labels(truth: np.ndarray, pred: np.ndarray, n_truth: int, n_pred: int) -> np.ndarray:
+    """A one-to-one map pred label -> truth label, greedy on the confusion matrix (largest count first; lowest indices on ties).
+    Labels < 0 are ignored; a predicted label left without a partner maps to -1."""
+    truth, pred = np.asarray(truth), np.asarray(pred)
+    ok = (truth >= 0) & (pred >= 0)
+    conf = np.zeros((n_pred, n_truth), dtype=np.int64)
+    np.add.at(conf, (pred[ok], truth[ok]), 1)
+    out = np.full(n_pred, -1, dtype=np.int64)
+    used_t = np.zeros(n_truth, dtype=bool)
+    for _ in range(min(n_pred, n_truth)):
+        c = np.where(out[:, None] >= 0, -1, np.where(used_t[None, :], -1, conf))
+        k, t = np.unravel_index(int(np.argmax(c)), c.shape)
+        if c[k, t] < 0:
+            break
+        out[k], used_t[t] = t, True
+    return out
+
+
+def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int = 16, seed: int = 0, max_iter: int = 50, tol: float = 1e-7,
+                floor: float = 1e-3, min_snp: int = 0, alphas: Sequence[float] = (0.0, 0.5), rounds: int = 1,
+                match: Optional[Tuple[np.ndarray, Sequence[str]]] = None, barcodes: Optional[Sequence[str]] = None, device: int = 0,
+                mode: int = capi.DMX_MODE_STRICT, doublet_prior: float = 0.5, temperature: float = 1.0,
+                snps: Optional[Sequence[Tuple]] = None) -> dict:
+    """EM clustering of the barcodes of `store_or_pileup` (a Store, or a HostPileup with barcodes=...) into n_clusters donors, then
+    the final demultiplexing pass and `rounds` hard-refine rounds (module docstring).  `match` = (g[S][NV][3], sample_ids) scores each
+    cluster against genotyped samples (<prefix>.match.tsv).  Returns a dict: the winning restart, per-restart LL, iterations, the
+    cluster genotype matrix gp[S][K][3] and the prior q[S][3]."""
+    if isinstance(store_or_pileup, engine.HostPileup):
+        pl = store_or_pileup
+        if barcodes is None:
+            raise ValueError("cluster_run: a HostPileup needs barcodes=")
+    else:
+        pl, barcodes = store_or_pileup.freeze(), store_or_pileup.barcodes()
+    B, S, K, R = pl.n_cells, pl.n_snps, int(n_clusters), int(restarts)
+    check_args(K, R, max_iter, tol, floor, B, len(pl.pair_nrd))
+    C = R * K
+    mask = pl.n_snp_per_cell >= min_snp if min_snp > 0 else None
+    kw = dict(barcodes=barcodes, doublet_prior=doublet_prior, device=device, mode=mode, min_snp=min_snp)
+    dense = pl.pair_snp is None
+    eng = engine.Engine(C, alphas, doublet_prior, device=device, mode=mode)
+    em_rows = []
+    try:
+        # prior: pooled REF / ALT counts of every barcode (one refinement with all barcodes in column 0)
+        flat = np.full((S, C, 3), 1.0 / 3.0, dtype=np.float32)
+        eng.set_genotypes(flat)
+        eng.set_pileup(pl)
+        _, _, n_ref, n_alt, _ = eng.refine_genotypes(np.zeros(B, dtype=np.int32), flat, floor)
+        del flat
+        q = hwe_prior(n_ref[:, 0], n_alt[:, 0])
+        eng.cluster_stage()
+        # first M-step from each restart's random hard assignment, pi uniform
+        eng.cluster_mstep(one_hot_weights(initial_labels(seed, R, B, K), K, mask), q, floor, fetch=False)
+        log_pi = np.full((R, K), -np.log(K))
+        prev = None
+        it = 0
+        for it in range(1, max_iter + 1):
+            eng.set_genotypes_device(eng.cluster_device_ptr(), S)
+            if dense:
+                eng.set_pileup(pl)          # a dense pileup's SNP-minor copy of the matrix is made when it is staged
+            eng.run_singlet()
+            ll, cs = eng.cluster_estep(R, K, log_pi, temperature, mask)
+            em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r])) for r in range(R)]
+            log_pi = update_log_pi(cs, R, K)
+            eng.cluster_mstep(None, q, floor, fetch=False)
+            if converged(prev, ll, tol):
+                break
+            prev = ll
+        win = best_restart(ll)
+        _, _, gp = eng.get_cluster(S)
+        g = np.ascontiguousarray(gp[:, win * K:(win + 1) * K, :])
+    finally:
+        eng.close()
+    write_em_tsv(out_prefix + ".em.tsv", em_rows)
+    ids = cluster_ids(K)
+    engine.demuxlet_run(pl, g, ids, alphas, out_prefix, **kw)
+    # hard-refine rounds: the previous round's singlets only, prior q for every cluster
+    qk = np.ascontiguousarray(np.broadcast_to(q[:, None, :], (S, K, 3)))
+    reng = engine.Engine(K, alphas, doublet_prior, device=device, mode=mode)
+    try:
+        reng.set_genotypes(qk)
+        reng.set_pileup(pl)
+        prev_prefix = out_prefix
+        for r in range(1, max(rounds, 1) + 1):
+            assign = refine.assignments_from_best(prev_prefix + ".best", ids, barcodes)
+            ll_r, n_cell, n_ref_r, n_alt_r, gr = reng.refine_genotypes(assign, qk, floor)
+            if r > rounds:
+                break                       # rounds = 0: the refinement only feeds <prefix>.clust.tsv
+            prev_prefix = f"{out_prefix}.r{r}"
+            engine.demuxlet_run(pl, gr, ids, alphas, prev_prefix, **kw)
+    finally:
+        reng.close()
+    refine.write_refined_tsv(out_prefix + ".clust.tsv", snps, ids, ll_r, n_cell, n_ref_r, n_alt_r, gr)
+    if match is not None:
+        mg, msamples = match
+        mg = np.ascontiguousarray(mg, dtype=np.float32)
+        if mg.shape[0] != S or mg.shape[1] != len(msamples):
+            raise ValueError(f"match: genotype matrix {mg.shape} for {S} SNPs and {len(msamples)} samples")
+        meng = engine.Engine(len(msamples), alphas, doublet_prior, device=device, mode=mode)
+        try:
+            meng.set_genotypes(mg)
+            meng.set_pileup(pl)
+            meng.run_singlet()
+            llks, _ = meng.get_singlet()
+        finally:
+            meng.close()
+        called = refine.assignments_from_best(prev_prefix + ".best", ids, barcodes)
+        n_cell_m, sum_llk = match_table(llks, called, K)
+        write_match_tsv(out_prefix + ".match.tsv", n_cell_m, sum_llk, msamples)
+    return dict(restart=win, ll=ll, iterations=it, gp=g, prior=q, last_prefix=prev_prefix)
+
+
+def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
+    ap = argparse.ArgumentParser(prog="python -m demuxlet_amd.cluster", description="genotype-free demultiplexing: EM clustering into K donors")
+    ap.add_argument("--pileup", required=True, help="<x>.pileup.txt written by `demuxlet --pileup-only`")
+    ap.add_argument("--n-clusters", type=int, required=True, help="K, the number of donors in the pool")
+    ap.add_argument("--out", required=True, help="output prefix: <out>.best/.single/.sing2, <out>.r<N>.*, <out>.em.tsv, <out>.clust.tsv")
+    ap.add_argument("--restarts", type=int, default=16, help="independent random starts; the best log-likelihood wins (default 16)")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--max-iter", type=int, default=50)
+    ap.add_argument("--tol", type=float, default=1e-7, help="stop when every restart's |dLL| < tol * |LL| (default 1e-7)")
+    ap.add_argument("--floor", type=float, default=1e-3, help="added to the prior of every covered row (default 1e-3)")
+    ap.add_argument("--min-snp", type=int, default=0, help="barcodes with fewer covered SNPs take no part in the EM and get no call")
+    ap.add_argument("--alpha", type=float, nargs="+", default=[0.0, 0.5], help="grid of alpha values (default 0 0.5)")
+    ap.add_argument("--doublet-prior", type=float, default=0.5)
+    ap.add_argument("--rounds", type=int, default=1, help="hard-refine rounds after the final pass (default 1)")
+    ap.add_argument("--match", action="store_true", help="score the clusters against the dump's genotyped samples (<out>.match.tsv)")
+    ap.add_argument("--fast", action="store_true", help="DMX_MODE_FAST for every pass")
+    ap.add_argument("--gpu", type=int, default=0)
+    a = ap.parse_args(argv)
+    if a.n_clusters < 2:
+        ap.error("--n-clusters must be at least 2")
+    if a.restarts < 1 or a.n_clusters * a.restarts > MAX_COLUMNS:
+        ap.error(f"--restarts x --n-clusters must be in [1, {MAX_COLUMNS}]")
+    return a
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    a = parse_args(argv)
+    d = refine.read_pileup_txt(a.pileup)
+    match = None
+    if a.match:
+        if not d.sample_ids:
+            raise SystemExit(f"--match: {a.pileup} has no genotyped samples")
+        match = (d.g, d.sample_ids)
+    cluster_run(d.pileup, a.n_clusters, a.out, restarts=a.restarts, seed=a.seed, max_iter=a.max_iter, tol=a.tol, floor=a.floor,
+                min_snp=a.min_snp, alphas=a.alpha, rounds=a.rounds, match=match, barcodes=d.barcodes, device=a.gpu,
+                mode=capi.DMX_MODE_FAST if a.fast else capi.DMX_MODE_STRICT, doublet_prior=a.doublet_prior, snps=d.snps)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

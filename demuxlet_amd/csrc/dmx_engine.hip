@@ -2055,6 +2055,193 @@ __global__ __launch_bounds__(256) void k_refine_finish(const double* __restrict_
   gp[o * 3] = (float)(w0 / sum); gp[o * 3 + 1] = (float)(w1 / sum); gp[o * 3 + 2] = (float)(w2 / sum);
 }
 
+// ---- genotype-free clustering (dmx_engine_cluster_*) ------------------------------------------------------------
+// The stage writes, for every pair of the staged pileup, lgl[3] = log GL (the refinement's vector: gl_seed / gl_finish, then
+// dmx_log_fast_pinned) and its stored REF / ALT reads (ref | alt << 16), in SNP-major order with ascending cell id inside a SNP, and the
+// cell id of each slot.  One wavefront per cell walks its pairs as k_refine_partial does; `dst` maps a cell-major pair to its slot
+// (NULL: the dense layout, slot = t * B + cell for pair t of the cell; else k_cluster_slots made it).
+__global__ __launch_bounds__(kThreads) void k_cluster_lgl(PileupView pv, int nrd_width, const double* __restrict__ tabs, int64_t p_base,
+                                                          const int32_t* __restrict__ dst, double* __restrict__ lgl, uint32_t* __restrict__ cnt,
+                                                          int32_t* __restrict__ cell_of, int32_t* __restrict__ deep) {
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += blockDim.x) s_log[i] = tabs[kLut + i];
+  __syncthreads();
+  const DmxLogPins lk = dmx_log_pins();
+  const int lane = threadIdx.x & 63;
+  const int32_t cell = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (cell >= pv.B) return;
+  const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+  int64_t rd_base = pv.cell_read_off[cell];
+  for (int64_t p0 = p_beg; p0 < p_end; p0 += 64) {
+    const int64_t p = p0 + lane;
+    const bool v = p < p_end;
+    const uint32_t n = v ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+    const uint32_t incl = seg_scan_incl<64>(n);
+    const int64_t off = rd_base + (int64_t)(incl - n);
+    rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    if (v) {
+      const uint32_t rd4 = load_rd4(pv, off, n);
+      const GlSeed sd = gl_seed(tabs, n, rd4);
+      double G0, G1, G2;
+      gl_finish(sd, n, rd4, pv.reads, off, tabs, G0, G1, G2);
+      uint32_t alt = 0;
+      for (uint32_t r = 0; r < n && r < 4; ++r) alt += (rd4 >> (8 * r + 7)) & 1u;
+      for (uint32_t r = 4; r < n; ++r) alt += (uint32_t)pv.reads[off + r] >> 7;
+      const int64_t j = dst ? (int64_t)dst[p - p_base] : (p - p_beg) * (int64_t)pv.B + cell;
+      lgl[3 * j] = dmx_log_fast_pinned(G0, s_log, lk);      // GL >= 1e-6 / (1 + 3e-6): a normal positive argument
+      lgl[3 * j + 1] = dmx_log_fast_pinned(G1, s_log, lk);
+      lgl[3 * j + 2] = dmx_log_fast_pinned(G2, s_log, lk);
+      if (n > 0xFFFFu) *deep = 1;                           // the stage refuses pairs of more than 65 535 stored reads
+      cnt[j] = (n - alt) | (alt << 16);
+      cell_of[j] = cell;
+    }
+  }
+}
+
+// Sparse stage: the slot of a pair is snp_off[s] + (barcodes of lower id with a pair at s), computed without atomics.  The barcodes are
+// cut into groups of `gsz`, the SNPs into slabs of kClSlab (k_snp_blocks' table gives each barcode's first pair in a slab); one
+// wavefront per (slab, group) walks the group's barcodes in ascending id with LDS counters of the slab's SNPs — a barcode has at most
+// one pair per SNP, so lanes never collide, and the LDS executes one wavefront's instructions in program order.
+//   RANK = false: M[g][s] = the group's barcodes with a pair at s.
+//   RANK = true:  the counters start at snp_off[s] + M[g][s] (k_cluster_colscan made M exclusive over the groups) and each pair takes
+//                 the next slot: dst[p - p_base].
+constexpr int kClSlabShift = 12, kClSlab = 1 << kClSlabShift;
+template <bool RANK>
+__global__ __launch_bounds__(64) void k_cluster_slots(PileupView pv, const int64_t* __restrict__ blk, int32_t nblk, int32_t gsz, int64_t p_base,
+                                                      int32_t* __restrict__ M, const int64_t* __restrict__ snp_off, int32_t* __restrict__ dst) {
+  __shared__ int32_t s_c[kClSlab];
+  const int lane = threadIdx.x;
+  const int32_t slab = blockIdx.x, g = blockIdx.y, S = pv.S;
+  const int32_t s0 = slab << kClSlabShift, lim = min(kClSlab, S - s0);
+  for (int i = lane; i < kClSlab; i += 64) s_c[i] = (RANK && i < lim) ? (int32_t)snp_off[s0 + i] + M[(size_t)g * S + s0 + i] : 0;
+  __syncthreads();
+  const int32_t c0 = g * gsz, c1 = min(pv.B, c0 + gsz);
+  for (int32_t cell = c0; cell < c1; ++cell) {
+    const int64_t* bt = blk + ((size_t)cell * (nblk + 1) + slab) * 2;
+    const int64_t pe = bt[2];
+    for (int64_t p0 = bt[0]; p0 < pe; p0 += 64) {
+      const int64_t p = p0 + lane;
+      const int32_t k = p < pe ? pv.pair_snp[p] - s0 : -1;
+      if ((unsigned)k < (unsigned)lim) {
+        if (RANK) dst[p - p_base] = s_c[k];
+        s_c[k] += 1;
+      }
+      DMX_WAVE_LDS_ORDER();
+    }
+  }
+  __syncthreads();
+  if (!RANK) for (int i = lane; i < lim; i += 64) M[(size_t)g * S + s0 + i] = s_c[i];
+}
+// per SNP: M[g][s] -> its exclusive prefix over the groups, tot[s] = the SNP's pairs
+__global__ __launch_bounds__(256) void k_cluster_colscan(int32_t* __restrict__ M, int32_t n_groups, int32_t S, int32_t* __restrict__ tot) {
+  const int32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= S) return;
+  int32_t a = 0;
+  for (int32_t g = 0; g < n_groups; ++g) { const int32_t t = M[(size_t)g * S + s]; M[(size_t)g * S + s] = a; a += t; }
+  tot[s] = a;
+}
+
+// M-step.  One wavefront per SNP i, one lane per column c (blockIdx.y selects 64 columns): over the SNP's slots in ascending cell id,
+//   LL[i][c][g] = fma(w[b][c], lgl[g], LL) from 0,  W[i][c] += w[b][c];
+// then gp'[i][c][g] = q[g] exp(LL[g] - max LL) / sum, q[g] = prior[i][g] + floor, in float64, rounded to float32; W = 0: prior's bits.
+// The sum order is the contract (include/dmx.h): serial in slot order whatever the grid, no atomics.
+__global__ __launch_bounds__(256) void k_cluster_mstep(const int64_t* __restrict__ snp_off, const int32_t* __restrict__ cell_of,
+                                                       const double* __restrict__ lgl, const double* __restrict__ w, int32_t S, int32_t C,
+                                                       const float* __restrict__ prior, double floor_, double* __restrict__ LL,
+                                                       double* __restrict__ W, float* __restrict__ gp) {
+  const int32_t i = __builtin_amdgcn_readfirstlane((int32_t)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (i >= S) return;
+  const int32_t c = blockIdx.y * 64 + (threadIdx.x & 63);
+  const bool on = c < C;
+  const int32_t cc = on ? c : 0;
+  const int64_t j0 = snp_off[i], j1 = snp_off[i + 1];
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, ws = 0.0;
+  int64_t j = j0;
+  for (; j + 4 <= j1; j += 4) {
+    double x[4], l[12];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) x[u] = w[(size_t)cell_of[j + u] * C + cc];
+#pragma unroll
+    for (int u = 0; u < 12; ++u) l[u] = lgl[3 * j + u];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      a0 = fma(x[u], l[3 * u], a0); a1 = fma(x[u], l[3 * u + 1], a1); a2 = fma(x[u], l[3 * u + 2], a2); ws += x[u];
+    }
+  }
+  for (; j < j1; ++j) {
+    const double x = w[(size_t)cell_of[j] * C + cc];
+    a0 = fma(x, lgl[3 * j], a0); a1 = fma(x, lgl[3 * j + 1], a1); a2 = fma(x, lgl[3 * j + 2], a2); ws += x;
+  }
+  if (!on) return;
+  const size_t o = (size_t)i * C + c;
+  LL[3 * o] = a0; LL[3 * o + 1] = a1; LL[3 * o + 2] = a2; W[o] = ws;
+  if (ws == 0.0) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(prior) + (size_t)i * 3;
+    uint32_t* d = reinterpret_cast<uint32_t*>(gp) + 3 * o;
+    d[0] = src[0]; d[1] = src[1]; d[2] = src[2];
+    return;
+  }
+  const double mx = fmax(fmax(a0, a1), a2);
+  const double w0 = ((double)prior[(size_t)i * 3] + floor_) * exp(a0 - mx);
+  const double w1 = ((double)prior[(size_t)i * 3 + 1] + floor_) * exp(a1 - mx);
+  const double w2 = ((double)prior[(size_t)i * 3 + 2] + floor_) * exp(a2 - mx);
+  const double sum = w0 + w1 + w2;
+  gp[3 * o] = (float)(w0 / sum); gp[3 * o + 1] = (float)(w1 / sum); gp[3 * o + 2] = (float)(w2 / sum);
+}
+
+// E-step.  One thread per (barcode b, restart r), columns rK .. rK + K - 1 of K1's llks[B][C]:
+//   a_k = (llks[b][rK + k] + log_pi[r][k]) / T,  w[b][rK + k] = exp(a_k - max a) / sum;  lse[b][r] = logsumexp_k(llks + log_pi);
+// a barcode outside the mask gets w = 0 and lse = 0.
+__global__ __launch_bounds__(256) void k_cluster_estep(const double* __restrict__ llks, int32_t B, int32_t R, int32_t K, const double* __restrict__ log_pi,
+                                                       double inv_t, const uint8_t* __restrict__ mask, double* __restrict__ w, double* __restrict__ lse) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)B * R) return;
+  const int32_t b = (int32_t)(t / R), r = (int32_t)(t % R);
+  const size_t C = (size_t)R * K, o = (size_t)b * C + (size_t)r * K;
+  if (mask && !mask[b]) {
+    for (int32_t k = 0; k < K; ++k) w[o + k] = 0.0;
+    lse[(size_t)b * R + r] = 0.0;
+    return;
+  }
+  double m = -INFINITY, m1 = -INFINITY;
+  for (int32_t k = 0; k < K; ++k) {
+    const double x = llks[o + k] + log_pi[(size_t)r * K + k];
+    m1 = fmax(m1, x); m = fmax(m, x * inv_t);
+  }
+  double s = 0.0, s1 = 0.0;
+  for (int32_t k = 0; k < K; ++k) {
+    const double x = llks[o + k] + log_pi[(size_t)r * K + k];
+    const double e = exp(x * inv_t - m);
+    w[o + k] = e; s += e; s1 += exp(x - m1);
+  }
+  const double y = 1.0 / s;
+  for (int32_t k = 0; k < K; ++k) w[o + k] *= y;
+  lse[(size_t)b * R + r] = m1 + log(s1);
+}
+
+// The E-step's sums in a fixed order: chunk partials over kEChunk consecutive barcodes (one thread per output column, serial over the
+// chunk's barcodes), then k_cluster_efold adds the chunks in ascending order.  Columns 0 .. C-1: sum of w; C .. C+R-1: sum of lse.
+constexpr int kEChunk = 256;
+__global__ __launch_bounds__(256) void k_cluster_epart(const double* __restrict__ w, const double* __restrict__ lse, int32_t B, int32_t C, int32_t R,
+                                                       double* __restrict__ part) {
+  const int32_t col = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
+  if (col >= C + R) return;
+  const int32_t b0 = ch * kEChunk, b1 = min(B, b0 + kEChunk);
+  const bool is_w = col < C;
+  const double* src = is_w ? w + col : lse + (col - C);
+  const size_t stride = is_w ? (size_t)C : (size_t)R;
+  double a = 0.0;
+  for (int32_t b = b0; b < b1; ++b) a += src[(size_t)b * stride];
+  part[(size_t)ch * (C + R) + col] = a;
+}
+__global__ __launch_bounds__(256) void k_cluster_efold(const double* __restrict__ part, int32_t n_chunks, int32_t n_cols, double* __restrict__ out) {
+  const int32_t col = blockIdx.x * blockDim.x + threadIdx.x;
+  if (col >= n_cols) return;
+  double a = 0.0;
+  for (int32_t ch = 0; ch < n_chunks; ++ch) a += part[(size_t)ch * n_cols + col];
+  out[col] = a;
+}
+
 // SNP-minor copies for dense pileups: gT[r][s] = g[s][r] (r = k*3+l, float32 as stored) and g0T[l][s] = gp0s[s][l].
 __global__ void k_transpose_geno(const float* __restrict__ g, const double* __restrict__ gp0, int32_t S, int32_t V,
                                  float* __restrict__ gT, double* __restrict__ g0T) {
@@ -6364,6 +6551,20 @@ struct dmx_engine {
   int32_t ref_S = 0; bool have_refined = false;
   hipEvent_t rev[4] = {};
   dmx_refine_info ref_info{};
+  // genotype-free clustering (dmx_engine_cluster_*): the SNP-major stage cache (a snapshot: staging a pileup again does not touch it),
+  // the last E-step's weights and sums, the last M-step's results; two gp' buffers, as for the refinement
+  int64_t* d_coff = nullptr; size_t coff_cap = 0;
+  int32_t* d_ccell = nullptr; size_t ccell_cap = 0;
+  double* d_clgl = nullptr; size_t clgl_cap = 0;
+  uint32_t* d_ccnt = nullptr; size_t ccnt_cap = 0;
+  int64_t cl_P = 0; int32_t cl_B = 0, cl_S = 0; bool have_cstage = false;
+  double* d_cw = nullptr; size_t cw_cap = 0; double* d_cwh = nullptr; size_t cwh_cap = 0; bool have_cw = false; int32_t cw_C = 0;
+  double* d_clse = nullptr; size_t clse_cap = 0; double* d_cpart = nullptr; size_t cpart_cap = 0; double* d_cpi = nullptr; size_t cpi_cap = 0;
+  uint8_t* d_cmask = nullptr; size_t cmask_cap = 0;
+  double* d_cll = nullptr; size_t cll_cap = 0; double* d_cW = nullptr; size_t cW_cap = 0; float* d_cq = nullptr; size_t cq_cap = 0;
+  float* d_cgp[2] = {nullptr, nullptr}; size_t cgp_cap[2] = {0, 0}; int cgp_cur = -1; int32_t cm_S = 0, cm_C = 0; bool have_cm = false;
+  hipEvent_t cev[2] = {};
+  dmx_cluster_info cl_info{};
 };
 
 namespace {
@@ -6505,6 +6706,11 @@ extern "C" int dmx_engine_destroy(dmx_engine* e) {
   for (void* p : {(void*)e->d_rblk, (void*)e->d_rplan, e->d_rpart, (void*)e->d_rprior, (void*)e->d_rll, (void*)e->d_rcnt, (void*)e->d_rgp[0], (void*)e->d_rgp[1]})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->rev) if (ev) (void)hipEventDestroy(ev);
+  for (void* p : {(void*)e->d_coff, (void*)e->d_ccell, (void*)e->d_clgl, (void*)e->d_ccnt, (void*)e->d_cw, (void*)e->d_cwh, (void*)e->d_clse,
+                  (void*)e->d_cpart, (void*)e->d_cpi, (void*)e->d_cmask, (void*)e->d_cll, (void*)e->d_cW, (void*)e->d_cq, (void*)e->d_cgp[0],
+                  (void*)e->d_cgp[1]})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t& ev : e->cev) if (ev) (void)hipEventDestroy(ev);
   for (int i = 0; i < 2; ++i) { if (e->h_stage[i]) (void)hipHostFree(e->h_stage[i]); if (e->ev_stage[i]) (void)hipEventDestroy(e->ev_stage[i]); }
   for (hipEvent_t& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& r : e->ring_s) for (hipEvent_t& ev : r) if (ev) (void)hipEventDestroy(ev);
@@ -8034,6 +8240,246 @@ extern "C" int dmx_engine_refine_info(dmx_engine* e, dmx_refine_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_refine_info: null argument");
   if (!e->have_refined) return set_error(DMX_ERR_STATE, "dmx_engine_refine_info: no refinement on the staged pileup (dmx_engine_refine_genotypes first)");
   *out = e->ref_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Genotype-free clustering: the stage cache, the M-step and the E-step of the EM that demuxlet_amd/cluster.py
+// drives; K1 (dmx_engine_run_singlet) is the E-step's likelihood.
+extern "C" int dmx_engine_cluster_stage(dmx_engine* e) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_stage: null engine");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_stage: no pileup staged (dmx_engine_set_pileup first)");
+  const int32_t B = e->pv.B, S = e->pv.S;
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->cev[0]) for (hipEvent_t& ev : e->cev) HIP_TRY(hipEventCreate(&ev));
+  int64_t po[2] = {0, 0};
+  if (B > 0) {
+    HIP_TRY(hipMemcpyAsync(&po[0], e->pv.cell_pair_off, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(&po[1], e->pv.cell_pair_off + B, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
+  const int64_t p_base = po[0], P = po[1] - po[0];
+  const bool dense = e->pv.pair_snp == nullptr;
+  if (!dense && P >= ((int64_t)1 << 31))
+    return set_error(DMX_ERR_ARG, "dmx_engine_cluster_stage: %lld pairs; the sparse stage places pairs by 32-bit slots (below 2^31)", (long long)P);
+  // the cache (32 bytes per pair) and, for a sparse layout, the placement's scratch: the slab table, the group counts M, the per-SNP
+  // totals and the slot of every pair.  Groups of 64 barcodes, or more when M would pass 1 GiB.
+  const int32_t nblk = (int32_t)(((int64_t)S + kClSlab - 1) >> kClSlabShift);
+  int32_t gsz = 64;
+  while ((double)((B + gsz - 1) / gsz) * S * sizeof(int32_t) > (double)(1u << 30)) gsz *= 2;
+  const int32_t ng = (B + gsz - 1) / gsz;
+  if (!dense && P > 0 && ng > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_stage: %d cells exceed this build's limit", B);
+  const size_t cache_b = sizeof(int64_t) * ((size_t)S + 1) + (size_t)P * (sizeof(int32_t) + 3 * sizeof(double) + sizeof(uint32_t));
+  const size_t scratch_b = (!dense && P > 0) ? 16 * (size_t)B * ((size_t)nblk + 1) + sizeof(int32_t) * ((size_t)ng * S + S + (size_t)P) : 0;
+  for (void** p : {(void**)&e->d_coff, (void**)&e->d_ccell, (void**)&e->d_clgl, (void**)&e->d_ccnt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+  e->coff_cap = e->ccell_cap = e->clgl_cap = e->ccnt_cap = 0;
+  e->have_cstage = false;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if ((double)(cache_b + scratch_b) > 0.9 * (double)free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_cluster_stage: the cache of %lld pairs needs %.2f GB (+%.2f GB scratch), %.2f GB of device memory are free",
+                     (long long)P, cache_b / 1e9, scratch_b / 1e9, free_b / 1e9);
+  if (int rc = ensure_dev((void**)&e->d_coff, &e->coff_cap, sizeof(int64_t) * ((size_t)S + 1))) return rc;
+  if (int rc = ensure_dev((void**)&e->d_ccell, &e->ccell_cap, sizeof(int32_t) * (size_t)P)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_clgl, &e->clgl_cap, 3 * sizeof(double) * (size_t)P)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_ccnt, &e->ccnt_cap, sizeof(uint32_t) * (size_t)P)) return rc;
+  int32_t* d_deep = nullptr;
+  HIP_TRY(hipMalloc((void**)&d_deep, sizeof(int32_t)));
+  HIP_TRY(hipMemsetAsync(d_deep, 0, sizeof(int32_t), e->stream));
+  HIP_TRY(hipEventRecord(e->cev[0], e->stream));
+  int64_t* d_sblk = nullptr; int32_t *d_M = nullptr, *d_tot = nullptr, *d_dst = nullptr;
+  int rc = DMX_OK;
+  std::vector<int64_t> off((size_t)S + 1, 0);
+  if (dense) {
+    const int64_t sp = B > 0 ? P / B : 0;                       // pairs per barcode (set_pileup checked that every barcode has them)
+    for (int32_t t = 0; t <= S; ++t) off[(size_t)t] = std::min<int64_t>(t, sp) * B;
+    HIP_TRY(hipMemcpyAsync(e->d_coff, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, e->stream));
+  } else if (P == 0) {
+    HIP_TRY(hipMemsetAsync(e->d_coff, 0, sizeof(int64_t) * ((size_t)S + 1), e->stream));
+  } else {
+    std::vector<int32_t> tot((size_t)S);
+    hipError_t he = hipMalloc((void**)&d_sblk, 16 * (size_t)B * ((size_t)nblk + 1));
+    if (he == hipSuccess) he = hipMalloc((void**)&d_M, sizeof(int32_t) * (size_t)ng * S);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_tot, sizeof(int32_t) * (size_t)S);
+    if (he == hipSuccess) he = hipMalloc((void**)&d_dst, sizeof(int32_t) * (size_t)P);
+    if (he == hipSuccess) {
+      hipLaunchKernelGGL(k_snp_blocks, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, kClSlabShift, nblk, d_sblk);
+      hipLaunchKernelGGL(k_cluster_slots<false>, dim3((unsigned)nblk, (unsigned)ng), dim3(64), 0, e->stream, e->pv, (const int64_t*)d_sblk, nblk, gsz, p_base,
+                         d_M, (const int64_t*)nullptr, (int32_t*)nullptr);
+      hipLaunchKernelGGL(k_cluster_colscan, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, e->stream, d_M, ng, S, d_tot);
+      he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(tot.data(), d_tot, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    if (he == hipSuccess) {
+      for (int32_t t = 0; t < S; ++t) off[(size_t)t + 1] = off[(size_t)t] + tot[(size_t)t];
+      if (off[(size_t)S] != P) rc = set_error(DMX_ERR_STATE, "dmx_engine_cluster_stage: %lld pairs placed of %lld", (long long)off[(size_t)S], (long long)P);
+    }
+    if (he == hipSuccess && rc == DMX_OK) he = hipMemcpyAsync(e->d_coff, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess && rc == DMX_OK) {
+      hipLaunchKernelGGL(k_cluster_slots<true>, dim3((unsigned)nblk, (unsigned)ng), dim3(64), 0, e->stream, e->pv, (const int64_t*)d_sblk, nblk, gsz, p_base,
+                         d_M, (const int64_t*)e->d_coff, d_dst);
+      he = hipGetLastError();
+    }
+    if (he != hipSuccess && rc == DMX_OK) rc = set_error(DMX_ERR_HIP, "dmx_engine_cluster_stage: placement: %s", hipGetErrorString(he));
+  }
+  if (rc == DMX_OK && B > 0) {
+    hipLaunchKernelGGL(k_cluster_lgl, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, (const double*)e->d_lut, p_base,
+                       (const int32_t*)d_dst, e->d_clgl, e->d_ccnt, e->d_ccell, d_deep);
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) rc = set_error(DMX_ERR_HIP, "dmx_engine_cluster_stage: k_cluster_lgl: %s", hipGetErrorString(he));
+  }
+  if (rc == DMX_OK) { const hipError_t he = hipEventRecord(e->cev[1], e->stream); if (he != hipSuccess) rc = set_error(DMX_ERR_HIP, "hipEventRecord: %s", hipGetErrorString(he)); }
+  const hipError_t hs = hipStreamSynchronize(e->stream);
+  if (rc == DMX_OK && hs != hipSuccess) rc = set_error(DMX_ERR_HIP, "dmx_engine_cluster_stage: %s", hipGetErrorString(hs));
+  int32_t deep = 0;
+  if (rc == DMX_OK) { const hipError_t he = hipMemcpy(&deep, d_deep, sizeof(int32_t), hipMemcpyDeviceToHost); if (he != hipSuccess) rc = set_error(DMX_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(he)); }
+  for (void* p : {(void*)d_sblk, (void*)d_M, (void*)d_tot, (void*)d_dst, (void*)d_deep}) if (p) (void)hipFree(p);
+  if (rc != DMX_OK) return rc;
+  if (deep) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_stage: a pair has more than 65 535 stored reads");
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->cev[0], e->cev[1]));
+  dmx_cluster_info& inf = e->cl_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.stage_ms = ms; inf.cache_bytes = (int64_t)cache_b; inf.n_pairs = P; inf.n_cells = B; inf.n_snps = S; inf.sorted = !dense && P > 0;
+  inf.scratch_bytes = (int64_t)scratch_b;
+  e->cl_P = P; e->cl_B = B; e->cl_S = S; e->have_cstage = true;
+  e->have_cm = false; e->have_cw = false;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_mstep(dmx_engine* e, const dmx_cluster_mstep_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: null argument");
+  if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_mstep: no stage cache (dmx_engine_cluster_stage first)");
+  const int32_t B = e->cl_B, S = e->cl_S, C = e->V;
+  if (rq->n_cells != B || rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: %d cells x %d SNPs, the stage cache has %d x %d", rq->n_cells, rq->n_snps, B, S);
+  if (rq->n_cols != C) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: n_cols %d, the engine has %d columns", rq->n_cols, C);
+  if (S > 0 && !rq->prior) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: missing prior");
+  if (!(rq->floor >= 0.0) || !std::isfinite(rq->floor)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: floor %g", rq->floor);
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t nw = (size_t)B * C, rows = (size_t)S * C;
+  const double* w = nullptr;
+  if (rq->weights_memory == DMX_CLUSTER_LAST_ESTEP) {
+    if (!e->have_cw || e->cw_C != C) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_mstep: no E-step weights of this cache (dmx_engine_cluster_estep first)");
+    w = e->d_cw;
+  } else if (rq->weights_memory == DMX_MEM_HOST || rq->weights_memory == DMX_MEM_DEVICE) {
+    if (nw > 0 && !rq->weights) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: missing weights");
+    if (rq->weights_memory == DMX_MEM_HOST) {
+      if (int rc = ensure_dev((void**)&e->d_cwh, &e->cwh_cap, sizeof(double) * nw)) return rc;
+      if (nw) HIP_TRY(hipMemcpyAsync(e->d_cwh, rq->weights, sizeof(double) * nw, hipMemcpyHostToDevice, e->stream));
+      w = e->d_cwh;
+    } else {
+      w = rq->weights;
+    }
+  } else {
+    return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: weights_memory %d", rq->weights_memory);
+  }
+  if (!e->cev[0]) for (hipEvent_t& ev : e->cev) HIP_TRY(hipEventCreate(&ev));
+  if (int rc = ensure_dev((void**)&e->d_cq, &e->cq_cap, sizeof(float) * 3 * (size_t)S)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cll, &e->cll_cap, sizeof(double) * 3 * rows)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cW, &e->cW_cap, sizeof(double) * rows)) return rc;
+  const int nxt = e->d_g == e->d_cgp[0] ? 1 : 0;                      // never the buffer the engine's genotype matrix is
+  if (int rc = ensure_dev((void**)&e->d_cgp[nxt], &e->cgp_cap[nxt], sizeof(float) * 3 * rows)) return rc;
+  if (S) HIP_TRY(hipMemcpyAsync(e->d_cq, rq->prior, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipEventRecord(e->cev[0], e->stream));
+  if (rows) {
+    hipLaunchKernelGGL(k_cluster_mstep, dim3((unsigned)((S + 3) / 4), (unsigned)((C + 63) / 64)), dim3(256), 0, e->stream, (const int64_t*)e->d_coff,
+                       (const int32_t*)e->d_ccell, (const double*)e->d_clgl, w, S, C, (const float*)e->d_cq, rq->floor, e->d_cll, e->d_cW, e->d_cgp[nxt]);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(e->cev[1], e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's prior / weights may go away after return
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->cev[0], e->cev[1]));
+  e->cl_info.mstep_ms = ms; e->cl_info.n_cols = C;
+  e->cgp_cur = nxt; e->cm_S = S; e->cm_C = C; e->have_cm = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_estep(dmx_engine* e, const dmx_cluster_estep_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep: null argument");
+  if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep: no stage cache (dmx_engine_cluster_stage first)");
+  if (!e->have_sing) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep: no singlet likelihoods (dmx_engine_run_singlet first)");
+  const int32_t B = e->pv.B, R = rq->n_restarts, K = rq->n_clusters, C = e->V;
+  if (B != e->cl_B) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep: the staged pileup has %d cells, the stage cache %d", B, e->cl_B);
+  if (R < 1 || K < 1 || (int64_t)R * K != C) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep: %d restarts x %d clusters, the engine has %d columns", R, K, C);
+  if (!rq->log_pi) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep: missing log_pi");
+  if (!(rq->temperature > 0.0) || !std::isfinite(rq->temperature)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep: temperature %g", rq->temperature);
+  const int32_t nch = (B + kEChunk - 1) / kEChunk;
+  if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep: %d cells exceed this build's limit", B);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->cev[0]) for (hipEvent_t& ev : e->cev) HIP_TRY(hipEventCreate(&ev));
+  const int32_t ncol = C + R;
+  if (int rc = ensure_dev((void**)&e->d_cw, &e->cw_cap, sizeof(double) * (size_t)B * C)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_clse, &e->clse_cap, sizeof(double) * (size_t)B * R)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cpart, &e->cpart_cap, sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cpi, &e->cpi_cap, sizeof(double) * (size_t)C)) return rc;
+  if (rq->mask) if (int rc = ensure_dev((void**)&e->d_cmask, &e->cmask_cap, (size_t)B)) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_cpi, rq->log_pi, sizeof(double) * (size_t)C, hipMemcpyHostToDevice, e->stream));
+  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
+  double* d_out = e->d_cpart + (size_t)nch * ncol;
+  HIP_TRY(hipEventRecord(e->cev[0], e->stream));
+  if (B > 0) {
+    hipLaunchKernelGGL(k_cluster_estep, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R, K,
+                       (const double*)e->d_cpi, 1.0 / rq->temperature, rq->mask ? (const uint8_t*)e->d_cmask : nullptr, e->d_cw, e->d_clse);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_cw,
+                       (const double*)e->d_clse, B, C, R, e->d_cpart);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->cev[1], e->stream));
+  std::vector<double> out((size_t)ncol);
+  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (rq->col_sum) std::memcpy(rq->col_sum, out.data(), sizeof(double) * (size_t)C);
+  if (rq->ll) std::memcpy(rq->ll, out.data() + C, sizeof(double) * (size_t)R);
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->cev[0], e->cev[1]));
+  e->cl_info.estep_ms = ms;
+  e->cw_C = C; e->have_cw = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_cluster(dmx_engine* e, double* ll, double* wsum, float* gp, double* weights) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_cluster: null engine");
+  if ((ll || wsum || gp) && !e->have_cm) return set_error(DMX_ERR_STATE, "dmx_engine_get_cluster: no M-step on this stage cache (dmx_engine_cluster_mstep first)");
+  if (weights && !e->have_cw) return set_error(DMX_ERR_STATE, "dmx_engine_get_cluster: no E-step on this stage cache (dmx_engine_cluster_estep first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t rows = (size_t)e->cm_S * e->cm_C, nw = (size_t)e->cl_B * e->cw_C;
+  if (ll && rows) HIP_TRY(hipMemcpy(ll, e->d_cll, sizeof(double) * 3 * rows, hipMemcpyDeviceToHost));
+  if (wsum && rows) HIP_TRY(hipMemcpy(wsum, e->d_cW, sizeof(double) * rows, hipMemcpyDeviceToHost));
+  if (gp && rows) HIP_TRY(hipMemcpy(gp, e->d_cgp[e->cgp_cur], sizeof(float) * 3 * rows, hipMemcpyDeviceToHost));
+  if (weights && nw) HIP_TRY(hipMemcpy(weights, e->d_cw, sizeof(double) * nw, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_cluster_stage(dmx_engine* e, int64_t* snp_off, int32_t* cell, double* lgl, uint32_t* ref_alt) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_cluster_stage: null engine");
+  if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_get_cluster_stage: no stage cache (dmx_engine_cluster_stage first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t P = (size_t)e->cl_P;
+  if (snp_off) HIP_TRY(hipMemcpy(snp_off, e->d_coff, sizeof(int64_t) * ((size_t)e->cl_S + 1), hipMemcpyDeviceToHost));
+  if (cell && P) HIP_TRY(hipMemcpy(cell, e->d_ccell, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
+  if (lgl && P) HIP_TRY(hipMemcpy(lgl, e->d_clgl, sizeof(double) * 3 * P, hipMemcpyDeviceToHost));
+  if (ref_alt && P) HIP_TRY(hipMemcpy(ref_alt, e->d_ccnt, sizeof(uint32_t) * P, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_device_ptr(dmx_engine* e, const float** out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_device_ptr: null argument");
+  if (!e->have_cm) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_device_ptr: no M-step on this stage cache (dmx_engine_cluster_mstep first)");
+  *out = e->d_cgp[e->cgp_cur];
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_info(dmx_engine* e, dmx_cluster_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_info: null argument");
+  if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_info: no stage cache (dmx_engine_cluster_stage first)");
+  *out = e->cl_info;
   return DMX_OK;
 }
 

@@ -299,6 +299,84 @@ class Engine:
         check(self._L.dmx_engine_refine_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.RefineInfo._fields_ if n != "reserved"}
 
+    def cluster_stage(self) -> None:
+        """dmx_engine_cluster_stage: the SNP-major cache of the staged pileup (per-pair log GL, REF / ALT reads, cell ids)."""
+        check(self._L.dmx_engine_cluster_stage(self._h))
+
+    def get_cluster_stage(self):
+        """The stage cache: (snp_off[S + 1] i64, cell[P] i32, lgl[P][3] f64, n_ref[P], n_alt[P] i64)."""
+        inf = self.cluster_info()
+        S, P = inf["n_snps"], inf["n_pairs"]
+        off = np.zeros(S + 1, dtype=np.int64)
+        cell = np.zeros(P, dtype=np.int32)
+        lgl = np.zeros((P, 3))
+        ra = np.zeros(P, dtype=np.uint32)
+        check(self._L.dmx_engine_get_cluster_stage(self._h, off.ctypes.data, cell.ctypes.data, lgl.ctypes.data, ra.ctypes.data))
+        return off, cell, lgl, (ra & 0xFFFF).astype(np.int64), (ra >> 16).astype(np.int64)
+
+    def cluster_mstep(self, weights, prior: np.ndarray, floor: float = 1e-3, fetch: bool = True):
+        """dmx_engine_cluster_mstep: weights is a host array [B][V] f64, a device pointer (int), or None = the last E-step's; prior [S][3].
+        Returns (LL[S][V][3] f64, W[S][V] f64, gp'[S][V][3] f32), or None with fetch=False (gp' stays on the device: cluster_device_ptr)."""
+        prior = np.ascontiguousarray(prior, dtype=np.float32)
+        if prior.ndim != 2 or prior.shape[1] != 3:
+            raise ValueError("prior must be [S][3]")
+        S = prior.shape[0]
+        w = None
+        if weights is None:
+            mem, ptr = capi.DMX_CLUSTER_LAST_ESTEP, None
+        elif isinstance(weights, int):
+            mem, ptr = capi.DMX_MEM_DEVICE, weights
+        else:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (self.B, self.V):
+                raise ValueError(f"weights must be [{self.B}][{self.V}]")
+            mem, ptr = capi.DMX_MEM_HOST, (w.ctypes.data if w.size else None)
+        rq = capi.ClusterMstepRequest(self.B, S, self.V, mem, ptr, prior.ctypes.data if prior.size else None, float(floor))
+        check(self._L.dmx_engine_cluster_mstep(self._h, C.byref(rq)))
+        if not fetch:
+            return None
+        return self.get_cluster(S)
+
+    def get_cluster(self, n_snps: int):
+        ll = np.zeros((n_snps, self.V, 3))
+        W = np.zeros((n_snps, self.V))
+        gp = np.zeros((n_snps, self.V, 3), dtype=np.float32)
+        check(self._L.dmx_engine_get_cluster(self._h, ll.ctypes.data, W.ctypes.data, gp.ctypes.data, None))
+        return ll, W, gp
+
+    def cluster_weights(self) -> np.ndarray:
+        """The last E-step's weights [B][V] f64."""
+        w = np.zeros((self.B, self.V))
+        check(self._L.dmx_engine_get_cluster(self._h, None, None, None, w.ctypes.data))
+        return w
+
+    def cluster_estep(self, n_restarts: int, n_clusters: int, log_pi, temperature: float = 1.0, mask=None):
+        """dmx_engine_cluster_estep on K1's llks of the last run_singlet: the weights stay on the device; returns (ll[R], col_sum[R * K])."""
+        lp = np.ascontiguousarray(log_pi, dtype=np.float64).reshape(-1)
+        if lp.size != n_restarts * n_clusters:
+            raise ValueError("log_pi must be [R][K]")
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        if m is not None and m.shape != (self.B,):
+            raise ValueError(f"mask must be [{self.B}]")
+        ll = np.zeros(n_restarts)
+        cs = np.zeros(n_restarts * n_clusters)
+        rq = capi.ClusterEstepRequest(int(n_restarts), int(n_clusters), lp.ctypes.data, float(temperature), m.ctypes.data if m is not None and m.size else None,
+                                      ll.ctypes.data, cs.ctypes.data)
+        check(self._L.dmx_engine_cluster_estep(self._h, C.byref(rq)))
+        return ll, cs
+
+    def cluster_device_ptr(self) -> int:
+        """Device pointer of the last M-step's gp' [S][V][3] f32 (for set_genotypes_device)."""
+        p = C.c_void_p()
+        check(self._L.dmx_engine_cluster_device_ptr(self._h, C.byref(p)))
+        return int(p.value)
+
+    def cluster_info(self) -> dict:
+        """HIP-event times (ms) of the last stage / M-step / E-step and the cache's size (dmx_engine_cluster_info)."""
+        r = capi.ClusterInfo()
+        check(self._L.dmx_engine_cluster_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.ClusterInfo._fields_ if n != "reserved"}
+
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()
         check(self._L.dmx_engine_device_view(self._h, C.byref(v)))

@@ -29,7 +29,7 @@ extern "C" {
                                argument of the new entry point.  Additions only otherwise: callers of ABI <= 5 run unchanged.
                                8: dmx_engine_format_pair / dmx_pair_text_* (`.pair` rows formatted on the device); later, still ABI 8:
                                dmx_engine_refine_genotypes / _get_refined / _refined_device_ptr / _refine_info (genotype refinement from
-                               called singlets).  Additions only. */
+                               called singlets); dmx_engine_cluster_* (genotype-free clustering).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -296,6 +296,77 @@ int dmx_engine_get_refined(dmx_engine*, double* llk, int32_t* n_cell, int32_t* n
  * destroyed; a later refinement writes its gp' to the OTHER of two buffers when this one is the engine's genotype matrix, else may reuse it. */
 int dmx_engine_refined_device_ptr(dmx_engine*, const float** out);
 int dmx_engine_refine_info(dmx_engine*, dmx_refine_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Genotype-free clustering (no counterpart in the reference): the pieces of an EM over C = V columns of cluster
+ * genotypes, driven by demuxlet_amd/cluster.py.  The E-step's likelihoods are K1's llks (dmx_engine_run_singlet with the columns as the
+ * genotype matrix); these calls add the rest.  Each runs on the engine's stream, synchronises it before returning (host inputs may be
+ * freed then) and leaves every other result of the engine as it was.
+ *
+ * dmx_engine_cluster_stage: a cache of the staged pileup in SNP-major order, ascending cell id inside a SNP — per pair (slot j) the cell
+ *   id, lgl[j][g] = log GL[g] (the refinement's per-pair vector, section 12, and its log) and the stored REF / ALT reads; snp_off[S + 1]
+ *   gives each SNP's slots.  Dense layouts place pair t of cell b at slot t * B + b; sparse ones at snp_off[s] + the number of
+ *   barcodes of lower id with a pair at s, counted per group of barcodes and SNP slab in LDS (a stable counting sort keyed by SNP; no
+ *   atomics decide a slot).  About 32 bytes per pair: DMX_ERR_NOMEM, and no cache, when that and the placement's scratch do not fit
+ *   the free device memory; DMX_ERR_ARG for a sparse pileup of 2^31 pairs or more, or a pair of more than 65 535 stored reads.  The cache is a snapshot: staging a pileup again leaves it alone (the E-step and the M-step check that
+ *   the barcode and SNP counts agree); the next dmx_engine_cluster_stage replaces it.
+ *
+ * dmx_engine_cluster_mstep: for weights w[B][C] (float64) and a per-SNP prior q[S][3] (float32, host), for every SNP i and column c:
+ *   LL[i][c][g] = sum over the slots of SNP i of w[b][c] * lgl[g],  W[i][c] = sum of w[b][c],
+ *   gp'[i][c][g] = (q[i][g] + floor) exp(LL[g] - max LL) / sum over g of the same, in float64, rounded to float32; a row with W = 0 is
+ *   q's row, bit for bit.  Sum order: the slots of a SNP in ascending cell id, one after the other, as acc = fma(w, lgl, acc) from 0
+ *   (W: acc += w); no floating-point atomics, so the bits depend neither on the launch geometry nor on what ran before.  gp' goes to
+ *   the OTHER of two buffers when the current one is the engine's genotype matrix (dmx_engine_set_genotypes(..., DMX_MEM_DEVICE) with
+ *   dmx_engine_cluster_device_ptr), so an M-step never overwrites the matrix K1 reads.
+ *
+ * dmx_engine_cluster_estep: from K1's llks[B][C] of the last run_singlet, C = R * K columns grouped as R restarts x K clusters, per
+ *   barcode b and restart r:  a_k = (llks[b][rK + k] + log_pi[r][k]) / T,  w[b][rK + k] = exp(a_k - max a) / sum over k;  a barcode
+ *   with mask[b] = 0 gets w = 0.  ll[r] = sum over the barcodes in the mask of logsumexp_k(llks[b][rK + k] + log_pi[r][k]), col_sum[c]
+ *   = sum over b of w[b][c].  Both sums add the barcodes in chunks of 256 in barcode order, then the chunk sums in ascending order
+ *   (no atomics).  The weights stay on the device for the next M-step (DMX_CLUSTER_LAST_ESTEP). */
+enum { DMX_CLUSTER_LAST_ESTEP = 2 };   /* dmx_cluster_mstep_request.weights_memory: the weights of the last dmx_engine_cluster_estep */
+typedef struct {
+  int32_t n_cells;             /* = the cache's barcodes */
+  int32_t n_snps;              /* = the cache's SNPs = the genotype matrix's n_snps */
+  int32_t n_cols;              /* C = the engine's V */
+  int32_t weights_memory;      /* DMX_MEM_HOST, DMX_MEM_DEVICE or DMX_CLUSTER_LAST_ESTEP (weights ignored) */
+  const double* weights;       /* [n_cells][n_cols] float64 */
+  const float* prior;          /* [n_snps][3] float32, HOST */
+  double  floor;               /* >= 0; 1e-3 is the usual value */
+  int32_t reserved[4];         /* 0 */
+} dmx_cluster_mstep_request;
+typedef struct {
+  int32_t n_restarts, n_clusters;   /* R, K: R * K = the engine's V */
+  const double* log_pi;        /* [R][K] HOST */
+  double  temperature;         /* T > 0; 1 is plain EM */
+  const uint8_t* mask;         /* [B] HOST, or NULL = every barcode */
+  double* ll;                  /* [R] HOST out (may be NULL) */
+  double* col_sum;             /* [R * K] HOST out (may be NULL) */
+  int32_t reserved[4];         /* 0 */
+} dmx_cluster_estep_request;
+typedef struct {
+  double  stage_ms;            /* HIP-event times of the last stage (sort + k_cluster_lgl), */
+  double  mstep_ms;            /* ... of the last M-step (k_cluster_mstep), */
+  double  estep_ms;            /* ... and of the last E-step (k_cluster_estep + the ordered sums) */
+  int64_t cache_bytes;         /* device bytes of the stage cache */
+  int64_t scratch_bytes;       /* device bytes the stage borrowed while it ran (sparse layouts: the placement) */
+  int64_t n_pairs;             /* slots of the cache */
+  int32_t n_cells, n_snps, sorted, n_cols;   /* sorted: 1 = a sparse layout went through the placement; n_cols: the last M-step's */
+  int32_t reserved[2];
+} dmx_cluster_info;
+int dmx_engine_cluster_stage(dmx_engine*);
+int dmx_engine_cluster_mstep(dmx_engine*, const dmx_cluster_mstep_request*);
+int dmx_engine_cluster_estep(dmx_engine*, const dmx_cluster_estep_request*);
+/* Device->host copies of the last M-step (any pointer may be NULL): ll[S][C][3] f64, wsum[S][C] f64, gp[S][C][3] f32; and of the last
+ * E-step's weights[B][C] f64 (DMX_ERR_STATE when that part has not run). */
+int dmx_engine_get_cluster(dmx_engine*, double* ll, double* wsum, float* gp, double* weights);
+/* Device->host copy of the stage cache (any pointer may be NULL): snp_off[S + 1] i64, cell[P] i32, lgl[P][3] f64, ref_alt[P] u32
+ * (REF reads | ALT reads << 16). */
+int dmx_engine_get_cluster_stage(dmx_engine*, int64_t* snp_off, int32_t* cell, double* lgl, uint32_t* ref_alt);
+/* The device pointer of the last M-step's gp' [S][C][3] (for dmx_engine_set_genotypes(..., DMX_MEM_DEVICE)); valid until the engine is
+ * destroyed. */
+int dmx_engine_cluster_device_ptr(dmx_engine*, const float** out);
+int dmx_engine_cluster_info(dmx_engine*, dmx_cluster_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * a6,a10..a14  finaliser and writers — replaces cmd_cram_demuxlet.cpp:465-527 (.single), :713-875 (.sing2/.pair/.best).
