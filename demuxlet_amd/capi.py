@@ -37,6 +37,7 @@ SYMBOLS = [
     "dmx_engine_refine_genotypes", "dmx_engine_get_refined", "dmx_engine_refined_device_ptr", "dmx_engine_refine_info",
     "dmx_engine_cluster_stage", "dmx_engine_cluster_mstep", "dmx_engine_cluster_estep", "dmx_engine_get_cluster", "dmx_engine_get_cluster_stage",
     "dmx_engine_cluster_device_ptr", "dmx_engine_cluster_info",
+    "dmx_engine_ambient", "dmx_engine_get_ambient", "dmx_engine_ambient_info",
 ]
 
 
@@ -85,6 +86,16 @@ class ClusterInfo(C.Structure):           # dmx_cluster_info
     _fields_ = [("stage_ms", C.c_double), ("mstep_ms", C.c_double), ("estep_ms", C.c_double), ("cache_bytes", C.c_int64), ("scratch_bytes", C.c_int64),
                 ("n_pairs", C.c_int64), ("n_cells", C.c_int32), ("n_snps", C.c_int32), ("sorted", C.c_int32), ("n_cols", C.c_int32),
                 ("reserved", C.c_int32 * 2)]
+
+
+class AmbientRequest(C.Structure):       # dmx_ambient_request
+    _fields_ = [("n_cells", C.c_int32), ("assign_memory", C.c_int32), ("assign", C.c_void_p), ("n_snps", C.c_int32), ("n_grid", C.c_int32),
+                ("ambient", C.c_void_p), ("grid", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class AmbientInfo(C.Structure):          # dmx_ambient_info
+    _fields_ = [("kernel_ms", C.c_double), ("profile_bytes", C.c_int64), ("n_cells", C.c_int32), ("n_grid", C.c_int32), ("n_assigned", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
 
 
 class DmxError(RuntimeError):
@@ -217,6 +228,7 @@ def load() -> C.CDLL:
         "dmx_engine_cluster_stage": [vp], "dmx_engine_cluster_mstep": [vp, vp], "dmx_engine_cluster_estep": [vp, vp],
         "dmx_engine_get_cluster": [vp, vp, vp, vp, vp], "dmx_engine_get_cluster_stage": [vp, vp, vp, vp, vp], "dmx_engine_cluster_device_ptr": [vp, vp],
         "dmx_engine_cluster_info": [vp, vp],
+        "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -2242,6 +2242,114 @@ __global__ __launch_bounds__(256) void k_cluster_efold(const double* __restrict_
   out[col] = a;
 }
 
+// ---- ambient contamination profile (dmx_engine_ambient) ---------------------------------------------------------
+// For a barcode b assigned to sample v and a grid point rho: LL_b(rho) = sum over b's pairs, in stored (ascending SNP) order, of
+// log(gp[i][v][0] f_0 + gp[i][v][1] f_1 + gp[i][v][2] f_2), f_g = product over the pair's stored reads of pR (1 - p_g) + pA p_g,
+// p_g = (1 - rho) g / 2 + rho a_i.  One wavefront per (barcode, block of 64 grid points), one lane per grid point: every lane walks
+// the same pairs and sums its own LL serially, so nothing crosses lanes and the bits depend only on the lane's rho.  The wavefront
+// stages 64 pair headers at a time (read count, read offset by a DPP scan, first four read bytes, a_i, the gp row as float64) in
+// LDS, then steps through them with broadcast reads.  f_g is rescaled by an exact power of two, 2^-e with e the exponent of
+// max f_g over the genotypes with gp != 0, whenever that maximum falls below 2^-300 (checked every 8 reads; one read scales it by
+// >= 2^-44 with PhredHelper's tables); the exponents add up in E and LL gets log(L) + E ln 2.  A term that falls out of range
+// below that maximum is smaller than 2^-925 of L.
+constexpr int kAmbWaves = 4;                     // wavefronts per workgroup: four (barcode, grid block) units share the LDS tables
+constexpr double kAmbRescaleBelow = 0x1p-300;
+struct AmbPair { double a, g0, g1, g2; int64_t off; uint32_t n, rd4; };    // n = 0: the pair does not contribute
+
+__global__ __launch_bounds__(64 * kAmbWaves) void k_ambient(PileupView pv, int nrd_width, const double* __restrict__ tabs, const float* __restrict__ g,
+                                                          int32_t V, const int32_t* __restrict__ assign, const double* __restrict__ amb,
+                                                          const double* __restrict__ grid, int32_t Q, int32_t n_qblk, int64_t n_units,
+                                                          double* __restrict__ ll, int32_t* __restrict__ n_snp, int32_t* __restrict__ n_read) {
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_pra[256][2];               // by read byte (allele << 7 | bq): {pR, pA}
+  __shared__ AmbPair s_hdr[kAmbWaves][64];
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += 64 * kAmbWaves) s_log[i] = tabs[kLut + i];
+  for (int i = threadIdx.x; i < 256; i += 64 * kAmbWaves) {
+    const double mat = tabs[i & 127], e3 = tabs[128 + (i & 127)];
+    s_pra[i][0] = (i >> 7) ? e3 : mat;
+    s_pra[i][1] = (i >> 7) ? mat : e3;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t unit = (int64_t)blockIdx.x * kAmbWaves + wave;
+  if (unit >= n_units) return;
+  const int32_t cell = (int32_t)(unit / n_qblk), qb = (int32_t)(unit % n_qblk);
+  const int32_t q = qb * 64 + lane;
+  const int32_t v = assign[cell];
+  double acc = 0.0;
+  int32_t ns = 0, nr = 0;
+  if (v >= 0) {
+    AmbPair* hdr = s_hdr[wave];
+    const double rho = q < Q ? grid[q] : 0.0;    // lanes past Q run along and write nothing
+    const double om = 1.0 - rho, half = 0.5 * om;
+    const DmxLogPins lk = dmx_log_pins();
+    const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+    int64_t rd_base = pv.cell_read_off[cell];
+    for (int64_t p0 = p_beg; p0 < p_end; p0 += 64) {
+      const int64_t p = p0 + lane;
+      const bool in = p < p_end;
+      const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+      const uint32_t incl = seg_scan_incl<64>(n);
+      AmbPair h{};
+      h.off = rd_base + (int64_t)(incl - n);
+      rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      if (n > 0) {
+        const int32_t snp = pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg);
+        const float* gr = g + ((size_t)snp * V + v) * 3;
+        const float g0 = gr[0], g1 = gr[1], g2 = gr[2];
+        h.g0 = g0; h.g1 = g1; h.g2 = g2;
+        h.a = amb[snp];
+        h.rd4 = load_rd4(pv, h.off, n);
+        h.n = (g0 != 0.f || g1 != 0.f || g2 != 0.f) ? n : 0u;
+      }
+      hdr[lane] = h;
+      DMX_WAVE_LDS_ORDER();
+      const int cnt = (int)min<int64_t>(64, p_end - p0);
+      for (int j = 0; j < cnt; ++j) {
+        const uint32_t nj = (uint32_t)__builtin_amdgcn_readfirstlane((int)hdr[j].n);
+        if (nj == 0) continue;
+        const double ra = rho * hdr[j].a;
+        const double p_0 = ra, p_1 = half + ra, p_2 = om + ra;
+        const double q_0 = 1.0 - p_0, q_1 = 1.0 - p_1, q_2 = 1.0 - p_2;
+        const int64_t off = hdr[j].off;
+        uint32_t w = hdr[j].rd4;
+        double pR = s_pra[w & 0xFF][0], pA = s_pra[w & 0xFF][1];
+        double f0 = pR * q_0 + pA * p_0, f1 = pR * q_1 + pA * p_1, f2 = pR * q_2 + pA * p_2;
+        if (nj >= 8) {                               // a pair that may be rescaled: f_g of a zero gp entry is 0, so that the scale follows the
+          if (hdr[j].g0 == 0.0) f0 = 0.0;            // entries that count and nothing ignored can grow past them (0 x inf)
+          if (hdr[j].g1 == 0.0) f1 = 0.0;
+          if (hdr[j].g2 == 0.0) f2 = 0.0;
+        }
+        int32_t E = 0;
+        for (uint32_t r = 1; r < nj; ++r) {
+          if ((r & 3) == 0) w = load_rd4(pv, off + r, nj - r);
+          const uint32_t byte = (w >> (8 * (r & 3))) & 0xFF;
+          pR = s_pra[byte][0]; pA = s_pra[byte][1];
+          f0 *= pR * q_0 + pA * p_0; f1 *= pR * q_1 + pA * p_1; f2 *= pR * q_2 + pA * p_2;
+          if ((r & 7) == 7) {
+            const double mx = fmax(f0, fmax(f1, f2));
+            if (mx < kAmbRescaleBelow && mx > 0.0) {
+              int e;
+              (void)frexp(mx, &e);
+              f0 = ldexp(f0, -e); f1 = ldexp(f1, -e); f2 = ldexp(f2, -e);
+              E += e;
+            }
+          }
+        }
+        const double L = hdr[j].g0 * f0 + hdr[j].g1 * f1 + hdr[j].g2 * f2;
+        double lg = dmx_log_is_special(L) ? log(L) : dmx_log_fast_pinned(L, s_log, lk);
+        if (E != 0) lg = __builtin_fma((double)E, DMX_LOG_LN2HI, __builtin_fma((double)E, DMX_LOG_LN2LO, lg));
+        acc += lg;
+        ns += 1; nr += (int32_t)nj;
+      }
+      DMX_WAVE_LDS_ORDER();
+    }
+  }
+  if (q < Q) ll[(size_t)cell * Q + q] = acc;
+  if (qb == 0 && lane == 0) { n_snp[cell] = ns; n_read[cell] = nr; }
+}
+
 // SNP-minor copies for dense pileups: gT[r][s] = g[s][r] (r = k*3+l, float32 as stored) and g0T[l][s] = gp0s[s][l].
 __global__ void k_transpose_geno(const float* __restrict__ g, const double* __restrict__ gp0, int32_t S, int32_t V,
                                  float* __restrict__ gT, double* __restrict__ g0T) {
@@ -6565,6 +6673,15 @@ struct dmx_engine {
   float* d_cgp[2] = {nullptr, nullptr}; size_t cgp_cap[2] = {0, 0}; int cgp_cur = -1; int32_t cm_S = 0, cm_C = 0; bool have_cm = false;
   hipEvent_t cev[2] = {};
   dmx_cluster_info cl_info{};
+  // ambient contamination profile (dmx_engine_ambient): its own copies of the inputs and the B x Q results
+  int32_t* d_aasg = nullptr; size_t aasg_cap = 0;
+  double* d_aamb = nullptr; size_t aamb_cap = 0;
+  double* d_agrid = nullptr; size_t agrid_cap = 0;
+  double* d_all = nullptr; size_t all_cap = 0;
+  int32_t* d_acnt = nullptr; size_t acnt_cap = 0;
+  int32_t amb_B = 0, amb_Q = 0; bool have_amb = false;
+  hipEvent_t aev[2] = {};
+  dmx_ambient_info amb_info{};
 };
 
 namespace {
@@ -6711,6 +6828,9 @@ extern "C" int dmx_engine_destroy(dmx_engine* e) {
                   (void*)e->d_cgp[1]})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->cev) if (ev) (void)hipEventDestroy(ev);
+  for (void* p : {(void*)e->d_aasg, (void*)e->d_aamb, (void*)e->d_agrid, (void*)e->d_all, (void*)e->d_acnt})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t& ev : e->aev) if (ev) (void)hipEventDestroy(ev);
   for (int i = 0; i < 2; ++i) { if (e->h_stage[i]) (void)hipHostFree(e->h_stage[i]); if (e->ev_stage[i]) (void)hipEventDestroy(e->ev_stage[i]); }
   for (hipEvent_t& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& r : e->ring_s) for (hipEvent_t& ev : r) if (ev) (void)hipEventDestroy(ev);
@@ -7168,7 +7288,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
     }
   }
   e->have_sing = e->have_grid = false;
-  e->rblk_valid = false; e->have_refined = false;
+  e->rblk_valid = false; e->have_refined = false; e->have_amb = false;
   e->have_pileup = true;
   e->k1_fn = e->k2_fn = e->k3b_fn = nullptr; e->k1_placement = 0;      // nothing has run on this pileup yet
   return DMX_OK;
@@ -8480,6 +8600,98 @@ extern "C" int dmx_engine_cluster_info(dmx_engine* e, dmx_cluster_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_info: null argument");
   if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_info: no stage cache (dmx_engine_cluster_stage first)");
   *out = e->cl_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Ambient contamination profile: the arguments are checked on the host (assign, a and the grid are small), then
+// one launch of k_ambient over B x ceil(Q / 64) wavefronts.
+extern "C" int dmx_engine_ambient(dmx_engine* e, const dmx_ambient_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_ambient: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_ambient: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S, Q = rq->n_grid;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_ambient: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (Q < 1 || Q > 256) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: n_grid %d is not in [1, 256]", Q);
+  if (!rq->grid || (B > 0 && !rq->assign) || (S > 0 && !rq->ambient)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: missing assign / ambient / grid");
+  if (rq->assign_memory != DMX_MEM_HOST && rq->assign_memory != DMX_MEM_DEVICE)
+    return set_error(DMX_ERR_ARG, "dmx_engine_ambient: assign_memory %d", rq->assign_memory);
+  for (int32_t q = 0; q < Q; ++q) {
+    const double r = rq->grid[q];
+    if (!(r >= 0.0 && r <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: grid[%d] = %g is not in [0, 1]", q, r);
+    if (q > 0 && !(r > rq->grid[q - 1])) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: the grid is not strictly ascending at %d", q);
+  }
+  for (int32_t i = 0; i < S; ++i)
+    if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->aev[0]) for (hipEvent_t& ev : e->aev) HIP_TRY(hipEventCreate(&ev));
+  std::vector<int32_t> a((size_t)B);
+  if (B > 0) {
+    if (rq->assign_memory == DMX_MEM_DEVICE) {
+      HIP_TRY(hipMemcpyAsync(a.data(), rq->assign, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+      std::memcpy(a.data(), rq->assign, sizeof(int32_t) * (size_t)B);
+    }
+  }
+  int32_t n_asg = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    if (a[(size_t)b] < -1 || a[(size_t)b] >= V) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: assign[%d] = %d is not in [-1, %d)", b, a[(size_t)b], V);
+    n_asg += a[(size_t)b] >= 0;
+  }
+  const size_t prof = sizeof(double) * (size_t)B * (size_t)Q;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (prof > e->all_cap && prof + prof / 16 > free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_ambient: the %d x %d profile needs %zu bytes, %zu are free", B, Q, prof, free_b);
+  if (int rc = ensure_dev((void**)&e->d_all, &e->all_cap, prof)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_acnt, &e->acnt_cap, sizeof(int32_t) * 2 * (size_t)B)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_aasg, &e->aasg_cap, sizeof(int32_t) * (size_t)B)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_aamb, &e->aamb_cap, sizeof(double) * (size_t)S)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_agrid, &e->agrid_cap, sizeof(double) * (size_t)Q)) return rc;
+  if (B > 0) HIP_TRY(hipMemcpyAsync(e->d_aasg, a.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, e->stream));
+  if (S > 0) HIP_TRY(hipMemcpyAsync(e->d_aamb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_agrid, rq->grid, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, e->stream));
+  const int32_t n_qblk = (Q + 63) / 64;
+  const int64_t n_units = (int64_t)B * n_qblk;
+  HIP_TRY(hipEventRecord(e->aev[0], e->stream));
+  if (n_units > 0) {
+    hipLaunchKernelGGL(k_ambient, dim3((unsigned)((n_units + kAmbWaves - 1) / kAmbWaves)), dim3(64 * kAmbWaves), 0, e->stream, e->pv, e->nrd_width,
+                       (const double*)e->d_lut, e->d_g, V, (const int32_t*)e->d_aasg, (const double*)e->d_aamb, (const double*)e->d_agrid, Q, n_qblk,
+                       n_units, e->d_all, e->d_acnt, e->d_acnt + B);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(e->aev[1], e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->aev[0], e->aev[1]));
+  dmx_ambient_info& inf = e->amb_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.kernel_ms = ms; inf.profile_bytes = (int64_t)prof; inf.n_cells = B; inf.n_grid = Q; inf.n_assigned = n_asg;
+  e->amb_B = B; e->amb_Q = Q; e->have_amb = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_ambient(dmx_engine* e, double* ll, int32_t* n_snp, int32_t* n_read) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_ambient: null engine");
+  if (!e->have_amb) return set_error(DMX_ERR_STATE, "dmx_engine_get_ambient: no profile on the staged pileup (dmx_engine_ambient first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t B = (size_t)e->amb_B;
+  if (!B) return DMX_OK;
+  if (ll) HIP_TRY(hipMemcpy(ll, e->d_all, sizeof(double) * B * (size_t)e->amb_Q, hipMemcpyDeviceToHost));
+  if (n_snp) HIP_TRY(hipMemcpy(n_snp, e->d_acnt, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+  if (n_read) HIP_TRY(hipMemcpy(n_read, e->d_acnt + B, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_ambient_info(dmx_engine* e, dmx_ambient_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_info: null argument");
+  if (!e->have_amb) return set_error(DMX_ERR_STATE, "dmx_engine_ambient_info: no profile on the staged pileup (dmx_engine_ambient first)");
+  *out = e->amb_info;
   return DMX_OK;
 }
 

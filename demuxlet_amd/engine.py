@@ -377,6 +377,36 @@ class Engine:
         check(self._L.dmx_engine_cluster_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.ClusterInfo._fields_ if n != "reserved"}
 
+    def ambient_profile(self, assign, ambient, grid):
+        """dmx_engine_ambient over the staged pileup: LL[b][q] of each barcode assigned to sample assign[b] (-1 = not used) with a fraction
+        grid[q] of its reads from a soup of ALT frequency ambient[i].  `assign` is a host array, or a device pointer (int) to B int32.
+        Returns (ll[B][Q] f64, n_snp[B] i32, n_read[B] i32)."""
+        amb = np.ascontiguousarray(ambient, dtype=np.float64)
+        gr = np.ascontiguousarray(grid, dtype=np.float64)
+        if amb.ndim != 1 or gr.ndim != 1:
+            raise ValueError("ambient and grid must be 1-D")
+        if isinstance(assign, int):
+            a, mem, ptr = None, capi.DMX_MEM_DEVICE, assign
+        else:
+            a = np.ascontiguousarray(assign, dtype=np.int32)
+            if a.shape != (self.B,):
+                raise ValueError(f"assign must be [{self.B}]")
+            mem, ptr = capi.DMX_MEM_HOST, (a.ctypes.data if a.size else None)
+        Q = len(gr)
+        rq = capi.AmbientRequest(self.B, mem, ptr, len(amb), Q, amb.ctypes.data if amb.size else None, gr.ctypes.data if gr.size else None)
+        check(self._L.dmx_engine_ambient(self._h, C.byref(rq)))
+        ll = np.zeros((self.B, Q))
+        n_snp = np.zeros(self.B, dtype=np.int32)
+        n_read = np.zeros(self.B, dtype=np.int32)
+        check(self._L.dmx_engine_get_ambient(self._h, ll.ctypes.data, n_snp.ctypes.data, n_read.ctypes.data))
+        return ll, n_snp, n_read
+
+    def ambient_info(self) -> dict:
+        """HIP-event time (ms) of the last ambient profile and the profile's size (dmx_engine_ambient_info)."""
+        r = capi.AmbientInfo()
+        check(self._L.dmx_engine_ambient_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.AmbientInfo._fields_ if n != "reserved"}
+
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()
         check(self._L.dmx_engine_device_view(self._h, C.byref(v)))

@@ -127,6 +127,58 @@ def make_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: fl
                        totl, totl.copy(), uniq, truth)
 
 
+def make_ambient_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: float, rbar: float, rho,
+                        ambient: Optional[np.ndarray] = None, dense_layout: bool = False, chunk_cells: int = 256
+                        ) -> Tuple[SynthPileup, np.ndarray, np.ndarray]:
+    """Singlet barcodes (cell c is sample c mod V) with ambient contamination: each read comes from the soup with probability rho[c]
+    (ALT w.p. a_i) and from the cell otherwise (ALT w.p. its dosage / 2); then sequencing error as in make_pileup.  `rho` is a scalar or
+    [B]; `ambient` defaults to the donors' mean dosage / 2.  Returns (pileup, rho[B], a[S])."""
+    S, V, _ = alleles.shape
+    dosage = np.clip(alleles, 0, 1).sum(axis=2).astype(np.float64)      # [S][V]
+    a = dosage.mean(axis=1) / 2.0 if ambient is None else np.asarray(ambient, dtype=np.float64)
+    rho = np.broadcast_to(np.asarray(rho, dtype=np.float64), (B,)).copy()
+    err_of_bq = np.power(10.0, -np.arange(64) / 10.0)
+    cell_pair_off = np.zeros(B + 1, dtype=np.int64)
+    cell_read_off = np.zeros(B + 1, dtype=np.int64)
+    snp_chunks, nrd_chunks, rd_chunks = [], [], []
+    totl = np.zeros(B, dtype=np.int32)
+    truth = np.full((B, 2), -1, dtype=np.int32)
+    for c0 in range(0, B, chunk_cells):
+        c1 = min(B, c0 + chunk_cells)
+        nc = c1 - c0
+        s1 = (np.arange(c0, c1) % V).astype(np.int32)
+        truth[c0:c1, 0] = s1
+        cov = np.ones((nc, S), dtype=bool) if delta >= 1.0 else rng.random((nc, S)) < delta
+        cc, ss = np.nonzero(cov)
+        npairs = len(cc)
+        nreads = 1 + rng.poisson(max(rbar - 1.0, 0.0), size=npairs)
+        pair_of_read = np.repeat(np.arange(npairs), nreads)
+        rc, rs = cc[pair_of_read], ss[pair_of_read]
+        soup = rng.random(len(rc)) < rho[c0 + rc]
+        p_alt = np.where(soup, a[rs], dosage[rs, s1[rc]] / 2.0)
+        alt = rng.random(len(rc)) < p_alt
+        bq = rng.integers(13, 41, size=len(rc)).astype(np.uint8)
+        e = rng.random(len(rc)) < err_of_bq[bq]
+        u = rng.integers(0, 3, size=len(rc))
+        allele = np.where(e, np.where(u == 0, 1 - alt.astype(np.int32), 2), alt.astype(np.int32)).astype(np.uint8)
+        keep = allele != 2
+        cell_pair_off[c0 + 1:c1 + 1] = np.bincount(cc, minlength=nc)
+        cell_read_off[c0 + 1:c1 + 1] = np.bincount(rc[keep], minlength=nc)
+        totl[c0:c1] = np.bincount(rc, minlength=nc)
+        snp_chunks.append(ss.astype(np.int32))
+        nrd_chunks.append(np.bincount(pair_of_read[keep], minlength=npairs))
+        rd_chunks.append(((allele[keep] << 7) | bq[keep]).astype(np.uint8))
+    np.cumsum(cell_pair_off, out=cell_pair_off)
+    np.cumsum(cell_read_off, out=cell_read_off)
+    nrd = np.concatenate(nrd_chunks) if nrd_chunks else np.zeros(0, dtype=np.int64)
+    nrd = nrd.astype(np.uint8 if (len(nrd) == 0 or nrd.max() <= 255) else np.uint16)
+    pair_snp = np.concatenate(snp_chunks) if snp_chunks else np.zeros(0, dtype=np.int32)
+    reads = np.concatenate(rd_chunks) if rd_chunks else np.zeros(0, dtype=np.uint8)
+    use_dense = dense_layout and delta >= 1.0
+    sp = SynthPileup(B, S, cell_pair_off, cell_read_off, None if use_dense else pair_snp, nrd, reads, totl, totl.copy(), totl.copy(), truth)
+    return sp, rho, a
+
+
 def barcode_name(i: int) -> str:
     """Deterministic 16-mer barcode whose byte-wise sort order is NOT the id order (exercises the sorted-output rule)."""
     x = (i * 2654435761 + 12345) & 0xFFFFFFFF

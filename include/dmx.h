@@ -29,7 +29,8 @@ extern "C" {
                                argument of the new entry point.  Additions only otherwise: callers of ABI <= 5 run unchanged.
                                8: dmx_engine_format_pair / dmx_pair_text_* (`.pair` rows formatted on the device); later, still ABI 8:
                                dmx_engine_refine_genotypes / _get_refined / _refined_device_ptr / _refine_info (genotype refinement from
-                               called singlets); dmx_engine_cluster_* (genotype-free clustering).  Additions only. */
+                               called singlets); dmx_engine_cluster_* (genotype-free clustering); dmx_engine_ambient / _get_ambient /
+                               _ambient_info (per-barcode ambient contamination profile).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -367,6 +368,46 @@ int dmx_engine_get_cluster_stage(dmx_engine*, int64_t* snp_off, int32_t* cell, d
  * destroyed. */
 int dmx_engine_cluster_device_ptr(dmx_engine*, const float** out);
 int dmx_engine_cluster_info(dmx_engine*, dmx_cluster_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Ambient contamination profile (no counterpart in the reference).  Soup is the average of many lysed cells: at
+ * SNP i its reads are ALT with a fixed frequency a_i.  For an assignment of barcodes to samples (assign[b] = 0..V-1, or -1 = not used),
+ * ambient ALT frequencies a[n_snps] and a grid of contamination fractions rho[q], q < Q, over the staged pileup, the phred tables and
+ * the engine's genotype matrix gp (float32), for every assigned barcode b (v = assign[b]) and every q:
+ *   p_g(rho) = (1 - rho) g / 2 + rho a_i  (g = 0, 1, 2);
+ *   f_g      = product over the pair's stored reads, in stored order, of pR (1 - p_g) + pA p_g, pR = allele 0 ? mat[bq] : err[bq] / 3,
+ *              pA = allele 1 ? mat[bq] : err[bq] / 3 (the reference's per-read doublet factor, cmd_cram_demuxlet.cpp:606-625, with the
+ *              second genotype replaced by the soup);
+ *   LL[b][q] = sum over b's pairs in ascending SNP order of log(gp[i][v][0] f_0 + gp[i][v][1] f_1 + gp[i][v][2] f_2).
+ * No per-read renormalisation and no 1e-6 floor: at rho = 0 this is the likelihood of the reads under the called genotype.  A pair with
+ * no stored read, or whose gp row is all zero, contributes nothing; n_snp[b] / n_read[b] count the pairs / reads that did.  f_g is kept
+ * in range by exact power-of-two rescaling, the exponent carried into the log; the log is dmx_log.  Each (b, q) is one serial sum with
+ * no floating-point atomics: the same inputs give the same bits whatever the grid's length or what ran before, and a grid split over
+ * two calls gives the same bits at the shared points.  Unassigned barcodes get zero rows.  The call runs on the engine's stream,
+ * synchronises it before returning (host inputs may be freed then) and leaves every other result of the engine as it was.
+ * DMX_ERR_ARG: Q outside [1, 256], a grid point outside [0, 1] or not strictly ascending, an a_i outside [0, 1], assign[b] outside
+ * [-1, V), n_cells / n_snps that do not match the staged pileup / the genotype matrix.  DMX_ERR_STATE: no pileup or no genotypes yet.
+ * DMX_ERR_NOMEM: the B x Q profile does not fit the free device memory. */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t assign_memory;       /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `assign` lives */
+  const int32_t* assign;       /* [n_cells] */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t n_grid;              /* Q, 1..256 */
+  const double* ambient;       /* [n_snps] float64 in [0, 1], HOST */
+  const double* grid;          /* [n_grid] float64, strictly ascending, in [0, 1], HOST */
+  int32_t reserved[4];         /* 0 */
+} dmx_ambient_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the last call's k_ambient */
+  int64_t profile_bytes;       /* device bytes of the B x Q profile */
+  int32_t n_cells, n_grid, n_assigned;
+  int32_t reserved[3];
+} dmx_ambient_info;
+int dmx_engine_ambient(dmx_engine*, const dmx_ambient_request*);
+/* Device->host copies of the last profile (any pointer may be NULL): ll[B][Q] f64, n_snp[B] / n_read[B] i32. */
+int dmx_engine_get_ambient(dmx_engine*, double* ll, int32_t* n_snp, int32_t* n_read);
+int dmx_engine_ambient_info(dmx_engine*, dmx_ambient_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * a6,a10..a14  finaliser and writers — replaces cmd_cram_demuxlet.cpp:465-527 (.single), :713-875 (.sing2/.pair/.best).
