@@ -37,6 +37,7 @@ SYMBOLS = [
     "dmx_engine_refine_genotypes", "dmx_engine_get_refined", "dmx_engine_refined_device_ptr", "dmx_engine_refine_info",
     "dmx_engine_cluster_stage", "dmx_engine_cluster_mstep", "dmx_engine_cluster_estep", "dmx_engine_get_cluster", "dmx_engine_get_cluster_stage",
     "dmx_engine_cluster_device_ptr", "dmx_engine_cluster_info",
+    "dmx_engine_cluster_doublet", "dmx_engine_get_cluster_doublet", "dmx_engine_cluster_estep_doublet", "dmx_engine_cluster_doublet_info",
     "dmx_engine_ambient", "dmx_engine_get_ambient", "dmx_engine_ambient_info",
 ]
 
@@ -86,6 +87,16 @@ class ClusterInfo(C.Structure):           # dmx_cluster_info
     _fields_ = [("stage_ms", C.c_double), ("mstep_ms", C.c_double), ("estep_ms", C.c_double), ("cache_bytes", C.c_int64), ("scratch_bytes", C.c_int64),
                 ("n_pairs", C.c_int64), ("n_cells", C.c_int32), ("n_snps", C.c_int32), ("sorted", C.c_int32), ("n_cols", C.c_int32),
                 ("reserved", C.c_int32 * 2)]
+
+
+class ClusterEstepDoubletRequest(C.Structure):   # dmx_cluster_estep_doublet_request
+    _fields_ = [("n_restarts", C.c_int32), ("n_clusters", C.c_int32), ("log_pi", C.c_void_p), ("log_delta", C.c_void_p), ("temperature", C.c_double),
+                ("mask", C.c_void_p), ("ll", C.c_void_p), ("col_sum", C.c_void_p), ("dbl_mass", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterDoubletInfo(C.Structure):    # dmx_cluster_doublet_info
+    _fields_ = [("doublet_ms", C.c_double), ("estep_ms", C.c_double), ("lld_bytes", C.c_int64), ("n_cells", C.c_int32), ("n_restarts", C.c_int32),
+                ("n_clusters", C.c_int32), ("n_pairs", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class AmbientRequest(C.Structure):       # dmx_ambient_request
@@ -228,6 +239,8 @@ def load() -> C.CDLL:
         "dmx_engine_cluster_stage": [vp], "dmx_engine_cluster_mstep": [vp, vp], "dmx_engine_cluster_estep": [vp, vp],
         "dmx_engine_get_cluster": [vp, vp, vp, vp, vp], "dmx_engine_get_cluster_stage": [vp, vp, vp, vp, vp], "dmx_engine_cluster_device_ptr": [vp, vp],
         "dmx_engine_cluster_info": [vp, vp],
+        "dmx_engine_cluster_doublet": [vp, i32, i32], "dmx_engine_get_cluster_doublet": [vp, vp, vp], "dmx_engine_cluster_estep_doublet": [vp, vp],
+        "dmx_engine_cluster_doublet_info": [vp, vp],
         "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],
     }
     for name, args in sig.items():

@@ -9,9 +9,12 @@ V = R * K columns:
 The restart with the highest log-likelihood gives the K genotype columns (sample ids CLUST0 .. CLUST{K-1}); the unchanged
 `demuxlet_run` writes <prefix>.best/.single/.sing2 from them (doublets come out of its grid), and each round r >= 1 refines the
 clusters' genotypes from the previous round's singlets only (the refinement of section 12, prior q) and runs again to <prefix>.r<r>.*.
+With em_doublets (--em-doublets) each restart also has a doublet component for every pair of its clusters, a
+50/50 mixture (alpha = 0.5) with prior share delta_r: cluster_doublet scores them after K1, cluster_estep_doublet gives the singlet
+weights (a doublet's mass goes to no cluster) and the doublet mass from which delta_r is re-estimated.
 
     python -m demuxlet_amd.cluster --pileup <x>.pileup.txt --n-clusters K --out <prefix> [--restarts R] [--seed S] [--max-iter N]
-        [--tol T] [--floor F] [--min-snp M] [--alpha A ...] [--rounds N] [--match] [--fast] [--gpu G]
+        [--tol T] [--floor F] [--min-snp M] [--alpha A ...] [--rounds N] [--match] [--em-doublets] [--fast] [--gpu G]
 
 reads the dump that `demuxlet --pileup-only` writes; its genotype matrix is ignored unless --match is given."""
 from __future__ import annotations
@@ -30,6 +33,10 @@ MAX_COLUMNS = 4094          # dmx_engine_create's widest panel: R * K columns in
 # SNPs (tests/test_gpu_cluster.py): 3 of 6 single restarts found the donors at K = 4, 0 of 6 at K = 8; the best of 16 did at both.
 PI_FLOOR = 1e-6             # smallest mixing weight a cluster keeps between iterations
 EM_HEADER = "ITER\tRESTART\tLLK\tPI\n"
+EM_HEADER_DBL = "ITER\tRESTART\tLLK\tPI\tDBL\n"
+# doublet-aware EM: each restart's doublet share delta starts at DELTA0 and is re-estimated after every E-step, clipped to
+# [DELTA_MIN, DELTA_MAX] (a share above one half would let the doublet components absorb a cluster)
+DELTA0, DELTA_MIN, DELTA_MAX = 0.1, 1e-3, 0.5
 MATCH_HEADER = "CLUST\tSM_ID\tN.CELL\tSUM.LLK\tBEST\n"
 
 
@@ -86,6 +93,18 @@ def update_log_pi(col_sum: np.ndarray, restarts: int, n_clusters: int) -> np.nda
     return np.log(pi)
 
 
+def pair_index(n_clusters: int) -> np.ndarray:
+    """[P][2] int: the pairs (k, l), k < l, in the lexicographic order of the doublet components (P = K (K - 1) / 2)."""
+    k, l = np.triu_indices(n_clusters, 1)
+    return np.stack([k, l], axis=1)
+
+
+def update_delta(dbl_mass: np.ndarray, n_mask: int) -> np.ndarray:
+    """delta[R] from the doublet E-step's per-restart doublet mass and the number of barcodes in the mask, clipped."""
+    d = np.asarray(dbl_mass, dtype=np.float64) / max(int(n_mask), 1)
+    return np.clip(d, DELTA_MIN, DELTA_MAX)
+
+
 def converged(prev: Optional[np.ndarray], cur: np.ndarray, tol: float) -> bool:
     """Every restart's |dLL| < tol * |LL|."""
     if prev is None:
@@ -99,12 +118,14 @@ def best_restart(ll: np.ndarray) -> int:
     return int(np.flatnonzero(ll == ll.max())[0])
 
 
-def write_em_tsv(path: str, rows: Sequence[Tuple[int, int, float, Sequence[float]]]) -> None:
-    """<prefix>.em.tsv: one row per (iteration, restart): ITER RESTART LLK PI (the mixing weights the E-step used, comma-joined)."""
+def write_em_tsv(path: str, rows: Sequence[Tuple], doublets: bool = False) -> None:
+    """<prefix>.em.tsv: one row per (iteration, restart): ITER RESTART LLK PI (the mixing weights the E-step used, comma-joined); with
+    doublets, rows (it, r, ll, pi, delta) and a trailing DBL column: the doublet share delta the E-step used."""
     with open(path, "w") as f:
-        f.write(EM_HEADER)
-        for it, r, ll, pi in rows:
-            f.write(f"{it}\t{r}\t{ll:.6f}\t" + ",".join(f"{x:.6g}" for x in pi) + "\n")
+        f.write(EM_HEADER_DBL if doublets else EM_HEADER)
+        for row in rows:
+            it, r, ll, pi = row[:4]
+            f.write(f"{it}\t{r}\t{ll:.6f}\t" + ",".join(f"{x:.6g}" for x in pi) + (f"\t{row[4]:.6g}" if doublets else "") + "\n")
 
 
 def match_table(llks: np.ndarray, called: np.ndarray, n_clusters: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -151,11 +172,11 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
                 floor: float = 1e-3, min_snp: int = 0, alphas: Sequence[float] = (0.0, 0.5), rounds: int = 1,
                 match: Optional[Tuple[np.ndarray, Sequence[str]]] = None, barcodes: Optional[Sequence[str]] = None, device: int = 0,
                 mode: int = capi.DMX_MODE_STRICT, doublet_prior: float = 0.5, temperature: float = 1.0,
-                snps: Optional[Sequence[Tuple]] = None) -> dict:
+                snps: Optional[Sequence[Tuple]] = None, em_doublets: bool = False) -> dict:
     """EM clustering of the barcodes of `store_or_pileup` (a Store, or a HostPileup with barcodes=...) into n_clusters donors, then
     the final demultiplexing pass and `rounds` hard-refine rounds (module docstring).  `match` = (g[S][NV][3], sample_ids) scores each
     cluster against genotyped samples (<prefix>.match.tsv).  Returns a dict: the winning restart, per-restart LL, iterations, the
-    cluster genotype matrix gp[S][K][3] and the prior q[S][3]."""
+    cluster genotype matrix gp[S][K][3] and the prior q[S][3]; with em_doublets also `delta`, the winning restart's doublet share."""
     if isinstance(store_or_pileup, engine.HostPileup):
         pl = store_or_pileup
         if barcodes is None:
@@ -182,6 +203,8 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
         # first M-step from each restart's random hard assignment, pi uniform
         eng.cluster_mstep(one_hot_weights(initial_labels(seed, R, B, K), K, mask), q, floor, fetch=False)
         log_pi = np.full((R, K), -np.log(K))
+        delta = np.full(R, DELTA0)
+        n_mask = B if mask is None else int(np.count_nonzero(mask))
         prev = None
         it = 0
         for it in range(1, max_iter + 1):
@@ -189,8 +212,14 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
             if dense:
                 eng.set_pileup(pl)          # a dense pileup's SNP-minor copy of the matrix is made when it is staged
             eng.run_singlet()
-            ll, cs = eng.cluster_estep(R, K, log_pi, temperature, mask)
-            em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r])) for r in range(R)]
+            if em_doublets:
+                eng.cluster_doublet(R, K)
+                ll, cs, dm = eng.cluster_estep_doublet(R, K, log_pi, np.log(delta), temperature, mask)
+                em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r]), float(delta[r])) for r in range(R)]
+                delta = update_delta(dm, n_mask)
+            else:
+                ll, cs = eng.cluster_estep(R, K, log_pi, temperature, mask)
+                em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r])) for r in range(R)]
             log_pi = update_log_pi(cs, R, K)
             eng.cluster_mstep(None, q, floor, fetch=False)
             if converged(prev, ll, tol):
@@ -201,7 +230,7 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
         g = np.ascontiguousarray(gp[:, win * K:(win + 1) * K, :])
     finally:
         eng.close()
-    write_em_tsv(out_prefix + ".em.tsv", em_rows)
+    write_em_tsv(out_prefix + ".em.tsv", em_rows, doublets=em_doublets)
     ids = cluster_ids(K)
     engine.demuxlet_run(pl, g, ids, alphas, out_prefix, **kw)
     # hard-refine rounds: the previous round's singlets only, prior q for every cluster
@@ -237,7 +266,10 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
         called = refine.assignments_from_best(prev_prefix + ".best", ids, barcodes)
         n_cell_m, sum_llk = match_table(llks, called, K)
         write_match_tsv(out_prefix + ".match.tsv", n_cell_m, sum_llk, msamples)
-    return dict(restart=win, ll=ll, iterations=it, gp=g, prior=q, last_prefix=prev_prefix)
+    res = dict(restart=win, ll=ll, iterations=it, gp=g, prior=q, last_prefix=prev_prefix)
+    if em_doublets:
+        res["delta"] = float(delta[win])
+    return res
 
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
@@ -255,6 +287,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--doublet-prior", type=float, default=0.5)
     ap.add_argument("--rounds", type=int, default=1, help="hard-refine rounds after the final pass (default 1)")
     ap.add_argument("--match", action="store_true", help="score the clusters against the dump's genotyped samples (<out>.match.tsv)")
+    ap.add_argument("--em-doublets", action="store_true",
+                    help="doublet components (alpha = 0.5) for every pair of clusters in the EM; <out>.em.tsv gains a DBL column")
     ap.add_argument("--fast", action="store_true", help="DMX_MODE_FAST for every pass")
     ap.add_argument("--gpu", type=int, default=0)
     a = ap.parse_args(argv)
@@ -275,7 +309,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         match = (d.g, d.sample_ids)
     cluster_run(d.pileup, a.n_clusters, a.out, restarts=a.restarts, seed=a.seed, max_iter=a.max_iter, tol=a.tol, floor=a.floor,
                 min_snp=a.min_snp, alphas=a.alpha, rounds=a.rounds, match=match, barcodes=d.barcodes, device=a.gpu,
-                mode=capi.DMX_MODE_FAST if a.fast else capi.DMX_MODE_STRICT, doublet_prior=a.doublet_prior, snps=d.snps)
+                mode=capi.DMX_MODE_FAST if a.fast else capi.DMX_MODE_STRICT, doublet_prior=a.doublet_prior, snps=d.snps,
+                em_doublets=a.em_doublets)
     return 0
 
 

@@ -2220,19 +2220,21 @@ __global__ __launch_bounds__(256) void k_cluster_estep(const double* __restrict_
 }
 
 // The E-step's sums in a fixed order: chunk partials over kEChunk consecutive barcodes (one thread per output column, serial over the
-// chunk's barcodes), then k_cluster_efold adds the chunks in ascending order.  Columns 0 .. C-1: sum of w; C .. C+R-1: sum of lse.
+// chunk's barcodes), then k_cluster_efold adds the chunks in ascending order.  Columns 0 .. C-1: sum of w; C .. C+R-1: sum of lse;
+// with dm (the doublet E-step) C+R .. C+2R-1: sum of the doublet mass dm[b][r].
 constexpr int kEChunk = 256;
-__global__ __launch_bounds__(256) void k_cluster_epart(const double* __restrict__ w, const double* __restrict__ lse, int32_t B, int32_t C, int32_t R,
-                                                       double* __restrict__ part) {
+__global__ __launch_bounds__(256) void k_cluster_epart(const double* __restrict__ w, const double* __restrict__ lse, const double* __restrict__ dm,
+                                                       int32_t B, int32_t C, int32_t R, double* __restrict__ part) {
   const int32_t col = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
-  if (col >= C + R) return;
+  const int32_t ncol = C + R + (dm ? R : 0);
+  if (col >= ncol) return;
   const int32_t b0 = ch * kEChunk, b1 = min(B, b0 + kEChunk);
   const bool is_w = col < C;
-  const double* src = is_w ? w + col : lse + (col - C);
+  const double* src = is_w ? w + col : col < C + R ? lse + (col - C) : dm + (col - C - R);
   const size_t stride = is_w ? (size_t)C : (size_t)R;
   double a = 0.0;
   for (int32_t b = b0; b < b1; ++b) a += src[(size_t)b * stride];
-  part[(size_t)ch * (C + R) + col] = a;
+  part[(size_t)ch * ncol + col] = a;
 }
 __global__ __launch_bounds__(256) void k_cluster_efold(const double* __restrict__ part, int32_t n_chunks, int32_t n_cols, double* __restrict__ out) {
   const int32_t col = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2240,6 +2242,156 @@ __global__ __launch_bounds__(256) void k_cluster_efold(const double* __restrict_
   double a = 0.0;
   for (int32_t ch = 0; ch < n_chunks; ++ch) a += part[(size_t)ch * n_cols + col];
   out[col] = a;
+}
+
+// ---- doublet-aware clustering (dmx_engine_cluster_doublet / _estep_doublet) ---------------------------------------
+// LLD[b][r][p] for every barcode b, restart r and pair p = (k, l), k < l, of the restart's K columns (lexicographic; pairs[p] = k | l << 16):
+//   the sum over b's pairs in stored (ascending SNP) order of log(sum over x, y of gp[i][rK + k][x] gp[i][rK + l][y] pG[x + y]),
+// pG[s] the reference's per-pair doublet factors at alpha = 0.5 (cmd_cram_demuxlet.cpp:594-663): per stored read, pG[s] *= pR (1 - s/4)
+// + pA s/4, then every pG divided by their maximum; then + 1e-6 and the same renormalisation.  Only these five products exist at
+// alpha = 0.5 (the reference's nine entries repeat them bit for bit), and with the grid {0, 0.5} their maximum is the reference's.
+// One wavefront per (barcode, block of 64 pair-columns of the R x P), one lane per pair-column.  The wavefront stages 64 pairs at a
+// time in LDS, one per lane (its SNP and its five pG values: the reads walk is lane-parallel over pairs), then every lane steps through
+// them with broadcast reads and adds its own term serially.  Nothing crosses lanes and there are no atomics, so a pair-column's bits
+// depend only on its two genotype columns and the barcode's reads: not on R, the block it falls in, or what ran before.
+// The first block of a barcode also writes lsc[b] = the sum over its pairs, in the same order, of log(pG[0] + pG[2] + pG[4]): pG[2x]
+// is the singlet genotype x's factor on the doublet's max-normalised scale, so LLD - lsc is on K1's sum-normalised one (the E-step).
+constexpr int kDblWaves = 4;                     // wavefronts per workgroup: four (barcode, column block) units share the LDS tables
+struct DblPair { double pg[5]; int32_t snp; int32_t pad; };
+
+__global__ __launch_bounds__(64 * kDblWaves) void k_cluster_dbl(PileupView pv, int nrd_width, const double* __restrict__ tabs, const float* __restrict__ g,
+                                                              int32_t V, int32_t K, int32_t P, const uint32_t* __restrict__ pairs, int32_t n_cols,
+                                                              int32_t n_cblk, int64_t n_units, double* __restrict__ lld, double* __restrict__ lsc) {
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_pra[256][2];               // by read byte (allele << 7 | bq): {pR, pA}
+  __shared__ DblPair s_hdr[kDblWaves][64];
+  __shared__ double s_ls[kDblWaves][64];         // log(pG[0] + pG[2] + pG[4]) of the staged pairs (first block of a barcode only)
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += 64 * kDblWaves) s_log[i] = tabs[kLut + i];
+  for (int i = threadIdx.x; i < 256; i += 64 * kDblWaves) {
+    const double mat = tabs[i & 127], e3 = tabs[128 + (i & 127)];
+    s_pra[i][0] = (i >> 7) ? e3 : mat;
+    s_pra[i][1] = (i >> 7) ? mat : e3;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t unit = (int64_t)blockIdx.x * kDblWaves + wave;
+  if (unit >= n_units) return;
+  const int32_t cell = (int32_t)(unit / n_cblk), cb = __builtin_amdgcn_readfirstlane((int32_t)(unit % n_cblk));
+  double* ls = s_ls[wave];
+  const int32_t c = cb * 64 + lane;
+  const bool on = c < n_cols;                    // lanes past the last column run along with column 0 and write nothing
+  const int32_t cc = on ? c : 0;
+  const int32_t r = cc / P, kl = (int32_t)pairs[cc - r * P];
+  const size_t ck = (size_t)(r * K + (kl & 0xFFFF)) * 3, cl = (size_t)(r * K + (kl >> 16)) * 3;
+  const size_t row = (size_t)V * 3;
+  DblPair* hdr = s_hdr[wave];
+  const DmxLogPins lk = dmx_log_pins();
+  const double wA[5] = {0.0, 0.25, 0.5, 0.75, 1.0}, wR[5] = {1.0, 0.75, 0.5, 0.25, 0.0};
+  double acc = 0.0, acc_s = 0.0;
+  const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+  int64_t rd_base = pv.cell_read_off[cell];
+  for (int64_t p0 = p_beg; p0 < p_end; p0 += 64) {
+    const int64_t p = p0 + lane;
+    const bool in = p < p_end;
+    const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+    const uint32_t incl = seg_scan_incl<64>(n);
+    const int64_t off = rd_base + (int64_t)(incl - n);
+    rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    if (in) {
+      double pg[5] = {1.0, 1.0, 1.0, 1.0, 1.0};
+      uint32_t w = load_rd4(pv, off, n);
+      for (uint32_t t = 0; t < n; ++t) {
+        if (t > 0 && (t & 3) == 0) w = load_rd4(pv, off + t, n - t);
+        const uint32_t byte = (w >> (8 * (t & 3))) & 0xFF;
+        const double pR = s_pra[byte][0], pA = s_pra[byte][1];
+        double mx = 0.0;
+#pragma unroll
+        for (int s = 0; s < 5; ++s) { pg[s] *= pR * wR[s] + pA * wA[s]; mx = fmax(mx, pg[s]); }
+#pragma unroll
+        for (int s = 0; s < 5; ++s) pg[s] /= mx;
+      }
+      double mx = 0.0;
+#pragma unroll
+      for (int s = 0; s < 5; ++s) { pg[s] += 1e-6; mx = fmax(mx, pg[s]); }
+      DblPair h;
+#pragma unroll
+      for (int s = 0; s < 5; ++s) h.pg[s] = pg[s] / mx;
+      if (cb == 0) ls[lane] = log(h.pg[0] + h.pg[2] + h.pg[4]);
+      h.snp = pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg);
+      h.pad = 0;
+      hdr[lane] = h;
+    }
+    DMX_WAVE_LDS_ORDER();
+    const int cnt = (int)min<int64_t>(64, p_end - p0);
+    if (cb == 0) for (int j = 0; j < cnt; ++j) acc_s += ls[j];
+    for (int j = 0; j < cnt; ++j) {
+      const int32_t snp = __builtin_amdgcn_readfirstlane(hdr[j].snp);
+      const double q0 = hdr[j].pg[0], q1 = hdr[j].pg[1], q2 = hdr[j].pg[2], q3 = hdr[j].pg[3], q4 = hdr[j].pg[4];
+      const float* gr = g + (size_t)snp * row;
+      const double a0 = gr[ck], a1 = gr[ck + 1], a2 = gr[ck + 2];
+      const double b0 = gr[cl], b1 = gr[cl + 1], b2 = gr[cl + 2];
+      // sum over x of a_x (sum over y of b_y pG[x + y])
+      const double t0 = __builtin_fma(b2, q2, __builtin_fma(b1, q1, b0 * q0));
+      const double t1 = __builtin_fma(b2, q3, __builtin_fma(b1, q2, b0 * q1));
+      const double t2 = __builtin_fma(b2, q4, __builtin_fma(b1, q3, b0 * q2));
+      const double L = __builtin_fma(a2, t2, __builtin_fma(a1, t1, a0 * t0));
+      acc += dmx_log_is_special(L) ? log(L) : dmx_log_fast_pinned(L, s_log, lk);
+    }
+    DMX_WAVE_LDS_ORDER();
+  }
+  if (on) lld[(size_t)cell * n_cols + c] = acc;
+  if (cb == 0 && lane == 0) lsc[cell] = acc_s;
+}
+
+// Doublet E-step.  One thread per (barcode b, restart r): K singlet components with scores a_k = (llks[b][rK + k] + lps[r][k]) / T and
+// P doublet components with d_p = (lld[b][r][p] - lsc[b] + lpd[r][p]) / T (the host made the log priors: lps = log(1 - delta) + log pi,
+// lpd = log delta + log(2 pi_k pi_l / (1 - sum pi^2))).  w[b][rK + k] = exp(a_k - M) / Z, dm[b][r] = sum_p exp(d_p - M) / Z
+// (M the maximum, Z the sum over all K + P), lse[b][r] = logsumexp over all K + P of the unscaled scores.  A barcode outside the
+// mask gets w = 0, dm = 0 and lse = 0.  With every lpd = -inf this is k_cluster_estep's arithmetic, bit for bit.
+__global__ __launch_bounds__(256) void k_cluster_estep_dbl(const double* __restrict__ llks, const double* __restrict__ lld,
+                                                           const double* __restrict__ lsc, int32_t B, int32_t R,
+                                                           int32_t K, int32_t P, const double* __restrict__ lps, const double* __restrict__ lpd,
+                                                           double inv_t, const uint8_t* __restrict__ mask, double* __restrict__ w,
+                                                           double* __restrict__ lse, double* __restrict__ dm) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)B * R) return;
+  const int32_t b = (int32_t)(t / R), r = (int32_t)(t % R);
+  const size_t C = (size_t)R * K, o = (size_t)b * C + (size_t)r * K;
+  const double* ld = lld + ((size_t)b * R + r) * P;
+  const double* pd = lpd + (size_t)r * P;
+  const double sc = lsc[b];
+  if (mask && !mask[b]) {
+    for (int32_t k = 0; k < K; ++k) w[o + k] = 0.0;
+    lse[(size_t)b * R + r] = 0.0;
+    dm[(size_t)b * R + r] = 0.0;
+    return;
+  }
+  double m = -INFINITY, m1 = -INFINITY;
+  for (int32_t k = 0; k < K; ++k) {
+    const double x = llks[o + k] + lps[(size_t)r * K + k];
+    m1 = fmax(m1, x); m = fmax(m, x * inv_t);
+  }
+  for (int32_t p = 0; p < P; ++p) {
+    const double x = (ld[p] - sc) + pd[p];
+    m1 = fmax(m1, x); m = fmax(m, x * inv_t);
+  }
+  double s = 0.0, s1 = 0.0, sd = 0.0;
+  for (int32_t k = 0; k < K; ++k) {
+    const double x = llks[o + k] + lps[(size_t)r * K + k];
+    const double e = exp(x * inv_t - m);
+    w[o + k] = e; s += e; s1 += exp(x - m1);
+  }
+  for (int32_t p = 0; p < P; ++p) {
+    const double x = (ld[p] - sc) + pd[p];
+    const double e = exp(x * inv_t - m);
+    sd += e; s1 += exp(x - m1);
+  }
+  s += sd;
+  const double y = 1.0 / s;
+  for (int32_t k = 0; k < K; ++k) w[o + k] *= y;
+  dm[(size_t)b * R + r] = sd * y;
+  lse[(size_t)b * R + r] = m1 + log(s1);
 }
 
 // ---- ambient contamination profile (dmx_engine_ambient) ---------------------------------------------------------
@@ -6673,6 +6825,15 @@ struct dmx_engine {
   float* d_cgp[2] = {nullptr, nullptr}; size_t cgp_cap[2] = {0, 0}; int cgp_cur = -1; int32_t cm_S = 0, cm_C = 0; bool have_cm = false;
   hipEvent_t cev[2] = {};
   dmx_cluster_info cl_info{};
+  // doublet-aware clustering (dmx_engine_cluster_doublet / _estep_doublet): the pair table, LLD[B][R][P], the per-barcode doublet mass
+  // and the host-made log priors; LLD belongs to the staged pileup (staging again drops it)
+  uint32_t* d_cpairs = nullptr; size_t cpairs_cap = 0;
+  double* d_clld = nullptr; size_t clld_cap = 0;
+  double* d_cdm = nullptr; size_t cdm_cap = 0;
+  double* d_clp = nullptr; size_t clp_cap = 0;
+  int32_t cd_B = 0, cd_R = 0, cd_K = 0; bool have_cdbl = false;
+  hipEvent_t dev_[2] = {};
+  dmx_cluster_doublet_info cd_info{};
   // ambient contamination profile (dmx_engine_ambient): its own copies of the inputs and the B x Q results
   int32_t* d_aasg = nullptr; size_t aasg_cap = 0;
   double* d_aamb = nullptr; size_t aamb_cap = 0;
@@ -6828,6 +6989,9 @@ extern "C" int dmx_engine_destroy(dmx_engine* e) {
                   (void*)e->d_cgp[1]})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->cev) if (ev) (void)hipEventDestroy(ev);
+  for (void* p : {(void*)e->d_cpairs, (void*)e->d_clld, (void*)e->d_cdm, (void*)e->d_clp})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t& ev : e->dev_) if (ev) (void)hipEventDestroy(ev);
   for (void* p : {(void*)e->d_aasg, (void*)e->d_aamb, (void*)e->d_agrid, (void*)e->d_all, (void*)e->d_acnt})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->aev) if (ev) (void)hipEventDestroy(ev);
@@ -7288,7 +7452,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
     }
   }
   e->have_sing = e->have_grid = false;
-  e->rblk_valid = false; e->have_refined = false; e->have_amb = false;
+  e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_cdbl = false;
   e->have_pileup = true;
   e->k1_fn = e->k2_fn = e->k3b_fn = nullptr; e->k1_placement = 0;      // nothing has run on this pileup yet
   return DMX_OK;
@@ -8544,7 +8708,7 @@ extern "C" int dmx_engine_cluster_estep(dmx_engine* e, const dmx_cluster_estep_r
                        (const double*)e->d_cpi, 1.0 / rq->temperature, rq->mask ? (const uint8_t*)e->d_cmask : nullptr, e->d_cw, e->d_clse);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_cw,
-                       (const double*)e->d_clse, B, C, R, e->d_cpart);
+                       (const double*)e->d_clse, (const double*)nullptr, B, C, R, e->d_cpart);
     HIP_TRY(hipGetLastError());
   }
   hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
@@ -8600,6 +8764,143 @@ extern "C" int dmx_engine_cluster_info(dmx_engine* e, dmx_cluster_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_info: null argument");
   if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_info: no stage cache (dmx_engine_cluster_stage first)");
   *out = e->cl_info;
+  return DMX_OK;
+}
+
+// Doublet-aware clustering: LLD of the pairs of clusters within each restart (k_cluster_dbl over B x
+// ceil(R P / 64) wavefronts), then the E-step over K singlet and P doublet components whose sums go through k_cluster_epart /
+// k_cluster_efold with R more columns.
+extern "C" int dmx_engine_cluster_doublet(dmx_engine* e, int32_t n_restarts, int32_t n_clusters) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: null engine");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_doublet: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_doublet: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, R = n_restarts, K = n_clusters, V = e->V;
+  if (e->pv.S != e->S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_cluster_doublet: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", e->S, e->pv.S);
+  if (K < 2 || K > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: %d clusters; the doublet components need 2 .. 65 535", K);
+  if (R < 1 || (int64_t)R * K != V) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: %d restarts x %d clusters, the engine has %d columns", R, K, V);
+  const int64_t P = (int64_t)K * (K - 1) / 2, ncols = (int64_t)R * P;
+  if (ncols > INT32_MAX) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: %lld pair-columns exceed this build's limit", (long long)ncols);
+  const int32_t n_cblk = (int32_t)((ncols + 63) / 64);
+  const int64_t n_units = (int64_t)B * n_cblk;
+  if ((n_units + kDblWaves - 1) / kDblWaves > INT32_MAX) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: %d cells x %lld pair-columns exceed this build's limit", B, (long long)ncols);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->dev_[0]) for (hipEvent_t& ev : e->dev_) HIP_TRY(hipEventCreate(&ev));
+  const size_t lld_b = sizeof(double) * ((size_t)B * (size_t)ncols + (size_t)B), pairs_b = sizeof(uint32_t) * (size_t)P;   // LLD, then lsc[B]
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const size_t need = (lld_b > e->clld_cap ? lld_b : 0) + (pairs_b > e->cpairs_cap ? pairs_b : 0);
+  if (need > 0 && (double)need > 0.9 * (double)free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_cluster_doublet: LLD of %d cells x %d restarts x %lld pairs needs %.2f GB (+%.2f MB pair table), %.2f GB of device memory are free",
+                     B, R, (long long)P, lld_b / 1e9, pairs_b / 1e6, free_b / 1e9);
+  e->have_cdbl = false;
+  if (int rc = ensure_dev((void**)&e->d_clld, &e->clld_cap, lld_b)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cpairs, &e->cpairs_cap, pairs_b)) return rc;
+  std::vector<uint32_t> pr((size_t)P);
+  for (int32_t k = 0, p = 0; k < K; ++k)
+    for (int32_t l = k + 1; l < K; ++l) pr[(size_t)p++] = (uint32_t)k | ((uint32_t)l << 16);
+  HIP_TRY(hipMemcpyAsync(e->d_cpairs, pr.data(), pairs_b, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipEventRecord(e->dev_[0], e->stream));
+  if (n_units > 0) {
+    hipLaunchKernelGGL(k_cluster_dbl, dim3((unsigned)((n_units + kDblWaves - 1) / kDblWaves)), dim3(64 * kDblWaves), 0, e->stream, e->pv, e->nrd_width,
+                       (const double*)e->d_lut, (const float*)e->d_g, V, K, (int32_t)P, (const uint32_t*)e->d_cpairs, (int32_t)ncols, n_cblk, n_units,
+                       e->d_clld, e->d_clld + (size_t)B * ncols);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(e->dev_[1], e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->dev_[0], e->dev_[1]));
+  dmx_cluster_doublet_info& inf = e->cd_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.doublet_ms = ms; inf.lld_bytes = (int64_t)lld_b; inf.n_cells = B; inf.n_restarts = R; inf.n_clusters = K; inf.n_pairs = (int32_t)P;
+  e->cd_B = B; e->cd_R = R; e->cd_K = K; e->have_cdbl = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_cluster_doublet(dmx_engine* e, double* lld, double* lsc) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_cluster_doublet: null engine");
+  if (!e->have_cdbl) return set_error(DMX_ERR_STATE, "dmx_engine_get_cluster_doublet: no doublet likelihoods on the staged pileup (dmx_engine_cluster_doublet first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t n = (size_t)e->cd_B * e->cd_R * ((size_t)e->cd_K * (e->cd_K - 1) / 2);
+  if (lld && n) HIP_TRY(hipMemcpy(lld, e->d_clld, sizeof(double) * n, hipMemcpyDeviceToHost));
+  if (lsc && e->cd_B) HIP_TRY(hipMemcpy(lsc, e->d_clld + n, sizeof(double) * (size_t)e->cd_B, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_estep_doublet(dmx_engine* e, const dmx_cluster_estep_doublet_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_doublet: null argument");
+  if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_doublet: no stage cache (dmx_engine_cluster_stage first)");
+  if (!e->have_sing) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_doublet: no singlet likelihoods (dmx_engine_run_singlet first)");
+  const int32_t B = e->pv.B, R = rq->n_restarts, K = rq->n_clusters, C = e->V;
+  if (B != e->cl_B) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_doublet: the staged pileup has %d cells, the stage cache %d", B, e->cl_B);
+  if (K < 2 || R < 1 || (int64_t)R * K != C) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_doublet: %d restarts x %d clusters, the engine has %d columns", R, K, C);
+  if (!e->have_cdbl || e->cd_B != B || e->cd_R != R || e->cd_K != K)
+    return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_doublet: no doublet likelihoods of %d restarts x %d clusters (dmx_engine_cluster_doublet first)", R, K);
+  if (!rq->log_pi || !rq->log_delta) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_doublet: missing log_pi / log_delta");
+  if (!(rq->temperature > 0.0) || !std::isfinite(rq->temperature)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_doublet: temperature %g", rq->temperature);
+  for (int32_t r = 0; r < R; ++r)
+    if (!(rq->log_delta[r] < 0.0)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_doublet: log_delta[%d] = %g; delta must be in [0, 1)", r, rq->log_delta[r]);
+  const int32_t nch = (B + kEChunk - 1) / kEChunk;
+  if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_doublet: %d cells exceed this build's limit", B);
+  const int64_t P = (int64_t)K * (K - 1) / 2;
+  // the log priors: singlet k  log(1 - delta) + log pi_k;  doublet (k, l)  log delta + log 2 + log pi_k + log pi_l - log(1 - sum pi^2)
+  std::vector<double> lp((size_t)C + (size_t)R * P);
+  double* lps = lp.data(); double* lpd = lp.data() + C;
+  for (int32_t r = 0; r < R; ++r) {
+    const double* pi = rq->log_pi + (size_t)r * K;
+    const double ld = rq->log_delta[r], l1m = std::log1p(-std::exp(ld));
+    double s2 = 0.0;
+    for (int32_t k = 0; k < K; ++k) { lps[(size_t)r * K + k] = pi[k] + l1m; s2 += std::exp(2.0 * pi[k]); }
+    const double lden = std::log1p(-s2);
+    int64_t p = 0;
+    for (int32_t k = 0; k < K; ++k)
+      for (int32_t l = k + 1; l < K; ++l, ++p)
+        lpd[(size_t)r * P + p] = (ld == -INFINITY || !(s2 < 1.0)) ? -INFINITY : ld + M_LN2 + pi[k] + pi[l] - lden;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->dev_[0]) for (hipEvent_t& ev : e->dev_) HIP_TRY(hipEventCreate(&ev));
+  const int32_t ncol = C + 2 * R;
+  if (int rc = ensure_dev((void**)&e->d_cw, &e->cw_cap, sizeof(double) * (size_t)B * C)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_clse, &e->clse_cap, sizeof(double) * (size_t)B * R)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cdm, &e->cdm_cap, sizeof(double) * (size_t)B * R)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cpart, &e->cpart_cap, sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_clp, &e->clp_cap, sizeof(double) * lp.size())) return rc;
+  if (rq->mask) if (int rc = ensure_dev((void**)&e->d_cmask, &e->cmask_cap, (size_t)B)) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_clp, lp.data(), sizeof(double) * lp.size(), hipMemcpyHostToDevice, e->stream));
+  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
+  double* d_out = e->d_cpart + (size_t)nch * ncol;
+  HIP_TRY(hipEventRecord(e->dev_[0], e->stream));
+  if (B > 0) {
+    hipLaunchKernelGGL(k_cluster_estep_dbl, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks,
+                       (const double*)e->d_clld, (const double*)(e->d_clld + (size_t)B * R * P), B, R, K, (int32_t)P, (const double*)e->d_clp, (const double*)(e->d_clp + C), 1.0 / rq->temperature,
+                       rq->mask ? (const uint8_t*)e->d_cmask : nullptr, e->d_cw, e->d_clse, e->d_cdm);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_cw,
+                       (const double*)e->d_clse, (const double*)e->d_cdm, B, C, R, e->d_cpart);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->dev_[1], e->stream));
+  std::vector<double> out((size_t)ncol);
+  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (rq->col_sum) std::memcpy(rq->col_sum, out.data(), sizeof(double) * (size_t)C);
+  if (rq->ll) std::memcpy(rq->ll, out.data() + C, sizeof(double) * (size_t)R);
+  if (rq->dbl_mass) std::memcpy(rq->dbl_mass, out.data() + C + R, sizeof(double) * (size_t)R);
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->dev_[0], e->dev_[1]));
+  e->cd_info.estep_ms = ms;
+  e->cw_C = C; e->have_cw = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_doublet_info(dmx_engine* e, dmx_cluster_doublet_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet_info: null argument");
+  if (!e->have_cdbl) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_doublet_info: no doublet likelihoods on the staged pileup (dmx_engine_cluster_doublet first)");
+  *out = e->cd_info;
   return DMX_OK;
 }
 

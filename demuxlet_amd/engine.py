@@ -377,6 +377,44 @@ class Engine:
         check(self._L.dmx_engine_cluster_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.ClusterInfo._fields_ if n != "reserved"}
 
+    def cluster_doublet(self, n_restarts: int, n_clusters: int) -> None:
+        """dmx_engine_cluster_doublet: LLD[B][R][P] of the pairs k < l of clusters within each restart (alpha = 0.5), kept on the device."""
+        check(self._L.dmx_engine_cluster_doublet(self._h, int(n_restarts), int(n_clusters)))
+
+    def get_cluster_doublet(self):
+        """The last (LLD [B][R][P] f64, pairs (k, l), k < l, in lexicographic order; lsc [B] f64, the scale term: LLD - lsc is on K1's scale)."""
+        inf = self.cluster_doublet_info()
+        lld = np.zeros((inf["n_cells"], inf["n_restarts"], inf["n_pairs"]))
+        lsc = np.zeros(inf["n_cells"])
+        check(self._L.dmx_engine_get_cluster_doublet(self._h, lld.ctypes.data if lld.size else None, lsc.ctypes.data if lsc.size else None))
+        return lld, lsc
+
+    def cluster_estep_doublet(self, n_restarts: int, n_clusters: int, log_pi, log_delta, temperature: float = 1.0, mask=None):
+        """dmx_engine_cluster_estep_doublet on K1's llks of the last run_singlet and the last LLD: the singlet weights stay on the device;
+        returns (ll[R], col_sum[R * K], dbl_mass[R])."""
+        lp = np.ascontiguousarray(log_pi, dtype=np.float64).reshape(-1)
+        ld = np.ascontiguousarray(log_delta, dtype=np.float64).reshape(-1)
+        if lp.size != n_restarts * n_clusters:
+            raise ValueError("log_pi must be [R][K]")
+        if ld.size != n_restarts:
+            raise ValueError("log_delta must be [R]")
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        if m is not None and m.shape != (self.B,):
+            raise ValueError(f"mask must be [{self.B}]")
+        ll = np.zeros(n_restarts)
+        cs = np.zeros(n_restarts * n_clusters)
+        dm = np.zeros(n_restarts)
+        rq = capi.ClusterEstepDoubletRequest(int(n_restarts), int(n_clusters), lp.ctypes.data, ld.ctypes.data, float(temperature),
+                                             m.ctypes.data if m is not None and m.size else None, ll.ctypes.data, cs.ctypes.data, dm.ctypes.data)
+        check(self._L.dmx_engine_cluster_estep_doublet(self._h, C.byref(rq)))
+        return ll, cs, dm
+
+    def cluster_doublet_info(self) -> dict:
+        """HIP-event times (ms) of the last doublet likelihoods / doublet E-step and LLD's size (dmx_engine_cluster_doublet_info)."""
+        r = capi.ClusterDoubletInfo()
+        check(self._L.dmx_engine_cluster_doublet_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.ClusterDoubletInfo._fields_ if n != "reserved"}
+
     def ambient_profile(self, assign, ambient, grid):
         """dmx_engine_ambient over the staged pileup: LL[b][q] of each barcode assigned to sample assign[b] (-1 = not used) with a fraction
         grid[q] of its reads from a soup of ALT frequency ambient[i].  `assign` is a host array, or a device pointer (int) to B int32.

@@ -30,7 +30,8 @@ extern "C" {
                                8: dmx_engine_format_pair / dmx_pair_text_* (`.pair` rows formatted on the device); later, still ABI 8:
                                dmx_engine_refine_genotypes / _get_refined / _refined_device_ptr / _refine_info (genotype refinement from
                                called singlets); dmx_engine_cluster_* (genotype-free clustering); dmx_engine_ambient / _get_ambient /
-                               _ambient_info (per-barcode ambient contamination profile).  Additions only. */
+                               _ambient_info (per-barcode ambient contamination profile); dmx_engine_cluster_doublet / _get_cluster_doublet /
+                               _cluster_estep_doublet / _cluster_doublet_info (doublet-aware clustering).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -368,6 +369,56 @@ int dmx_engine_get_cluster_stage(dmx_engine*, int64_t* snp_off, int32_t* cell, d
  * destroyed. */
 int dmx_engine_cluster_device_ptr(dmx_engine*, const float** out);
 int dmx_engine_cluster_info(dmx_engine*, dmx_cluster_info* out);
+
+/* Doublet-aware clustering (no counterpart in the reference): doublets of two clusters of the same restart as
+ * components of the EM, so that their reads do not pull any cluster's genotypes toward heterozygous.
+ *
+ * dmx_engine_cluster_doublet: with the engine's V = R * K columns read as R restarts x K clusters, for every barcode b, restart r and
+ *   pair p = (k, l), k < l, numbered lexicographically (P = K (K - 1) / 2 pairs), over the staged pileup, the phred tables and the
+ *   genotype matrix gp (float32) that K1 reads:
+ *     LLD[b][r][p] = sum over b's pairs in ascending SNP order of log(sum over x, y of gp[i][rK + k][x] gp[i][rK + l][y] pG[x + y]),
+ *   pG[s] the reference's per-pair doublet factors at alpha = 0.5 (cmd_cram_demuxlet.cpp:594-663; weight s / 4, five distinct values):
+ *   per stored read the products, then division by their maximum; then + 1e-6 and the same renormalisation.  With the alpha grid
+ *   {0, 0.5} that maximum is the reference's, so LLD = the reference's llksAB[b][rK + k][rK + l][alpha = 0.5] up to rounding; the log
+ *   is dmx_log.  Each (b, r, p) is one serial sum with no floating-point atomics: the bits do not depend on R, on the position of
+ *   the restart's columns in the engine, or on what ran before.  Beside it, per barcode, lsc[b] = the sum over its pairs in the same
+ *   order of log(pG[0] + pG[2] + pG[4]): pG[2x] is the singlet genotype x's factor on the doublet's max-normalised scale, so
+ *   LLD - lsc is on the sum-normalised scale of K1's llks (the E-step compares the two).  DMX_ERR_ARG: K < 2 or R * K != V;
+ *   DMX_ERR_NOMEM: the B x (R x P + 1) float64 result does not fit the free device memory; DMX_ERR_STATE: no pileup or no genotypes.
+ *   Staging a pileup again drops it.
+ *
+ * dmx_engine_cluster_estep_doublet: the E-step over K singlet and P doublet components per (barcode, restart), from K1's llks of the
+ *   last run_singlet and the LLD of the last dmx_engine_cluster_doublet (same R and K).  Log priors: singlet k log(1 - delta_r) +
+ *   log pi_rk; doublet (k, l) log delta_r + log(2 pi_rk pi_rl / (1 - sum over k of pi_rk^2)).  The singlet llk is K1's llks[b][rK + k],
+ *   the doublet llk LLD[b][r][p] - lsc[b].  Every score is (llk + log prior) / T;
+ *   w[b][rK + k] = the singlet components' posteriors (they sum to 1 - m_b,r, m_b,r the doublet components' total),
+ *   ll[r] = sum over the barcodes in the mask of logsumexp over all K + P components of llk + log prior, col_sum[c] = sum over b of
+ *   w[b][c], dbl_mass[r] = sum over b of m_b,r; the sums are those of dmx_engine_cluster_estep (chunks of 256 barcodes, then the chunks
+ *   in order).  log_delta[r] = -inf (delta = 0) gives dmx_engine_cluster_estep's results.  The weights stay on the device for the next
+ *   M-step (DMX_CLUSTER_LAST_ESTEP) and dmx_engine_get_cluster returns them.  DMX_ERR_ARG: a log_delta that is NaN or >= 0. */
+typedef struct {
+  int32_t n_restarts, n_clusters;   /* R, K: R * K = the engine's V, K >= 2 */
+  const double* log_pi;        /* [R][K] HOST */
+  const double* log_delta;     /* [R] HOST: log of each restart's doublet share, < 0; -inf = no doublets */
+  double  temperature;         /* T > 0; 1 is plain EM */
+  const uint8_t* mask;         /* [B] HOST, or NULL = every barcode */
+  double* ll;                  /* [R] HOST out (may be NULL) */
+  double* col_sum;             /* [R * K] HOST out (may be NULL) */
+  double* dbl_mass;            /* [R] HOST out (may be NULL) */
+  int32_t reserved[4];         /* 0 */
+} dmx_cluster_estep_doublet_request;
+typedef struct {
+  double  doublet_ms;          /* HIP-event time of the last dmx_engine_cluster_doublet (k_cluster_dbl) */
+  double  estep_ms;            /* ... and of the last doublet E-step (k_cluster_estep_dbl + the ordered sums) */
+  int64_t lld_bytes;           /* device bytes of LLD[B][R][P] and lsc[B] */
+  int32_t n_cells, n_restarts, n_clusters, n_pairs;   /* n_pairs: P = K (K - 1) / 2 per restart */
+  int32_t reserved[4];
+} dmx_cluster_doublet_info;
+int dmx_engine_cluster_doublet(dmx_engine*, int32_t n_restarts, int32_t n_clusters);
+/* Device->host copies of the last LLD (either pointer may be NULL): lld[B][R][P] f64, lsc[B] f64 (DMX_ERR_STATE before a run). */
+int dmx_engine_get_cluster_doublet(dmx_engine*, double* lld, double* lsc);
+int dmx_engine_cluster_estep_doublet(dmx_engine*, const dmx_cluster_estep_doublet_request*);
+int dmx_engine_cluster_doublet_info(dmx_engine*, dmx_cluster_doublet_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Ambient contamination profile (no counterpart in the reference).  Soup is the average of many lysed cells: at
