@@ -1,23 +1,31 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the likelihood engine on synthetic pileups of the BASELINE.json configs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6] [--cells B] [--fast] [--only] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6] [--cells B] [--fast] [--full [--only] [--no-cpu-baseline]]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one resident batch: K1 singlet accumulation (cmd_cram_demuxlet.cpp:412-461), then —
 for the doublet configs — K2 doublet grid (:576-710) and K3 per-cell reduction (:713-734,:746-758,:799-828).  Inputs are
 generated in HBM before the timed region.
 
+A plain run does only what the headline needs: it generates the inputs, runs the warm-up and the timed steps, writes the
+--dump-outputs arrays and prints the line (its roofline figures come from the timed launches' own kernel events and the committed
+counter files).  `--full` adds everything else the benchmark measures or checks, each after the main record's timed steps: the CPU
+baseline and the oracle comparison of the timed rows (`--no-cpu-baseline` drops them), the log() microkernel, each kernel's time
+alone (two more steps with the kernels one after the other), the end-to-end legs and the nested configurations below (`--only`
+drops those).  `--e2e-write-pair` asks for its leg with or without `--full`.
+
 N = 1 (the driver's headline line): BASELINE.json configs[2] = cfg3, the heaviest single-GPU configuration and the one that
-exercises the whole metric (singlet + doublet), in STRICT mode (the reference's operation order).  The same run appends, as
-nested records under "also", cfg3 in FAST mode, cfg2 (singlet-only), cfg5 (sparse PL) and — the strong-scaling base of the
+exercises the whole metric (singlet + doublet), in STRICT mode (the reference's operation order).  With `--full` the same run appends,
+as nested records under "also", cfg3 in FAST mode, cfg2 (singlet-only), cfg5 (sparse PL) and — the strong-scaling base of the
 N > 1 line — ALL of cfg4 (100k barcodes x 100k SNPs x 64 samples, 1e10 covered pairs, 22.5 GB of pileup) on this one GPU in
-both modes, and cfg4's 12 500-barcode shard (one GPU's share of the 8-GPU run), each timed the same way with fewer steps.  `--only` skips them.
+both modes, and cfg4's 12 500-barcode shard (one GPU's share of the 8-GPU run), each timed the same way with fewer steps.
 
 Output contract: stdout carries exactly ONE compact JSON line (< 6 KB: the driver's keys, `config`, `roofline`, `roofline_valu`,
-`cpu_baseline` and one short object per nested configuration under `also`; no prose).  The full record (every per-kernel time, the
-executed-flop figures, end-to-end stage seconds, sample descriptions) is written to `bench_full.json` beside this file (path in
-DMX_BENCH_FULL) and to stderr.
+and with `--full` `cpu_baseline`, `parity_check` and one short object per nested configuration under `also`; no prose).  The full
+record (every per-kernel time, the executed-flop figures, end-to-end stage seconds, sample descriptions) is written to
+`bench_full.json` beside this file (path in DMX_BENCH_FULL) and to stderr.
 
 `--gpus N` is what decides the number of ranks.  Launched plainly (`python bench.py --gpus N`, no WORLD_SIZE in the environment) with
 N > 1, this script checks that N GPUs are visible and re-executes itself under `python -m torch.distributed.run --nnodes=1
@@ -27,7 +35,8 @@ world size is N and that the N ranks sit on N distinct devices; anything else ex
 N > 1: BASELINE.json configs[3] = cfg4 (100k barcodes x 100k SNPs x 64 samples, GT), STRONG scaling: the 100k barcodes are cut
 into N contiguous equal ranges (barcodes are independent, cmd_cram_demuxlet.cpp:576; dense pileup = equal work), rank r
 generates and owns range r, and every step ends with THE one collective of the job: the RCCL gather of the fixed-size
-per-barcode records to rank 0.  Rank 0 prints ONE JSON line.
+per-barcode records to rank 0.  Rank 0 prints ONE JSON line.  With `--full` the sharded job is timed once more in FAST mode and run
+as the whole job with --write-pair on every rank.
 
 `--dump-outputs DIR`: after the timed steps of the main record, what its last step computed is written as DIR/<name>.npy (float64),
 the arrays a caller of the timed path receives: N = 1 the engine's llks, llk0s and — doublet configs — l00, grid (llksAB) and one
@@ -514,9 +523,10 @@ class Ctx:
     pass
 
 
-def run_config(cx, cfgno, cfg, mode, steps, warmup, with_cpu, with_log, with_e2e=False, parity_s=0.0, defer_cpu=False, dump_dir=None):
+def run_config(cx, cfgno, cfg, mode, steps, warmup, with_cpu, with_log, with_e2e=False, parity_s=0.0, defer_cpu=False, dump_dir=None,
+               with_alone=False):
     """Generate the workload of one configuration on this rank's GPU, time `steps` passes, return the record (rank 0).  dump_dir: write the
-    last timed step's outputs there (--dump-outputs)."""
+    last timed step's outputs there (--dump-outputs).  with_alone: time each kernel alone in two more, untimed steps (`kernel_ms_alone`)."""
     torch, dist, engine, synth, synth_torch = cx.torch, cx.dist, cx.engine, cx.synth, cx.synth_torch
     dev, world, rank, local = cx.dev, cx.world, cx.rank, cx.local
     fast = mode == "fast"
@@ -628,7 +638,9 @@ def run_config(cx, cfgno, cfg, mode, steps, warmup, with_cpu, with_log, with_e2e
     k2_only_ms = float(km.doublet_ms) if cfg["doublet"] else 0.0
     k3_ms, k3b_ms = (float(km.reduce_ms), float(km.certify_ms)) if cfg["doublet"] else (0.0, 0.0)
     alone = None
-    if beside:
+    if beside and not with_alone:
+        k1_ms = None                                    # beside K2, K1 has no time of its own without the steps below (--full)
+    elif beside:
         # K1 ran beside K2 in the timed steps (the product's way, dmx_engine_run): K1's own event span is mostly waiting and K2's
         # contains what K1 took from it.  Two extra, untimed steps with the kernels one after the other give each kernel ALONE
         # (full record only: `kernel_ms_alone`).
@@ -966,10 +978,13 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=0, choices=[0] + sorted(CONFIGS),
-                    help="0 = the driver's default: cfg3 (+ nested cfg3-fast/cfg2/cfg5/cfg4-whole records) at N=1, cfg4 sharded at N>1")
+                    help="0 = the driver's default: cfg3 (with --full: + nested cfg3-fast/cfg2/cfg5/cfg4-whole records) at N=1, cfg4 sharded at N>1")
     ap.add_argument("--cells", type=int, default=0, help="override the TOTAL barcode count (smaller = quicker run; not the headline)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--only", action="store_true", help="N=1: skip the nested records of the other configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also measure and check everything else (CPU baseline, oracle comparison, log "
+                         "microkernel, per-kernel times alone, end-to-end legs, nested configurations); see the docstring")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the oracle comparisons")
+    ap.add_argument("--only", action="store_true", help="with --full: skip the nested records of the other configurations and the end-to-end legs")
     ap.add_argument("--samples", type=int, default=0, help="override the number of samples (experiments; not the headline)")
     ap.add_argument("--field", default="", help="override the genotype field GT|GP|PL (experiments; not the headline)")
     ap.add_argument("--fast", action="store_true", help="DMX_MODE_FAST for the main record (opt-in, not the headline)")
@@ -1069,13 +1084,15 @@ def main():
         # (the CPU baseline runs on rank 0 at every N: a SCALE line is judged by the same rule as the N = 1 line.  Its engine rows are taken
         #  right after the timed steps; with a process group the oracle itself runs after the group's last barrier — see the end of main)
         cx.deferred_cpu = None
+        # a plain run stops after the main record's timed steps and dump; everything else is --full's
+        full_default = args.full and default_run and not args.only
         out = run_config(cx, cfgno, cfg, "fast" if args.fast else "strict", args.steps, args.warmup,
-                         with_cpu=not args.no_cpu_baseline, with_log=single,
-                         with_e2e=(single and default_run and not args.only) or (single and args.e2e_write_pair and "e2e4wp"),
-                         defer_cpu=cx.use_dist, dump_dir=args.dump_outputs or None)
+                         with_cpu=args.full and not args.no_cpu_baseline, with_log=single and args.full,
+                         with_e2e=(single and full_default) or (single and args.e2e_write_pair and "e2e4wp"),
+                         defer_cpu=cx.use_dist, dump_dir=args.dump_outputs or None, with_alone=args.full)
         keys = ("value", "unit", "n_gpus", "ms_per_step", "steps", "warmup", "config", "roofline", "roofline_valu", "fp64_valu", "pair_evals_per_s",
                 "ranks_seen", "per_rank_ms_per_step", "gather_ms", "parity_check")
-        if single and default_run and not args.only:
+        if single and full_default:
             # nested records of the same run: the other single-GPU BASELINE configurations and the opt-in mode, fewer steps each
             also = []
             k, w = max(2, min(args.steps, 5)), min(args.warmup, 1)
@@ -1096,7 +1113,7 @@ def main():
                 # cfg4 gets one per kernel: the shard's STRICT k_doublet_clsp and the whole job's FAST one)
                 par = 0.0 if args.no_cpu_baseline or (no == 4 and mode == "strict" and not shard) else 2.0
                 r = run_config(cx, no, c, mode, kk, w, with_cpu=False, with_log=False,
-                               with_e2e=((no == 6 and mode == "fast") and "e2e6") or (bool(shard) and "e2e4wp"), parity_s=par)
+                               with_e2e=((no == 6 and mode == "fast") and "e2e6") or (bool(shard) and "e2e4wp"), parity_s=par, with_alone=True)
                 if r.get("end_to_end"):
                     out["end_to_end"]["cfg6"] = r.pop("end_to_end")
                 if r.get("end_to_end_write_pair"):            # cfg4's shard with --write-pair: the job, not only the kernels
@@ -1105,12 +1122,12 @@ def main():
                     r["config"]["tag"] = f"cfg{no}-shard/{mode}"
                 also.append({key: r[key] for key in keys if key in r})
             out["also"] = also
-        if cx.world > 1 and default_run and not args.only:
+        if cx.world > 1 and full_default:
             # the sharded job once more in the opt-in FAST mode (every rank takes part: it ends with the same gather)
-            r = run_config(cx, cfgno, cfg, "fast", max(2, min(args.steps, 5)), min(args.warmup, 1), with_cpu=False, with_log=False)
+            r = run_config(cx, cfgno, cfg, "fast", max(2, min(args.steps, 5)), min(args.warmup, 1), with_cpu=False, with_log=False, with_alone=True)
             if cx.rank == 0:
                 out["also"] = [{key: r[key] for key in keys if key in r}]
-        if cx.use_dist and ((default_run and not args.only) or args.e2e_write_pair) and cx.inputs is not None:
+        if cx.use_dist and (full_default or args.e2e_write_pair) and cx.inputs is not None:
             # ... and the JOB, not only its kernels: BASELINE config 4 is "full doublet + --write-pair".  Every rank runs
             # dmx_demuxlet_run with write_pair on ITS range at the same time (its own files; the `.pair` rows are formatted on its GPU and go to
             # write(2)), so the host cores and the file system are shared as they would be in the real job; the record is rank 0's stage seconds

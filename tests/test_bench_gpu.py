@@ -1,5 +1,5 @@
-"""GPU (-m gpu): bench.py's contract — stdout is exactly one JSON line with the driver's keys, the roofline and CPU-baseline
-objects, and sane values — on a reduced barcode count so that the test takes seconds."""
+"""GPU (-m gpu): bench.py's contract — stdout is exactly one JSON line with the driver's keys, the roofline and (with --full) the
+CPU-baseline objects, and sane values — on a reduced barcode count so that the test takes seconds."""
 import json
 import subprocess
 import sys
@@ -26,7 +26,7 @@ def run_bench(*extra):
 
 
 def test_bench_line_singlet():
-    d = run_bench("--config", "2", "--cells", "1024")
+    d = run_bench("--config", "2", "--cells", "1024", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -55,15 +55,15 @@ def test_bench_parity_check_on_the_timed_path_doublet():
     """cfg3's depth and panel on 8 barcodes, STRICT and FAST: the line carries the comparison of dmx_engine_run's rows (the timed steps' own
     results) with the oracle — values within 1e-9 (FAST: the printed entries), K3's records making the oracle's calls."""
     for extra in ((), ("--fast",)):
-        d = run_bench("--config", "3", "--cells", "8", "--only", *extra)
+        d = run_bench("--config", "3", "--cells", "8", "--full", "--only", *extra)
         p = d["parity_check"]
         assert 1 <= p["barcodes"] <= 8 and p["max_abs_delta"] <= 1e-9 and p["calls_identical"] is True and p["ok"] is True, p
         assert d["cpu_baseline"]["value"] > 0
 
 
 def test_bench_default_line_is_cfg3_with_nested_records():
-    """The driver's N=1 command (no --config): cfg3 STRICT as the line, cfg3-FAST / cfg2 / cfg5 as nested records."""
-    d = run_bench("--cells", "64")
+    """The driver's N=1 command (no --config) with --full: cfg3 STRICT as the line, cfg3-FAST / cfg2 / cfg5 as nested records."""
+    d = run_bench("--cells", "64", "--full")
     assert d["config"]["workload"].startswith("cfg3") and d["config"]["mode"] == "strict" and d["pair_evals_per_s"] > 0
     assert d["roofline"]["kernel"] == "k_doublet" and d["scaling"] == "none"
     names = [a["workload"] for a in d["also"]]
@@ -80,12 +80,25 @@ def test_bench_default_line_is_cfg3_with_nested_records():
     assert d["roofline_valu"]["kernel"].startswith("k_doublet")
 
 
+def test_bench_plain_run_is_the_headline_only():
+    """The driver's N=1 command without --full: the main record's timed steps and nothing else — the driver's keys and the roofline of the
+    timed launches, no nested records, end-to-end legs, CPU baseline, oracle comparison, log microkernel or per-kernel steps alone."""
+    d = run_bench("--cells", "64")
+    assert d["config"]["workload"].startswith("cfg3") and d["config"]["mode"] == "strict" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2 and d["warmup"] == 1 and d["pair_evals_per_s"] > 0
+    assert d["roofline"]["kernel"] == "k_doublet" and 0 < d["roofline"]["kernel_ms"] <= d["ms_per_step"] * 1.001
+    for k in ("also", "end_to_end", "cpu_baseline", "parity_check"):
+        assert k not in d, k
+    full = json.loads((ROOT / d["full_record"]).read_text())
+    assert full["fp64_valu"]["kernel_ms_alone"] is None and full["fp64_valu"]["kernel_ms"]["k_singlet"] is None and "log_microkernel" not in full
+
+
 def test_bench_sharded_path_with_a_one_rank_group():
     """The N>1 code path (cfg4 ranges + the end-of-step RCCL gather) on the one GPU this box has: a 1-rank process group."""
     import os
     env = dict(os.environ, DMX_BENCH_FORCE_DIST="1", MASTER_PORT="29533")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "4",
-                        "--cells", "96", "--e2e-write-pair"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
+                        "--cells", "96", "--full", "--e2e-write-pair"], capture_output=True, text=True, cwd=ROOT, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip()][0])
     assert d["ranks_seen"] == 1 and len(d["per_rank_ms_per_step"]) == 1 and d["gather_ms"] >= 0

@@ -13,7 +13,7 @@ SFX=""; case "$EXTRA" in *--fast*) SFX="_fast";; esac
 OUT=$PWD/gpurun_out/prof_${TAG}_cfg${CFG}${SFX}; mkdir -p $OUT
 KRE="k_singlet|k_doublet_|k_reduce|k_certify"
 STEPS=${STEPS:-5}; PSTEPS=${PSTEPS:-2}
-python bench.py --config $CFG $EXTRA --steps $STEPS --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --config $CFG $EXTRA --full --steps $STEPS --warmup 2 > $OUT/bench.json 2> $OUT/bench.err
 ( cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$CFG$SFX -o kt -- python $OLDPWD/bench.py --config $CFG $EXTRA --steps $STEPS --warmup 2 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2>/dev/null )
 find /tmp/kt_$CFG$SFX -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 i=0
