@@ -3,8 +3,8 @@
 Generative model (ours; the reference ships no generator): per SNP AF ~ U(0.05,0.95), per-sample genotype ~
 Binomial(2, AF); a cell is a singlet of sample (c mod V) w.p. 0.9, else a 50/50 doublet with a second, different
 sample; each (cell, SNP) is covered w.p. delta; a covered pair carries 1+Poisson(rbar-1) unique UMIs; a read shows ALT
-w.p. g/2 of its source sample, bq ~ U{13..40}, and a base error w.p. 10^(-bq/10) moves it to one of the three other
-bases (so allele 2 = "other" occurs).
+w.p. g/2 of its source sample, bq ~ U{13..40} (or another quality profile, see draw_bq), and a base error w.p. 10^(-bq/10)
+moves it to one of the three other bases (so allele 2 = "other" occurs).
 
 Two back-ends:
   * numpy  (host; tests, fixtures, small problems, events with strings for the UMI-store path)
@@ -54,6 +54,27 @@ def raw_pl_from_alleles(rng: np.random.Generator, alleles: np.ndarray) -> np.nda
     return pl
 
 
+# base qualities where the engine changes code path (pair / triple / LDS tables, PhredHelper's 0.75 floor at q <= 1, the top of the ABI)
+EDGE_QUALS = np.array([0, 1, 2, 12, 13, 40, 41, 42, 47, 48, 63, 64, 93, 126, 127], dtype=np.uint8)
+QUAL_PROFILES = (None, "full", "edges", "max")          # None (or "default"): U{13..40}
+ERR_OF_BQ = np.power(10.0, -np.arange(128) / 10.0)
+
+
+def draw_bq(rng: np.random.Generator, n: int, quals: Optional[str] = None) -> np.ndarray:
+    """n base qualities of a profile: None = U{13..40} (the only draw of the default, so seeded problems do not change), "full" = U{0..127}
+    (the whole C-ABI range), "edges" = half EDGE_QUALS, half U{13..40} (so pairs mix both), "max" = every read at 127 (no draw)."""
+    if quals is None or quals == "default":
+        return rng.integers(13, 41, size=n).astype(np.uint8)
+    if quals == "full":
+        return rng.integers(0, 128, size=n).astype(np.uint8)
+    if quals == "edges":
+        edge = EDGE_QUALS[rng.integers(0, len(EDGE_QUALS), size=n)]
+        return np.where(rng.random(n) < 0.5, edge, rng.integers(13, 41, size=n)).astype(np.uint8)
+    if quals == "max":
+        return np.full(n, 127, dtype=np.uint8)
+    raise ValueError(f"unknown quality profile {quals!r}")
+
+
 @dataclass
 class SynthPileup:
     """CSR pileup in the C-ABI's layout (cells in id order)."""
@@ -71,10 +92,10 @@ class SynthPileup:
 
 
 def make_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: float, rbar: float,
-                dense_layout: bool = False, doublet_rate: float = 0.1, chunk_cells: int = 256) -> SynthPileup:
+                dense_layout: bool = False, doublet_rate: float = 0.1, chunk_cells: int = 256, quals: Optional[str] = None) -> SynthPileup:
+    """`quals`: the base-quality profile of the reads (draw_bq)."""
     S, V, _ = alleles.shape
     dosage = np.clip(alleles, 0, 1).sum(axis=2).astype(np.float64)      # [S][V]
-    err_of_bq = np.power(10.0, -np.arange(64) / 10.0)
     cell_pair_off = np.zeros(B + 1, dtype=np.int64)
     cell_read_off = np.zeros(B + 1, dtype=np.int64)
     snp_chunks, nrd_chunks, rd_chunks = [], [], []
@@ -100,8 +121,8 @@ def make_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: fl
         rc, rs = cc[pair_of_read], ss[pair_of_read]
         src = np.where(is_dbl[rc] & (rng.random(len(rc)) < 0.5), s2[rc], s1[rc])
         alt = rng.random(len(rc)) < dosage[rs, src] / 2.0
-        bq = rng.integers(13, 41, size=len(rc)).astype(np.uint8)
-        e = rng.random(len(rc)) < err_of_bq[bq]
+        bq = draw_bq(rng, len(rc), quals)
+        e = rng.random(len(rc)) < ERR_OF_BQ[bq]
         u = rng.integers(0, 3, size=len(rc))
         allele = np.where(e, np.where(u == 0, 1 - alt.astype(np.int32), 2), alt.astype(np.int32)).astype(np.uint8)
         keep = allele != 2
@@ -128,16 +149,15 @@ def make_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: fl
 
 
 def make_ambient_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: float, rbar: float, rho,
-                        ambient: Optional[np.ndarray] = None, dense_layout: bool = False, chunk_cells: int = 256
+                        ambient: Optional[np.ndarray] = None, dense_layout: bool = False, chunk_cells: int = 256, quals: Optional[str] = None
                         ) -> Tuple[SynthPileup, np.ndarray, np.ndarray]:
     """Singlet barcodes (cell c is sample c mod V) with ambient contamination: each read comes from the soup with probability rho[c]
     (ALT w.p. a_i) and from the cell otherwise (ALT w.p. its dosage / 2); then sequencing error as in make_pileup.  `rho` is a scalar or
-    [B]; `ambient` defaults to the donors' mean dosage / 2.  Returns (pileup, rho[B], a[S])."""
+    [B]; `ambient` defaults to the donors' mean dosage / 2; `quals` as in make_pileup.  Returns (pileup, rho[B], a[S])."""
     S, V, _ = alleles.shape
     dosage = np.clip(alleles, 0, 1).sum(axis=2).astype(np.float64)      # [S][V]
     a = dosage.mean(axis=1) / 2.0 if ambient is None else np.asarray(ambient, dtype=np.float64)
     rho = np.broadcast_to(np.asarray(rho, dtype=np.float64), (B,)).copy()
-    err_of_bq = np.power(10.0, -np.arange(64) / 10.0)
     cell_pair_off = np.zeros(B + 1, dtype=np.int64)
     cell_read_off = np.zeros(B + 1, dtype=np.int64)
     snp_chunks, nrd_chunks, rd_chunks = [], [], []
@@ -157,8 +177,8 @@ def make_ambient_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, d
         soup = rng.random(len(rc)) < rho[c0 + rc]
         p_alt = np.where(soup, a[rs], dosage[rs, s1[rc]] / 2.0)
         alt = rng.random(len(rc)) < p_alt
-        bq = rng.integers(13, 41, size=len(rc)).astype(np.uint8)
-        e = rng.random(len(rc)) < err_of_bq[bq]
+        bq = draw_bq(rng, len(rc), quals)
+        e = rng.random(len(rc)) < ERR_OF_BQ[bq]
         u = rng.integers(0, 3, size=len(rc))
         allele = np.where(e, np.where(u == 0, 1 - alt.astype(np.int32), 2), alt.astype(np.int32)).astype(np.uint8)
         keep = allele != 2

@@ -24,16 +24,22 @@ def pair_log_factors(nrd, start, reads, a_pair, grid, mat, err):
     gg = np.arange(3, dtype=np.float64)[None, :, None]
     p = (1.0 - rho) * gg / 2.0 + rho * np.asarray(a_pair, dtype=np.float64)[:, None, None]       # [P][3][Q]
     out = np.zeros((P, 3, Q))
-    e3 = err / 3.0
+    comp = np.zeros((P, 3, Q))              # Neumaier compensation: a pair of thousands of reads at quality 127 sums to ~-1e5, where a
+    e3 = err / 3.0                          # plain running sum would be off by ~1e-9 (one rounding of ulp(1e5) / 2 per read)
     for r in range(int(nrd.max()) if P else 0):
         idx = np.flatnonzero(nrd > r)
         b = reads[start[idx] + r].astype(np.int64)
         bq, alt = b & 127, (b >> 7) != 0
         pR = np.where(alt, e3[bq], mat[bq])[:, None, None]
         pA = np.where(alt, mat[bq], e3[bq])[:, None, None]
-        with np.errstate(divide="ignore"):
-            out[idx] += np.log(pR * (1.0 - p[idx]) + pA * p[idx])
-    return out
+        with np.errstate(divide="ignore", invalid="ignore"):
+            x = np.log(pR * (1.0 - p[idx]) + pA * p[idx])
+            s = out[idx]
+            t = s + x
+            c = np.where(np.abs(s) >= np.abs(x), (s - t) + x, (x - t) + s)
+        comp[idx] += np.where(np.isfinite(c), c, 0.0)
+        out[idx] = t
+    return out + comp
 
 
 def ref_profile(cell_pair_off, pair_snp, pair_nrd, reads, assign, g, a, grid, mat, err, chunk=4096):

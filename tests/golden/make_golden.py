@@ -43,10 +43,10 @@ def geno_matrix(rng, S, V, field, gt_error, missing_rate=0.0):
 
 
 def make_case(name, seed, B, S, V, alphas, field, delta, rbar, gt_error=0.01, write_pair=False, min_snp=0, min_total=0,
-              min_uniq=0, doublet_prior=0.5, missing_rate=0.0, empty_cells=0):
+              min_uniq=0, doublet_prior=0.5, missing_rate=0.0, empty_cells=0, quals=None):
     rng = np.random.default_rng(seed)
     raw, g = geno_matrix(rng, S, V, field, gt_error, missing_rate)
-    sp = synth.make_pileup(rng, np.where(raw.alleles < 0, 0, raw.alleles), B, delta, rbar, doublet_rate=0.3)
+    sp = synth.make_pileup(rng, np.where(raw.alleles < 0, 0, raw.alleles), B, delta, rbar, doublet_rate=0.3, quals=quals)
     bc, snp, umi, al, bq, new = synth.pileup_to_events(rng, sp)
     for k in range(empty_cells):         # cells whose reads overlap no SNP: .single rows only (cmd_cram_demuxlet.cpp:592)
         bc += [f"ZZEMPTY{k}-1"] * 3
@@ -201,6 +201,13 @@ def main():
         # in FAST mode, the printed-entries kernel with its LDS-direct row loads); and a 100-sample soft-field panel (entry slabs)
         make_case("gp_v32_a2_dense", 110, B=12, S=160, V=32, alphas=(0.0, 0.5), field="GP", delta=1.0, rbar=1.25, write_pair=True),
         make_case("pl_v100_a2", 111, B=5, S=220, V=100, alphas=(0.0, 0.5), field="PL", delta=0.35, rbar=1.5),
+        # base qualities at the engine's code-path edges (synth.EDGE_QUALS: 0 and 1 under PhredHelper's 0.75 floor, 41/42 around the LDS
+        # one-read table, 47/48 around the triple tables, 63/64 around the pair tables, 93, 126, 127) mixed with 13..40, pairs of up to ~20 reads
+        make_case("gt_v16_a2_edges_pair", 112, B=16, S=300, V=16, alphas=(0.0, 0.5), field="GT", delta=0.3, rbar=5.0, write_pair=True,
+                  missing_rate=0.05, quals="edges"),
+        make_case("gp_v32_a2_edges_dense", 113, B=8, S=90, V=32, alphas=(0.0, 0.5), field="GP", delta=1.0, rbar=4.0,
+                  quals="edges"),
+        make_case("pl_v8_a3_edges", 114, B=24, S=300, V=8, alphas=(0.0, 0.25, 0.5), field="PL", delta=0.3, rbar=6.0, quals="edges"),
     ]
     only = set(sys.argv[1:])                 # python make_golden.py [case ...]: regenerate just these
     if only:

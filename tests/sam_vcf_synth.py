@@ -55,8 +55,9 @@ def make_vcf(rng, contigs, n_per_contig, samples, path, with_noise=True, contig_
     return recs
 
 
-def make_reads(rng, contigs, recs, n_reads, barcodes, path_sam, path_bam=None):
-    """Coordinate-sorted reads, many of them placed over variants; returns the parsed read dicts (after writing)."""
+def make_reads(rng, contigs, recs, n_reads, barcodes, path_sam, path_bam=None, qual_range=(2, 42)):
+    """Coordinate-sorted reads, many of them placed over variants; base qualities uniform in [qual_range[0], qual_range[1]); returns the
+    parsed read dicts (after writing)."""
     import bisect
     by_chrom = {}
     for r in recs:
@@ -93,7 +94,7 @@ def make_reads(rng, contigs, recs, n_reads, barcodes, path_sam, path_bam=None):
                 rpos += n
         if rng.random() < 0.02:
             seq[rng.integers(0, qlen)] = "N"
-        qual = "".join(chr(33 + int(q)) for q in rng.integers(2, 42, size=qlen))
+        qual = "".join(chr(33 + int(q)) for q in rng.integers(qual_range[0], qual_range[1], size=qlen))
         flag = int(rng.choice([0, 16, 0, 16, 0x400, 0x100, 0x4], p=[0.4, 0.4, 0.05, 0.05, 0.04, 0.03, 0.03]))
         mapq = int(rng.choice([60, 255, 30, 10, 0], p=[0.5, 0.2, 0.15, 0.1, 0.05]))
         tags = []

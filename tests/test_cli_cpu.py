@@ -92,6 +92,23 @@ def test_scan_matches_restatement(cli, oracle, tmp_path, field, fmt):
     check_dump_against_scan(oracle, dump, snps, events, gts, recs, sm_cols, field)
 
 
+@pytest.mark.parametrize("fmt", ["sam", "bam"])
+def test_scan_over_the_whole_quality_range(cli, oracle, tmp_path, fmt):
+    """--min-BQ 0 --cap-BQ 93 on reads whose qualities span 0..93 (long-read and newer short-read platforms): every quality reaches the
+    pileup uncapped, byte for byte the restatement's."""
+    rng = np.random.default_rng(930)
+    recs = sv.make_vcf(rng, CONTIGS, 120, SAMPLES, tmp_path / "v.vcf.gz")
+    reads = sv.make_reads(rng, CONTIGS, recs, 4000, [f"BC{i:02d}-1" for i in range(25)], tmp_path / "r.sam", tmp_path / "r.bam", qual_range=(0, 94))
+    out = tmp_path / "o"
+    subprocess.run([cli, "--sam", str(tmp_path / f"r.{fmt}"), "--vcf", str(tmp_path / "v.vcf.gz"), "--field", "GT", "--out", str(out),
+                    "--min-BQ", "0", "--cap-BQ", "93", "--pileup-only"], check=True, stderr=subprocess.DEVNULL)
+    dump = parse_dump(str(out) + ".pileup.txt")
+    snps, events, gts, sm_cols = sv.scan(reads, recs, CONTIGS, SAMPLES, min_bq=0, cap_bq=93)
+    bq = np.array([e[4] for e in events])
+    assert len(events) > 1000 and bq.min() == 0 and bq.max() == 93
+    check_dump_against_scan(oracle, dump, snps, events, gts, recs, sm_cols, "GT")
+
+
 def test_sam_and_bam_give_the_same_pileup(cli, tmp_path):
     """Every container the readers accept gives the same pileup: SAM text, gzip'd SAM, BAM in BGZF blocks (what samtools
     writes; inflated on several threads: block size forced down so that batches span many blocks), BAM as one ordinary

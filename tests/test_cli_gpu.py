@@ -37,18 +37,27 @@ def compare_files(got_path, want_path, best=False):
                                               ("GT", "sam", ["--fast"]), ("GP", "bam", ["--fast"]),
                                               ("GP", "sam", ["--alpha", "0", "--alpha", "0.25", "--alpha", "0.5", "--fast"]),   # k_doublet_anf
                                               ("PL", "bam", ["--alpha", "0", "--alpha", "0.3", "--fast", "--write-pair"]),
-                                              ("GT", "sam", ["--strict"])])                                 # the default (DMX_MODE_STRICT), spelled out
+                                              ("GT", "sam", ["--strict"]),                                  # the default (DMX_MODE_STRICT), spelled out
+                                              # SAM qualities over 0..93, none skipped or capped: reads beyond the engine's pair / triple / LDS tables
+                                              ("GT", "sam", ["--min-BQ", "0", "--cap-BQ", "93", "--write-pair"]),
+                                              ("GP", "bam", ["--min-BQ", "0", "--cap-BQ", "93", "--fast"])])
 def test_cli_end_to_end(oracle, tmp_path, field, fmt, extra):
     from demuxlet_amd import build
     build.build()
     rng = np.random.default_rng(77 + len(field) + len(extra))
     recs = sv.make_vcf(rng, CONTIGS, 150, SAMPLES, tmp_path / "v.vcf.gz", with_noise=(field != "GP"))
-    reads = sv.make_reads(rng, CONTIGS, recs, 6000, [f"BC{i:02d}-1" for i in range(20)], tmp_path / "r.sam", tmp_path / "r.bam")
+    min_bq = int(extra[extra.index("--min-BQ") + 1]) if "--min-BQ" in extra else 13
+    cap_bq = int(extra[extra.index("--cap-BQ") + 1]) if "--cap-BQ" in extra else 40
+    reads = sv.make_reads(rng, CONTIGS, recs, 6000, [f"BC{i:02d}-1" for i in range(20)], tmp_path / "r.sam", tmp_path / "r.bam",
+                          qual_range=(0, cap_bq + 1) if cap_bq > 41 else (2, 42))
     out = tmp_path / "o"
     subprocess.run([str(CLI), "--sam", str(tmp_path / f"r.{fmt}"), "--vcf", str(tmp_path / "v.vcf.gz"), "--field", field, "--out", str(out)] + extra,
                    check=True, stderr=subprocess.DEVNULL)
     # expectation: scan restatement -> oracle
-    snps, events, gts, sm_cols = sv.scan(reads, recs, CONTIGS, SAMPLES)
+    snps, events, gts, sm_cols = sv.scan(reads, recs, CONTIGS, SAMPLES, min_bq=min_bq, cap_bq=cap_bq)
+    if cap_bq > 41:
+        bq = np.array([e[4] for e in events])
+        assert bq.min() == 0 and bq.max() == cap_bq
     if field == "GT":
         g = np.stack([oracle.geno_from_gt(np.array(a), 0.01) for a in gts])
     elif field == "PL":

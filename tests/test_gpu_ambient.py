@@ -379,3 +379,47 @@ def test_ambient_cli_end_to_end(m, tmp_path):
     finally:
         e.close()
     assert np.allclose(a, (alt + 1) / (tot + 2), rtol=0, atol=1e-15)
+
+
+@pytest.mark.parametrize("quals", ["full", "edges", "max"])
+@pytest.mark.parametrize("dense,width", [(False, 2), (True, 1)])
+def test_ambient_parity_quality_range(m, dense, width, quals):
+    """k_ambient against ambient_ref on reads of quality 0..127 (the 0.75 error floor at q <= 1, err(127)) and soup contamination, then on the
+    depth mix of tests/quality_mix.py (0..6, 14..17, 40, u16 pairs of 256..300 reads, all-ALT pairs on hom-REF rows)."""
+    from quality_mix import mixed_depth_pileup
+    rng = np.random.default_rng(5500 + int(dense) + {"full": 0, "edges": 2, "max": 4}[quals])
+    S, V, B = (131, 8, 60) if dense else (600, 16, 120)
+    raw = m["synth"].make_raw_genotypes(rng, S, V)
+    g = gt_matrix(m, raw)
+    rho = rng.choice([0.0, 0.1, 0.3], size=B)
+    sp, _, a = m["synth"].make_ambient_pileup(rng, raw.alleles, B, 1.0 if dense else 0.1, 2.0, rho, dense_layout=dense, quals=quals)
+    assign = sp.truth[:, 0].copy()
+    assign[rng.random(B) < 0.2] = -1
+    check(m, sp, g, assign, a, make_grid(33), width)
+    mix = mixed_depth_pileup(rng, raw.alleles, B, 1.0 if dense else 0.2, quals=quals, dense=dense, deep=0 if dense else 3,
+                             doublet_rate=0.0)
+    check(m, mix, g, assign, a, make_grid(33))
+
+
+@pytest.mark.parametrize("n_alt", [3000, 3100])
+def test_ambient_deep_pair_at_quality_127(m, n_alt):
+    """The rescale's worst case: one pair of ~3 000 reads, every one ALT at quality 127, on a hom-REF row with hard zeros (each read scales
+    the cell's term by err(127)/3), at rho = 0 and at the ends of the grid — against ambient_ref, which takes engine.phred_tables()."""
+    rng = np.random.default_rng(n_alt)
+    S, V = 40, 4
+    raw = m["synth"].make_raw_genotypes(rng, S, V)
+    g = gt_matrix(m, raw)
+    g[5, :] = np.array([1.0, 0.0, 0.0], dtype=np.float32)
+    deep = np.full(n_alt, (1 << 7) | 127, dtype=np.uint8)
+    other = [(s, np.array([(1 << 7) | 127, 127, 0, 1], dtype=np.uint8)) for s in (2, 9, 17)]
+    pairs = [other[0], (5, deep)] + other[1:]
+    po = np.array([0, len(pairs)], dtype=np.int64)
+    ro = np.array([0, sum(len(r) for _, r in pairs)], dtype=np.int64)
+    t = np.ones(1, dtype=np.int32)
+    sp = m["synth"].SynthPileup(1, S, po, ro, np.array([s for s, _ in pairs], dtype=np.int32), np.array([len(r) for _, r in pairs], dtype=np.uint16),
+                                np.concatenate([r for _, r in pairs]).astype(np.uint8), t, t, t, np.array([[0, -1]], dtype=np.int32))
+    a = rng.uniform(0.05, 0.95, size=S)
+    a[5] = 1.0                                      # the soup is all ALT there: the grid's ends differ by ~90 000 in LL
+    grid = np.array([0.0, 1e-12, 1e-6, 0.5, 1.0 - 1e-9, 1.0])
+    ll, _, _ = check(m, sp, g, np.zeros(1, dtype=np.int32), a, grid)
+    assert np.isfinite(ll).all() and ll[0, 0] < -50000 and ll[0, -1] > -100

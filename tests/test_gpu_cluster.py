@@ -397,3 +397,31 @@ def test_device_hand_off_sparse_without_restaging(m):
         f.close()
     for x, y in zip(dev, host):
         assert np.array_equal(x.view(np.uint64), y.view(np.uint64))
+
+
+@pytest.mark.parametrize("quals", ["full", "edges", "max"])
+@pytest.mark.parametrize("dense", [False, True])
+def test_stage_and_mstep_quality_range(m, dense, quals):
+    """The cluster stage (per-pair log-GLs) and the M-step on reads of quality 0..127 and the depth mix of tests/quality_mix.py (0..6, 14..17,
+    40, u16 pairs of 256..300 reads, all-ALT pairs on hom-REF rows)."""
+    from quality_mix import mixed_depth_pileup
+    rng = np.random.default_rng(9900 + int(dense) + {"full": 0, "edges": 2, "max": 4}[quals])
+    S, B, C = (130, 60, 6) if dense else (900, 150, 9)
+    raw = m["synth"].make_raw_genotypes(rng, S, 4)
+    sp = mixed_depth_pileup(rng, raw.alleles, B, 0.2, quals=quals, dense=dense, deep=3)
+    assert sp.pair_nrd.dtype == np.uint16
+    w = rng.dirichlet(np.ones(C), size=B) * rng.random((B, 1))
+    w[rng.random(B) < 0.2] = 0.0
+    q = m["cluster"].hwe_prior(rng.integers(0, 20, S), rng.integers(0, 20, S))
+    e = staged_engine(m, sp, C)
+    try:
+        off, cell, lgl = check_stage(m, e, sp)
+        LL, W, gp = e.cluster_mstep(w, q, 1e-3)
+    finally:
+        e.close()
+    RL, RW, Rgp = ref_mstep(off, cell, lgl, w, q, 1e-3)
+    assert np.abs(LL - RL).max() <= 1e-9
+    assert (np.abs(W - RW) <= 1e-12 * np.maximum(np.abs(RW), 1.0)).all()
+    cov = RW > 0
+    ulp = np.abs(gp.view(np.int32).astype(np.int64) - Rgp.view(np.int32).astype(np.int64))
+    assert ulp[cov].max(initial=0) <= 2

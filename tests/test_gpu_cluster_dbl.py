@@ -396,3 +396,32 @@ def test_cli_on_pileup_dump(m, tmp_path):
     assert all(len(ln.split("\t")) == 5 and 1e-3 <= float(ln.split("\t")[4]) <= 0.5 for ln in em[1:])
     acc = accuracy(m, sp.truth, barcodes, str(tmp_path / "c"), 3)
     assert acc[0] >= 0.9
+
+
+@pytest.mark.parametrize("quals", ["full", "edges", "max"])
+@pytest.mark.parametrize("R,K,kind,dense", [(2, 5, "GT", False), (1, 12, "GP", True), (3, 3, "PL", False)])
+def test_lld_parity_quality_range(m, oracle, R, K, kind, dense, quals):
+    """k_cluster_dbl's LLD against cluster_dbl_ref and the oracle's llksAB on reads of quality 0..127 and the depth mix of
+    tests/quality_mix.py (0..6, 14..17, 40, u16 pairs of 256..300 reads, all-ALT pairs on hom-REF rows)."""
+    from quality_mix import mixed_depth_pileup
+    rng = np.random.default_rng(4400 + R * K + {"full": 0, "edges": 1, "max": 2}[quals])
+    V = R * K
+    S, B = (90, 20) if dense else (300, 40)
+    raw = m["synth"].make_raw_genotypes(rng, S, V)
+    sp = mixed_depth_pileup(rng, raw.alleles, B, 0.3, quals=quals, dense=dense, deep=0 if dense else 3)
+    g = genotypes(m, rng, raw.alleles, kind)
+    e = m["engine"].Engine(V, (0.0, 0.5), 0.5)
+    try:
+        e.set_genotypes(g)
+        e.set_pileup(host_pileup(m, sp))
+        e.cluster_doublet(R, K)
+        lld, lsc = e.get_cluster_doublet()
+    finally:
+        e.close()
+    mat, err = m["engine"].phred_tables()
+    ref, rsc = D.lld(sp, g, R, K, mat, err)
+    assert np.abs(lld - ref).max() <= 1e-9, np.abs(lld - ref).max()
+    assert np.abs(lsc - rsc).max() <= 1e-9, np.abs(lsc - rsc).max()
+    has = np.diff(sp.cell_pair_off) > 0
+    o = lld_from_grid(oracle_llksAB(oracle, sp, g), R, K)
+    assert np.abs(lld[has] - o[has]).max() <= 1e-9

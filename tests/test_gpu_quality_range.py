@@ -1,0 +1,146 @@
+"""GPU (-m gpu): every K1 and K2 kernel family over the whole base-quality range of the C-ABI (0..127) and the read-count regimes of the
+kernels, against the oracle.
+
+The kernels choose their code path by base quality: gl_seed's pair tables need both reads below 64, its triple tables all three below
+kTripleBq = 48, k_singlet_can / k_singlet_canp keep an LDS copy of the one-read table below kCtBq = 42, PhredHelper's error floor is 0.75
+at q <= 1, and kSafeReads = 15 (the reciprocal-refined division) rests on err(127)/3 being the smallest factor one read can apply.
+Each family is forced with the DMX_* experiment switches and its kernel name is asserted, so a dispatch change cannot skip a case
+silently; each runs with the phase-1 final and seed tables at their defaults, off, and on at every depth.
+Tolerance: STRICT within 1e-9 of the oracle everywhere; FAST within the same 1e-9 on the entries demuxlet prints or decides on
+(test_gpu_parity.py::test_fast_mode_stays_within_tolerance)."""
+import numpy as np
+import pytest
+
+from golden_util import printed_mask
+from quality_mix import genotypes, host_pileup, mixed_depth_pileup, oracle_run
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-9
+A2, A3 = (0.0, 0.5), (0.0, 0.25, 0.5)
+SWITCHES = ("DMX_K1_CANP", "DMX_A2_NO_SYMU", "DMX_A2_SYM", "DMX_NO_ANF", "DMX_K2_GENERIC", "DMX_FINALS_ANY_DEPTH", "DMX_SYM_NO_FINALS",
+            "DMX_A2_NO_FINALS", "DMX_SYM_NO_SEEDS", "DMX_A2_NO_SEEDS", "DMX_CERTIFY_NO_FINALS", "DMX_CERTIFY_NO_SEEDS", "DMX_NO_CLASSES",
+            "DMX_K1_NO_CANP", "DMX_K1_NO_LEAN", "DMX_K1_NO_OWN")
+TABLES = {
+    "tables_default": {},
+    "tables_off": {k: "1" for k in ("DMX_SYM_NO_FINALS", "DMX_A2_NO_FINALS", "DMX_SYM_NO_SEEDS", "DMX_A2_NO_SEEDS", "DMX_CERTIFY_NO_FINALS",
+                                    "DMX_CERTIFY_NO_SEEDS")},
+    "tables_any_depth": {"DMX_FINALS_ANY_DEPTH": "1"},
+}
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from demuxlet_amd import build, capi, engine
+    build.build()
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    capi.load()
+    return engine
+
+
+def run_with_env(eng, monkeypatch, g, sp, alphas, mode, env):
+    from demuxlet_amd import capi
+    monkeypatch.setenv("DMX_EXPERIMENTS", "1")
+    for k in SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    e = eng.Engine(g.shape[1], alphas, 0.5, mode=capi.DMX_MODE_FAST if mode == "fast" else capi.DMX_MODE_STRICT)
+    e.set_genotypes(g); e.set_pileup(host_pileup(eng, sp)); e.run(); e.sync()
+    names = e.kernel_names()
+    llks, llk0s = e.get_singlet()
+    grid, l00, summ = e.get_doublet()
+    e.close()
+    return dict(llks=llks, llk0s=llk0s, grid=grid, l00=l00, summ=summ, names=names)
+
+
+def max_diffs(out, ref, alphas, mode):
+    proc = ref.processed.astype(bool)
+    V, A = out["grid"].shape[1], len(alphas)
+    mask = np.broadcast_to(printed_mask(V, A)[None] if mode == "fast" else np.ones((1, V, V, A), dtype=bool), out["grid"].shape) & proc[:, None, None, None]
+    d = dict(llks=np.abs(out["llks"] - ref.llks).max(), llk0s=np.abs(out["llk0s"] - ref.llk0s).max(),
+             grid=np.abs(out["grid"] - ref.llksAB)[mask].max() if mask.any() else 0.0,
+             l00=np.abs(out["l00"][proc] - ref.llks00[proc]).max() if proc.any() else 0.0)
+    return d
+
+
+# (case id, field, V, alphas, mode, switches, K1 name prefix, K2 name prefix, dense, u16 pairs).  Which V / field / switch picks a family:
+# launch_singlet and launch_doublet in dmx_engine.hip.  k_singlet_can(p) need one-byte read counts, so their cases have no u16 pairs.
+FAMILIES = [
+    # K1
+    ("k1_singlet", "GP", 8, A2, "strict", {}, "k_singlet<", "k_doublet_a2<", False, 3),
+    ("k1_singlet_own", "GP", 16, A2, "strict", {}, "k_singlet_own<", "k_doublet_a2u16", False, 3),
+    ("k1_singlet_cls", "GT", 18, A2, "strict", {}, "k_singlet_cls<", "k_doublet_cls<", False, 3),
+    ("k1_singlet_can", "GT", 8, A2, "strict", {}, "k_singlet_can<", "k_doublet_cls<", False, 0),
+    ("k1_singlet_canp", "GT", 8, A2, "strict", {"DMX_K1_CANP": "1"}, "k_singlet_canp<", "k_doublet_cls<", True, 0),
+    ("k1_singlet_clsw", "GT", 40, A2, "strict", {}, "k_singlet_clsw<", "k_doublet_clsp<", False, 3),
+    ("k1_wide_v129_gp", "GP", 129, A2, "strict", {}, "k_singlet<", "k_doublet_a2<", False, 2),
+    ("k1_wide_v129_gt", "GT", 129, A2, "strict", {}, "k_singlet_clsw<", "k_doublet_cls<", False, 2),
+    # K2
+    ("k2_cls_v24", "GT", 24, A2, "strict", {}, "k_singlet_clsw<", "k_doublet_cls<", False, 3),
+    ("k2_clsp_fast", "GT", 40, A2, "fast", {}, "k_singlet_clsw<", "k_doublet_clsp<", False, 3),
+    ("k2_clsym", "GT", 8, A2, "fast", {}, "k_singlet_cls<", "k_doublet_clsym<", False, 3),
+    ("k2_clsym_v24", "GT", 24, A2, "fast", {}, "k_singlet_clsw<", "k_doublet_clsym<", False, 3),
+    ("k2_clsn", "GT", 16, A3, "strict", {}, "k_singlet_cls<", "k_doublet_clsn<", False, 3),
+    ("k2_a2u16", "GP", 16, A2, "strict", {}, "k_singlet_own<", "k_doublet_a2u16", False, 3),
+    ("k2_a2u", "GP", 32, A2, "strict", {}, "k_singlet_own<", "k_doublet_a2u<", False, 3),
+    ("k2_a2", "GP", 32, A2, "strict", {"DMX_A2_NO_SYMU": "1"}, "k_singlet_own<", "k_doublet_a2<", True, 0),
+    ("k2_a2s", "GP", 32, A2, "strict", {"DMX_A2_SYM": "1"}, "k_singlet_own<", "k_doublet_a2s<", False, 3),
+    ("k2_sym_v8", "GP", 8, A2, "fast", {}, "k_singlet<", "k_doublet_sym<", False, 3),
+    ("k2_sym_v32", "PL", 32, A2, "fast", {}, "k_singlet_own<", "k_doublet_sym<", True, 0),
+    ("k2_an", "PL", 16, A3, "strict", {}, "k_singlet_own<", "k_doublet_an<", False, 3),
+    ("k2_anf", "GP", 16, A3, "fast", {}, "k_singlet_own<", "k_doublet_anf<", False, 3),
+    ("k2_a2f", "GP", 16, (0.0, 0.25), "fast", {"DMX_NO_ANF": "1"}, "k_singlet_own<", "k_doublet_a2f<", False, 3),
+    ("k2_generic", "GP", 8, A2, "strict", {"DMX_K2_GENERIC": "1"}, "k_singlet<", "k_doublet_generic<", False, 3),
+]
+
+
+def family_problem(eng, case, field, V, dense, deep, quals):
+    from demuxlet_amd import synth
+    seed = 31000 + 7 * V + sum(map(ord, case)) + {"full": 0, "edges": 1, "max": 2}[quals]
+    rng = np.random.default_rng(seed)
+    S, B = (131, 11) if dense else ((220, 12) if V > 64 else (300, 24))
+    raw = synth.make_raw_genotypes(rng, S, V)
+    g = genotypes(eng, rng, raw.alleles, field)
+    sp = mixed_depth_pileup(rng, raw.alleles, B, 0.3, quals=quals, dense=dense, deep=deep)
+    return g, sp
+
+
+@pytest.mark.parametrize("quals", ["full", "edges", "max"])
+@pytest.mark.parametrize("case,field,V,alphas,mode,env,k1,k2,dense,deep", FAMILIES, ids=[f[0] for f in FAMILIES])
+def test_kernel_family_against_oracle(eng, oracle, monkeypatch, case, field, V, alphas, mode, env, k1, k2, dense, deep, quals):
+    g, sp = family_problem(eng, case, field, V, dense, deep, quals)
+    bq = sp.reads & 0x7F
+    assert (bq == 127).all() if quals == "max" else (bq.min() <= 1 and bq.max() >= 126)
+    ref = oracle_run(oracle, sp, g, alphas)
+    for tname, tenv in TABLES.items():
+        out = run_with_env(eng, monkeypatch, g, sp, alphas, mode, {**env, **tenv})
+        names = out["names"]
+        assert names["singlet"].startswith(k1) and names["doublet"].startswith(k2), (tname, names)
+        d = max_diffs(out, ref, alphas, mode)
+        print(f"{case} {quals} {tname}: {names['singlet']} | {names['doublet']} | {names['certify']}: "
+              + " ".join(f"{k} {v:.2e}" for k, v in d.items()))
+        assert max(d.values()) < TOL, (tname, d)
+
+
+@pytest.mark.parametrize("depths", [(14, 15, 16, 17), (40,), (250, 300, 400)], ids=["14-17", "40", "hundreds"])
+@pytest.mark.parametrize("field,V", [("GT", 8), ("GP", 32), ("PL", 16), ("GT", 40)])
+@pytest.mark.parametrize("mode", ["strict", "fast"])
+def test_depth_edges_at_quality_127(eng, oracle, monkeypatch, field, V, mode, depths):
+    """Pairs of exactly 14..17 reads (both sides of kSafeReads = 15), 40 reads and a few hundred (u16 counts, the plain division), every
+    read at quality 127, half the pairs all-ALT on a hom-REF source row (or all-REF on a hom-ALT one): the likelihoods shrink by
+    err(127)/3 per read, the worst case of the division and of the final tables."""
+    from demuxlet_amd import synth
+    rng = np.random.default_rng(127000 + V + sum(depths) + (1 if mode == "fast" else 0))
+    S, B = (120, 8) if max(depths) > 100 else (300, 16)
+    raw = synth.make_raw_genotypes(rng, S, V)
+    g = genotypes(eng, rng, raw.alleles, field)
+    sp = mixed_depth_pileup(rng, raw.alleles, B, 0.25, quals="max", depths=depths, adversarial=0.5)
+    assert set(np.unique(sp.pair_nrd)) <= set(depths) and (sp.reads & 0x7F == 127).all()
+    ref = oracle_run(oracle, sp, g, A2)
+    for tname, tenv in TABLES.items():
+        out = run_with_env(eng, monkeypatch, g, sp, A2, mode, tenv)
+        d = max_diffs(out, ref, A2, mode)
+        print(f"{field} V={V} {mode} depths={depths} {tname}: {out['names']['singlet']} | {out['names']['doublet']}: "
+              + " ".join(f"{k} {v:.2e}" for k, v in d.items()))
+        assert max(d.values()) < TOL, (tname, d)

@@ -353,3 +353,20 @@ def test_refine_run_rounds(m, tmp_path):
     assert c1 >= c0, (c0, c1)
     lines = (tmp_path / "o.refined.tsv").read_text().splitlines()
     assert lines[0].startswith("RID\tPOS\tREF\tALT\tSM_ID\tN.CELL") and len(lines) > S
+
+
+@pytest.mark.parametrize("quals", ["full", "edges", "max"])
+@pytest.mark.parametrize("field", ["GT", "GP"])
+def test_refine_parity_quality_range(m, field, quals):
+    """Base qualities over 0..127 (the 0.75 error floor at q <= 1, err(127)) and the depth mix of tests/quality_mix.py: 0..6, 14..17 (both
+    sides of kSafeReads), 40 and u16 pairs of 256..300 reads, a share of them all-ALT on hom-REF rows (or the reverse)."""
+    from quality_mix import mixed_depth_pileup
+    rng = np.random.default_rng(8800 + len(field) + {"full": 0, "edges": 1, "max": 2}[quals])
+    S, V, B = 400, 8, 200
+    raw = m["synth"].make_raw_genotypes(rng, S, V)
+    g = make_prior(m, rng, raw, field)
+    sp = mixed_depth_pileup(rng, raw.alleles, B, 0.2, quals=quals, deep=4)
+    assert sp.pair_nrd.dtype == np.uint16
+    assign = sp.truth[:, 0].copy()
+    assign[sp.truth[:, 1] >= 0] = -1
+    check(m, sp, g, assign)

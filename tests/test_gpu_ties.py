@@ -44,9 +44,10 @@ def assert_same_file(got: Path, want: Path, what):
     raise AssertionError(f"{what}: {got.name} differs from the oracle's in {len(bad)} of {len(la)} rows; first:\n  got  {bad[0][1]}\n  want {bad[0][2]}")
 
 
-def tie_problem(eng, seed, V, field, B, S=60, groups=((0, 1), (2, 3, 4)), delta=0.15):
+def tie_problem(eng, seed, V, field, B, S=60, groups=((0, 1), (2, 3, 4)), delta=0.15, quals=None):
     """S SNPs x V samples in which the samples of every group carry IDENTICAL genotype rows (same raw field values, so the float32 rows are
-    bit-identical), and B barcodes covering about S*delta SNPs each (3-20 for the defaults), a third of them doublets."""
+    bit-identical), and B barcodes covering about S*delta SNPs each (3-20 for the defaults), a third of them doublets; `quals`: the reads'
+    base-quality profile (synth.draw_bq)."""
     from demuxlet_amd import synth
     rng = np.random.default_rng(seed)
     raw = synth.make_raw_genotypes(rng, S, V)
@@ -68,7 +69,7 @@ def tie_problem(eng, seed, V, field, B, S=60, groups=((0, 1), (2, 3, 4)), delta=
         for j in grp[1:]:
             if j < V:
                 assert np.array_equal(g[:, j], g[:, grp[0]])
-    sp = synth.make_pileup(rng, al, B, delta, 1.3, dense_layout=False, doublet_rate=0.35)
+    sp = synth.make_pileup(rng, al, B, delta, 1.3, dense_layout=False, doublet_rate=0.35, quals=quals)
     pl = eng.HostPileup(sp.n_cells, sp.n_snps, sp.cell_pair_off, sp.cell_read_off, sp.pair_snp, sp.pair_nrd, sp.reads, sp.rd_totl, sp.rd_pass, sp.rd_uniq)
     return g, pl
 
@@ -162,6 +163,18 @@ def test_identical_samples_and_few_snps(eng, oracle, tmp_path, V, field, alphas,
     n = np.diff(pl.cell_pair_off)
     assert 3 <= np.percentile(n, 10) and np.percentile(n, 90) <= 20
     run_both_paths(eng, oracle, tmp_path, g, pl, alphas, mode, f"V={V} {field} A={len(alphas)} {mode}", min_fetched_frac=0.05)
+
+
+@pytest.mark.parametrize("mode", ["strict", "fast"])
+@pytest.mark.parametrize("V,field", [(8, "GT"), (16, "GP"), (33, "GT"), (32, "PL")])
+def test_identical_samples_at_edge_qualities(eng, oracle, tmp_path, V, field, mode):
+    """The tie regime with base qualities at the engine's code-path edges (synth.EDGE_QUALS: the 0.75 error floor at q <= 1, the LDS, triple
+    and pair table limits 42 / 48 / 64, and up to 127): k_certify's seed and final tables and the host arbiter's MixTables (two reads below 64)
+    meet reads they do not cover.  All files byte-identical to the oracle's."""
+    g, pl = tie_problem(eng, 7200 + V, V, field, 200, quals="edges")
+    bq = pl.reads & 0x7F
+    assert bq.min() <= 1 and bq.max() >= 126 and ((bq >= 64).sum() > len(bq) // 10)
+    run_both_paths(eng, oracle, tmp_path, g, pl, (0.0, 0.5), mode, f"edge qualities V={V} {field} {mode}", min_fetched_frac=0.05)
 
 
 def test_every_sample_duplicated(eng, oracle, tmp_path):
