@@ -38,6 +38,7 @@ SYMBOLS = [
     "dmx_engine_cluster_stage", "dmx_engine_cluster_mstep", "dmx_engine_cluster_estep", "dmx_engine_get_cluster", "dmx_engine_get_cluster_stage",
     "dmx_engine_cluster_device_ptr", "dmx_engine_cluster_info",
     "dmx_engine_cluster_doublet", "dmx_engine_get_cluster_doublet", "dmx_engine_cluster_estep_doublet", "dmx_engine_cluster_doublet_info",
+    "dmx_engine_cluster_merge_score", "dmx_engine_cluster_estep_grouped", "dmx_engine_cluster_sm_info",
     "dmx_engine_ambient", "dmx_engine_get_ambient", "dmx_engine_ambient_info",
 ]
 
@@ -97,6 +98,17 @@ class ClusterEstepDoubletRequest(C.Structure):   # dmx_cluster_estep_doublet_req
 class ClusterDoubletInfo(C.Structure):    # dmx_cluster_doublet_info
     _fields_ = [("doublet_ms", C.c_double), ("estep_ms", C.c_double), ("lld_bytes", C.c_int64), ("n_cells", C.c_int32), ("n_restarts", C.c_int32),
                 ("n_clusters", C.c_int32), ("n_pairs", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterEstepGroupedRequest(C.Structure):   # dmx_cluster_estep_grouped_request
+    _fields_ = [("n_restarts", C.c_int32), ("n_clusters", C.c_int32), ("log_pi", C.c_void_p), ("temperature", C.c_double), ("mask", C.c_void_p),
+                ("group", C.c_void_p), ("restarts_per_group", C.c_int32), ("reserved0", C.c_int32), ("ll", C.c_void_p), ("col_sum", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class ClusterSmInfo(C.Structure):         # dmx_cluster_sm_info
+    _fields_ = [("merge_ms", C.c_double), ("grouped_estep_ms", C.c_double), ("n_restarts", C.c_int32), ("n_clusters", C.c_int32),
+                ("n_pairs", C.c_int32), ("n_chunks", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class AmbientRequest(C.Structure):       # dmx_ambient_request
@@ -241,6 +253,8 @@ def load() -> C.CDLL:
         "dmx_engine_cluster_info": [vp, vp],
         "dmx_engine_cluster_doublet": [vp, i32, i32], "dmx_engine_get_cluster_doublet": [vp, vp, vp], "dmx_engine_cluster_estep_doublet": [vp, vp],
         "dmx_engine_cluster_doublet_info": [vp, vp],
+        "dmx_engine_cluster_merge_score": [vp, i32, i32, vp, C.c_double, vp, vp], "dmx_engine_cluster_estep_grouped": [vp, vp],
+        "dmx_engine_cluster_sm_info": [vp, vp],
         "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],
     }
     for name, args in sig.items():

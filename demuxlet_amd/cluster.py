@@ -13,8 +13,12 @@ With em_doublets (--em-doublets) each restart also has a d
 50/50 mixture (alpha = 0.5) with prior share delta_r: cluster_doublet scores them after K1, cluster_estep_doublet gives the singlet
 weights (a doublet's mass goes to no cluster) and the doublet mass from which delta_r is re-estimated.
 
+With split_merge (--split-merge) the winning restart then goes through split-merge moves: merge scores of every
+pair of its clusters (cluster_merge_score), a 2-component sub-EM inside every cluster (cluster_estep_grouped), and candidate restarts
+that merge one pair and split one cluster into the freed column; the best candidate replaces the winner when its converged LL is higher.
+
     python -m demuxlet_amd.cluster --pileup <x>.pileup.txt --n-clusters K --out <prefix> [--restarts R] [--seed S] [--max-iter N]
-        [--tol T] [--floor F] [--min-snp M] [--alpha A ...] [--rounds N] [--match] [--em-doublets] [--fast] [--gpu G]
+        [--tol T] [--floor F] [--min-snp M] [--alpha A ...] [--rounds N] [--match] [--em-doublets] [--split-merge] [--fast] [--gpu G]
 
 reads the dump that `demuxlet --pileup-only` writes; its genotype matrix is ignored unless --match is given."""
 from __future__ import annotations
@@ -38,6 +42,11 @@ EM_HEADER_DBL = "ITER\tRESTART\tLLK\tPI\tDBL\n"
 # [DELTA_MIN, DELTA_MAX] (a share above one half would let the doublet components absorb a cluster)
 DELTA0, DELTA_MIN, DELTA_MAX = 0.1, 1e-3, 0.5
 MATCH_HEADER = "CLUST\tSM_ID\tN.CELL\tSUM.LLK\tBEST\n"
+# split-merge moves: the top A merges x top S splits are the candidates of a move, each split by the best of Rs random-half sub-restarts
+SM_CANDIDATES = (3, 3)
+SM_SPLIT_RESTARTS = 4
+SM_MAX_K = 64               # dmx_engine_cluster_merge_score stages K columns per SNP in LDS
+MOVES_HEADER = "MOVE\tCAND\tMERGE_K\tMERGE_L\tSPLIT\tBF\tSPLIT_GAIN\tLLK_BEFORE\tLLK_AFTER\tITER\tACCEPTED\n"
 
 
 def cluster_ids(k: int) -> List[str]:
@@ -60,6 +69,33 @@ def check_args(n_clusters: int, restarts: int, max_iter: int, tol: float, floor:
         raise ValueError(f"empty pileup: {n_cells} barcodes, {n_pairs} covered (barcode, SNP) pairs for {n_clusters} clusters")
 
 
+def check_sm_args(n_clusters: int, candidates: Sequence[int], split_restarts: int, max_moves: Optional[int]) -> None:
+    """The error paths of split_merge=True, before any device work."""
+    a, b = (int(x) for x in candidates)
+    if n_clusters > SM_MAX_K:
+        raise ValueError(f"split-merge moves support at most {SM_MAX_K} clusters, not {n_clusters}")
+    if a < 1 or b < 1 or split_restarts < 1:
+        raise ValueError("--sm-candidates and --sm-split-restarts must be >= 1")
+    if a * b * n_clusters > MAX_COLUMNS or 2 * split_restarts * n_clusters > MAX_COLUMNS:
+        raise ValueError(f"{a} x {b} candidates or {split_restarts} split restarts of {n_clusters} clusters exceed {MAX_COLUMNS} columns")
+    if max_moves is not None and max_moves < 0:
+        raise ValueError(f"--sm-max-moves {max_moves}: at least 0")
+
+
+def check_init_labels(labels, n_cells: int, n_clusters: int) -> np.ndarray:
+    """init_labels as int32 [R][B] with every entry in [-1, K) (-1: the barcode takes no part in the first M-step)."""
+    lab = np.asarray(labels)
+    if lab.ndim == 1:
+        lab = lab[None, :]
+    if lab.ndim != 2 or lab.shape[1] != n_cells or lab.shape[0] < 1:
+        raise ValueError(f"init_labels must be [R][{n_cells}], not {lab.shape}")
+    if not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError("init_labels must be integers")
+    if lab.size and (lab.min() < -1 or lab.max() >= n_clusters):
+        raise ValueError(f"init_labels must be in [-1, {n_clusters})")
+    return np.ascontiguousarray(lab, dtype=np.int32)
+
+
 def hwe_prior(n_ref: np.ndarray, n_alt: np.ndarray) -> np.ndarray:
     """q[S][3] float32 = Hardy-Weinberg genotype frequencies of p = (n_alt + 1) / (n_ref + n_alt + 2), the pooled ALT frequency."""
     p = (np.asarray(n_alt, dtype=np.float64) + 1.0) / (np.asarray(n_ref, dtype=np.float64) + np.asarray(n_alt, dtype=np.float64) + 2.0)
@@ -77,7 +113,8 @@ def one_hot_weights(labels: np.ndarray, n_clusters: int, mask: Optional[np.ndarr
     R, B = labels.shape
     w = np.zeros((B, R * n_clusters))
     for r in range(R):
-        w[np.arange(B), r * n_clusters + labels[r]] = 1.0
+        on = labels[r] >= 0                         # init_labels may leave a barcode out (-1)
+        w[np.flatnonzero(on), r * n_clusters + labels[r][on]] = 1.0
     if mask is not None:
         w[~np.asarray(mask, dtype=bool)] = 0.0
     return w
@@ -168,15 +205,246 @@ def match_labels(truth: np.ndarray, pred: np.ndarray, n_truth: int, n_pred: int)
     return out
 
 
+# ---- split-merge moves: pure functions the CPU tests reach ---------------------------------------------------------
+def rank_candidates(bf: np.ndarray, gain: np.ndarray, n_merge: int, n_split: int) -> List[Tuple[int, int, int]]:
+    """The candidates (k, l, m) of one move: the n_merge pairs (k, l) of highest BF (pair_index order) and the n_split clusters m of highest
+    gain, merges outer and splits inner, each in descending score with the lower index first on a tie; a combination with m in {k, l}
+    and a split of non-finite gain (a cluster too small to split) are skipped."""
+    bf, gain = np.asarray(bf, dtype=np.float64), np.asarray(gain, dtype=np.float64)
+    K = gain.shape[0]
+    pairs = pair_index(K)
+    merges = np.argsort(-bf, kind="stable")[:n_merge]
+    ok = np.flatnonzero(np.isfinite(gain))
+    splits = ok[np.argsort(-gain[ok], kind="stable")][:n_split]
+    return [(int(pairs[p][0]), int(pairs[p][1]), int(m)) for p in merges for m in splits if m not in (pairs[p][0], pairs[p][1])]
+
+
+def best_candidate(ll: np.ndarray, tol: float) -> int:
+    """The candidate to accept: the first (the best ranked) whose converged LL is within tol * |LL| of the highest, since candidates that
+    reach the same optimum differ only by the EM's convergence tolerance."""
+    ll = np.asarray(ll, dtype=np.float64)
+    top = ll.max()
+    return int(np.flatnonzero(ll >= top - tol * abs(top))[0])
+
+
+def split_groups(w: np.ndarray, mask: Optional[np.ndarray] = None) -> np.ndarray:
+    """group[B] int32: each barcode's hard label, the argmax of its E-step weights w[B][K] (the lowest cluster on a tie); -1 for a barcode
+    outside the mask or with a singlet mass below 0.5 (with em_doublets the weights sum to 1 - the doublet mass)."""
+    w = np.asarray(w, dtype=np.float64)
+    g = np.argmax(w, axis=1).astype(np.int32) if w.shape[1] else np.zeros(w.shape[0], dtype=np.int32)
+    off = w.sum(axis=1) < 0.5
+    if mask is not None:
+        off |= ~np.asarray(mask, dtype=bool)
+    g[off] = -1
+    return g
+
+
+def sub_restart_weights(group: np.ndarray, n_clusters: int, split_restarts: int, seed) -> np.ndarray:
+    """w[B][K * Rs * 2]: the one-hot start of the sub-EM.  Sub-restart s of cluster m (restart m * Rs + s, columns 2 (m Rs + s) + {0, 1})
+    gives every barcode of group m a random half, drawn from np.random.default_rng(seed) as integers(0, 2, size=(Rs, B)); barcodes of
+    group -1 get no weight."""
+    group = np.asarray(group, dtype=np.int64)
+    B, Rs = group.shape[0], int(split_restarts)
+    half = np.random.default_rng(seed).integers(0, 2, size=(Rs, B))
+    w = np.zeros((B, n_clusters * Rs * 2))
+    idx = np.flatnonzero(group >= 0)
+    for s in range(Rs):
+        w[idx, 2 * (group[idx] * Rs + s) + half[s, idx]] = 1.0
+    return w
+
+
+def split_gain(ll_sub: np.ndarray, llks: np.ndarray, group: np.ndarray, split_restarts: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(gain[K], best[K]): best[m] = the sub-restart of highest LL (the lowest on a tie), gain[m] = max_s ll_sub[m, s] - the sum over the
+    barcodes of group m of llks[b][m]; -inf for a cluster of fewer than two barcodes."""
+    K = llks.shape[1]
+    ll = np.asarray(ll_sub, dtype=np.float64).reshape(K, split_restarts)
+    best = np.argmax(ll, axis=1)
+    group = np.asarray(group)
+    gain = np.full(K, -np.inf)
+    for m in range(K):
+        mine = group == m
+        if np.count_nonzero(mine) >= 2:
+            gain[m] = ll[m, best[m]] - llks[mine, m].sum()
+    return gain, best
+
+
+def split_posteriors(w_sub: np.ndarray, group: np.ndarray, best: np.ndarray, split_restarts: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(s_a[K][B], s_b[K][B]): the sub-EM posteriors of the two halves of cluster m, from its best sub-restart; a barcode outside group m
+    gets 1/2 and 1/2, so that s_a + s_b = 1 and a split keeps all of cluster m's mass."""
+    K = len(best)
+    group = np.asarray(group)
+    s_a, s_b = np.full((K, group.shape[0]), 0.5), np.full((K, group.shape[0]), 0.5)
+    for m in range(K):
+        mine = group == m
+        c = 2 * (m * split_restarts + int(best[m]))
+        a, b = w_sub[mine, c], w_sub[mine, c + 1]
+        tot = a + b
+        s_a[m, mine] = np.where(tot > 0, a / np.where(tot > 0, tot, 1.0), 0.5)
+        s_b[m, mine] = 1.0 - s_a[m, mine]
+    return s_a, s_b
+
+
+def candidate_weights(w: np.ndarray, cands: Sequence[Tuple[int, int, int]], s_a: np.ndarray, s_b: np.ndarray) -> np.ndarray:
+    """[B][n * K]: candidate j = (k, l, m) is restart j: column k gets w_k + w_l, column l gets w_m * s_a[m], column m gets w_m * s_b[m];
+    every other column keeps w."""
+    w = np.asarray(w, dtype=np.float64)
+    B, K = w.shape
+    out = np.empty((B, len(cands) * K))
+    for j, (k, l, m) in enumerate(cands):
+        c = w.copy()
+        c[:, k] = w[:, k] + w[:, l]
+        c[:, l] = w[:, m] * s_a[m]
+        c[:, m] = w[:, m] * s_b[m]
+        out[:, j * K:(j + 1) * K] = c
+    return out
+
+
+def write_moves_tsv(path: str, rows: Sequence[dict]) -> None:
+    """<prefix>.moves.tsv: one row per evaluated candidate (MOVES_HEADER); MERGE_K < MERGE_L is the merged pair, SPLIT the split cluster,
+    LLK_BEFORE the current LL, LLK_AFTER the candidate's converged LL after ITER iterations, ACCEPTED 1 for the move's accepted candidate."""
+    with open(path, "w") as f:
+        f.write(MOVES_HEADER)
+        for r in rows:
+            f.write(f"{r['move']}\t{r['cand']}\t{r['merge_k']}\t{r['merge_l']}\t{r['split']}\t{r['bf']:.6f}\t{r['gain']:.6f}\t"
+                    f"{r['ll_before']:.6f}\t{r['ll_after']:.6f}\t{r['iterations']}\t{int(r['accepted'])}\n")
+
+
+def em_loop(eng, pl, S: int, R: int, K: int, q: np.ndarray, floor: float, log_pi: np.ndarray, delta: np.ndarray, mask, n_mask: int,
+            max_iter: int, tol: float, temperature: float, em_doublets: bool, em_rows: Optional[list] = None):
+    """The EM iterations of R restarts x K clusters after a first M-step (module docstring): returns (ll[R] of the last E-step, log_pi and
+    delta after it, iterations).  The engine ends with the M-step of the last E-step's weights."""
+    dense = pl.pair_snp is None
+    prev = None
+    it = 0
+    ll = None
+    for it in range(1, max_iter + 1):
+        eng.set_genotypes_device(eng.cluster_device_ptr(), S)
+        if dense:
+            eng.set_pileup(pl)          # a dense pileup's SNP-minor copy of the matrix is made when it is staged
+        eng.run_singlet()
+        if em_doublets:
+            eng.cluster_doublet(R, K)
+            ll, cs, dm = eng.cluster_estep_doublet(R, K, log_pi, np.log(delta), temperature, mask)
+            if em_rows is not None:
+                em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r]), float(delta[r])) for r in range(R)]
+            delta = update_delta(dm, n_mask)
+        else:
+            ll, cs = eng.cluster_estep(R, K, log_pi, temperature, mask)
+            if em_rows is not None:
+                em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r])) for r in range(R)]
+        log_pi = update_log_pi(cs, R, K)
+        eng.cluster_mstep(None, q, floor, fetch=False)
+        if converged(prev, ll, tol):
+            break
+        prev = ll
+    return ll, log_pi, delta, it
+
+
+def sub_em(eng, pl, S: int, K: int, Rs: int, q: np.ndarray, floor: float, w0: np.ndarray, group: np.ndarray, max_iter: int, tol: float):
+    """The 2-component sub-EM inside every cluster at once: restarts m * Rs + s of K * Rs, the grouped E-step restricting restart r to
+    group r // Rs.  Returns (ll[K * Rs], the last E-step's weights [B][K * Rs * 2])."""
+    R2 = K * Rs
+    dense = pl.pair_snp is None
+    eng.cluster_mstep(w0, q, floor, fetch=False)
+    log_pi = np.full((R2, 2), -np.log(2.0))
+    prev = None
+    for _ in range(max_iter):
+        eng.set_genotypes_device(eng.cluster_device_ptr(), S)
+        if dense:
+            eng.set_pileup(pl)
+        eng.run_singlet()
+        ll, cs = eng.cluster_estep_grouped(R2, 2, log_pi, group, Rs)
+        log_pi = update_log_pi(cs, R2, 2)
+        eng.cluster_mstep(None, q, floor, fetch=False)
+        if prev is not None and np.all(np.abs(ll - prev) <= tol * np.abs(ll)):    # <=: an empty group's LL stays exactly 0
+            break
+        prev = ll
+    return ll, eng.cluster_weights()
+
+
+def _staged_engine(V: int, pl, S: int, alphas, doublet_prior: float, device: int, mode: int):
+    e = engine.Engine(V, alphas, doublet_prior, device=device, mode=mode)
+    e.set_genotypes(np.full((S, V, 3), 1.0 / 3.0, dtype=np.float32))
+    e.set_pileup(pl)
+    e.cluster_stage()
+    return e
+
+
+def split_merge_moves(eng, r_cur: int, R_cur: int, ll_cur: float, delta_cur: float, pl, S: int, K: int, q: np.ndarray, floor: float, mask,
+                      n_mask: int, max_iter: int, tol: float, temperature: float, em_doublets: bool, seed: int, max_moves: int,
+                      candidates: Sequence[int], split_restarts: int, alphas, doublet_prior: float, device: int, mode: int):
+    """Split-merge moves from restart r_cur of R_cur restarts in `eng` (whose last M-step holds that restart's final weights): merge
+    scores, the sub-EM, the candidates as restarts of a normal EM, acceptance by converged LL; repeated until a move is rejected or
+    max_moves.  Returns (gp[S][K][3] of the accepted state, or None when no move was accepted; the rows of .moves.tsv).  The engines it
+    makes are closed; `eng` is left to the caller."""
+    rows: List[dict] = []
+    if K < 3 or max_moves < 1:
+        return None, rows                  # K = 2: every split overlaps the merged pair
+    Rs = int(split_restarts)
+    n_merge, n_split = (int(x) for x in candidates)
+    cur, cur_owned, g_acc = eng, False, None
+    sub = _staged_engine(K * Rs * 2, pl, S, alphas, doublet_prior, device, mode)
+    try:
+        for move in range(1, max_moves + 1):
+            bf, _ = cur.cluster_merge_score(R_cur, K, q, floor)
+            bf = bf[r_cur]
+            w_cur = cur.cluster_weights()[:, r_cur * K:(r_cur + 1) * K]
+            llks = cur.get_singlet()[0][:, r_cur * K:(r_cur + 1) * K]
+            group = split_groups(w_cur, mask)
+            ll_sub, w_sub = sub_em(sub, pl, S, K, Rs, q, floor, sub_restart_weights(group, K, Rs, [seed, move]), group, max_iter, tol)
+            gain, best = split_gain(ll_sub, llks, group, Rs)
+            cands = rank_candidates(bf, gain, n_merge, n_split)
+            if not cands:
+                break
+            s_a, s_b = split_posteriors(w_sub, group, best, Rs)
+            wc = candidate_weights(w_cur, cands, s_a, s_b)
+            n = len(cands)
+            ce = _staged_engine(n * K, pl, S, alphas, doublet_prior, device, mode)
+            try:
+                ce.cluster_mstep(wc, q, floor, fetch=False)
+                log_pi = update_log_pi(wc.sum(axis=0), n, K)
+                ll_c, _, delta_c, it_c = em_loop(ce, pl, S, n, K, q, floor, log_pi, np.full(n, delta_cur), mask, n_mask, max_iter, tol,
+                                                 temperature, em_doublets)
+            except BaseException:
+                ce.close()
+                raise
+            j = best_candidate(ll_c, tol)
+            ok = bool(ll_c[j] - ll_cur > tol * abs(ll_cur))
+            pairs = {(k, l): p for p, (k, l) in enumerate(pair_index(K).tolist())}
+            for c, (k, l, m) in enumerate(cands):
+                rows.append(dict(move=move, cand=c, merge_k=k, merge_l=l, split=m, bf=float(bf[pairs[(k, l)]]), gain=float(gain[m]),
+                                 ll_before=float(ll_cur), ll_after=float(ll_c[c]), iterations=it_c, accepted=ok and c == j))
+            if not ok:
+                ce.close()
+                break
+            if cur_owned:
+                cur.close()
+            cur, cur_owned, r_cur, R_cur = ce, True, j, n
+            ll_cur, delta_cur = float(ll_c[j]), float(delta_c[j])
+            _, _, gp = cur.get_cluster(S)
+            g_acc = np.ascontiguousarray(gp[:, j * K:(j + 1) * K, :])
+    finally:
+        sub.close()
+        if cur_owned:
+            cur.close()
+    return g_acc, rows
+
+
 def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int = 16, seed: int = 0, max_iter: int = 50, tol: float = 1e-7,
                 floor: float = 1e-3, min_snp: int = 0, alphas: Sequence[float] = (0.0, 0.5), rounds: int = 1,
                 match: Optional[Tuple[np.ndarray, Sequence[str]]] = None, barcodes: Optional[Sequence[str]] = None, device: int = 0,
                 mode: int = capi.DMX_MODE_STRICT, doublet_prior: float = 0.5, temperature: float = 1.0,
-                snps: Optional[Sequence[Tuple]] = None, em_doublets: bool = False) -> dict:
+                snps: Optional[Sequence[Tuple]] = None, em_doublets: bool = False, init_labels: Optional[np.ndarray] = None,
+                split_merge: bool = False, sm_max_moves: Optional[int] = None, sm_candidates: Sequence[int] = SM_CANDIDATES,
+                sm_split_restarts: int = SM_SPLIT_RESTARTS) -> dict:
     """EM clustering of the barcodes of `store_or_pileup` (a Store, or a HostPileup with barcodes=...) into n_clusters donors, then
     the final demultiplexing pass and `rounds` hard-refine rounds (module docstring).  `match` = (g[S][NV][3], sample_ids) scores each
-    cluster against genotyped samples (<prefix>.match.tsv).  Returns a dict: the winning restart, per-restart LL, iterations, the
-    cluster genotype matrix gp[S][K][3] and the prior q[S][3]; with em_doublets also `delta`, the winning restart's doublet share."""
+    cluster against genotyped samples (<prefix>.match.tsv).  `init_labels` ([R][B] int, values in [-1, K); -1 = no weight in the first
+    M-step) replaces the seeded random start, e.g. to start from an earlier clustering; its R replaces `restarts`.  With split_merge the
+    winning restart goes through split-merge moves (at most sm_max_moves, default K; sm_candidates = (merges, splits) per move,
+    sm_split_restarts random-half sub-restarts per split) and <prefix>.moves.tsv records every candidate.  Returns a dict: the winning
+    restart, per-restart LL, iterations, the cluster genotype matrix gp[S][K][3] and the prior q[S][3]; with em_doublets also `delta`,
+    the winning restart's doublet share; with split_merge also `moves`, the rows of .moves.tsv."""
     if isinstance(store_or_pileup, engine.HostPileup):
         pl = store_or_pileup
         if barcodes is None:
@@ -184,12 +452,17 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
     else:
         pl, barcodes = store_or_pileup.freeze(), store_or_pileup.barcodes()
     B, S, K, R = pl.n_cells, pl.n_snps, int(n_clusters), int(restarts)
+    if init_labels is not None:
+        init_labels = check_init_labels(init_labels, B, K)
+        R = init_labels.shape[0]
     check_args(K, R, max_iter, tol, floor, B, len(pl.pair_nrd))
+    if split_merge:
+        check_sm_args(K, sm_candidates, sm_split_restarts, sm_max_moves)
     C = R * K
     mask = pl.n_snp_per_cell >= min_snp if min_snp > 0 else None
     kw = dict(barcodes=barcodes, doublet_prior=doublet_prior, device=device, mode=mode, min_snp=min_snp)
-    dense = pl.pair_snp is None
     eng = engine.Engine(C, alphas, doublet_prior, device=device, mode=mode)
+    moves: List[dict] = []
     em_rows = []
     try:
         # prior: pooled REF / ALT counts of every barcode (one refinement with all barcodes in column 0)
@@ -201,36 +474,27 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
         q = hwe_prior(n_ref[:, 0], n_alt[:, 0])
         eng.cluster_stage()
         # first M-step from each restart's random hard assignment, pi uniform
-        eng.cluster_mstep(one_hot_weights(initial_labels(seed, R, B, K), K, mask), q, floor, fetch=False)
+        labels = init_labels if init_labels is not None else initial_labels(seed, R, B, K)
+        eng.cluster_mstep(one_hot_weights(labels, K, mask), q, floor, fetch=False)
         log_pi = np.full((R, K), -np.log(K))
         delta = np.full(R, DELTA0)
         n_mask = B if mask is None else int(np.count_nonzero(mask))
-        prev = None
-        it = 0
-        for it in range(1, max_iter + 1):
-            eng.set_genotypes_device(eng.cluster_device_ptr(), S)
-            if dense:
-                eng.set_pileup(pl)          # a dense pileup's SNP-minor copy of the matrix is made when it is staged
-            eng.run_singlet()
-            if em_doublets:
-                eng.cluster_doublet(R, K)
-                ll, cs, dm = eng.cluster_estep_doublet(R, K, log_pi, np.log(delta), temperature, mask)
-                em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r]), float(delta[r])) for r in range(R)]
-                delta = update_delta(dm, n_mask)
-            else:
-                ll, cs = eng.cluster_estep(R, K, log_pi, temperature, mask)
-                em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r])) for r in range(R)]
-            log_pi = update_log_pi(cs, R, K)
-            eng.cluster_mstep(None, q, floor, fetch=False)
-            if converged(prev, ll, tol):
-                break
-            prev = ll
+        ll, log_pi, delta, it = em_loop(eng, pl, S, R, K, q, floor, log_pi, delta, mask, n_mask, max_iter, tol, temperature, em_doublets,
+                                        em_rows)
         win = best_restart(ll)
         _, _, gp = eng.get_cluster(S)
         g = np.ascontiguousarray(gp[:, win * K:(win + 1) * K, :])
+        if split_merge:
+            g_sm, moves = split_merge_moves(eng, win, R, float(ll[win]), float(delta[win]), pl, S, K, q, floor, mask, n_mask, max_iter, tol,
+                                            temperature, em_doublets, seed, K if sm_max_moves is None else int(sm_max_moves), sm_candidates,
+                                            sm_split_restarts, alphas, doublet_prior, device, mode)
+            if g_sm is not None:
+                g = g_sm
     finally:
         eng.close()
     write_em_tsv(out_prefix + ".em.tsv", em_rows, doublets=em_doublets)
+    if split_merge:
+        write_moves_tsv(out_prefix + ".moves.tsv", moves)
     ids = cluster_ids(K)
     engine.demuxlet_run(pl, g, ids, alphas, out_prefix, **kw)
     # hard-refine rounds: the previous round's singlets only, prior q for every cluster
@@ -269,6 +533,8 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
     res = dict(restart=win, ll=ll, iterations=it, gp=g, prior=q, last_prefix=prev_prefix)
     if em_doublets:
         res["delta"] = float(delta[win])
+    if split_merge:
+        res["moves"] = moves
     return res
 
 
@@ -289,6 +555,12 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--match", action="store_true", help="score the clusters against the dump's genotyped samples (<out>.match.tsv)")
     ap.add_argument("--em-doublets", action="store_true",
                     help="doublet components (alpha = 0.5) for every pair of clusters in the EM; <out>.em.tsv gains a DBL column")
+    ap.add_argument("--split-merge", action="store_true",
+                    help="split-merge moves on the winning restart after the EM (DESIGN.md section 16); writes <out>.moves.tsv")
+    ap.add_argument("--sm-max-moves", type=int, default=None, help="at most this many accepted moves (default K)")
+    ap.add_argument("--sm-candidates", type=int, nargs=2, default=list(SM_CANDIDATES), metavar=("MERGES", "SPLITS"),
+                    help="top merges x top splits evaluated per move (default 3 3)")
+    ap.add_argument("--sm-split-restarts", type=int, default=SM_SPLIT_RESTARTS, help="random-half sub-restarts per split (default 4)")
     ap.add_argument("--fast", action="store_true", help="DMX_MODE_FAST for every pass")
     ap.add_argument("--gpu", type=int, default=0)
     a = ap.parse_args(argv)
@@ -310,7 +582,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     cluster_run(d.pileup, a.n_clusters, a.out, restarts=a.restarts, seed=a.seed, max_iter=a.max_iter, tol=a.tol, floor=a.floor,
                 min_snp=a.min_snp, alphas=a.alpha, rounds=a.rounds, match=match, barcodes=d.barcodes, device=a.gpu,
                 mode=capi.DMX_MODE_FAST if a.fast else capi.DMX_MODE_STRICT, doublet_prior=a.doublet_prior, snps=d.snps,
-                em_doublets=a.em_doublets)
+                em_doublets=a.em_doublets, split_merge=a.split_merge, sm_max_moves=a.sm_max_moves, sm_candidates=tuple(a.sm_candidates),
+                sm_split_restarts=a.sm_split_restarts)
     return 0
 
 

@@ -2191,14 +2191,12 @@ __global__ __launch_bounds__(256) void k_cluster_mstep(const int64_t* __restrict
 
 // E-step.  One thread per (barcode b, restart r), columns rK .. rK + K - 1 of K1's llks[B][C]:
 //   a_k = (llks[b][rK + k] + log_pi[r][k]) / T,  w[b][rK + k] = exp(a_k - max a) / sum;  lse[b][r] = logsumexp_k(llks + log_pi);
-// a barcode outside the mask gets w = 0 and lse = 0.
-__global__ __launch_bounds__(256) void k_cluster_estep(const double* __restrict__ llks, int32_t B, int32_t R, int32_t K, const double* __restrict__ log_pi,
-                                                       double inv_t, const uint8_t* __restrict__ mask, double* __restrict__ w, double* __restrict__ lse) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= (int64_t)B * R) return;
-  const int32_t b = (int32_t)(t / R), r = (int32_t)(t % R);
+// a barcode outside the mask gets w = 0 and lse = 0.  The body is shared with the grouped E-step (k_cluster_estep_grp, section 16).
+__device__ __forceinline__ void cluster_estep_one(const double* __restrict__ llks, int32_t b, int32_t r, int32_t R, int32_t K,
+                                                  const double* __restrict__ log_pi, double inv_t, bool in, double* __restrict__ w,
+                                                  double* __restrict__ lse) {
   const size_t C = (size_t)R * K, o = (size_t)b * C + (size_t)r * K;
-  if (mask && !mask[b]) {
+  if (!in) {
     for (int32_t k = 0; k < K; ++k) w[o + k] = 0.0;
     lse[(size_t)b * R + r] = 0.0;
     return;
@@ -2217,6 +2215,13 @@ __global__ __launch_bounds__(256) void k_cluster_estep(const double* __restrict_
   const double y = 1.0 / s;
   for (int32_t k = 0; k < K; ++k) w[o + k] *= y;
   lse[(size_t)b * R + r] = m1 + log(s1);
+}
+__global__ __launch_bounds__(256) void k_cluster_estep(const double* __restrict__ llks, int32_t B, int32_t R, int32_t K, const double* __restrict__ log_pi,
+                                                       double inv_t, const uint8_t* __restrict__ mask, double* __restrict__ w, double* __restrict__ lse) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)B * R) return;
+  const int32_t b = (int32_t)(t / R), r = (int32_t)(t % R);
+  cluster_estep_one(llks, b, r, R, K, log_pi, inv_t, !(mask && !mask[b]), w, lse);
 }
 
 // The E-step's sums in a fixed order: chunk partials over kEChunk consecutive barcodes (one thread per output column, serial over the
@@ -2392,6 +2397,122 @@ __global__ __launch_bounds__(256) void k_cluster_estep_dbl(const double* __restr
   for (int32_t k = 0; k < K; ++k) w[o + k] *= y;
   dm[(size_t)b * R + r] = sd * y;
   lse[(size_t)b * R + r] = m1 + log(s1);
+}
+
+// ---- split-merge moves (dmx_engine_cluster_merge_score / _estep_grouped) ------------------------------------------
+// The M-step's own genotype prior at SNP i: log pi[g] = log((q[i][g] + floor) / sum over g of (q + floor)), and a three-term logsumexp.
+// One definition for the marginal and the pair kernels, so that the two read the same bits.
+__device__ __forceinline__ void sm_log_prior(const float* __restrict__ q, double floor_, int32_t i, double lp[3]) {
+  const double a0 = (double)q[(size_t)i * 3] + floor_, a1 = (double)q[(size_t)i * 3 + 1] + floor_, a2 = (double)q[(size_t)i * 3 + 2] + floor_;
+  const double s = a0 + a1 + a2;
+  lp[0] = log(a0 / s); lp[1] = log(a1 / s); lp[2] = log(a2 / s);
+}
+__device__ __forceinline__ double sm_lse3(double x0, double x1, double x2) {
+  const double m = fmax(fmax(x0, x1), x2);
+  return m + log(exp(x0 - m) + exp(x1 - m) + exp(x2 - m));
+}
+
+// The per-column marginal of the last M-step: one thread per (SNP i, column c) of its C columns,
+//   A[i][c] = lse_g(log pi[i][g] + LL[i][c][g]),  F[i][c] = (W[i][c] > 0).
+__global__ __launch_bounds__(256) void k_cluster_marg(const double* __restrict__ LL, const double* __restrict__ W, const float* __restrict__ q,
+                                                      double floor_, int32_t S, int32_t C, double* __restrict__ A, uint8_t* __restrict__ F) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)S * C) return;
+  const int32_t i = (int32_t)(t / C);
+  double lp[3];
+  sm_log_prior(q, floor_, i, lp);
+  A[t] = sm_lse3(lp[0] + LL[3 * t], lp[1] + LL[3 * t + 1], lp[2] + LL[3 * t + 2]);
+  F[t] = W[t] > 0.0 ? 1 : 0;
+}
+
+// Merge scores, partial over one chunk of kSmChunk SNPs: one workgroup per (chunk, restart r); thread t owns the pairs t, t + 256, ...
+// (p = (k, l), k < l, lexicographic; P <= 2016 for K <= 64, so at most kSmPairs per thread).  The chunk's K LL rows, A values, flags and
+// log priors go through LDS kSmStage SNPs at a time.  Per pair, over the SNPs in ascending order where both flags are set:
+//   acc += (lse_g(log pi[g] + LL[i][rK + k][g] + LL[i][rK + l][g]) - A[i][rK + k]) - A[i][rK + l],  n += 1,
+// serially from 0.  The chunk size is part of the contract (k_cluster_merge_fold adds the chunks in ascending order); a pair's bits
+// depend on its two columns' values only: not on the grid, R, the restart's position in the engine or what ran before.
+constexpr int kSmChunk = 256, kSmStage = 16, kSmMaxK = 64, kSmPairs = 8;
+__global__ __launch_bounds__(256) void k_cluster_merge_part(const double* __restrict__ LL, const double* __restrict__ A, const uint8_t* __restrict__ F,
+                                                            const float* __restrict__ q, double floor_, int32_t S, int32_t C, int32_t K, int32_t P,
+                                                            double* __restrict__ part, int32_t* __restrict__ npart) {
+  __shared__ double sLL[kSmStage][3 * kSmMaxK];
+  __shared__ double sA[kSmStage][kSmMaxK];
+  __shared__ double sLp[kSmStage][3];
+  __shared__ uint8_t sF[kSmStage][kSmMaxK];
+  const int32_t ch = blockIdx.x, r = blockIdx.y, nch = gridDim.x;
+  int32_t pk[kSmPairs], pl[kSmPairs];
+  bool act[kSmPairs];
+#pragma unroll
+  for (int u = 0; u < kSmPairs; ++u) {
+    int32_t rem = (int32_t)threadIdx.x + 256 * u, k = 0;
+    act[u] = rem < P;
+    if (!act[u]) rem = 0;                                    // inactive slot: skipped below, never written
+    while (rem >= K - 1 - k) { rem -= K - 1 - k; ++k; }
+    pk[u] = k; pl[u] = k + 1 + rem;
+  }
+  double acc[kSmPairs];
+  int32_t cnt[kSmPairs];
+#pragma unroll
+  for (int u = 0; u < kSmPairs; ++u) { acc[u] = 0.0; cnt[u] = 0; }
+  const int32_t i0 = ch * kSmChunk, i1 = min(S, i0 + kSmChunk);
+  const size_t c0 = (size_t)r * K;
+  for (int32_t s0 = i0; s0 < i1; s0 += kSmStage) {
+    const int32_t n = min(kSmStage, i1 - s0);
+    __syncthreads();
+    for (int32_t x = threadIdx.x; x < n * K; x += blockDim.x) {
+      const int32_t j = x / K, c = x - j * K;
+      const size_t o = (size_t)(s0 + j) * C + c0 + c;
+      sLL[j][3 * c] = LL[3 * o]; sLL[j][3 * c + 1] = LL[3 * o + 1]; sLL[j][3 * c + 2] = LL[3 * o + 2];
+      sA[j][c] = A[o]; sF[j][c] = F[o];
+    }
+    if ((int32_t)threadIdx.x < n) sm_log_prior(q, floor_, s0 + threadIdx.x, sLp[threadIdx.x]);
+    __syncthreads();
+    for (int32_t j = 0; j < n; ++j) {
+#pragma unroll
+      for (int u = 0; u < kSmPairs; ++u) {
+        const int32_t k = pk[u], l = pl[u];
+        if (act[u] && sF[j][k] && sF[j][l]) {
+          const double t = sm_lse3(sLp[j][0] + sLL[j][3 * k] + sLL[j][3 * l], sLp[j][1] + sLL[j][3 * k + 1] + sLL[j][3 * l + 1],
+                                   sLp[j][2] + sLL[j][3 * k + 2] + sLL[j][3 * l + 2]);
+          acc[u] += (t - sA[j][k]) - sA[j][l];
+          cnt[u] += 1;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kSmPairs; ++u) {
+    const int32_t p = (int32_t)threadIdx.x + 256 * u;
+    if (p < P) {
+      const size_t o = ((size_t)r * nch + ch) * P + p;
+      part[o] = acc[u]; npart[o] = cnt[u];
+    }
+  }
+}
+// One thread per (restart, pair): the chunks in ascending order.
+__global__ __launch_bounds__(256) void k_cluster_merge_fold(const double* __restrict__ part, const int32_t* __restrict__ npart, int32_t n_chunks,
+                                                            int32_t R, int32_t P, double* __restrict__ bf, int32_t* __restrict__ nsh) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)R * P) return;
+  const int32_t r = (int32_t)(t / P), p = (int32_t)(t % P);
+  double a = 0.0;
+  int32_t n = 0;
+  for (int32_t ch = 0; ch < n_chunks; ++ch) {
+    const size_t o = ((size_t)r * n_chunks + ch) * P + p;
+    a += part[o]; n += npart[o];
+  }
+  bf[t] = a; nsh[t] = n;
+}
+
+// Grouped E-step: k_cluster_estep's arithmetic (cluster_estep_one), but restart r sees only the barcodes with group[b] == r / rpg (and in
+// the mask); every other barcode gets w = 0 and lse = 0 in that restart.
+__global__ __launch_bounds__(256) void k_cluster_estep_grp(const double* __restrict__ llks, int32_t B, int32_t R, int32_t K, const double* __restrict__ log_pi,
+                                                           double inv_t, const uint8_t* __restrict__ mask, const int32_t* __restrict__ group, int32_t rpg,
+                                                           double* __restrict__ w, double* __restrict__ lse) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)B * R) return;
+  const int32_t b = (int32_t)(t / R), r = (int32_t)(t % R);
+  cluster_estep_one(llks, b, r, R, K, log_pi, inv_t, (!mask || mask[b]) && group[b] == r / rpg, w, lse);
 }
 
 // ---- ambient contamination profile (dmx_engine_ambient) ---------------------------------------------------------
@@ -6834,6 +6955,18 @@ struct dmx_engine {
   int32_t cd_B = 0, cd_R = 0, cd_K = 0; bool have_cdbl = false;
   hipEvent_t dev_[2] = {};
   dmx_cluster_doublet_info cd_info{};
+  // split-merge moves (dmx_engine_cluster_merge_score / _estep_grouped): the marginals A[S][C] and flags of the last M-step, the
+  // prior, the per-chunk partials and the folded scores; the group of each barcode
+  double* d_smA = nullptr; size_t smA_cap = 0;
+  uint8_t* d_smF = nullptr; size_t smF_cap = 0;
+  float* d_smq = nullptr; size_t smq_cap = 0;
+  double* d_smpart = nullptr; size_t smpart_cap = 0;
+  int32_t* d_smnpart = nullptr; size_t smnpart_cap = 0;
+  double* d_smout = nullptr; size_t smout_cap = 0;
+  int32_t* d_smnout = nullptr; size_t smnout_cap = 0;
+  int32_t* d_cgrp = nullptr; size_t cgrp_cap = 0;
+  hipEvent_t sev[2] = {};
+  dmx_cluster_sm_info sm_info{};
   // ambient contamination profile (dmx_engine_ambient): its own copies of the inputs and the B x Q results
   int32_t* d_aasg = nullptr; size_t aasg_cap = 0;
   double* d_aamb = nullptr; size_t aamb_cap = 0;
@@ -6992,6 +7125,10 @@ extern "C" int dmx_engine_destroy(dmx_engine* e) {
   for (void* p : {(void*)e->d_cpairs, (void*)e->d_clld, (void*)e->d_cdm, (void*)e->d_clp})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->dev_) if (ev) (void)hipEventDestroy(ev);
+  for (void* p : {(void*)e->d_smA, (void*)e->d_smF, (void*)e->d_smq, (void*)e->d_smpart, (void*)e->d_smnpart, (void*)e->d_smout, (void*)e->d_smnout,
+                  (void*)e->d_cgrp})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t& ev : e->sev) if (ev) (void)hipEventDestroy(ev);
   for (void* p : {(void*)e->d_aasg, (void*)e->d_aamb, (void*)e->d_agrid, (void*)e->d_all, (void*)e->d_acnt})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->aev) if (ev) (void)hipEventDestroy(ev);
@@ -8901,6 +9038,114 @@ extern "C" int dmx_engine_cluster_doublet_info(dmx_engine* e, dmx_cluster_double
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet_info: null argument");
   if (!e->have_cdbl) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_doublet_info: no doublet likelihoods on the staged pileup (dmx_engine_cluster_doublet first)");
   *out = e->cd_info;
+  return DMX_OK;
+}
+
+// Split-merge moves: the merge scores of the last M-step's columns (k_cluster_marg over S x C threads, then
+// k_cluster_merge_part over ceil(S / kSmChunk) x R workgroups and k_cluster_merge_fold), and the grouped E-step, whose sums go through
+// k_cluster_epart / k_cluster_efold as the plain E-step's do.
+extern "C" int dmx_engine_cluster_merge_score(dmx_engine* e, int32_t n_restarts, int32_t n_clusters, const float* prior, double floor_,
+                                              double* bf, int32_t* n_shared) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_score: null engine");
+  if (!e->have_cstage || !e->have_cm) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_merge_score: no M-step on this stage cache (dmx_engine_cluster_mstep first)");
+  const int32_t R = n_restarts, K = n_clusters, S = e->cm_S, C = e->cm_C;
+  if (K < 2 || K > kSmMaxK) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_score: %d clusters; merge scores need 2 .. %d", K, kSmMaxK);
+  if (R < 1 || (int64_t)R * K != C) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_score: %d restarts x %d clusters, the last M-step has %d columns", R, K, C);
+  if (R > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_score: %d restarts exceed this build's limit", R);
+  if (S > 0 && !prior) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_score: missing prior");
+  if (!(floor_ >= 0.0) || !std::isfinite(floor_)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_score: floor %g", floor_);
+  const int32_t P = K * (K - 1) / 2, nch = (S + kSmChunk - 1) / kSmChunk;
+  const size_t rows = (size_t)S * C, nout = (size_t)R * P, npart = (size_t)R * nch * P;
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->sev[0]) for (hipEvent_t& ev : e->sev) HIP_TRY(hipEventCreate(&ev));
+  if (int rc = ensure_dev((void**)&e->d_smA, &e->smA_cap, sizeof(double) * rows)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_smF, &e->smF_cap, rows)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_smq, &e->smq_cap, sizeof(float) * 3 * (size_t)S)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_smpart, &e->smpart_cap, sizeof(double) * npart)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_smnpart, &e->smnpart_cap, sizeof(int32_t) * npart)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_smout, &e->smout_cap, sizeof(double) * nout)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_smnout, &e->smnout_cap, sizeof(int32_t) * nout)) return rc;
+  if (S) HIP_TRY(hipMemcpyAsync(e->d_smq, prior, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipEventRecord(e->sev[0], e->stream));
+  if (rows) {
+    hipLaunchKernelGGL(k_cluster_marg, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cll, (const double*)e->d_cW,
+                       (const float*)e->d_smq, floor_, S, C, e->d_smA, e->d_smF);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cluster_merge_part, dim3((unsigned)nch, (unsigned)R), dim3(256), 0, e->stream, (const double*)e->d_cll, (const double*)e->d_smA,
+                       (const uint8_t*)e->d_smF, (const float*)e->d_smq, floor_, S, C, K, P, e->d_smpart, e->d_smnpart);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cluster_merge_fold, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_smpart,
+                     (const int32_t*)e->d_smnpart, nch, R, P, e->d_smout, e->d_smnout);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->sev[1], e->stream));
+  if (bf) HIP_TRY(hipMemcpyAsync(bf, e->d_smout, sizeof(double) * nout, hipMemcpyDeviceToHost, e->stream));
+  if (n_shared) HIP_TRY(hipMemcpyAsync(n_shared, e->d_smnout, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->sev[0], e->sev[1]));
+  e->sm_info.merge_ms = ms; e->sm_info.n_restarts = R; e->sm_info.n_clusters = K; e->sm_info.n_pairs = P; e->sm_info.n_chunks = nch;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_estep_grouped(dmx_engine* e, const dmx_cluster_estep_grouped_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: null argument");
+  if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_grouped: no stage cache (dmx_engine_cluster_stage first)");
+  if (!e->have_sing) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_grouped: no singlet likelihoods (dmx_engine_run_singlet first)");
+  const int32_t B = e->pv.B, R = rq->n_restarts, K = rq->n_clusters, C = e->V, Rs = rq->restarts_per_group;
+  if (B != e->cl_B) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_grouped: the staged pileup has %d cells, the stage cache %d", B, e->cl_B);
+  if (R < 1 || K < 1 || (int64_t)R * K != C) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: %d restarts x %d clusters, the engine has %d columns", R, K, C);
+  if (Rs < 1 || R % Rs != 0) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: %d restarts per group does not divide %d restarts", Rs, R);
+  if (!rq->log_pi) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: missing log_pi");
+  if (B > 0 && !rq->group) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: missing group");
+  if (!(rq->temperature > 0.0) || !std::isfinite(rq->temperature)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: temperature %g", rq->temperature);
+  const int32_t G = R / Rs;
+  for (int32_t b = 0; b < B; ++b)
+    if (rq->group[b] < -1 || rq->group[b] >= G)
+      return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: group[%d] = %d; groups are -1 .. %d", b, rq->group[b], G - 1);
+  const int32_t nch = (B + kEChunk - 1) / kEChunk;
+  if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: %d cells exceed this build's limit", B);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->sev[0]) for (hipEvent_t& ev : e->sev) HIP_TRY(hipEventCreate(&ev));
+  const int32_t ncol = C + R;
+  if (int rc = ensure_dev((void**)&e->d_cw, &e->cw_cap, sizeof(double) * (size_t)B * C)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_clse, &e->clse_cap, sizeof(double) * (size_t)B * R)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cpart, &e->cpart_cap, sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cpi, &e->cpi_cap, sizeof(double) * (size_t)C)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cgrp, &e->cgrp_cap, sizeof(int32_t) * (size_t)B)) return rc;
+  if (rq->mask) if (int rc = ensure_dev((void**)&e->d_cmask, &e->cmask_cap, (size_t)B)) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_cpi, rq->log_pi, sizeof(double) * (size_t)C, hipMemcpyHostToDevice, e->stream));
+  if (B) HIP_TRY(hipMemcpyAsync(e->d_cgrp, rq->group, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, e->stream));
+  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
+  double* d_out = e->d_cpart + (size_t)nch * ncol;
+  HIP_TRY(hipEventRecord(e->sev[0], e->stream));
+  if (B > 0) {
+    hipLaunchKernelGGL(k_cluster_estep_grp, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R, K,
+                       (const double*)e->d_cpi, 1.0 / rq->temperature, rq->mask ? (const uint8_t*)e->d_cmask : nullptr, (const int32_t*)e->d_cgrp, Rs,
+                       e->d_cw, e->d_clse);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_cw,
+                       (const double*)e->d_clse, (const double*)nullptr, B, C, R, e->d_cpart);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->sev[1], e->stream));
+  std::vector<double> out((size_t)ncol);
+  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (rq->col_sum) std::memcpy(rq->col_sum, out.data(), sizeof(double) * (size_t)C);
+  if (rq->ll) std::memcpy(rq->ll, out.data() + C, sizeof(double) * (size_t)R);
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->sev[0], e->sev[1]));
+  e->sm_info.grouped_estep_ms = ms;
+  e->cw_C = C; e->have_cw = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_sm_info(dmx_engine* e, dmx_cluster_sm_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_sm_info: null argument");
+  *out = e->sm_info;
   return DMX_OK;
 }
 

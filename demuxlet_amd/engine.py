@@ -415,6 +415,44 @@ class Engine:
         check(self._L.dmx_engine_cluster_doublet_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.ClusterDoubletInfo._fields_ if n != "reserved"}
 
+    def cluster_merge_score(self, n_restarts: int, n_clusters: int, prior: np.ndarray, floor: float = 1e-3):
+        """dmx_engine_cluster_merge_score on the last M-step: (bf[R][P] f64, n_shared[R][P] i32), pairs (k, l), k < l, lexicographic."""
+        prior = np.ascontiguousarray(prior, dtype=np.float32)
+        if prior.ndim != 2 or prior.shape[1] != 3:
+            raise ValueError("prior must be [S][3]")
+        P = n_clusters * (n_clusters - 1) // 2
+        bf = np.zeros((n_restarts, P))
+        ns = np.zeros((n_restarts, P), dtype=np.int32)
+        check(self._L.dmx_engine_cluster_merge_score(self._h, int(n_restarts), int(n_clusters), prior.ctypes.data if prior.size else None,
+                                                     float(floor), bf.ctypes.data if bf.size else None, ns.ctypes.data if ns.size else None))
+        return bf, ns
+
+    def cluster_estep_grouped(self, n_restarts: int, n_clusters: int, log_pi, group, restarts_per_group: int, temperature: float = 1.0, mask=None):
+        """dmx_engine_cluster_estep_grouped: restart r sees only the barcodes with group[b] == r // restarts_per_group; the weights stay on
+        the device; returns (ll[R], col_sum[R * K])."""
+        lp = np.ascontiguousarray(log_pi, dtype=np.float64).reshape(-1)
+        if lp.size != n_restarts * n_clusters:
+            raise ValueError("log_pi must be [R][K]")
+        grp = np.ascontiguousarray(group, dtype=np.int32)
+        if grp.shape != (self.B,):
+            raise ValueError(f"group must be [{self.B}]")
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        if m is not None and m.shape != (self.B,):
+            raise ValueError(f"mask must be [{self.B}]")
+        ll = np.zeros(n_restarts)
+        cs = np.zeros(n_restarts * n_clusters)
+        rq = capi.ClusterEstepGroupedRequest(int(n_restarts), int(n_clusters), lp.ctypes.data, float(temperature),
+                                             m.ctypes.data if m is not None and m.size else None, grp.ctypes.data if grp.size else None,
+                                             int(restarts_per_group), 0, ll.ctypes.data, cs.ctypes.data)
+        check(self._L.dmx_engine_cluster_estep_grouped(self._h, C.byref(rq)))
+        return ll, cs
+
+    def cluster_sm_info(self) -> dict:
+        """HIP-event times (ms) of the last merge score / grouped E-step (dmx_engine_cluster_sm_info)."""
+        r = capi.ClusterSmInfo()
+        check(self._L.dmx_engine_cluster_sm_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.ClusterSmInfo._fields_ if n != "reserved"}
+
     def ambient_profile(self, assign, ambient, grid):
         """dmx_engine_ambient over the staged pileup: LL[b][q] of each barcode assigned to sample assign[b] (-1 = not used) with a fraction
         grid[q] of its reads from a soup of ALT frequency ambient[i].  `assign` is a host array, or a device pointer (int) to B int32.

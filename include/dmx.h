@@ -31,7 +31,8 @@ extern "C" {
                                dmx_engine_refine_genotypes / _get_refined / _refined_device_ptr / _refine_info (genotype refinement from
                                called singlets); dmx_engine_cluster_* (genotype-free clustering); dmx_engine_ambient / _get_ambient /
                                _ambient_info (per-barcode ambient contamination profile); dmx_engine_cluster_doublet / _get_cluster_doublet /
-                               _cluster_estep_doublet / _cluster_doublet_info (doublet-aware clustering).  Additions only. */
+                               _cluster_estep_doublet / _cluster_doublet_info (doublet-aware clustering); dmx_engine_cluster_merge_score /
+                               _cluster_estep_grouped / _cluster_sm_info (split-merge moves).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -419,6 +420,47 @@ int dmx_engine_cluster_doublet(dmx_engine*, int32_t n_restarts, int32_t n_cluste
 int dmx_engine_get_cluster_doublet(dmx_engine*, double* lld, double* lsc);
 int dmx_engine_cluster_estep_doublet(dmx_engine*, const dmx_cluster_estep_doublet_request*);
 int dmx_engine_cluster_doublet_info(dmx_engine*, dmx_cluster_doublet_info* out);
+
+/* Split-merge moves for the clustering EM (no counterpart in the reference), driven by demuxlet_amd/cluster.py.
+ *
+ * dmx_engine_cluster_merge_score: for the last M-step's C = R * K columns read as R restarts x K clusters, with the M-step's own genotype
+ *   prior log pi[i][g] = log((prior[i][g] + floor) / sum over g of (prior[i][g] + floor)) (prior [S][3] float32, HOST) and its LL[i][c][g]
+ *   and W[i][c], for every restart r and pair p = (k, l), k < l, numbered lexicographically (P = K (K - 1) / 2):
+ *     bf[r][p] = sum over the SNPs i with W[i][rK + k] > 0 and W[i][rK + l] > 0 of
+ *                (lse_g(log pi[i][g] + LL[i][rK + k][g] + LL[i][rK + l][g]) - A[i][rK + k]) - A[i][rK + l],
+ *     A[i][c] = lse_g(log pi[i][g] + LL[i][c][g]),  n_shared[r][p] = the number of those SNPs;
+ *   the log Bayes factor "one donor" against "two donors" of the two clusters' pooled genotype likelihoods.  Other SNPs add exactly 0.
+ *   Sum order: the SNPs in chunks of 256 in ascending order, each chunk serially from 0, then the chunks in ascending order; no
+ *   floating-point atomics, so the bits depend neither on the launch geometry, R, the position of the restart's columns nor on what
+ *   ran before.  bf [R][P] f64 and n_shared [R][P] i32 are HOST outputs (either may be NULL).  DMX_ERR_STATE: no M-step on the stage
+ *   cache; DMX_ERR_ARG: R * K != the last M-step's columns, K outside [2, 64], a missing prior or a bad floor.
+ *
+ * dmx_engine_cluster_estep_grouped: dmx_engine_cluster_estep's arithmetic, except that restart r sees only the barcodes b with
+ *   group[b] == r / restarts_per_group (and in the mask): every other barcode gets w = 0 and adds nothing to ll[r] or col_sum.  The
+ *   sums are those of dmx_engine_cluster_estep.  With one group holding every barcode and restarts_per_group = R the results are
+ *   dmx_engine_cluster_estep's, bit for bit.  The weights stay on the device for the next M-step (DMX_CLUSTER_LAST_ESTEP).
+ *   DMX_ERR_ARG: R * K != V, a restarts_per_group that does not divide R, a missing group or a group id outside [-1, R / restarts_per_group). */
+typedef struct {
+  int32_t n_restarts, n_clusters;   /* R, K: R * K = the engine's V */
+  const double* log_pi;        /* [R][K] HOST */
+  double  temperature;         /* T > 0; 1 is plain EM */
+  const uint8_t* mask;         /* [B] HOST, or NULL = every barcode */
+  const int32_t* group;        /* [B] HOST: the group of each barcode, -1 = none */
+  int32_t restarts_per_group;  /* restarts r .. r + restarts_per_group - 1 of group r / restarts_per_group */
+  int32_t reserved0;           /* 0 */
+  double* ll;                  /* [R] HOST out (may be NULL) */
+  double* col_sum;             /* [R * K] HOST out (may be NULL) */
+  int32_t reserved[4];         /* 0 */
+} dmx_cluster_estep_grouped_request;
+typedef struct {
+  double  merge_ms;            /* HIP-event time of the last merge score (k_cluster_marg + k_cluster_merge_part + k_cluster_merge_fold) */
+  double  grouped_estep_ms;    /* ... and of the last grouped E-step (k_cluster_estep_grp + the ordered sums) */
+  int32_t n_restarts, n_clusters, n_pairs, n_chunks;   /* of the last merge score */
+  int32_t reserved[4];
+} dmx_cluster_sm_info;
+int dmx_engine_cluster_merge_score(dmx_engine*, int32_t n_restarts, int32_t n_clusters, const float* prior, double floor, double* bf, int32_t* n_shared);
+int dmx_engine_cluster_estep_grouped(dmx_engine*, const dmx_cluster_estep_grouped_request*);
+int dmx_engine_cluster_sm_info(dmx_engine*, dmx_cluster_sm_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Ambient contamination profile (no counterpart in the reference).  Soup is the average of many lysed cells: at
