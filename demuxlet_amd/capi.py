@@ -39,6 +39,8 @@ SYMBOLS = [
     "dmx_engine_cluster_device_ptr", "dmx_engine_cluster_info",
     "dmx_engine_cluster_doublet", "dmx_engine_get_cluster_doublet", "dmx_engine_cluster_estep_doublet", "dmx_engine_cluster_doublet_info",
     "dmx_engine_cluster_merge_score", "dmx_engine_cluster_estep_grouped", "dmx_engine_cluster_sm_info",
+    "dmx_engine_cluster_set_known", "dmx_engine_cluster_estep_known", "dmx_engine_cluster_mstep_window", "dmx_engine_get_cluster_known",
+    "dmx_engine_cluster_known_info",
     "dmx_engine_ambient", "dmx_engine_get_ambient", "dmx_engine_ambient_info",
 ]
 
@@ -109,6 +111,21 @@ class ClusterEstepGroupedRequest(C.Structure):   # dmx_cluster_estep_grouped_req
 class ClusterSmInfo(C.Structure):         # dmx_cluster_sm_info
     _fields_ = [("merge_ms", C.c_double), ("grouped_estep_ms", C.c_double), ("n_restarts", C.c_int32), ("n_clusters", C.c_int32),
                 ("n_pairs", C.c_int32), ("n_chunks", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterEstepKnownRequest(C.Structure):   # dmx_cluster_estep_known_request
+    _fields_ = [("n_restarts", C.c_int32), ("n_known", C.c_int32), ("n_free", C.c_int32), ("reserved0", C.c_int32), ("log_pi", C.c_void_p),
+                ("temperature", C.c_double), ("mask", C.c_void_p), ("ll", C.c_void_p), ("col_sum", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterMstepWindowRequest(C.Structure):  # dmx_cluster_mstep_window_request
+    _fields_ = [("n_cells", C.c_int32), ("n_snps", C.c_int32), ("n_restarts", C.c_int32), ("n_free", C.c_int32), ("weights_memory", C.c_int32),
+                ("reserved0", C.c_int32), ("weights", C.c_void_p), ("prior", C.c_void_p), ("floor", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterKnownInfo(C.Structure):      # dmx_cluster_known_info
+    _fields_ = [("estep_ms", C.c_double), ("mstep_ms", C.c_double), ("n_cells", C.c_int32), ("n_known", C.c_int32), ("n_restarts", C.c_int32),
+                ("n_free", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class AmbientRequest(C.Structure):       # dmx_ambient_request
@@ -255,6 +272,8 @@ def load() -> C.CDLL:
         "dmx_engine_cluster_doublet_info": [vp, vp],
         "dmx_engine_cluster_merge_score": [vp, i32, i32, vp, C.c_double, vp, vp], "dmx_engine_cluster_estep_grouped": [vp, vp],
         "dmx_engine_cluster_sm_info": [vp, vp],
+        "dmx_engine_cluster_set_known": [vp, i32, i32, vp, i32], "dmx_engine_cluster_estep_known": [vp, vp],
+        "dmx_engine_cluster_mstep_window": [vp, vp], "dmx_engine_get_cluster_known": [vp, vp], "dmx_engine_cluster_known_info": [vp, vp],
         "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],
     }
     for name, args in sig.items():

@@ -176,15 +176,16 @@ def match_table(llks: np.ndarray, called: np.ndarray, n_clusters: int) -> Tuple[
     return n, s
 
 
-def write_match_tsv(path: str, n_cell: np.ndarray, sum_llk: np.ndarray, sample_ids: Sequence[str]) -> None:
+def write_match_tsv(path: str, n_cell: np.ndarray, sum_llk: np.ndarray, sample_ids: Sequence[str], names: Optional[Sequence[str]] = None) -> None:
     """<prefix>.match.tsv: one row per (cluster, genotyped sample); BEST = 1 on the sample with the highest SUM.LLK of a cluster with
-    called singlets (the first on a tie)."""
+    called singlets (the first on a tie).  The clusters are named CLUST0 .. unless `names` are given."""
+    names = cluster_ids(sum_llk.shape[0]) if names is None else names
     with open(path, "w") as f:
         f.write(MATCH_HEADER)
         for k in range(sum_llk.shape[0]):
             best = int(np.argmax(sum_llk[k])) if n_cell[k] > 0 else -1
             for v, sm in enumerate(sample_ids):
-                f.write(f"CLUST{k}\t{sm}\t{int(n_cell[k])}\t{sum_llk[k, v]:.5f}\t{int(v == best)}\n")
+                f.write(f"{names[k]}\t{sm}\t{int(n_cell[k])}\t{sum_llk[k, v]:.5f}\t{int(v == best)}\n")
 
 
 def match_labels(truth: np.ndarray, pred: np.ndarray, n_truth: int, n_pred: int) -> np.ndarray:

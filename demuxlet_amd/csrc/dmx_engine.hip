@@ -2515,6 +2515,97 @@ __global__ __launch_bounds__(256) void k_cluster_estep_grp(const double* __restr
   cluster_estep_one(llks, b, r, R, K, log_pi, inv_t, (!mask || mask[b]) && group[b] == r / rpg, w, lse);
 }
 
+// ---- partly genotyped pools (dmx_engine_cluster_estep_known / _mstep_window) ------------------------------------
+// The engine's V = Vk + R M columns are [Vk known donors | restart 0's M free columns | ... | restart R-1's M], the known ones shared
+// by every restart.  E-step: one thread per (barcode b, restart r) over its Vk + M components, component k's llk at column
+//   k < Vk: k,  k >= Vk: Vk + r M + (k - Vk);   a_k = (llks[b][col] + log_pi[r][k]) / T,  w = exp(a_k - max a) / sum,
+// lse[b][r] = logsumexp_k(llks + log_pi); a barcode outside the mask gets w = 0 and lse = 0.  The operations, and their order, are
+// cluster_estep_one's, so with Vk = 0 the results are k_cluster_estep's bit for bit.  wk[b][r][k] holds every component's weight (for
+// the ordered column sums), wf[b][r M + m] the free ones (for the windowed M-step).
+__device__ __forceinline__ int64_t known_llk_col(int32_t k, int32_t r, int32_t Vk, int32_t M) {
+  return k < Vk ? (int64_t)k : (int64_t)Vk + (int64_t)r * M + (k - Vk);
+}
+__global__ __launch_bounds__(256) void k_cluster_estep_known(const double* __restrict__ llks, int32_t B, int32_t R, int32_t Vk, int32_t M,
+                                                             const double* __restrict__ log_pi, double inv_t, const uint8_t* __restrict__ mask,
+                                                             double* __restrict__ wk, double* __restrict__ wf, double* __restrict__ lse) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)B * R) return;
+  const int32_t b = (int32_t)(t / R), r = (int32_t)(t % R), K = Vk + M;
+  const size_t V = (size_t)Vk + (size_t)R * M, lo = (size_t)b * V, ko = ((size_t)b * R + r) * K, fo = (size_t)b * R * M + (size_t)r * M;
+  const double* lp = log_pi + (size_t)r * K;
+  if (mask && !mask[b]) {
+    for (int32_t k = 0; k < K; ++k) wk[ko + k] = 0.0;
+    for (int32_t k = 0; k < M; ++k) wf[fo + k] = 0.0;
+    lse[(size_t)b * R + r] = 0.0;
+    return;
+  }
+  double m = -INFINITY, m1 = -INFINITY;
+  for (int32_t k = 0; k < K; ++k) {
+    const double x = llks[lo + known_llk_col(k, r, Vk, M)] + lp[k];
+    m1 = fmax(m1, x); m = fmax(m, x * inv_t);
+  }
+  double s = 0.0, s1 = 0.0;
+  for (int32_t k = 0; k < K; ++k) {
+    const double x = llks[lo + known_llk_col(k, r, Vk, M)] + lp[k];
+    const double e = exp(x * inv_t - m);
+    wk[ko + k] = e; s += e; s1 += exp(x - m1);
+  }
+  const double y = 1.0 / s;
+  for (int32_t k = 0; k < K; ++k) {
+    const double v = wk[ko + k] * y;
+    wk[ko + k] = v;
+    if (k >= Vk) wf[fo + (k - Vk)] = v;
+  }
+  lse[(size_t)b * R + r] = m1 + log(s1);
+}
+
+// Windowed M-step: k_cluster_mstep's arithmetic and sum order over the C = R M free columns only (w[B][C], LL[S][C][3], W[S][C]); gp'
+// goes to columns Vk .. V-1 of gp[S][V][3] (the known columns are copied in by the caller).  With Vk = 0 every address and every
+// operation is k_cluster_mstep's, so the bits are.
+__global__ __launch_bounds__(256) void k_cluster_mstep_win(const int64_t* __restrict__ snp_off, const int32_t* __restrict__ cell_of,
+                                                           const double* __restrict__ lgl, const double* __restrict__ w, int32_t S, int32_t C,
+                                                           const float* __restrict__ prior, double floor_, double* __restrict__ LL,
+                                                           double* __restrict__ W, float* __restrict__ gp, int32_t Vk) {
+  const int32_t i = __builtin_amdgcn_readfirstlane((int32_t)(blockIdx.x * 4 + (threadIdx.x >> 6)));
+  if (i >= S) return;
+  const int32_t c = blockIdx.y * 64 + (threadIdx.x & 63);
+  const bool on = c < C;
+  const int32_t cc = on ? c : 0;
+  const int64_t j0 = snp_off[i], j1 = snp_off[i + 1];
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, ws = 0.0;
+  int64_t j = j0;
+  for (; j + 4 <= j1; j += 4) {
+    double x[4], l[12];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) x[u] = w[(size_t)cell_of[j + u] * C + cc];
+#pragma unroll
+    for (int u = 0; u < 12; ++u) l[u] = lgl[3 * j + u];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      a0 = fma(x[u], l[3 * u], a0); a1 = fma(x[u], l[3 * u + 1], a1); a2 = fma(x[u], l[3 * u + 2], a2); ws += x[u];
+    }
+  }
+  for (; j < j1; ++j) {
+    const double x = w[(size_t)cell_of[j] * C + cc];
+    a0 = fma(x, lgl[3 * j], a0); a1 = fma(x, lgl[3 * j + 1], a1); a2 = fma(x, lgl[3 * j + 2], a2); ws += x;
+  }
+  if (!on) return;
+  const size_t o = (size_t)i * C + c, og = (size_t)i * ((size_t)C + Vk) + Vk + c;
+  LL[3 * o] = a0; LL[3 * o + 1] = a1; LL[3 * o + 2] = a2; W[o] = ws;
+  if (ws == 0.0) {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(prior) + (size_t)i * 3;
+    uint32_t* d = reinterpret_cast<uint32_t*>(gp) + 3 * og;
+    d[0] = src[0]; d[1] = src[1]; d[2] = src[2];
+    return;
+  }
+  const double mx = fmax(fmax(a0, a1), a2);
+  const double w0 = ((double)prior[(size_t)i * 3] + floor_) * exp(a0 - mx);
+  const double w1 = ((double)prior[(size_t)i * 3 + 1] + floor_) * exp(a1 - mx);
+  const double w2 = ((double)prior[(size_t)i * 3 + 2] + floor_) * exp(a2 - mx);
+  const double sum = w0 + w1 + w2;
+  gp[3 * og] = (float)(w0 / sum); gp[3 * og + 1] = (float)(w1 / sum); gp[3 * og + 2] = (float)(w2 / sum);
+}
+
 // ---- ambient contamination profile (dmx_engine_ambient) ---------------------------------------------------------
 // For a barcode b assigned to sample v and a grid point rho: LL_b(rho) = sum over b's pairs, in stored (ascending SNP) order, of
 // log(gp[i][v][0] f_0 + gp[i][v][1] f_1 + gp[i][v][2] f_2), f_g = product over the pair's stored reads of pR (1 - p_g) + pA p_g,
@@ -6967,6 +7058,13 @@ struct dmx_engine {
   int32_t* d_cgrp = nullptr; size_t cgrp_cap = 0;
   hipEvent_t sev[2] = {};
   dmx_cluster_sm_info sm_info{};
+  // partly genotyped pools (dmx_engine_cluster_set_known / _estep_known / _mstep_window): the known rows gk[S][Vk][3], every
+  // component's weights [B][R][Vk + M] of the last known-column E-step; cgp_C is the column count of the last M-step's gp' buffer
+  float* d_ckn = nullptr; size_t ckn_cap = 0; int32_t ckn_S = 0, ckn_Vk = 0; bool have_ckn = false;
+  double* d_ckw = nullptr; size_t ckw_cap = 0; int32_t ckw_B = 0, ckw_R = 0, ckw_K = 0; bool have_ckw = false;
+  int32_t cgp_C = 0;
+  hipEvent_t kev[2] = {};
+  dmx_cluster_known_info kn_info{};
   // ambient contamination profile (dmx_engine_ambient): its own copies of the inputs and the B x Q results
   int32_t* d_aasg = nullptr; size_t aasg_cap = 0;
   double* d_aamb = nullptr; size_t aamb_cap = 0;
@@ -7129,6 +7227,8 @@ extern "C" int dmx_engine_destroy(dmx_engine* e) {
                   (void*)e->d_cgrp})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->sev) if (ev) (void)hipEventDestroy(ev);
+  for (void* p : {(void*)e->d_ckn, (void*)e->d_ckw}) if (p) (void)hipFree(p);
+  for (hipEvent_t& ev : e->kev) if (ev) (void)hipEventDestroy(ev);
   for (void* p : {(void*)e->d_aasg, (void*)e->d_aamb, (void*)e->d_agrid, (void*)e->d_all, (void*)e->d_acnt})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->aev) if (ev) (void)hipEventDestroy(ev);
@@ -8765,7 +8865,7 @@ extern "C" int dmx_engine_cluster_stage(dmx_engine* e) {
   inf.stage_ms = ms; inf.cache_bytes = (int64_t)cache_b; inf.n_pairs = P; inf.n_cells = B; inf.n_snps = S; inf.sorted = !dense && P > 0;
   inf.scratch_bytes = (int64_t)scratch_b;
   e->cl_P = P; e->cl_B = B; e->cl_S = S; e->have_cstage = true;
-  e->have_cm = false; e->have_cw = false;
+  e->have_cm = false; e->have_cw = false; e->have_ckw = false;
   return DMX_OK;
 }
 
@@ -8813,7 +8913,7 @@ extern "C" int dmx_engine_cluster_mstep(dmx_engine* e, const dmx_cluster_mstep_r
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, e->cev[0], e->cev[1]));
   e->cl_info.mstep_ms = ms; e->cl_info.n_cols = C;
-  e->cgp_cur = nxt; e->cm_S = S; e->cm_C = C; e->have_cm = true;
+  e->cgp_cur = nxt; e->cm_S = S; e->cm_C = C; e->cgp_C = C; e->have_cm = true;
   return DMX_OK;
 }
 
@@ -8872,7 +8972,8 @@ extern "C" int dmx_engine_get_cluster(dmx_engine* e, double* ll, double* wsum, f
   const size_t rows = (size_t)e->cm_S * e->cm_C, nw = (size_t)e->cl_B * e->cw_C;
   if (ll && rows) HIP_TRY(hipMemcpy(ll, e->d_cll, sizeof(double) * 3 * rows, hipMemcpyDeviceToHost));
   if (wsum && rows) HIP_TRY(hipMemcpy(wsum, e->d_cW, sizeof(double) * rows, hipMemcpyDeviceToHost));
-  if (gp && rows) HIP_TRY(hipMemcpy(gp, e->d_cgp[e->cgp_cur], sizeof(float) * 3 * rows, hipMemcpyDeviceToHost));
+  const size_t gp_rows = (size_t)e->cm_S * e->cgp_C;      // the windowed M-step's gp' has all V columns, its LL and W the free ones
+  if (gp && gp_rows) HIP_TRY(hipMemcpy(gp, e->d_cgp[e->cgp_cur], sizeof(float) * 3 * gp_rows, hipMemcpyDeviceToHost));
   if (weights && nw) HIP_TRY(hipMemcpy(weights, e->d_cw, sizeof(double) * nw, hipMemcpyDeviceToHost));
   return DMX_OK;
 }
@@ -9146,6 +9247,145 @@ extern "C" int dmx_engine_cluster_estep_grouped(dmx_engine* e, const dmx_cluster
 extern "C" int dmx_engine_cluster_sm_info(dmx_engine* e, dmx_cluster_sm_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_sm_info: null argument");
   *out = e->sm_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Partly genotyped pools: Vk known columns shared by R restarts of M free ones.  The E-step is
+// k_cluster_estep_known over B x R threads, whose sums over the R (Vk + M) components go through k_cluster_epart / k_cluster_efold; the
+// M-step is k_cluster_mstep_win over the R M free columns, after a copy of the known rows into the gp' buffer it writes.
+extern "C" int dmx_engine_cluster_set_known(dmx_engine* e, int32_t n_snps, int32_t n_known, const float* g, int32_t memory) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_set_known: null engine");
+  if (n_snps < 0 || n_known < 0 || n_known >= e->V)
+    return set_error(DMX_ERR_ARG, "dmx_engine_cluster_set_known: %d known columns of %d SNPs; the engine has %d columns and needs one free", n_known, n_snps, e->V);
+  if (memory != DMX_MEM_HOST && memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_set_known: memory %d", memory);
+  const size_t n = (size_t)n_snps * n_known * 3;
+  if (n && !g) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_set_known: missing rows");
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = ensure_dev((void**)&e->d_ckn, &e->ckn_cap, sizeof(float) * n)) return rc;
+  if (n) HIP_TRY(hipMemcpyAsync(e->d_ckn, g, sizeof(float) * n, memory == DMX_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  e->ckn_S = n_snps; e->ckn_Vk = n_known; e->have_ckn = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_estep_known(dmx_engine* e, const dmx_cluster_estep_known_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_known: null argument");
+  if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_known: no stage cache (dmx_engine_cluster_stage first)");
+  if (!e->have_sing) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_known: no singlet likelihoods (dmx_engine_run_singlet first)");
+  const int32_t B = e->pv.B, R = rq->n_restarts, Vk = rq->n_known, M = rq->n_free, V = e->V;
+  if (B != e->cl_B) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_estep_known: the staged pileup has %d cells, the stage cache %d", B, e->cl_B);
+  if (R < 1 || M < 1 || Vk < 0 || (int64_t)Vk + (int64_t)R * M != V)
+    return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_known: %d known + %d restarts x %d free columns, the engine has %d columns", Vk, R, M, V);
+  if (!rq->log_pi) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_known: missing log_pi");
+  if (!(rq->temperature > 0.0) || !std::isfinite(rq->temperature)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_known: temperature %g", rq->temperature);
+  const int32_t nch = (B + kEChunk - 1) / kEChunk;
+  if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_known: %d cells exceed this build's limit", B);
+  const int32_t K = Vk + M, CK = R * K, CF = R * M, ncol = CK + R;
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->kev[0]) for (hipEvent_t& ev : e->kev) HIP_TRY(hipEventCreate(&ev));
+  if (int rc = ensure_dev((void**)&e->d_ckw, &e->ckw_cap, sizeof(double) * (size_t)B * CK)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cw, &e->cw_cap, sizeof(double) * (size_t)B * CF)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_clse, &e->clse_cap, sizeof(double) * (size_t)B * R)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cpart, &e->cpart_cap, sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cpi, &e->cpi_cap, sizeof(double) * (size_t)CK)) return rc;
+  if (rq->mask) if (int rc = ensure_dev((void**)&e->d_cmask, &e->cmask_cap, (size_t)B)) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_cpi, rq->log_pi, sizeof(double) * (size_t)CK, hipMemcpyHostToDevice, e->stream));
+  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
+  double* d_out = e->d_cpart + (size_t)nch * ncol;
+  HIP_TRY(hipEventRecord(e->kev[0], e->stream));
+  if (B > 0) {
+    hipLaunchKernelGGL(k_cluster_estep_known, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R,
+                       Vk, M, (const double*)e->d_cpi, 1.0 / rq->temperature, rq->mask ? (const uint8_t*)e->d_cmask : nullptr, e->d_ckw, e->d_cw, e->d_clse);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_ckw,
+                       (const double*)e->d_clse, (const double*)nullptr, B, CK, R, e->d_cpart);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e->kev[1], e->stream));
+  std::vector<double> out((size_t)ncol);
+  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (rq->col_sum) std::memcpy(rq->col_sum, out.data(), sizeof(double) * (size_t)CK);
+  if (rq->ll) std::memcpy(rq->ll, out.data() + CK, sizeof(double) * (size_t)R);
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->kev[0], e->kev[1]));
+  e->kn_info.estep_ms = ms; e->kn_info.n_cells = B; e->kn_info.n_known = Vk; e->kn_info.n_restarts = R; e->kn_info.n_free = M;
+  e->cw_C = CF; e->have_cw = true;
+  e->ckw_B = B; e->ckw_R = R; e->ckw_K = K; e->have_ckw = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_mstep_window(dmx_engine* e, const dmx_cluster_mstep_window_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: null argument");
+  if (!e->have_cstage) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_mstep_window: no stage cache (dmx_engine_cluster_stage first)");
+  if (!e->have_ckn) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_mstep_window: no known rows (dmx_engine_cluster_set_known first)");
+  const int32_t B = e->cl_B, S = e->cl_S, V = e->V, R = rq->n_restarts, M = rq->n_free, Vk = e->ckn_Vk;
+  if (rq->n_cells != B || rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: %d cells x %d SNPs, the stage cache has %d x %d", rq->n_cells, rq->n_snps, B, S);
+  if (e->ckn_S != S) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: the known rows have %d SNPs, the stage cache %d", e->ckn_S, S);
+  if (R < 1 || M < 1 || (int64_t)Vk + (int64_t)R * M != V)
+    return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: %d known + %d restarts x %d free columns, the engine has %d columns", Vk, R, M, V);
+  if (S > 0 && !rq->prior) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: missing prior");
+  if (!(rq->floor >= 0.0) || !std::isfinite(rq->floor)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: floor %g", rq->floor);
+  HIP_TRY(hipSetDevice(e->device));
+  const int32_t C = R * M;
+  const size_t nw = (size_t)B * C, rows = (size_t)S * C;
+  const double* w = nullptr;
+  if (rq->weights_memory == DMX_CLUSTER_LAST_ESTEP) {
+    if (!e->have_cw || e->cw_C != C) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_mstep_window: no E-step weights of %d free columns (dmx_engine_cluster_estep_known first)", C);
+    w = e->d_cw;
+  } else if (rq->weights_memory == DMX_MEM_HOST || rq->weights_memory == DMX_MEM_DEVICE) {
+    if (nw > 0 && !rq->weights) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: missing weights");
+    if (rq->weights_memory == DMX_MEM_HOST) {
+      if (int rc = ensure_dev((void**)&e->d_cwh, &e->cwh_cap, sizeof(double) * nw)) return rc;
+      if (nw) HIP_TRY(hipMemcpyAsync(e->d_cwh, rq->weights, sizeof(double) * nw, hipMemcpyHostToDevice, e->stream));
+      w = e->d_cwh;
+    } else {
+      w = rq->weights;
+    }
+  } else {
+    return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: weights_memory %d", rq->weights_memory);
+  }
+  if (!e->kev[0]) for (hipEvent_t& ev : e->kev) HIP_TRY(hipEventCreate(&ev));
+  if (int rc = ensure_dev((void**)&e->d_cq, &e->cq_cap, sizeof(float) * 3 * (size_t)S)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cll, &e->cll_cap, sizeof(double) * 3 * rows)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_cW, &e->cW_cap, sizeof(double) * rows)) return rc;
+  const int nxt = e->d_g == e->d_cgp[0] ? 1 : 0;                      // never the buffer the engine's genotype matrix is
+  if (int rc = ensure_dev((void**)&e->d_cgp[nxt], &e->cgp_cap[nxt], sizeof(float) * 3 * (size_t)S * V)) return rc;
+  if (S) HIP_TRY(hipMemcpyAsync(e->d_cq, rq->prior, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipEventRecord(e->kev[0], e->stream));
+  if (S && Vk)
+    HIP_TRY(hipMemcpy2DAsync(e->d_cgp[nxt], sizeof(float) * 3 * (size_t)V, e->d_ckn, sizeof(float) * 3 * (size_t)Vk, sizeof(float) * 3 * (size_t)Vk,
+                             (size_t)S, hipMemcpyDeviceToDevice, e->stream));
+  if (rows) {
+    hipLaunchKernelGGL(k_cluster_mstep_win, dim3((unsigned)((S + 3) / 4), (unsigned)((C + 63) / 64)), dim3(256), 0, e->stream, (const int64_t*)e->d_coff,
+                       (const int32_t*)e->d_ccell, (const double*)e->d_clgl, w, S, C, (const float*)e->d_cq, rq->floor, e->d_cll, e->d_cW, e->d_cgp[nxt], Vk);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(e->kev[1], e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's prior / weights may go away after return
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->kev[0], e->kev[1]));
+  e->kn_info.mstep_ms = ms; e->kn_info.n_known = Vk; e->kn_info.n_restarts = R; e->kn_info.n_free = M;
+  e->cgp_cur = nxt; e->cm_S = S; e->cm_C = C; e->cgp_C = V; e->have_cm = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_cluster_known(dmx_engine* e, double* weights) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_cluster_known: null engine");
+  if (weights && !e->have_ckw) return set_error(DMX_ERR_STATE, "dmx_engine_get_cluster_known: no known-column E-step (dmx_engine_cluster_estep_known first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t n = (size_t)e->ckw_B * e->ckw_R * e->ckw_K;
+  if (weights && n) HIP_TRY(hipMemcpy(weights, e->d_ckw, sizeof(double) * n, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_known_info(dmx_engine* e, dmx_cluster_known_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_known_info: null argument");
+  *out = e->kn_info;
   return DMX_OK;
 }
 

@@ -453,6 +453,75 @@ class Engine:
         check(self._L.dmx_engine_cluster_sm_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.ClusterSmInfo._fields_ if n != "reserved"}
 
+    def cluster_set_known(self, g) -> None:
+        """dmx_engine_cluster_set_known: the known rows [S][Vk][3] f32 (a host array) shared by every restart of the windowed M-step."""
+        g = np.ascontiguousarray(g, dtype=np.float32)
+        if g.ndim != 3 or g.shape[2] != 3:
+            raise ValueError("known rows must be [S][Vk][3]")
+        check(self._L.dmx_engine_cluster_set_known(self._h, g.shape[0], g.shape[1], g.ctypes.data if g.size else None, capi.DMX_MEM_HOST))
+
+    def cluster_estep_known(self, n_restarts: int, n_known: int, n_free: int, log_pi, temperature: float = 1.0, mask=None):
+        """dmx_engine_cluster_estep_known on K1's llks of the last run_singlet, columns [Vk known | R x M free]: the free weights
+        [B][R * M] stay on the device; returns (ll[R], col_sum[R][Vk + M])."""
+        R, K = int(n_restarts), int(n_known) + int(n_free)
+        lp = np.ascontiguousarray(log_pi, dtype=np.float64).reshape(-1)
+        if lp.size != R * K:
+            raise ValueError("log_pi must be [R][Vk + M]")
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        if m is not None and m.shape != (self.B,):
+            raise ValueError(f"mask must be [{self.B}]")
+        ll = np.zeros(R)
+        cs = np.zeros((R, K))
+        rq = capi.ClusterEstepKnownRequest(R, int(n_known), int(n_free), 0, lp.ctypes.data, float(temperature),
+                                           m.ctypes.data if m is not None and m.size else None, ll.ctypes.data, cs.ctypes.data)
+        check(self._L.dmx_engine_cluster_estep_known(self._h, C.byref(rq)))
+        return ll, cs
+
+    def cluster_mstep_window(self, weights, n_restarts: int, n_free: int, prior: np.ndarray, floor: float = 1e-3, fetch: bool = True):
+        """dmx_engine_cluster_mstep_window over the R * M free columns: weights is a host array [B][R * M] f64, a device pointer (int), or
+        None = the last known-column E-step's; prior [S][3].  Returns (LL[S][R * M][3] f64, W[S][R * M] f64, gp'[S][V][3] f32, whose
+        first Vk columns are the known rows), or None with fetch=False (gp' stays on the device: cluster_device_ptr)."""
+        prior = np.ascontiguousarray(prior, dtype=np.float32)
+        if prior.ndim != 2 or prior.shape[1] != 3:
+            raise ValueError("prior must be [S][3]")
+        S, CF = prior.shape[0], int(n_restarts) * int(n_free)
+        w = None
+        if weights is None:
+            mem, ptr = capi.DMX_CLUSTER_LAST_ESTEP, None
+        elif isinstance(weights, int):
+            mem, ptr = capi.DMX_MEM_DEVICE, weights
+        else:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (self.B, CF):
+                raise ValueError(f"weights must be [{self.B}][{CF}]")
+            mem, ptr = capi.DMX_MEM_HOST, (w.ctypes.data if w.size else None)
+        rq = capi.ClusterMstepWindowRequest(self.B, S, int(n_restarts), int(n_free), mem, 0, ptr, prior.ctypes.data if prior.size else None,
+                                            float(floor))
+        check(self._L.dmx_engine_cluster_mstep_window(self._h, C.byref(rq)))
+        if not fetch:
+            return None
+        ll = np.zeros((S, CF, 3))
+        W = np.zeros((S, CF))
+        gp = np.zeros((S, self.V, 3), dtype=np.float32)
+        check(self._L.dmx_engine_get_cluster(self._h, ll.ctypes.data, W.ctypes.data, gp.ctypes.data, None))
+        return ll, W, gp
+
+    def cluster_known_weights(self):
+        """(every component's weights [B][R][Vk + M], the free weights [B][R * M]) of the last known-column E-step."""
+        inf = self.cluster_known_info()
+        B, R, Vk, M = inf["n_cells"], inf["n_restarts"], inf["n_known"], inf["n_free"]
+        wk = np.zeros((B, R, Vk + M))
+        wf = np.zeros((B, R * M))
+        check(self._L.dmx_engine_get_cluster_known(self._h, wk.ctypes.data))
+        check(self._L.dmx_engine_get_cluster(self._h, None, None, None, wf.ctypes.data))
+        return wk, wf
+
+    def cluster_known_info(self) -> dict:
+        """HIP-event times (ms) of the last known-column E-step / windowed M-step (dmx_engine_cluster_known_info)."""
+        r = capi.ClusterKnownInfo()
+        check(self._L.dmx_engine_cluster_known_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.ClusterKnownInfo._fields_ if n != "reserved"}
+
     def ambient_profile(self, assign, ambient, grid):
         """dmx_engine_ambient over the staged pileup: LL[b][q] of each barcode assigned to sample assign[b] (-1 = not used) with a fraction
         grid[q] of its reads from a soup of ALT frequency ambient[i].  `assign` is a host array, or a device pointer (int) to B int32.

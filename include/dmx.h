@@ -32,7 +32,9 @@ extern "C" {
                                called singlets); dmx_engine_cluster_* (genotype-free clustering); dmx_engine_ambient / _get_ambient /
                                _ambient_info (per-barcode ambient contamination profile); dmx_engine_cluster_doublet / _get_cluster_doublet /
                                _cluster_estep_doublet / _cluster_doublet_info (doublet-aware clustering); dmx_engine_cluster_merge_score /
-                               _cluster_estep_grouped / _cluster_sm_info (split-merge moves).  Additions only. */
+                               _cluster_estep_grouped / _cluster_sm_info (split-merge moves); dmx_engine_cluster_set_known /
+                               _cluster_estep_known / _cluster_mstep_window / _get_cluster_known / _cluster_known_info (partly
+                               genotyped pools).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -461,6 +463,62 @@ typedef struct {
 int dmx_engine_cluster_merge_score(dmx_engine*, int32_t n_restarts, int32_t n_clusters, const float* prior, double floor, double* bf, int32_t* n_shared);
 int dmx_engine_cluster_estep_grouped(dmx_engine*, const dmx_cluster_estep_grouped_request*);
 int dmx_engine_cluster_sm_info(dmx_engine*, dmx_cluster_sm_info* out);
+
+/* Partly genotyped pools (no counterpart in the reference), driven by demuxlet_amd/partial.py: Vk donors are
+ * known from the VCF and M more are learned by the clustering EM in R restarts.  The engine's V = Vk + R * M columns are
+ * [the Vk known donors | restart 0's M free columns | ... | restart R-1's M], so K1 scores the known columns once for all restarts.
+ *
+ * dmx_engine_cluster_set_known: the known rows g[n_snps][n_known][3] (float32, DMX_MEM_HOST or DMX_MEM_DEVICE); the engine keeps a
+ *   device copy.  n_known = 0 is accepted.  DMX_ERR_ARG: n_known outside [0, V), a missing pointer or a bad memory kind.
+ *
+ * dmx_engine_cluster_estep_known: from K1's llks[B][V] of the last run_singlet, per barcode b and restart r over its Vk + M components
+ *   (component k < Vk: column k; component Vk + m: column Vk + r M + m):  a_k = (llks[b][col] + log_pi[r][k]) / T,
+ *   w_k = exp(a_k - max a) / sum over k;  a barcode with mask[b] = 0 gets w = 0 and is left out of ll.  ll[r] = sum over the barcodes in
+ *   the mask of logsumexp_k(llks + log_pi), col_sum[r][k] = sum over b of w_k; the sums are those of dmx_engine_cluster_estep (chunks
+ *   of 256 barcodes in order, then the chunks in order; no atomics).  The free weights w[B][R * M] stay on the device for the next
+ *   windowed M-step (DMX_CLUSTER_LAST_ESTEP) and dmx_engine_get_cluster returns them; dmx_engine_get_cluster_known returns all
+ *   components' weights [B][R][Vk + M].  With n_known = 0 every result is dmx_engine_cluster_estep's (R, K = M), bit for bit.
+ *   DMX_ERR_ARG: Vk + R * M != V, M < 1, Vk < 0, a missing log_pi or a bad temperature.
+ *
+ * dmx_engine_cluster_mstep_window: dmx_engine_cluster_mstep's arithmetic and sum order over the R * M free columns only, weights
+ *   w[B][R * M]: LL[S][R * M][3] and W[S][R * M] (dmx_engine_get_cluster, dmx_engine_cluster_merge_score), and gp' into columns
+ *   Vk .. V-1 of a [S][V][3] buffer whose columns 0 .. Vk-1 hold the known rows of dmx_engine_cluster_set_known, bit for bit.  The
+ *   buffer is double-buffered as dmx_engine_cluster_mstep's (dmx_engine_cluster_device_ptr).  With no known columns every result is
+ *   dmx_engine_cluster_mstep's, bit for bit.  DMX_ERR_STATE: no stage cache or no known rows; DMX_ERR_ARG: Vk + R * M != V, M < 1, or
+ *   counts that disagree with the stage cache or the known rows. */
+typedef struct {
+  int32_t n_restarts, n_known, n_free;   /* R, Vk, M: Vk + R * M = the engine's V; Vk >= 0, M >= 1 */
+  int32_t reserved0;           /* 0 */
+  const double* log_pi;        /* [R][Vk + M] HOST */
+  double  temperature;         /* T > 0; 1 is plain EM */
+  const uint8_t* mask;         /* [B] HOST, or NULL = every barcode */
+  double* ll;                  /* [R] HOST out (may be NULL) */
+  double* col_sum;             /* [R][Vk + M] HOST out (may be NULL) */
+  int32_t reserved[4];         /* 0 */
+} dmx_cluster_estep_known_request;
+typedef struct {
+  int32_t n_cells;             /* = the cache's barcodes */
+  int32_t n_snps;              /* = the cache's SNPs = the known rows' */
+  int32_t n_restarts, n_free;  /* R, M: the known rows' Vk + R * M = the engine's V */
+  int32_t weights_memory;      /* DMX_MEM_HOST, DMX_MEM_DEVICE or DMX_CLUSTER_LAST_ESTEP (weights ignored) */
+  int32_t reserved0;           /* 0 */
+  const double* weights;       /* [n_cells][R * M] float64 */
+  const float* prior;          /* [n_snps][3] float32, HOST */
+  double  floor;               /* >= 0; 1e-3 is the usual value */
+  int32_t reserved[4];         /* 0 */
+} dmx_cluster_mstep_window_request;
+typedef struct {
+  double  estep_ms;            /* HIP-event times of the last known-column E-step (k_cluster_estep_known + the ordered sums) */
+  double  mstep_ms;            /* ... and of the last windowed M-step (the known rows' copy + k_cluster_mstep_win) */
+  int32_t n_cells, n_known, n_restarts, n_free;
+  int32_t reserved[4];
+} dmx_cluster_known_info;
+int dmx_engine_cluster_set_known(dmx_engine*, int32_t n_snps, int32_t n_known, const float* g, int32_t memory);
+int dmx_engine_cluster_estep_known(dmx_engine*, const dmx_cluster_estep_known_request*);
+int dmx_engine_cluster_mstep_window(dmx_engine*, const dmx_cluster_mstep_window_request*);
+/* Device->host copy of the last known-column E-step's weights [B][R][Vk + M] f64 (DMX_ERR_STATE before one). */
+int dmx_engine_get_cluster_known(dmx_engine*, double* weights);
+int dmx_engine_cluster_known_info(dmx_engine*, dmx_cluster_known_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Ambient contamination profile (no counterpart in the reference).  Soup is the average of many lysed cells: at
