@@ -42,6 +42,7 @@ SYMBOLS = [
     "dmx_engine_cluster_set_known", "dmx_engine_cluster_estep_known", "dmx_engine_cluster_mstep_window", "dmx_engine_get_cluster_known",
     "dmx_engine_cluster_known_info",
     "dmx_engine_ambient", "dmx_engine_get_ambient", "dmx_engine_ambient_info",
+    "dmx_engine_ambient_doublet", "dmx_engine_get_ambient_doublet", "dmx_engine_ambient_doublet_info",
 ]
 
 
@@ -136,6 +137,17 @@ class AmbientRequest(C.Structure):       # dmx_ambient_request
 class AmbientInfo(C.Structure):          # dmx_ambient_info
     _fields_ = [("kernel_ms", C.c_double), ("profile_bytes", C.c_int64), ("n_cells", C.c_int32), ("n_grid", C.c_int32), ("n_assigned", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
+
+
+class AmbientDoubletRequest(C.Structure):  # dmx_ambient_doublet_request
+    _fields_ = [("n_cells", C.c_int32), ("cand_memory", C.c_int32), ("cand", C.c_void_p), ("n_cand", C.c_int32), ("n_alpha", C.c_int32),
+                ("n_snps", C.c_int32), ("n_grid", C.c_int32), ("alpha", C.c_void_p), ("ambient", C.c_void_p), ("grid", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class AmbientDoubletInfo(C.Structure):   # dmx_ambient_doublet_info
+    _fields_ = [("kernel_ms", C.c_double), ("profile_bytes", C.c_int64), ("n_used", C.c_int64), ("n_cells", C.c_int32), ("n_cand", C.c_int32),
+                ("n_alpha", C.c_int32), ("n_grid", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class DmxError(RuntimeError):
@@ -275,6 +287,7 @@ def load() -> C.CDLL:
         "dmx_engine_cluster_set_known": [vp, i32, i32, vp, i32], "dmx_engine_cluster_estep_known": [vp, vp],
         "dmx_engine_cluster_mstep_window": [vp, vp], "dmx_engine_get_cluster_known": [vp, vp], "dmx_engine_cluster_known_info": [vp, vp],
         "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],
+        "dmx_engine_ambient_doublet": [vp, vp], "dmx_engine_get_ambient_doublet": [vp, vp, vp, vp], "dmx_engine_ambient_doublet_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -2714,6 +2714,201 @@ __global__ __launch_bounds__(64 * kAmbWaves) void k_ambient(PileupView pv, int n
   if (qb == 0 && lane == 0) { n_snp[cell] = ns; n_read[cell] = nr; }
 }
 
+// ---- ambient-aware doublet profile (dmx_engine_ambient_doublet) --------------------------------------------------
+// For a barcode b, a candidate pair (v1, v2), a mixing share alpha of v2 and a grid point rho:
+//   p_lm = (1 - rho) (0.5 l + (m - l) 0.5 alpha) + rho a_i,   f_lm = product over the pair's stored reads of pR (1 - p_lm) + pA p_lm,
+//   LL = sum over b's pairs, in stored (ascending SNP) order, of log(sum_l sum_m gp[i][v1][l] gp[i][v2][m] f_lm)  (l-major, m-minor).
+// k_ambient's skeleton: one wavefront per (barcode, alpha, block of 64 grid points), one lane per grid point, PT pair headers staged in LDS
+// per trip.  The nine f_lm depend on the pair, alpha and rho but not on the candidate: a lane forms them once per pair and folds them
+// into one running sum per candidate (nine exact float32 x float32 weights, nine multiply-adds, one log), so a further candidate costs
+// the fold and not the read loop.  The candidates' two gp rows (2 x 3 float32) ride in the staged header; a header's mask has bit c set
+// when both rows of candidate c have a non-zero entry, and a pair with mask 0 or no stored read is skipped.  The nine mixing
+// constants are wave-uniform and sit in scalar registers.
+// Range: a pair of fewer than 8 reads cannot leave the normal range (one read scales f by >= 2^-44) and takes the plain path.  A deeper
+// pair keeps one exponent PER ENTRY: every 8 reads an f_lm below 2^-300 is scaled by the exact power of two that brings it to
+// [0.5, 1) and the exponent goes to E_lm; a candidate takes E = max E_lm over its entries with a non-zero weight, sums
+// w_lm f_lm 2^(E_lm - E) (exact shifts; an entry more than ~700 binades below the largest adds nothing) and gets log(L) + E ln 2.  A
+// shared exponent would not do here: for an ALT-heavy pair the hom-REF x hom-REF entry is thousands of binades below the largest of the
+// nine, and it is the only one a hom-REF x hom-REF candidate counts.
+// Nothing crosses lanes and every entry is one serial sum: its bits depend on b's data, (v1, v2), alpha and rho only (the CC / PT
+// instantiation changes which slots exist and how many headers a trip stages, not an entry's operations or their order).
+constexpr int kAmbDblWaves = 4;
+constexpr int kAmbDblMaxCand = 8, kAmbDblMaxAlpha = 8;
+template <int CC> struct AmbDblPair { double a; int64_t off; uint32_t n, rd4, mask, pad; float gp[CC][6]; };   // n = 0: skipped
+
+__device__ __forceinline__ double amb_uniform(double x) {          // a wave-uniform double into a scalar register pair
+  return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+}
+
+// One pair: the nine read products of this lane's rho, then the fold into the running sums of the candidates in `mask`.
+template <int CC, bool DEEP>
+__device__ __forceinline__ void amb_dbl_pair(const PileupView& pv, const AmbDblPair<CC>& h, uint32_t nj, uint32_t mask, const double (&cm)[9],
+                                             double rho, double om, const double (*s_pra)[2], const double* s_log, const DmxLogPins& lk,
+                                             double (&acc)[CC]) {
+  const double ra = rho * h.a;
+  double pp[9], qq[9], f[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) { pp[k] = om * cm[k] + ra; qq[k] = 1.0 - pp[k]; }
+  const int64_t off = h.off;
+  uint32_t w = h.rd4;
+  double pR = s_pra[w & 0xFF][0], pA = s_pra[w & 0xFF][1];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) f[k] = pR * qq[k] + pA * pp[k];
+  int32_t E[9];
+  if (DEEP) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E[k] = 0;
+  }
+  for (uint32_t r = 1; r < nj; ++r) {
+    if ((r & 3) == 0) w = load_rd4(pv, off + r, nj - r);
+    const uint32_t byte = (w >> (8 * (r & 3))) & 0xFF;
+    pR = s_pra[byte][0]; pA = s_pra[byte][1];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) f[k] *= pR * qq[k] + pA * pp[k];
+    if (DEEP && (r & 7) == 7) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k)
+        if (f[k] < kAmbRescaleBelow && f[k] > 0.0) {
+          int e;
+          (void)frexp(f[k], &e);
+          f[k] = ldexp(f[k], -e);
+          E[k] += e;
+        }
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CC; ++c) {
+    if (!((mask >> c) & 1u)) continue;
+    double g1[3], g2[3];
+#pragma unroll
+    for (int l = 0; l < 3; ++l) { g1[l] = (double)h.gp[c][l]; g2[l] = (double)h.gp[c][3 + l]; }
+    double L = 0.0;
+    int32_t em = 0;
+    if (DEEP) {
+      em = INT32_MIN / 2;
+#pragma unroll
+      for (int k = 0; k < 9; ++k)
+        if (g1[k / 3] * g2[k % 3] != 0.0 && f[k] > 0.0) em = max(em, E[k]);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const double wk = g1[k / 3] * g2[k % 3];                 // float32 x float32: exact in float64
+        const double t = wk != 0.0 ? wk * ldexp(f[k], max(E[k] - em, -1100)) : 0.0;
+        L = k == 0 ? t : L + t;
+      }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const double t = (g1[k / 3] * g2[k % 3]) * f[k];
+        L = k == 0 ? t : L + t;
+      }
+    }
+    double lg = dmx_log_is_special(L) ? log(L) : dmx_log_fast_pinned(L, s_log, lk);
+    if (DEEP && em != 0) lg = __builtin_fma((double)em, DMX_LOG_LN2HI, __builtin_fma((double)em, DMX_LOG_LN2LO, lg));
+    acc[c] += lg;
+  }
+}
+
+template <int CC, int PT>
+__global__ __launch_bounds__(64 * kAmbDblWaves) void k_ambient_dbl(PileupView pv, int nrd_width, const double* __restrict__ tabs, const float* __restrict__ g,
+                                                                 int32_t V, const int32_t* __restrict__ cand, int32_t C, const double* __restrict__ amb,
+                                                                 const double* __restrict__ alpha, int32_t A, const double* __restrict__ grid, int32_t Q,
+                                                                 int32_t n_qblk, int64_t n_units, double* __restrict__ ll, int32_t* __restrict__ n_snp,
+                                                                 int32_t* __restrict__ n_read) {
+  static_assert(CC >= 1 && CC <= kAmbDblMaxCand && PT >= 1 && PT <= 64, "candidate slots / staged headers per trip");
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_pra[256][2];               // by read byte (allele << 7 | bq): {pR, pA}
+  __shared__ AmbDblPair<CC> s_hdr[kAmbDblWaves][PT];
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += 64 * kAmbDblWaves) s_log[i] = tabs[kLut + i];
+  for (int i = threadIdx.x; i < 256; i += 64 * kAmbDblWaves) {
+    const double mat = tabs[i & 127], e3 = tabs[128 + (i & 127)];
+    s_pra[i][0] = (i >> 7) ? e3 : mat;
+    s_pra[i][1] = (i >> 7) ? mat : e3;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t unit = (int64_t)blockIdx.x * kAmbDblWaves + wave;
+  if (unit >= n_units) return;
+  const int32_t qb = (int32_t)(unit % n_qblk), ai = (int32_t)((unit / n_qblk) % A), cell = (int32_t)(unit / ((int64_t)n_qblk * A));
+  const int32_t q = qb * 64 + lane;
+  int32_t v1[CC], v2[CC], ns[CC], nr[CC];
+  double acc[CC];
+  uint32_t used = 0;
+#pragma unroll
+  for (int c = 0; c < CC; ++c) {
+    v1[c] = -1; v2[c] = -1; ns[c] = 0; nr[c] = 0; acc[c] = 0.0;
+    if (c < C) {
+      v1[c] = cand[((size_t)cell * C + c) * 2];
+      v2[c] = cand[((size_t)cell * C + c) * 2 + 1];
+      if (v1[c] >= 0) used |= 1u << c;
+    }
+  }
+  if (used) {
+    AmbDblPair<CC>* hdr = s_hdr[wave];
+    const double rho = q < Q ? grid[q] : 0.0;    // lanes past Q run along and write nothing
+    const double om = 1.0 - rho;
+    const double al = alpha[ai];
+    double cm[9];
+#pragma unroll
+    for (int l = 0; l < 3; ++l)
+#pragma unroll
+      for (int m = 0; m < 3; ++m) cm[l * 3 + m] = amb_uniform(0.5 * l + (m - l) * 0.5 * al);
+    const DmxLogPins lk = dmx_log_pins();
+    const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+    int64_t rd_base = pv.cell_read_off[cell];
+    for (int64_t p0 = p_beg; p0 < p_end; p0 += PT) {
+      const int64_t p = p0 + lane;
+      const bool in = lane < PT && p < p_end;
+      const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+      const uint32_t incl = seg_scan_incl<64>(n);
+      const int64_t off = rd_base + (int64_t)(incl - n);
+      rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      if (lane < PT) {
+        AmbDblPair<CC>& h = hdr[lane];
+        uint32_t mask = 0;
+        if (n > 0) {
+          const int32_t snp = pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg);
+          const float* gs = g + (size_t)snp * V * 3;
+#pragma unroll
+          for (int c = 0; c < CC; ++c) {
+            if (!((used >> c) & 1u)) continue;
+            const float* r1 = gs + (size_t)v1[c] * 3;
+            const float* r2 = gs + (size_t)v2[c] * 3;
+            const float x0 = r1[0], x1 = r1[1], x2 = r1[2], y0 = r2[0], y1 = r2[1], y2 = r2[2];
+            h.gp[c][0] = x0; h.gp[c][1] = x1; h.gp[c][2] = x2; h.gp[c][3] = y0; h.gp[c][4] = y1; h.gp[c][5] = y2;
+            if ((x0 != 0.f || x1 != 0.f || x2 != 0.f) && (y0 != 0.f || y1 != 0.f || y2 != 0.f)) mask |= 1u << c;
+          }
+          h.a = amb[snp];
+          h.rd4 = load_rd4(pv, off, n);
+        }
+        h.off = off;
+        h.mask = mask;
+        h.n = mask ? n : 0u;
+      }
+      DMX_WAVE_LDS_ORDER();
+      const int cnt = (int)min<int64_t>(PT, p_end - p0);
+      for (int j = 0; j < cnt; ++j) {
+        const uint32_t nj = (uint32_t)__builtin_amdgcn_readfirstlane((int)hdr[j].n);
+        if (nj == 0) continue;
+        const uint32_t mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)hdr[j].mask);
+        if (nj < 8) amb_dbl_pair<CC, false>(pv, hdr[j], nj, mask, cm, rho, om, s_pra, s_log, lk, acc);
+        else amb_dbl_pair<CC, true>(pv, hdr[j], nj, mask, cm, rho, om, s_pra, s_log, lk, acc);
+#pragma unroll
+        for (int c = 0; c < CC; ++c)
+          if ((mask >> c) & 1u) { ns[c] += 1; nr[c] += (int32_t)nj; }
+      }
+      DMX_WAVE_LDS_ORDER();
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < CC; ++c) {
+    if (c >= C) continue;
+    const size_t o = (size_t)cell * C + c;
+    if (q < Q) ll[(o * A + ai) * Q + q] = acc[c];
+    if (ai == 0 && qb == 0 && lane == 0) { n_snp[o] = ns[c]; n_read[o] = nr[c]; }
+  }
+}
+
 // SNP-minor copies for dense pileups: gT[r][s] = g[s][r] (r = k*3+l, float32 as stored) and g0T[l][s] = gp0s[s][l].
 __global__ void k_transpose_geno(const float* __restrict__ g, const double* __restrict__ gp0, int32_t S, int32_t V,
                                  float* __restrict__ gT, double* __restrict__ g0T) {
@@ -7074,6 +7269,15 @@ struct dmx_engine {
   int32_t amb_B = 0, amb_Q = 0; bool have_amb = false;
   hipEvent_t aev[2] = {};
   dmx_ambient_info amb_info{};
+  // ambient-aware doublet profile (dmx_engine_ambient_doublet): buffers of its own, so that the last singlet profile stays
+  int32_t* d_dcand = nullptr; size_t dcand_cap = 0;
+  double* d_damb = nullptr; size_t damb_cap = 0;
+  double* d_dgrid = nullptr; size_t dgrid_cap = 0;   // grid[Q], then alpha[A]
+  double* d_dll = nullptr; size_t dll_cap = 0;
+  int32_t* d_dcnt = nullptr; size_t dcnt_cap = 0;
+  int32_t adbl_B = 0, adbl_C = 0, adbl_A = 0, adbl_Q = 0; bool have_adbl = false;
+  hipEvent_t dbev[2] = {};
+  dmx_ambient_doublet_info adbl_info{};
 };
 
 namespace {
@@ -7232,6 +7436,9 @@ extern "C" int dmx_engine_destroy(dmx_engine* e) {
   for (void* p : {(void*)e->d_aasg, (void*)e->d_aamb, (void*)e->d_agrid, (void*)e->d_all, (void*)e->d_acnt})
     if (p) (void)hipFree(p);
   for (hipEvent_t& ev : e->aev) if (ev) (void)hipEventDestroy(ev);
+  for (void* p : {(void*)e->d_dcand, (void*)e->d_damb, (void*)e->d_dgrid, (void*)e->d_dll, (void*)e->d_dcnt})
+    if (p) (void)hipFree(p);
+  for (hipEvent_t& ev : e->dbev) if (ev) (void)hipEventDestroy(ev);
   for (int i = 0; i < 2; ++i) { if (e->h_stage[i]) (void)hipHostFree(e->h_stage[i]); if (e->ev_stage[i]) (void)hipEventDestroy(e->ev_stage[i]); }
   for (hipEvent_t& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
   for (auto& r : e->ring_s) for (hipEvent_t& ev : r) if (ev) (void)hipEventDestroy(ev);
@@ -7689,7 +7896,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
     }
   }
   e->have_sing = e->have_grid = false;
-  e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_cdbl = false;
+  e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_adbl = false; e->have_cdbl = false;
   e->have_pileup = true;
   e->k1_fn = e->k2_fn = e->k3b_fn = nullptr; e->k1_placement = 0;      // nothing has run on this pileup yet
   return DMX_OK;
@@ -9478,6 +9685,126 @@ extern "C" int dmx_engine_ambient_info(dmx_engine* e, dmx_ambient_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_info: null argument");
   if (!e->have_amb) return set_error(DMX_ERR_STATE, "dmx_engine_ambient_info: no profile on the staged pileup (dmx_engine_ambient first)");
   *out = e->amb_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Ambient-aware doublet profile: the arguments are checked on the host (cand, a and the two grids are small), then
+// one launch of k_ambient_dbl over B x A x ceil(Q / 64) wavefronts, instantiated for the smallest of 1 / 2 / 4 / 8 candidate slots that
+// holds C.  Every buffer is the call's own: the last dmx_engine_ambient profile stays readable.
+namespace {
+template <int CC, int PT>
+void launch_ambient_dbl(dmx_engine* e, int32_t C, int32_t A, int32_t Q, int32_t n_qblk, int64_t n_units) {
+  hipLaunchKernelGGL((k_ambient_dbl<CC, PT>), dim3((unsigned)((n_units + kAmbDblWaves - 1) / kAmbDblWaves)), dim3(64 * kAmbDblWaves), 0, e->stream,
+                     e->pv, e->nrd_width, (const double*)e->d_lut, e->d_g, e->V, (const int32_t*)e->d_dcand, C, (const double*)e->d_damb,
+                     (const double*)(e->d_dgrid + Q), A, (const double*)e->d_dgrid, Q, n_qblk, n_units, e->d_dll, e->d_dcnt,
+                     e->d_dcnt + (size_t)e->pv.B * C);
+}
+}  // namespace
+
+extern "C" int dmx_engine_ambient_doublet(dmx_engine* e, const dmx_ambient_doublet_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_ambient_doublet: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_ambient_doublet: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S, C = rq->n_cand, A = rq->n_alpha, Q = rq->n_grid;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_ambient_doublet: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (C < 1 || C > kAmbDblMaxCand) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_cand %d is not in [1, %d]", C, kAmbDblMaxCand);
+  if (A < 1 || A > kAmbDblMaxAlpha) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_alpha %d is not in [1, %d]", A, kAmbDblMaxAlpha);
+  if (Q < 1 || Q > 256) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_grid %d is not in [1, 256]", Q);
+  if (!rq->grid || !rq->alpha || (B > 0 && !rq->cand) || (S > 0 && !rq->ambient))
+    return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: missing cand / alpha / ambient / grid");
+  if (rq->cand_memory != DMX_MEM_HOST && rq->cand_memory != DMX_MEM_DEVICE)
+    return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: cand_memory %d", rq->cand_memory);
+  for (int32_t n = 0; n < A; ++n) {
+    const double x = rq->alpha[n];
+    if (!(x >= 0.0 && x <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: alpha[%d] = %g is not in [0, 1]", n, x);
+    if (n > 0 && !(x > rq->alpha[n - 1])) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: alpha is not strictly ascending at %d", n);
+  }
+  for (int32_t q = 0; q < Q; ++q) {
+    const double r = rq->grid[q];
+    if (!(r >= 0.0 && r <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: grid[%d] = %g is not in [0, 1]", q, r);
+    if (q > 0 && !(r > rq->grid[q - 1])) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: the grid is not strictly ascending at %d", q);
+  }
+  for (int32_t i = 0; i < S; ++i)
+    if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0))
+      return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  HIP_TRY(hipSetDevice(e->device));
+  if (!e->dbev[0]) for (hipEvent_t& ev : e->dbev) HIP_TRY(hipEventCreate(&ev));
+  const size_t n_slot = (size_t)B * (size_t)C;
+  std::vector<int32_t> cd(n_slot * 2);
+  if (n_slot > 0) {
+    if (rq->cand_memory == DMX_MEM_DEVICE) {
+      HIP_TRY(hipMemcpyAsync(cd.data(), rq->cand, sizeof(int32_t) * 2 * n_slot, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+      std::memcpy(cd.data(), rq->cand, sizeof(int32_t) * 2 * n_slot);
+    }
+  }
+  int64_t n_used = 0;
+  for (size_t k = 0; k < n_slot; ++k) {
+    const int32_t v1 = cd[2 * k], v2 = cd[2 * k + 1];
+    if (v1 == -1) continue;
+    if (v1 < 0 || v1 >= V || v2 < 0 || v2 >= V || v1 == v2)
+      return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: cand[%zu][%zu] = (%d, %d) is not -1 or two different samples in [0, %d)",
+                       k / (size_t)C, k % (size_t)C, v1, v2, V);
+    ++n_used;
+  }
+  const size_t prof = sizeof(double) * n_slot * (size_t)A * (size_t)Q;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (prof > e->dll_cap && prof + prof / 16 > free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_ambient_doublet: the %d x %d x %d x %d profile needs %zu bytes, %zu are free", B, C, A, Q, prof, free_b);
+  if (int rc = ensure_dev((void**)&e->d_dll, &e->dll_cap, prof)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_dcnt, &e->dcnt_cap, sizeof(int32_t) * 2 * n_slot)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_dcand, &e->dcand_cap, sizeof(int32_t) * 2 * n_slot)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_damb, &e->damb_cap, sizeof(double) * (size_t)S)) return rc;
+  if (int rc = ensure_dev((void**)&e->d_dgrid, &e->dgrid_cap, sizeof(double) * (size_t)(Q + A))) return rc;
+  if (n_slot > 0) HIP_TRY(hipMemcpyAsync(e->d_dcand, cd.data(), sizeof(int32_t) * 2 * n_slot, hipMemcpyHostToDevice, e->stream));
+  if (S > 0) HIP_TRY(hipMemcpyAsync(e->d_damb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_dgrid, rq->grid, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_dgrid + Q, rq->alpha, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, e->stream));
+  const int32_t n_qblk = (Q + 63) / 64;
+  const int64_t n_units = (int64_t)B * A * n_qblk;
+  HIP_TRY(hipEventRecord(e->dbev[0], e->stream));
+  if (n_units > 0) {
+    if (C == 1) launch_ambient_dbl<1, 64>(e, C, A, Q, n_qblk, n_units);
+    else if (C == 2) launch_ambient_dbl<2, 64>(e, C, A, Q, n_qblk, n_units);
+    else if (C <= 4) launch_ambient_dbl<4, 32>(e, C, A, Q, n_qblk, n_units);
+    else launch_ambient_dbl<8, 32>(e, C, A, Q, n_qblk, n_units);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(e->dbev[1], e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return; cd is pageable host memory
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, e->dbev[0], e->dbev[1]));
+  dmx_ambient_doublet_info& inf = e->adbl_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.kernel_ms = ms; inf.profile_bytes = (int64_t)prof; inf.n_used = n_used;
+  inf.n_cells = B; inf.n_cand = C; inf.n_alpha = A; inf.n_grid = Q;
+  e->adbl_B = B; e->adbl_C = C; e->adbl_A = A; e->adbl_Q = Q; e->have_adbl = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_ambient_doublet(dmx_engine* e, double* ll, int32_t* n_snp, int32_t* n_read) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_ambient_doublet: null engine");
+  if (!e->have_adbl) return set_error(DMX_ERR_STATE, "dmx_engine_get_ambient_doublet: no profile on the staged pileup (dmx_engine_ambient_doublet first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t n_slot = (size_t)e->adbl_B * (size_t)e->adbl_C;
+  if (!n_slot) return DMX_OK;
+  if (ll) HIP_TRY(hipMemcpy(ll, e->d_dll, sizeof(double) * n_slot * (size_t)e->adbl_A * (size_t)e->adbl_Q, hipMemcpyDeviceToHost));
+  if (n_snp) HIP_TRY(hipMemcpy(n_snp, e->d_dcnt, sizeof(int32_t) * n_slot, hipMemcpyDeviceToHost));
+  if (n_read) HIP_TRY(hipMemcpy(n_read, e->d_dcnt + n_slot, sizeof(int32_t) * n_slot, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_ambient_doublet_info(dmx_engine* e, dmx_ambient_doublet_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet_info: null argument");
+  if (!e->have_adbl) return set_error(DMX_ERR_STATE, "dmx_engine_ambient_doublet_info: no profile on the staged pileup (dmx_engine_ambient_doublet first)");
+  *out = e->adbl_info;
   return DMX_OK;
 }
 

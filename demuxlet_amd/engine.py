@@ -552,6 +552,41 @@ class Engine:
         check(self._L.dmx_engine_ambient_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.AmbientInfo._fields_ if n != "reserved"}
 
+    def ambient_doublet_profile(self, cand, alphas, ambient, grid, n_cand=None):
+        """dmx_engine_ambient_doublet over the staged pileup: LL[b][c][n][q] of barcode b as a doublet of the samples cand[b][c] = (v1, v2)
+        (v1 = -1: slot not used), v2 contributing a share alphas[n] of the cell's reads, with a fraction grid[q] of all reads from a soup of
+        ALT frequency ambient[i].  `cand` is a host array [B][C][2], or a device pointer (int) to B x n_cand x 2 int32.
+        Returns (ll[B][C][A][Q] f64, n_snp[B][C] i32, n_read[B][C] i32)."""
+        amb = np.ascontiguousarray(ambient, dtype=np.float64)
+        gr = np.ascontiguousarray(grid, dtype=np.float64)
+        al = np.ascontiguousarray(alphas, dtype=np.float64)
+        if amb.ndim != 1 or gr.ndim != 1 or al.ndim != 1:
+            raise ValueError("alphas, ambient and grid must be 1-D")
+        if isinstance(cand, int):
+            if n_cand is None:
+                raise ValueError("a device cand needs n_cand=")
+            cd, mem, ptr, Cn = None, capi.DMX_MEM_DEVICE, cand, int(n_cand)
+        else:
+            cd = np.ascontiguousarray(cand, dtype=np.int32)
+            if cd.ndim != 3 or cd.shape[0] != self.B or cd.shape[2] != 2:
+                raise ValueError(f"cand must be [{self.B}][C][2]")
+            mem, ptr, Cn = capi.DMX_MEM_HOST, (cd.ctypes.data if cd.size else None), cd.shape[1]
+        A, Q = len(al), len(gr)
+        rq = capi.AmbientDoubletRequest(self.B, mem, ptr, Cn, A, len(amb), Q, al.ctypes.data if al.size else None,
+                                        amb.ctypes.data if amb.size else None, gr.ctypes.data if gr.size else None)
+        check(self._L.dmx_engine_ambient_doublet(self._h, C.byref(rq)))
+        ll = np.zeros((self.B, Cn, A, Q))
+        n_snp = np.zeros((self.B, Cn), dtype=np.int32)
+        n_read = np.zeros((self.B, Cn), dtype=np.int32)
+        check(self._L.dmx_engine_get_ambient_doublet(self._h, ll.ctypes.data, n_snp.ctypes.data, n_read.ctypes.data))
+        return ll, n_snp, n_read
+
+    def ambient_doublet_info(self) -> dict:
+        """HIP-event time (ms) of the last ambient-aware doublet profile and its size (dmx_engine_ambient_doublet_info)."""
+        r = capi.AmbientDoubletInfo()
+        check(self._L.dmx_engine_ambient_doublet_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.AmbientDoubletInfo._fields_ if n != "reserved"}
+
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()
         check(self._L.dmx_engine_device_view(self._h, C.byref(v)))

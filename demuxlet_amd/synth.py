@@ -199,6 +199,63 @@ def make_ambient_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, d
     return sp, rho, a
 
 
+def make_ambient_mixed_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: float, rbar: float, rho, doublet, alpha=0.5,
+                              ambient: Optional[np.ndarray] = None, dense_layout: bool = False, chunk_cells: int = 256,
+                              quals: Optional[str] = None) -> Tuple[SynthPileup, np.ndarray, np.ndarray, np.ndarray]:
+    """Singlets and doublets, each with its own contamination.  Cell c is sample c mod V; where doublet[c] is true a second, different
+    sample is drawn and contributes a share alpha[c] of the cell's reads.  Each read comes from the soup with probability rho[c] (ALT
+    w.p. a_i), otherwise from the second sample w.p. alpha[c] and from the first elsewise (ALT w.p. the dosage / 2); then sequencing error
+    as in make_pileup.  `rho`, `doublet` and `alpha` are scalars or [B]; `ambient` defaults to the donors' mean dosage / 2.  Returns
+    (pileup, rho[B], alpha[B], a[S]); pileup.truth[c] = (first, second or -1) and alpha[c] = 0 for singlets."""
+    S, V, _ = alleles.shape
+    dosage = np.clip(alleles, 0, 1).sum(axis=2).astype(np.float64)      # [S][V]
+    a = dosage.mean(axis=1) / 2.0 if ambient is None else np.asarray(ambient, dtype=np.float64)
+    rho = np.broadcast_to(np.asarray(rho, dtype=np.float64), (B,)).copy()
+    dbl = np.broadcast_to(np.asarray(doublet, dtype=bool), (B,)) & (V > 1)
+    alpha = np.where(dbl, np.broadcast_to(np.asarray(alpha, dtype=np.float64), (B,)), 0.0)
+    cell_pair_off = np.zeros(B + 1, dtype=np.int64)
+    cell_read_off = np.zeros(B + 1, dtype=np.int64)
+    snp_chunks, nrd_chunks, rd_chunks = [], [], []
+    totl = np.zeros(B, dtype=np.int32)
+    truth = np.full((B, 2), -1, dtype=np.int32)
+    for c0 in range(0, B, chunk_cells):
+        c1 = min(B, c0 + chunk_cells)
+        nc = c1 - c0
+        s1 = (np.arange(c0, c1) % V).astype(np.int32)
+        s2 = ((s1 + 1 + rng.integers(0, max(V - 1, 1), size=nc)) % V).astype(np.int32)
+        truth[c0:c1, 0] = s1
+        truth[c0:c1, 1] = np.where(dbl[c0:c1], s2, -1)
+        cov = np.ones((nc, S), dtype=bool) if delta >= 1.0 else rng.random((nc, S)) < delta
+        cc, ss = np.nonzero(cov)
+        npairs = len(cc)
+        nreads = 1 + rng.poisson(max(rbar - 1.0, 0.0), size=npairs)
+        pair_of_read = np.repeat(np.arange(npairs), nreads)
+        rc, rs = cc[pair_of_read], ss[pair_of_read]
+        soup = rng.random(len(rc)) < rho[c0 + rc]
+        src = np.where(rng.random(len(rc)) < alpha[c0 + rc], s2[rc], s1[rc])
+        alt = rng.random(len(rc)) < np.where(soup, a[rs], dosage[rs, src] / 2.0)
+        bq = draw_bq(rng, len(rc), quals)
+        e = rng.random(len(rc)) < ERR_OF_BQ[bq]
+        u = rng.integers(0, 3, size=len(rc))
+        allele = np.where(e, np.where(u == 0, 1 - alt.astype(np.int32), 2), alt.astype(np.int32)).astype(np.uint8)
+        keep = allele != 2
+        cell_pair_off[c0 + 1:c1 + 1] = np.bincount(cc, minlength=nc)
+        cell_read_off[c0 + 1:c1 + 1] = np.bincount(rc[keep], minlength=nc)
+        totl[c0:c1] = np.bincount(rc, minlength=nc)
+        snp_chunks.append(ss.astype(np.int32))
+        nrd_chunks.append(np.bincount(pair_of_read[keep], minlength=npairs))
+        rd_chunks.append(((allele[keep] << 7) | bq[keep]).astype(np.uint8))
+    np.cumsum(cell_pair_off, out=cell_pair_off)
+    np.cumsum(cell_read_off, out=cell_read_off)
+    nrd = np.concatenate(nrd_chunks) if nrd_chunks else np.zeros(0, dtype=np.int64)
+    nrd = nrd.astype(np.uint8 if (len(nrd) == 0 or nrd.max() <= 255) else np.uint16)
+    pair_snp = np.concatenate(snp_chunks) if snp_chunks else np.zeros(0, dtype=np.int32)
+    reads = np.concatenate(rd_chunks) if rd_chunks else np.zeros(0, dtype=np.uint8)
+    use_dense = dense_layout and delta >= 1.0
+    sp = SynthPileup(B, S, cell_pair_off, cell_read_off, None if use_dense else pair_snp, nrd, reads, totl, totl.copy(), totl.copy(), truth)
+    return sp, rho, alpha, a
+
+
 def barcode_name(i: int) -> str:
     """Deterministic 16-mer barcode whose byte-wise sort order is NOT the id order (exercises the sorted-output rule)."""
     x = (i * 2654435761 + 12345) & 0xFFFFFFFF

@@ -34,7 +34,8 @@ extern "C" {
                                _cluster_estep_doublet / _cluster_doublet_info (doublet-aware clustering); dmx_engine_cluster_merge_score /
                                _cluster_estep_grouped / _cluster_sm_info (split-merge moves); dmx_engine_cluster_set_known /
                                _cluster_estep_known / _cluster_mstep_window / _get_cluster_known / _cluster_known_info (partly
-                               genotyped pools).  Additions only. */
+                               genotyped pools); dmx_engine_ambient_doublet / _get_ambient_doublet / _ambient_doublet_info (doublet
+                               likelihood with a soup term, to tell soupy singlets from doublets).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -559,6 +560,55 @@ int dmx_engine_ambient(dmx_engine*, const dmx_ambient_request*);
 /* Device->host copies of the last profile (any pointer may be NULL): ll[B][Q] f64, n_snp[B] / n_read[B] i32. */
 int dmx_engine_get_ambient(dmx_engine*, double* ll, int32_t* n_snp, int32_t* n_read);
 int dmx_engine_ambient_info(dmx_engine*, dmx_ambient_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Ambient-aware doublet profile (no counterpart in the reference): the doublet likelihood with the soup term of
+ * dmx_engine_ambient, so that a soupy singlet and a doublet can be compared on one scale.  For up to C candidate sample pairs per
+ * barcode, cand[b][c] = (v1, v2) with v1 = -1 = slot not used and otherwise 0 <= v1, v2 < V, v1 != v2, mixing shares alpha[n], n < A
+ * (the share of v2's reads), ambient ALT frequencies a[n_snps] and contamination fractions rho[q], q < Q, over the staged pileup, the
+ * phred tables and the engine's genotype matrix gp (float32), for every barcode b, used slot c, n and q:
+ *   p_lm      = (1 - rho) (0.5 l + (m - l) 0.5 alpha) + rho a_i  for l, m = 0, 1, 2: the reference's mixture of genotype l of the first
+ *               and m of the second sample (cmd_cram_demuxlet.cpp:616), diluted by the soup as dmx_engine_ambient dilutes a singlet;
+ *   f_lm      = product over the pair's stored reads, in stored order, of pR (1 - p_lm) + pA p_lm (pR / pA as for dmx_engine_ambient);
+ *   L_i       = sum_l sum_m gp[i][v1][l] gp[i][v2][m] f_lm, the float32 entries widened to float64 (their product is exact), l-major, m-minor;
+ *   LL[b][c][n][q] = sum over b's pairs in ascending SNP order of log(L_i), the log being dmx_log.
+ * No per-read renormalisation and no 1e-6 floor (:649): the values compare with dmx_engine_ambient's (alpha = 0 with a one-hot second
+ * row IS the singlet profile of v1), not with the engine's doublet grid.  A pair with no stored read, or where either sample's gp row
+ * is all zero, contributes nothing to that candidate; n_snp[b][c] / n_read[b][c] count the pairs / reads that did.  f_lm is kept in
+ * range by exact power-of-two rescaling, one exponent per entry, carried into the log: pairs of hundreds of reads give the finite value
+ * of the log-space sum.  Each (b, c, n, q) is one serial sum with no floating-point atomics and no cross-lane step: its bits depend on
+ * b's data, (v1, v2), alpha and rho only — not on C, A, Q, the slot, the other candidates or what ran before — and a grid (rho or alpha)
+ * split over two calls gives the same bits at the shared points.  Unused slots get zero rows.  The call runs on the engine's stream,
+ * synchronises it before returning (host inputs may be freed then), uses buffers of its own and leaves every other result of the
+ * engine, the last dmx_engine_ambient profile included, as it was.
+ * DMX_ERR_ARG: C or A outside [1, 8], Q outside [1, 256], alpha or grid outside [0, 1] or not strictly ascending, an a_i outside [0, 1],
+ * a candidate that is neither unused nor two different samples in [0, V), n_cells / n_snps that do not match the staged pileup / the
+ * genotype matrix.  DMX_ERR_STATE: no pileup or no genotypes yet.  DMX_ERR_NOMEM: the B x C x A x Q profile does not fit the free
+ * device memory. */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t cand_memory;         /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `cand` lives */
+  const int32_t* cand;         /* [n_cells][n_cand][2] */
+  int32_t n_cand;              /* C, 1..8 */
+  int32_t n_alpha;             /* A, 1..8 */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t n_grid;              /* Q, 1..256 */
+  const double* alpha;         /* [n_alpha] float64, strictly ascending, in [0, 1], HOST */
+  const double* ambient;       /* [n_snps] float64 in [0, 1], HOST */
+  const double* grid;          /* [n_grid] float64, strictly ascending, in [0, 1], HOST */
+  int32_t reserved[4];         /* 0 */
+} dmx_ambient_doublet_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the last call's k_ambient_dbl */
+  int64_t profile_bytes;       /* device bytes of the B x C x A x Q profile */
+  int64_t n_used;              /* candidate slots in use */
+  int32_t n_cells, n_cand, n_alpha, n_grid;
+  int32_t reserved[4];
+} dmx_ambient_doublet_info;
+int dmx_engine_ambient_doublet(dmx_engine*, const dmx_ambient_doublet_request*);
+/* Device->host copies of the last profile (any pointer may be NULL): ll[B][C][A][Q] f64, n_snp[B][C] / n_read[B][C] i32. */
+int dmx_engine_get_ambient_doublet(dmx_engine*, double* ll, int32_t* n_snp, int32_t* n_read);
+int dmx_engine_ambient_doublet_info(dmx_engine*, dmx_ambient_doublet_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * a6,a10..a14  finaliser and writers — replaces cmd_cram_demuxlet.cpp:465-527 (.single), :713-875 (.sing2/.pair/.best).
