@@ -36,15 +36,10 @@
 #include "dmx_internal.hpp"
 extern char** environ;
 #include "dmx_log.hpp"
+#include "dmx_engine_state.hpp"
 
 using dmx::set_error;
-
-#define HIP_TRY(expr)                                                                                          \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) return set_error(DMX_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), \
-                                           __FILE__, __LINE__);                                                \
-  } while (0)
+using dmx::DevBuf; using dmx::Event; using dmx::EventPair; using dmx::Stream; using dmx::PinnedBuf;
 
 namespace {
 
@@ -7154,48 +7149,49 @@ struct dmx_engine {
   bool certify = false;        // run k_certify (the host libm's log() was found inside dmx_log_bracket's brackets)
   double prior = 0.5;
   std::vector<double> alpha;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  hipStream_t k1_stream = nullptr;               // dmx_engine_run: K1 beside K2 (lowest priority: it fills what K2's last round leaves free)
-  hipEvent_t ev_fork = nullptr, ev_k1_done = nullptr;
-  double* d_lut = nullptr;
-  double* d_alpha = nullptr;
+  Stream own_stream; hipStream_t stream = nullptr;   // stream: own_stream or the caller's (dmx_engine_set_stream); not owned
+  Stream k1_stream;                              // dmx_engine_run: K1 beside K2 (lowest priority: it fills what K2's last round leaves free)
+  Event ev_fork, ev_k1_done;
+  DevBuf<double> d_lut;
+  DevBuf<double> d_alpha;
   // genotypes
-  const float* d_g = nullptr; float* d_g_own = nullptr; int32_t S = 0; double* d_gp0 = nullptr; float* d_gT = nullptr; double* d_g0T = nullptr;
-  float* d_rows = nullptr; uint8_t* d_ids = nullptr; uint32_t* d_idw = nullptr; uint32_t* d_idd = nullptr; int32_t nwd2 = 0; int32_t n_classes = 0;   // genotype classes (0 = not usable)
+  const float* d_g = nullptr;                    // not owned: d_g_own, a refinement's or M-step's gp' buffer, or the caller's device matrix
+  DevBuf<float> d_g_own; int32_t S = 0; DevBuf<double> d_gp0; DevBuf<float> d_gT; DevBuf<double> d_g0T;
+  DevBuf<float> d_rows; DevBuf<uint8_t> d_ids; DevBuf<uint32_t> d_idw, d_idd; int32_t nwd2 = 0; int32_t n_classes = 0;   // genotype classes (0 = not usable)
   // pileup
-  PileupView pv{}; int32_t nrd_width = 1; int64_t P = 0, R = 0; bool have_pileup = false;
-  void* own[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // device copies of a host pileup (grow-only: a job's ranges reuse them); [5]: gather sources
-  size_t own_cap[6] = {0, 0, 0, 0, 0, 0};
-  int32_t* d_sched = nullptr; size_t sched_cap = 0;
+  PileupView pv{}; int32_t nrd_width = 1; int64_t P = 0, R = 0; bool have_pileup = false;   // pv's pointers are not owned: own[] or the caller's device arrays
+  DevBuf<void> own[6];                           // device copies of a host pileup (grow-only: a job's ranges reuse them); [5]: gather sources
+  DevBuf<int32_t> d_sched;
   int64_t max_cell_pairs = 0;                                         // covered SNPs of the staged pileup's longest barcode
-  int32_t* d_bad = nullptr;                                          // set by k_check_snp_ids
+  DevBuf<int32_t> d_bad;                                             // set by k_check_snp_ids
   bool have_gT = false;                                              // d_gT / d_g0T hold the current genotype matrix
   // canonical GT classes (round 4): every called genotype of a --field GT matrix is one of three SNP-independent rows (hi, lo, lo) permuted
   // (bcf_filtered_reader.cpp:397-400); class ids are then 0 / 1 / 2 = that row with hi in place 0 / 1 / 2 and 3 = the SNP's one other row (a missing
   // genotype's HWE row, :381-388), and K1 takes log(GL . row) of the three canonical rows from a table indexed like the GL tables (d_ltab)
-  bool canon = false, ltab_valid = false; float can_hi = 0.f, can_lo = 0.f; double* d_ltab = nullptr; uint8_t* d_oth = nullptr;
-  uint4* d_snprec = nullptr; bool snprec_valid = false; double* d_ctab = nullptr; bool ctab_valid = false;   // k_singlet_can's per-SNP records and merged GL / class-log table
-  uint8_t* d_clsb = nullptr; bool clsb_valid = false; uint32_t clsb_stride = 0;                             // k_singlet_canp's per-sample class byte streams (k_build_clsb)
+  bool canon = false, ltab_valid = false; float can_hi = 0.f, can_lo = 0.f; DevBuf<double> d_ltab; DevBuf<uint8_t> d_oth;
+  DevBuf<uint4> d_snprec; bool snprec_valid = false; DevBuf<double> d_ctab; bool ctab_valid = false;   // k_singlet_can's per-SNP records and merged GL / class-log table
+  DevBuf<uint8_t> d_clsb; bool clsb_valid = false; uint32_t clsb_stride = 0;                        // k_singlet_canp's per-sample class byte streams (k_build_clsb)
   bool any_oth = false;                                   // some SNP of the canonical-class matrix has a fourth row (k_canon_apply's oth)
   bool off32 = false;                                     // every absolute pair index and read offset of the staged pileup fits 32 bits
   bool reads_padded = false;                              // four bytes past the staged pileup's last read byte are readable (k_singlet_can's unconditional 4-byte loads)
-  double* d_cseed = nullptr; bool cseed_valid = false;   // certify_pair_values' seeds (k_build_certify_seeds; a function of the phred tables)
-  double* d_cfin = nullptr; bool cfin_valid = false;     // ... and its final values for pairs of up to three tabled reads (k_build_certify_finals, round 6)
-  double* d_park = nullptr; size_t park_cap = 0;   // k_certify's per-barcode state between the launches of its SNP-blocked walk
-  int64_t* d_blk = nullptr; size_t blk_cap = 0; int32_t blk_shift = 0, blk_n = 0;   // k_snp_blocks table of the staged (sparse) pileup; blk_n = 0: none
+  DevBuf<double> d_cseed; bool cseed_valid = false;      // certify_pair_values' seeds (k_build_certify_seeds; a function of the phred tables)
+  DevBuf<double> d_cfin; bool cfin_valid = false;        // ... and its final values for pairs of up to three tabled reads (k_build_certify_finals, round 6)
+  DevBuf<double> d_park;                           // k_certify's per-barcode state between the launches of its SNP-blocked walk
+  DevBuf<int64_t> d_blk; int32_t blk_shift = 0, blk_n = 0;   // k_snp_blocks table of the staged (sparse) pileup; blk_n = 0: none
   bool geno_safe = false;                                            // every genotype row finite, non-negative, max >= 2^-400 (k_check_geno)
   // host -> device staging of the big pileup arrays: two pinned chunks filled by host threads while the other one is in flight
-  void* h_stage[2] = {nullptr, nullptr}; hipEvent_t ev_stage[2] = {nullptr, nullptr}; bool stage_busy[2] = {false, false}; int stage_cur = 0;
+  PinnedBuf h_stage[2]; Event ev_stage[2]; bool stage_busy[2] = {false, false}; int stage_cur = 0;
   // results
-  double *d_llks = nullptr, *d_llk0s = nullptr, *d_grid = nullptr, *d_l00 = nullptr;
-  dmx_cell_summary* d_sum = nullptr;
-  uint8_t* d_flag = nullptr;
-  double* d_sing = nullptr;
-  int32_t out_cap = 0, grid_cap = 0; bool have_grid = false, have_sing = false;   // cells the result buffers hold
-  hipEvent_t ev[8] = {};
+  DevBuf<double> d_llks, d_llk0s, d_grid, d_l00;
+  DevBuf<dmx_cell_summary> d_sum;
+  DevBuf<uint8_t> d_flag_base;
+  uint8_t* d_flag() const { return d_flag_base ? d_flag_base + kFlagHead : nullptr; }   // the flags proper: a view kFlagHead bytes into the buffer
+  DevBuf<double> d_sing;
+  int32_t out_cells = 0, grid_cells = 0; bool have_grid = false, have_sing = false;   // cells the result buffers hold
+  Event ev[8];
   // the last kRing launches of K1 and of K2 / K3 / K3b, bracketed by events on the engine's stream (dmx_engine_mean_kernel_times)
   static constexpr int kRing = 16;
-  hipEvent_t ring_s[kRing][2] = {}, ring_d[kRing][4] = {};
+  Event ring_s[kRing][2], ring_d[kRing][4];
   int64_t n_ring_s = 0, n_ring_d = 0; bool ring_certified[kRing] = {};
   bool timed[4] = {false, false, false, false};
   // Experiment switches.  The DMX_* variables that steer kernel selection — kernel experiments, the tests' forced
@@ -7208,121 +7204,89 @@ struct dmx_engine {
   bool k2_sym = false;                                               // launch_doublet picked a k_doublet_sym form (FAST, soft fields, grid {0, 0.5})
   // genotype refinement (dmx_engine_refine_genotypes): its own slab table of the staged pileup (K1's d_blk is not touched), the chunk plan,
   // the partials of one wave, the results; two gp' buffers, so that a refinement never overwrites the matrix the engine was handed by pointer
-  int64_t* d_rblk = nullptr; size_t rblk_cap = 0; bool rblk_valid = false; int32_t rblk_S = 0;
-  int32_t* d_rplan = nullptr; size_t rplan_cap = 0; std::vector<int32_t> h_rplan;
-  void* d_rpart = nullptr; size_t rpart_cap = 0;
-  float* d_rprior = nullptr; size_t rprior_cap = 0;
-  double* d_rll = nullptr; size_t rll_cap = 0;
-  int32_t* d_rcnt = nullptr; size_t rcnt_cap = 0;
-  float* d_rgp[2] = {nullptr, nullptr}; size_t rgp_cap[2] = {0, 0}; int rgp_cur = -1;
+  DevBuf<int64_t> d_rblk; bool rblk_valid = false; int32_t rblk_S = 0;
+  DevBuf<int32_t> d_rplan; std::vector<int32_t> h_rplan;
+  DevBuf<RefPartial> d_rpart;
+  DevBuf<float> d_rprior;
+  DevBuf<double> d_rll;
+  DevBuf<int32_t> d_rcnt;
+  DevBuf<float> d_rgp[2]; int rgp_cur = -1;
   int32_t ref_S = 0; bool have_refined = false;
-  hipEvent_t rev[4] = {};
+  Event rev[4];
   dmx_refine_info ref_info{};
   // genotype-free clustering (dmx_engine_cluster_*): the SNP-major stage cache (a snapshot: staging a pileup again does not touch it),
   // the last E-step's weights and sums, the last M-step's results; two gp' buffers, as for the refinement
-  int64_t* d_coff = nullptr; size_t coff_cap = 0;
-  int32_t* d_ccell = nullptr; size_t ccell_cap = 0;
-  double* d_clgl = nullptr; size_t clgl_cap = 0;
-  uint32_t* d_ccnt = nullptr; size_t ccnt_cap = 0;
+  DevBuf<int64_t> d_coff;
+  DevBuf<int32_t> d_ccell;
+  DevBuf<double> d_clgl;
+  DevBuf<uint32_t> d_ccnt;
   int64_t cl_P = 0; int32_t cl_B = 0, cl_S = 0; bool have_cstage = false;
-  double* d_cw = nullptr; size_t cw_cap = 0; double* d_cwh = nullptr; size_t cwh_cap = 0; bool have_cw = false; int32_t cw_C = 0;
-  double* d_clse = nullptr; size_t clse_cap = 0; double* d_cpart = nullptr; size_t cpart_cap = 0; double* d_cpi = nullptr; size_t cpi_cap = 0;
-  uint8_t* d_cmask = nullptr; size_t cmask_cap = 0;
-  double* d_cll = nullptr; size_t cll_cap = 0; double* d_cW = nullptr; size_t cW_cap = 0; float* d_cq = nullptr; size_t cq_cap = 0;
-  float* d_cgp[2] = {nullptr, nullptr}; size_t cgp_cap[2] = {0, 0}; int cgp_cur = -1; int32_t cm_S = 0, cm_C = 0; bool have_cm = false;
-  hipEvent_t cev[2] = {};
+  DevBuf<double> d_cw, d_cwh; bool have_cw = false; int32_t cw_C = 0;
+  DevBuf<double> d_clse, d_cpart, d_cpi;         // (an E-step's folded sums are the last row of d_cpart)
+  DevBuf<uint8_t> d_cmask;
+  DevBuf<double> d_cll, d_cW; DevBuf<float> d_cq;
+  DevBuf<float> d_cgp[2]; int cgp_cur = -1; int32_t cm_S = 0, cm_C = 0; bool have_cm = false;
+  EventPair cev;
   dmx_cluster_info cl_info{};
   // doublet-aware clustering (dmx_engine_cluster_doublet / _estep_doublet): the pair table, LLD[B][R][P], the per-barcode doublet mass
   // and the host-made log priors; LLD belongs to the staged pileup (staging again drops it)
-  uint32_t* d_cpairs = nullptr; size_t cpairs_cap = 0;
-  double* d_clld = nullptr; size_t clld_cap = 0;
-  double* d_cdm = nullptr; size_t cdm_cap = 0;
-  double* d_clp = nullptr; size_t clp_cap = 0;
+  DevBuf<uint32_t> d_cpairs;
+  DevBuf<double> d_clld;
+  DevBuf<double> d_cdm;
+  DevBuf<double> d_clp;
   int32_t cd_B = 0, cd_R = 0, cd_K = 0; bool have_cdbl = false;
-  hipEvent_t dev_[2] = {};
+  EventPair dev_;
   dmx_cluster_doublet_info cd_info{};
   // split-merge moves (dmx_engine_cluster_merge_score / _estep_grouped): the marginals A[S][C] and flags of the last M-step, the
   // prior, the per-chunk partials and the folded scores; the group of each barcode
-  double* d_smA = nullptr; size_t smA_cap = 0;
-  uint8_t* d_smF = nullptr; size_t smF_cap = 0;
-  float* d_smq = nullptr; size_t smq_cap = 0;
-  double* d_smpart = nullptr; size_t smpart_cap = 0;
-  int32_t* d_smnpart = nullptr; size_t smnpart_cap = 0;
-  double* d_smout = nullptr; size_t smout_cap = 0;
-  int32_t* d_smnout = nullptr; size_t smnout_cap = 0;
-  int32_t* d_cgrp = nullptr; size_t cgrp_cap = 0;
-  hipEvent_t sev[2] = {};
+  DevBuf<double> d_smA;
+  DevBuf<uint8_t> d_smF;
+  DevBuf<float> d_smq;
+  DevBuf<double> d_smpart;
+  DevBuf<int32_t> d_smnpart;
+  DevBuf<double> d_smout;
+  DevBuf<int32_t> d_smnout;
+  DevBuf<int32_t> d_cgrp;
+  EventPair sev;
   dmx_cluster_sm_info sm_info{};
   // partly genotyped pools (dmx_engine_cluster_set_known / _estep_known / _mstep_window): the known rows gk[S][Vk][3], every
   // component's weights [B][R][Vk + M] of the last known-column E-step; cgp_C is the column count of the last M-step's gp' buffer
-  float* d_ckn = nullptr; size_t ckn_cap = 0; int32_t ckn_S = 0, ckn_Vk = 0; bool have_ckn = false;
-  double* d_ckw = nullptr; size_t ckw_cap = 0; int32_t ckw_B = 0, ckw_R = 0, ckw_K = 0; bool have_ckw = false;
+  DevBuf<float> d_ckn; int32_t ckn_S = 0, ckn_Vk = 0; bool have_ckn = false;
+  DevBuf<double> d_ckw; int32_t ckw_B = 0, ckw_R = 0, ckw_K = 0; bool have_ckw = false;
   int32_t cgp_C = 0;
-  hipEvent_t kev[2] = {};
+  EventPair kev;
   dmx_cluster_known_info kn_info{};
   // ambient contamination profile (dmx_engine_ambient): its own copies of the inputs and the B x Q results
-  int32_t* d_aasg = nullptr; size_t aasg_cap = 0;
-  double* d_aamb = nullptr; size_t aamb_cap = 0;
-  double* d_agrid = nullptr; size_t agrid_cap = 0;
-  double* d_all = nullptr; size_t all_cap = 0;
-  int32_t* d_acnt = nullptr; size_t acnt_cap = 0;
+  DevBuf<int32_t> d_aasg;
+  DevBuf<double> d_aamb;
+  DevBuf<double> d_agrid;
+  DevBuf<double> d_all;
+  DevBuf<int32_t> d_acnt;
   int32_t amb_B = 0, amb_Q = 0; bool have_amb = false;
-  hipEvent_t aev[2] = {};
+  EventPair aev;
   dmx_ambient_info amb_info{};
   // ambient-aware doublet profile (dmx_engine_ambient_doublet): buffers of its own, so that the last singlet profile stays
-  int32_t* d_dcand = nullptr; size_t dcand_cap = 0;
-  double* d_damb = nullptr; size_t damb_cap = 0;
-  double* d_dgrid = nullptr; size_t dgrid_cap = 0;   // grid[Q], then alpha[A]
-  double* d_dll = nullptr; size_t dll_cap = 0;
-  int32_t* d_dcnt = nullptr; size_t dcnt_cap = 0;
+  DevBuf<int32_t> d_dcand;
+  DevBuf<double> d_damb;
+  DevBuf<double> d_dgrid;                        // grid[Q], then alpha[A]
+  DevBuf<double> d_dll;
+  DevBuf<int32_t> d_dcnt;
   int32_t adbl_B = 0, adbl_C = 0, adbl_A = 0, adbl_Q = 0; bool have_adbl = false;
-  hipEvent_t dbev[2] = {};
+  EventPair dbev;
   dmx_ambient_doublet_info adbl_info{};
 };
 
 namespace {
 
-int free_pileup(dmx_engine* e) {
-  for (int i = 0; i < 6; ++i) { if (e->own[i]) (void)hipFree(e->own[i]); e->own[i] = nullptr; e->own_cap[i] = 0; }
-  if (e->d_sched) (void)hipFree(e->d_sched);
-  e->d_sched = nullptr; e->sched_cap = 0;
+void free_pileup(dmx_engine* e) {
+  for (auto& b : e->own) b.reset();
+  e->d_sched.reset();
   e->have_pileup = false;
-  return DMX_OK;
 }
-// Device buffer of at least `bytes`, kept across calls.  hipFree waits for the whole device, so a job whose ranges alternate
-// between two engines must not free and allocate per range: buffers only grow (with some slack for the next, slightly larger range).
-int ensure_dev(void** p, size_t* cap, size_t bytes) {
-  bytes = std::max<size_t>(bytes, 16);
-  if (*p && *cap >= bytes) return DMX_OK;
-  if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-  const size_t want = bytes + bytes / 16;
-  HIP_TRY(hipMalloc(p, want));
-  *cap = want;
-  return DMX_OK;
-}
-int free_results(dmx_engine* e) {
-  if (e->d_llks) (void)hipFree(e->d_llks);
-  if (e->d_llk0s) (void)hipFree(e->d_llk0s);
-  if (e->d_grid) (void)hipFree(e->d_grid);
-  if (e->d_l00) (void)hipFree(e->d_l00);
-  if (e->d_sum) (void)hipFree(e->d_sum);
-  if (e->d_flag) (void)hipFree(e->d_flag - kFlagHead);
-  if (e->d_sing) (void)hipFree(e->d_sing);
-  e->d_flag = nullptr; e->d_sing = nullptr;
-  e->d_llks = e->d_llk0s = e->d_grid = e->d_l00 = nullptr; e->d_sum = nullptr;
-  e->out_cap = 0; e->grid_cap = 0; e->have_grid = e->have_sing = false;
-  return DMX_OK;
-}
-
-template <typename T>
-int upload(dmx_engine* e, const void* host, size_t count, void** slot, const T** view) {
-  void* d = nullptr;
-  const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-  HIP_TRY(hipMalloc(&d, bytes));
-  *slot = d;
-  if (count) HIP_TRY(hipMemcpyAsync(d, host, count * sizeof(T), hipMemcpyHostToDevice, e->stream));
-  *view = (const T*)d;
-  return DMX_OK;
+void free_results(dmx_engine* e) {
+  for (DevBuf<double>* b : {&e->d_llks, &e->d_llk0s, &e->d_grid, &e->d_l00, &e->d_sing}) b->reset();
+  e->d_sum.reset(); e->d_flag_base.reset();
+  e->out_cells = 0; e->grid_cells = 0; e->have_grid = e->have_sing = false;
 }
 
 }  // namespace
@@ -7358,102 +7322,52 @@ extern "C" int dmx_engine_create(const dmx_engine_config* cfg, dmx_engine** out)
   HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return set_error(DMX_ERR_NOGPU, "dmx_engine_create: device %d is %s; this library is built for gfx950 (MI355X) only", cfg->device, prop.gcnArchName);
-  dmx_engine* e = new (std::nothrow) dmx_engine;
+  std::unique_ptr<dmx_engine> owner(new (std::nothrow) dmx_engine);   // (an early return below frees whatever was created so far)
+  dmx_engine* e = owner.get();
   if (!e) return set_error(DMX_ERR_NOMEM, "dmx_engine_create: out of memory");
   e->V = cfg->n_samples; e->A = cfg->n_alpha; e->device = cfg->device; e->mode = cfg->mode; e->prior = cfg->doublet_prior;
   e->alpha.assign(cfg->alpha, cfg->alpha + cfg->n_alpha);
   if (const char* x = getenv("DMX_EXPERIMENTS")) if (x[0] == '1' && !x[1])
     for (char** ev = environ; ev && *ev; ++ev)
       if (!std::strncmp(*ev, "DMX_", 4)) if (const char* eq = std::strchr(*ev, '=')) e->knobs.emplace(std::string((const char*)*ev, (size_t)(eq - *ev)), std::string(eq + 1));
-  HIP_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
+  if (int rc = e->own_stream.create(hipStreamNonBlocking)) return rc;
   e->stream = e->own_stream;
   {
     int least = 0, greatest = 0;
     HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIP_TRY(hipStreamCreateWithPriority(&e->k1_stream, hipStreamNonBlocking, least));
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&e->ev_k1_done, hipEventDisableTiming));
+    if (int rc = e->k1_stream.create(hipStreamNonBlocking, least)) return rc;
+    if (int rc = e->ev_fork.create(hipEventDisableTiming)) return rc;
+    if (int rc = e->ev_k1_done.create(hipEventDisableTiming)) return rc;
   }
-  for (hipEvent_t& ev : e->ev) HIP_TRY(hipEventCreate(&ev));
-  for (auto& r : e->ring_s) for (hipEvent_t& ev : r) HIP_TRY(hipEventCreate(&ev));
-  for (auto& r : e->ring_d) for (hipEvent_t& ev : r) HIP_TRY(hipEventCreate(&ev));
-  HIP_TRY(hipMalloc((void**)&e->d_lut, sizeof(double) * kTabTotal));
+  for (Event& ev : e->ev) if (int rc = ev.create()) return rc;
+  for (auto& r : e->ring_s) for (Event& ev : r) if (int rc = ev.create()) return rc;
+  for (auto& r : e->ring_d) for (Event& ev : r) if (int rc = ev.create()) return rc;
+  if (int rc = e->d_lut.alloc(sizeof(double) * kTabTotal)) return rc;
   HIP_TRY(hipMemcpy(e->d_lut + kLut, dmx_log_table_host, sizeof(double) * DMX_LOG_TABLE_DOUBLES, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->d_lut + kTabLogLo, dmx_log_table_lo_host, sizeof(double) * 128, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->d_lut + kTabLog2, dmx_log2_table_host, sizeof(double) * DMX_LOG2_TABLE_DOUBLES, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(e->d_lut + kTabLog32, dmx_log32_table_host, sizeof(double) * DMX_LOG32_TABLE_DOUBLES, hipMemcpyHostToDevice));
   e->certify = !(cfg->flags & DMX_ENGINE_NO_CERTIFY) && !e->knob("DMX_NO_CERTIFY") && dmx::libm_log_within_brackets();
-  HIP_TRY(hipMalloc((void**)&e->d_alpha, sizeof(double) * 64));
+  if (int rc = e->d_alpha.alloc(sizeof(double) * 64)) return rc;
   HIP_TRY(hipMemcpy(e->d_alpha, e->alpha.data(), sizeof(double) * e->A, hipMemcpyHostToDevice));
   double mat[256], err[256];
   dmx_phred_tables(mat, err);
-  *out = e;
-  return dmx_engine_set_phred_tables(e, mat, err);
+  if (int rc = dmx_engine_set_phred_tables(e, mat, err)) return rc;
+  *out = owner.release();
+  return DMX_OK;
 }
 
 extern "C" int dmx_engine_destroy(dmx_engine* e) {
   if (!e) return DMX_OK;
   (void)hipSetDevice(e->device);
   (void)hipStreamSynchronize(e->stream);
-  free_pileup(e); free_results(e);
-  if (e->d_g_own) (void)hipFree(e->d_g_own);
-  if (e->d_gp0) (void)hipFree(e->d_gp0);
-  if (e->d_gT) (void)hipFree(e->d_gT);
-  if (e->d_g0T) (void)hipFree(e->d_g0T);
-  if (e->d_rows) (void)hipFree(e->d_rows);
-  if (e->d_ids) (void)hipFree(e->d_ids);
-  if (e->d_idw) (void)hipFree(e->d_idw);
-  if (e->d_idd) (void)hipFree(e->d_idd);
-  if (e->d_lut) (void)hipFree(e->d_lut);
-  if (e->d_alpha) (void)hipFree(e->d_alpha);
-  if (e->d_bad) (void)hipFree(e->d_bad);
-  if (e->d_blk) (void)hipFree(e->d_blk);
-  if (e->d_park) (void)hipFree(e->d_park);
-  if (e->d_cseed) (void)hipFree(e->d_cseed);
-  if (e->d_cfin) (void)hipFree(e->d_cfin);
-  if (e->d_clsb) (void)hipFree(e->d_clsb);
-  if (e->d_ltab) (void)hipFree(e->d_ltab);
-  if (e->d_oth) (void)hipFree(e->d_oth);
-  if (e->d_snprec) (void)hipFree(e->d_snprec);
-  if (e->d_ctab) (void)hipFree(e->d_ctab);
-  for (void* p : {(void*)e->d_rblk, (void*)e->d_rplan, e->d_rpart, (void*)e->d_rprior, (void*)e->d_rll, (void*)e->d_rcnt, (void*)e->d_rgp[0], (void*)e->d_rgp[1]})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t& ev : e->rev) if (ev) (void)hipEventDestroy(ev);
-  for (void* p : {(void*)e->d_coff, (void*)e->d_ccell, (void*)e->d_clgl, (void*)e->d_ccnt, (void*)e->d_cw, (void*)e->d_cwh, (void*)e->d_clse,
-                  (void*)e->d_cpart, (void*)e->d_cpi, (void*)e->d_cmask, (void*)e->d_cll, (void*)e->d_cW, (void*)e->d_cq, (void*)e->d_cgp[0],
-                  (void*)e->d_cgp[1]})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t& ev : e->cev) if (ev) (void)hipEventDestroy(ev);
-  for (void* p : {(void*)e->d_cpairs, (void*)e->d_clld, (void*)e->d_cdm, (void*)e->d_clp})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t& ev : e->dev_) if (ev) (void)hipEventDestroy(ev);
-  for (void* p : {(void*)e->d_smA, (void*)e->d_smF, (void*)e->d_smq, (void*)e->d_smpart, (void*)e->d_smnpart, (void*)e->d_smout, (void*)e->d_smnout,
-                  (void*)e->d_cgrp})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t& ev : e->sev) if (ev) (void)hipEventDestroy(ev);
-  for (void* p : {(void*)e->d_ckn, (void*)e->d_ckw}) if (p) (void)hipFree(p);
-  for (hipEvent_t& ev : e->kev) if (ev) (void)hipEventDestroy(ev);
-  for (void* p : {(void*)e->d_aasg, (void*)e->d_aamb, (void*)e->d_agrid, (void*)e->d_all, (void*)e->d_acnt})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t& ev : e->aev) if (ev) (void)hipEventDestroy(ev);
-  for (void* p : {(void*)e->d_dcand, (void*)e->d_damb, (void*)e->d_dgrid, (void*)e->d_dll, (void*)e->d_dcnt})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t& ev : e->dbev) if (ev) (void)hipEventDestroy(ev);
-  for (int i = 0; i < 2; ++i) { if (e->h_stage[i]) (void)hipHostFree(e->h_stage[i]); if (e->ev_stage[i]) (void)hipEventDestroy(e->ev_stage[i]); }
-  for (hipEvent_t& ev : e->ev) if (ev) (void)hipEventDestroy(ev);
-  for (auto& r : e->ring_s) for (hipEvent_t& ev : r) if (ev) (void)hipEventDestroy(ev);
-  for (auto& r : e->ring_d) for (hipEvent_t& ev : r) if (ev) (void)hipEventDestroy(ev);
-  if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
-  if (e->k1_stream) (void)hipStreamDestroy(e->k1_stream);
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->ev_k1_done) (void)hipEventDestroy(e->ev_k1_done);
   delete e;
   return DMX_OK;
 }
 
 extern "C" int dmx_engine_set_stream(dmx_engine* e, void* s) {
   if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_set_stream: null engine");
-  e->stream = s ? (hipStream_t)s : e->own_stream;
+  e->stream = s ? (hipStream_t)s : (hipStream_t)e->own_stream;
   return DMX_OK;
 }
 
@@ -7481,19 +7395,18 @@ extern "C" int dmx_engine_set_phred_tables(dmx_engine* e, const double mat[256],
 extern "C" int dmx_engine_set_genotypes(dmx_engine* e, const float* g, int32_t n_snps, int32_t memory) {
   if (!e || !g || n_snps < 0) return set_error(DMX_ERR_ARG, "dmx_engine_set_genotypes: bad arguments");
   HIP_TRY(hipSetDevice(e->device));
-  if (e->d_g_own) { (void)hipFree(e->d_g_own); e->d_g_own = nullptr; }
-  if (e->d_gp0) { (void)hipFree(e->d_gp0); e->d_gp0 = nullptr; }
+  e->d_g_own.reset(); e->d_gp0.reset();
   e->have_gT = false;
   const size_t n = (size_t)n_snps * e->V * 3;
   if (memory == DMX_MEM_DEVICE) {
     e->d_g = g;
   } else {
-    HIP_TRY(hipMalloc((void**)&e->d_g_own, std::max<size_t>(n * sizeof(float), 16)));
+    if (int rc = e->d_g_own.alloc(std::max<size_t>(n * sizeof(float), 16))) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_g_own, g, n * sizeof(float), hipMemcpyHostToDevice, e->stream));
     e->d_g = e->d_g_own;
   }
   e->S = n_snps;
-  HIP_TRY(hipMalloc((void**)&e->d_gp0, std::max<size_t>((size_t)n_snps * 3 * sizeof(double), 16)));
+  if (int rc = e->d_gp0.alloc(std::max<size_t>((size_t)n_snps * 3 * sizeof(double), 16))) return rc;
   if (n_snps > 0) {
     const int64_t items = (int64_t)n_snps * 3;
     HIP_TRY(hipEventRecord(e->ev[0], e->stream));
@@ -7504,26 +7417,22 @@ extern "C" int dmx_engine_set_genotypes(dmx_engine* e, const float* g, int32_t n
   }
 
   // genotype classes (<= 4 distinct rows per SNP: --field GT): enables the class kernels
-  if (e->d_rows) { (void)hipFree(e->d_rows); e->d_rows = nullptr; }
-  if (e->d_ids) { (void)hipFree(e->d_ids); e->d_ids = nullptr; }
-  if (e->d_idw) { (void)hipFree(e->d_idw); e->d_idw = nullptr; }
-  if (e->d_idd) { (void)hipFree(e->d_idd); e->d_idd = nullptr; }
+  e->d_rows.reset(); e->d_ids.reset(); e->d_idw.reset(); e->d_idd.reset();
   e->n_classes = 0;
   e->geno_safe = false;
   if (n_snps > 0) {
-    int32_t* d_max = nullptr;
-    HIP_TRY(hipMalloc((void**)&e->d_rows, (size_t)n_snps * kMaxCls * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&e->d_ids, (size_t)n_snps * e->V + 16));
-    HIP_TRY(hipMalloc((void**)&e->d_idw, (size_t)n_snps * ((e->V + 15) / 16) * sizeof(uint32_t) + 16));
+    DevBuf<int32_t> d_max, d_unsafe;
+    if (int rc = e->d_rows.alloc((size_t)n_snps * kMaxCls * 3 * sizeof(float))) return rc;
+    if (int rc = e->d_ids.alloc((size_t)n_snps * e->V + 16)) return rc;
+    if (int rc = e->d_idw.alloc((size_t)n_snps * ((e->V + 15) / 16) * sizeof(uint32_t) + 16)) return rc;
     e->nwd2 = ((e->V + e->V / 2 - 1) >> 4) + 5;                     // last window start (V-1 + V/2) >> 4, plus a window of <= 4 words, plus one
-    HIP_TRY(hipMalloc((void**)&e->d_idd, (size_t)n_snps * e->nwd2 * sizeof(uint32_t) + 16));
-    HIP_TRY(hipMalloc((void**)&d_max, sizeof(int32_t)));
+    if (int rc = e->d_idd.alloc((size_t)n_snps * e->nwd2 * sizeof(uint32_t) + 16)) return rc;
+    if (int rc = d_max.alloc(sizeof(int32_t))) return rc;
     HIP_TRY(hipMemsetAsync(d_max, 0, sizeof(int32_t), e->stream));
     hipLaunchKernelGGL(k_build_classes, dim3((unsigned)((n_snps + 255) / 256)), dim3(256), 0, e->stream, e->d_g, n_snps, e->V,
                        e->d_rows, e->d_ids, e->d_idw, e->d_idd, e->nwd2, d_max);
     HIP_TRY(hipGetLastError());
-    int32_t* d_unsafe = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_unsafe, sizeof(int32_t)));
+    if (int rc = d_unsafe.alloc(sizeof(int32_t))) return rc;
     HIP_TRY(hipMemsetAsync(d_unsafe, 0, sizeof(int32_t), e->stream));
     hipLaunchKernelGGL(k_check_geno, dim3(1024), dim3(256), 0, e->stream, e->d_g, (int64_t)n_snps * e->V, d_unsafe);
     HIP_TRY(hipGetLastError());
@@ -7531,16 +7440,16 @@ extern "C" int dmx_engine_set_genotypes(dmx_engine* e, const float* g, int32_t n
     HIP_TRY(hipMemcpyAsync(&h_max, d_max, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(&h_unsafe, d_unsafe, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
-    (void)hipFree(d_max); (void)hipFree(d_unsafe);
+    d_max.reset(); d_unsafe.reset();
     e->geno_safe = h_unsafe == 0 && !e->knob("DMX_FORCE_CHECK");
     e->n_classes = (h_max >= 1 && h_max <= kMaxCls) ? h_max : 0;
-    if (!e->n_classes) { (void)hipFree(e->d_rows); (void)hipFree(e->d_ids); (void)hipFree(e->d_idw); (void)hipFree(e->d_idd); e->d_rows = nullptr; e->d_ids = nullptr; e->d_idw = nullptr; e->d_idd = nullptr; }
+    if (!e->n_classes) { e->d_rows.reset(); e->d_ids.reset(); e->d_idw.reset(); e->d_idd.reset(); }
     // canonical GT classes (see k_canon_apply): relabel when the matrix has that shape
     e->canon = false; e->ltab_valid = false; e->ctab_valid = false; e->snprec_valid = false; e->clsb_valid = false;
-    if (e->d_oth) { (void)hipFree(e->d_oth); e->d_oth = nullptr; }
+    e->d_oth.reset();
     if (e->n_classes && !e->knob("DMX_NO_CANON")) {
-      int32_t* d_w = nullptr;
-      HIP_TRY(hipMalloc((void**)&d_w, 3 * sizeof(int32_t)));
+      DevBuf<int32_t> d_w;
+      if (int rc = d_w.alloc(3 * sizeof(int32_t))) return rc;
       int32_t h_w[3] = {0x7FFFFFFF, 0, 0};
       HIP_TRY(hipMemcpyAsync(d_w, h_w, sizeof h_w, hipMemcpyHostToDevice, e->stream));
       hipLaunchKernelGGL(k_find_canon, dim3((unsigned)((n_snps + 255) / 256)), dim3(256), 0, e->stream, e->d_rows, n_snps, d_w);
@@ -7566,7 +7475,7 @@ extern "C" int dmx_engine_set_genotypes(dmx_engine* e, const float* g, int32_t n
           HIP_TRY(hipMemcpyAsync(h_w + 1, d_w + 1, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
           HIP_TRY(hipStreamSynchronize(e->stream));
           if (h_w[1] == 0) {
-            HIP_TRY(hipMalloc((void**)&e->d_oth, (size_t)n_snps + 16));
+            if (int rc = e->d_oth.alloc((size_t)n_snps + 16)) return rc;
             hipLaunchKernelGGL(k_canon_apply, dim3((unsigned)((n_snps + 255) / 256)), dim3(256), 0, e->stream, e->d_rows, e->d_ids, e->d_idw,
                                e->d_idd, n_snps, e->V, e->nwd2, uh, ul, e->d_oth, d_w + 2);
             HIP_TRY(hipGetLastError());
@@ -7576,7 +7485,6 @@ extern "C" int dmx_engine_set_genotypes(dmx_engine* e, const float* g, int32_t n
           }
         }
       }
-      (void)hipFree(d_w);
     }
   }
   HIP_TRY(hipStreamSynchronize(e->stream));   // the host buffer may go away after return
@@ -7619,7 +7527,7 @@ struct StageWriter {
         if (e->stage_busy[slot]) { HIP_TRY(hipEventSynchronize(e->ev_stage[slot])); e->stage_busy[slot] = false; }
       }
       const size_t m = std::min(n, kStageBytes - fill);
-      par_memcpy((uint8_t*)e->h_stage[slot] + fill, src, m);
+      par_memcpy((uint8_t*)e->h_stage[slot].get() + fill, src, m);
       fill += m; src += m; n -= m;
       if (fill == kStageBytes) if (int rc = flush()) return rc;
     }
@@ -7627,7 +7535,7 @@ struct StageWriter {
   }
   int flush() {
     if (!fill) return DMX_OK;
-    HIP_TRY(hipMemcpyAsync(dst, e->h_stage[slot], fill, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(dst, e->h_stage[slot].get(), fill, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipEventRecord(e->ev_stage[slot], e->stream));
     e->stage_busy[slot] = true;
     dst += fill; fill = 0; e->stage_cur ^= 1;
@@ -7680,37 +7588,37 @@ int set_pileup_cells_device(dmx_engine* e, const dmx_pileup* pl, const int64_t* 
     e->pv.cell_pair_off = pl->cell_pair_off + c0; e->pv.cell_read_off = pl->cell_read_off + c0;
     e->pv.pair_snp = pl->pair_snp; e->pv.pair_nrd = pl->pair_nrd; e->pv.reads = pl->reads;
     if (!pl->pair_snp && P == 0) {               // no pairs at all: never the dense layout (NULL would select it)
-      if (int rc = ensure_dev(&e->own[2], &e->own_cap[2], 16)) return rc;
-      e->pv.pair_snp = (const int32_t*)e->own[2];
+      if (int rc = e->own[2].ensure(16)) return rc;
+      e->pv.pair_snp = (const int32_t*)e->own[2].get();
     }
     e->pv.R = pl->n_reads;                       // (the bound of the caller's read array: offsets are absolute in a view)
   } else {
     const size_t w = (size_t)pl->nrd_width;
-    if (int rc = ensure_dev(&e->own[0], &e->own_cap[0], sizeof(int64_t) * ((size_t)B + 1))) return rc;
-    if (int rc = ensure_dev(&e->own[1], &e->own_cap[1], sizeof(int64_t) * ((size_t)B + 1))) return rc;
-    if (int rc = ensure_dev(&e->own[2], &e->own_cap[2], dense ? 16 : sizeof(int32_t) * (size_t)P + 16)) return rc;
-    if (int rc = ensure_dev(&e->own[3], &e->own_cap[3], (size_t)P * w + 4)) return rc;
-    if (int rc = ensure_dev(&e->own[4], &e->own_cap[4], (size_t)R + 4)) return rc;
-    if (int rc = ensure_dev(&e->own[5], &e->own_cap[5], sizeof(int64_t) * 2 * (size_t)std::max(B, 1))) return rc;
+    if (int rc = e->own[0].ensure(sizeof(int64_t) * ((size_t)B + 1))) return rc;
+    if (int rc = e->own[1].ensure(sizeof(int64_t) * ((size_t)B + 1))) return rc;
+    if (int rc = e->own[2].ensure(dense ? 16 : sizeof(int32_t) * (size_t)P + 16)) return rc;
+    if (int rc = e->own[3].ensure((size_t)P * w + 4)) return rc;
+    if (int rc = e->own[4].ensure((size_t)R + 4)) return rc;
+    if (int rc = e->own[5].ensure(sizeof(int64_t) * 2 * (size_t)std::max(B, 1))) return rc;
     std::vector<int64_t> src((size_t)2 * std::max(B, 1));
     for (int32_t k = 0; k < B; ++k) { src[(size_t)k] = h_po[cells[k]]; src[(size_t)B + k] = h_ro[cells[k]]; }
     HIP_TRY(hipMemcpyAsync(e->own[0], h_off.data(), sizeof(int64_t) * ((size_t)B + 1), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->own[1], h_roff.data(), sizeof(int64_t) * ((size_t)B + 1), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemcpyAsync(e->own[5], src.data(), sizeof(int64_t) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
     if (B) {
-      hipLaunchKernelGGL(k_gather_cells, dim3((unsigned)B), dim3(256), 0, e->stream, (const int64_t*)e->own[5], (const int64_t*)e->own[5] + B,
-                         (const int64_t*)e->own[0], (const int64_t*)e->own[1], dense ? nullptr : pl->pair_snp, (const uint8_t*)pl->pair_nrd, (int)w,
-                         pl->reads, (int32_t*)e->own[2], (uint8_t*)e->own[3], (uint8_t*)e->own[4]);
+      hipLaunchKernelGGL(k_gather_cells, dim3((unsigned)B), dim3(256), 0, e->stream, (const int64_t*)e->own[5].get(), (const int64_t*)e->own[5].get() + B,
+                         (const int64_t*)e->own[0].get(), (const int64_t*)e->own[1].get(), dense ? nullptr : pl->pair_snp, (const uint8_t*)pl->pair_nrd, (int)w,
+                         pl->reads, (int32_t*)e->own[2].get(), (uint8_t*)e->own[3].get(), (uint8_t*)e->own[4].get());
       HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(e->stream));     // (h_off, h_roff, src go away)
-    e->pv.cell_pair_off = (const int64_t*)e->own[0]; e->pv.cell_read_off = (const int64_t*)e->own[1];
-    e->pv.pair_snp = (dense && P > 0) ? nullptr : (const int32_t*)e->own[2];
-    e->pv.pair_nrd = (const uint8_t*)e->own[3]; e->pv.reads = (const uint8_t*)e->own[4];
+    e->pv.cell_pair_off = (const int64_t*)e->own[0].get(); e->pv.cell_read_off = (const int64_t*)e->own[1].get();
+    e->pv.pair_snp = (dense && P > 0) ? nullptr : (const int32_t*)e->own[2].get();
+    e->pv.pair_nrd = (const uint8_t*)e->own[3].get(); e->pv.reads = (const uint8_t*)e->own[4].get();
     e->pv.R = R;
   }
   if (e->pv.pair_snp && P > 0) {                  // what the kernels will index the genotype matrix with (a view checks its own pairs only)
-    if (!e->d_bad) HIP_TRY(hipMalloc((void**)&e->d_bad, sizeof(int32_t)));
+    if (!e->d_bad) if (int rc = e->d_bad.alloc(sizeof(int32_t))) return rc;
     HIP_TRY(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), e->stream));
     const int32_t* first = consecutive ? pl->pair_snp + h_po[B ? (cells ? cells[0] : 0) : 0] : e->pv.pair_snp;
     hipLaunchKernelGGL(k_check_snp_ids, dim3(1024), dim3(256), 0, e->stream, first, P, e->S, e->d_bad);
@@ -7721,7 +7629,7 @@ int set_pileup_cells_device(dmx_engine* e, const dmx_pileup* pl, const int64_t* 
   std::iota(sched.begin(), sched.end(), 0);
   std::stable_sort(sched.begin(), sched.end(), [&](int32_t a, int32_t b) { return (h_off[a + 1] - h_off[a]) > (h_off[b + 1] - h_off[b]); });
   e->max_cell_pairs = B ? h_off[sched[0] + 1] - h_off[sched[0]] : 0;   // (the longest barcode comes first)
-  if (int rc = ensure_dev((void**)&e->d_sched, &e->sched_cap, sizeof(int32_t) * (size_t)B)) return rc;
+  if (int rc = e->d_sched.ensure(sizeof(int32_t) * (size_t)B)) return rc;
   if (B) HIP_TRY(hipMemcpyAsync(e->d_sched, sched.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, e->stream));
   int32_t bad = 0;
   if (e->pv.pair_snp && P > 0) HIP_TRY(hipMemcpyAsync(&bad, e->d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
@@ -7747,16 +7655,14 @@ int set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int32_t* cells, 
   }
   const int64_t P = h_off[(size_t)B], R = h_roff[(size_t)B];
   const size_t w = (size_t)pl->nrd_width;
-  if (int rc = ensure_dev(&e->own[0], &e->own_cap[0], sizeof(int64_t) * ((size_t)B + 1))) return rc;
-  if (int rc = ensure_dev(&e->own[1], &e->own_cap[1], sizeof(int64_t) * ((size_t)B + 1))) return rc;
-  if (int rc = ensure_dev(&e->own[2], &e->own_cap[2], dense ? 16 : sizeof(int32_t) * (size_t)P)) return rc;
-  if (int rc = ensure_dev(&e->own[3], &e->own_cap[3], (size_t)P * w + 4)) return rc;
-  if (int rc = ensure_dev(&e->own[4], &e->own_cap[4], (size_t)R + 4)) return rc;
-  if (!e->h_stage[0]) {
-    for (int i = 0; i < 2; ++i) {
-      HIP_TRY(hipHostMalloc(&e->h_stage[i], kStageBytes, hipHostMallocDefault));
-      HIP_TRY(hipEventCreateWithFlags(&e->ev_stage[i], hipEventDisableTiming));
-    }
+  if (int rc = e->own[0].ensure(sizeof(int64_t) * ((size_t)B + 1))) return rc;
+  if (int rc = e->own[1].ensure(sizeof(int64_t) * ((size_t)B + 1))) return rc;
+  if (int rc = e->own[2].ensure(dense ? 16 : sizeof(int32_t) * (size_t)P)) return rc;
+  if (int rc = e->own[3].ensure((size_t)P * w + 4)) return rc;
+  if (int rc = e->own[4].ensure((size_t)R + 4)) return rc;
+  for (int i = 0; i < 2; ++i) {
+    if (int rc = e->h_stage[i].ensure(kStageBytes)) return rc;
+    if (int rc = e->ev_stage[i].create(hipEventDisableTiming)) return rc;
   }
   HIP_TRY(hipMemcpyAsync(e->own[0], h_off.data(), sizeof(int64_t) * ((size_t)B + 1), hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->own[1], h_roff.data(), sizeof(int64_t) * ((size_t)B + 1), hipMemcpyHostToDevice, e->stream));
@@ -7779,11 +7685,11 @@ int set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int32_t* cells, 
     }
     if (int rc = sw.flush()) return rc;
   }
-  e->pv.cell_pair_off = (const int64_t*)e->own[0]; e->pv.cell_read_off = (const int64_t*)e->own[1];
-  e->pv.pair_snp = (dense && P > 0) ? nullptr : (const int32_t*)e->own[2];   // a range without any pair is sparse with empty cells
-  e->pv.pair_nrd = (const uint8_t*)e->own[3]; e->pv.reads = (const uint8_t*)e->own[4];
+  e->pv.cell_pair_off = (const int64_t*)e->own[0].get(); e->pv.cell_read_off = (const int64_t*)e->own[1].get();
+  e->pv.pair_snp = (dense && P > 0) ? nullptr : (const int32_t*)e->own[2].get();   // a range without any pair is sparse with empty cells
+  e->pv.pair_nrd = (const uint8_t*)e->own[3].get(); e->pv.reads = (const uint8_t*)e->own[4].get();
   if (!dense && P > 0) {                          // what the kernels will index the genotype matrix with
-    if (!e->d_bad) HIP_TRY(hipMalloc((void**)&e->d_bad, sizeof(int32_t)));
+    if (!e->d_bad) if (int rc = e->d_bad.alloc(sizeof(int32_t))) return rc;
     HIP_TRY(hipMemsetAsync(e->d_bad, 0, sizeof(int32_t), e->stream));
     hipLaunchKernelGGL(k_check_snp_ids, dim3(1024), dim3(256), 0, e->stream, e->pv.pair_snp, P, e->S, e->d_bad);
     HIP_TRY(hipGetLastError());
@@ -7794,7 +7700,7 @@ int set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int32_t* cells, 
   std::iota(sched.begin(), sched.end(), 0);
   std::stable_sort(sched.begin(), sched.end(), [&](int32_t a, int32_t b) { return (h_off[a + 1] - h_off[a]) > (h_off[b + 1] - h_off[b]); });
   e->max_cell_pairs = B ? h_off[sched[0] + 1] - h_off[sched[0]] : 0;   // (the longest barcode comes first)
-  if (int rc = ensure_dev((void**)&e->d_sched, &e->sched_cap, sizeof(int32_t) * (size_t)B)) return rc;
+  if (int rc = e->d_sched.ensure(sizeof(int32_t) * (size_t)B)) return rc;
   if (B) HIP_TRY(hipMemcpyAsync(e->d_sched, sched.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, e->stream));
   int32_t bad = 0;
   if (!dense && P > 0) HIP_TRY(hipMemcpyAsync(&bad, e->d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
@@ -7846,10 +7752,9 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   }
   // dense pileups: SNP-minor copies of the genotype probabilities for the singlet kernel (once per genotype matrix)
   if (!e->pv.pair_snp && e->S > 0 && !e->have_gT) {
-    if (e->d_gT) { (void)hipFree(e->d_gT); e->d_gT = nullptr; }
-    if (e->d_g0T) { (void)hipFree(e->d_g0T); e->d_g0T = nullptr; }
-    HIP_TRY(hipMalloc((void**)&e->d_gT, (size_t)e->S * e->V * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&e->d_g0T, (size_t)e->S * 3 * sizeof(double)));
+    e->d_gT.reset(); e->d_g0T.reset();
+    if (int rc = e->d_gT.alloc((size_t)e->S * e->V * 3 * sizeof(float))) return rc;
+    if (int rc = e->d_g0T.alloc((size_t)e->S * 3 * sizeof(double))) return rc;
     hipLaunchKernelGGL(k_transpose_geno, dim3(2048), dim3(256), 0, e->stream, e->d_g, e->d_gp0, e->S, e->V, e->d_gT, e->d_g0T);
     HIP_TRY(hipGetLastError());
     e->have_gT = true;
@@ -7866,24 +7771,24 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
     const int32_t nblk = (int32_t)(((int64_t)e->S + (1ll << shift) - 1) >> shift);
     // worth it only when the matrix is well beyond one L2 and a barcode still has a few tiles of pairs per block
     if (nblk > 1 && (env || ((double)e->S * row_bytes > 3.0 * 1024 * 1024 && (double)e->P / std::max(B, 1) / nblk >= 96.0))) {
-      if (int rc = ensure_dev((void**)&e->d_blk, &e->blk_cap, sizeof(int64_t) * 2 * (size_t)B * (nblk + 1))) return rc;
+      if (int rc = e->d_blk.ensure(sizeof(int64_t) * 2 * (size_t)B * (nblk + 1))) return rc;
       hipLaunchKernelGGL(k_snp_blocks, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, shift, nblk, e->d_blk);
       HIP_TRY(hipGetLastError());
       e->blk_shift = shift; e->blk_n = nblk;
     }
   }
-  if (e->out_cap < B || !e->d_llks) {
+  if (e->out_cells < B || !e->d_llks) {
     free_results(e);
     const int32_t cap = B + B / 16 + 16;
-    HIP_TRY(hipMalloc((void**)&e->d_llks, sizeof(double) * (size_t)cap * e->V));
-    HIP_TRY(hipMalloc((void**)&e->d_llk0s, sizeof(double) * (size_t)cap));
-    e->out_cap = cap;
+    if (int rc = e->d_llks.alloc(sizeof(double) * (size_t)cap * e->V)) return rc;
+    if (int rc = e->d_llk0s.alloc(sizeof(double) * (size_t)cap)) return rc;
+    e->out_cells = cap;
   }
   // k_singlet_can's preconditions: every ABSOLUTE pair index / read offset the kernels form fits 32 bits (a view of a caller's device arrays
   // indexes the caller's whole arrays), and the four bytes behind the last read byte are readable (the engine's own copies are allocated
   // with slack; a caller's device array is, when its allocation extends that far)
   {
-    const bool own_reads = e->pv.reads == (const uint8_t*)e->own[4];
+    const bool own_reads = e->pv.reads == (const uint8_t*)e->own[4].get();
     const uint64_t maxP = own_reads ? (uint64_t)e->P : (uint64_t)std::max<int64_t>(pl->n_pairs, e->P);
     const uint64_t maxR = (uint64_t)std::max<int64_t>(e->pv.R, e->R);
     e->off32 = maxP + 4 * 64 < (1ull << 32) && maxR + 64 < (1ull << 32);
@@ -7915,7 +7820,7 @@ namespace {
 // they save — measured, k_certify 7.57 -> 8.23 ms).  *out stays NULL when the pileup is deeper, or too small to pay for the table.
 int ensure_seeds(dmx_engine* e, const double** out) {      // k_build_certify_seeds' table (default grid {0, 0.5}: k_certify<FIVE>, k_doublet_sym)
   if (!e->cseed_valid) {
-    if (!e->d_cseed) HIP_TRY(hipMalloc((void**)&e->d_cseed, sizeof(double) * 2 * kCSeedStride * (size_t)kCSeedN));
+    if (!e->d_cseed) if (int rc = e->d_cseed.alloc(sizeof(double) * 2 * kCSeedStride * (size_t)kCSeedN)) return rc;
     hipLaunchKernelGGL(k_build_certify_seeds, dim3((unsigned)((kCSeedN + 255) / 256)), dim3(256), 0, e->stream, e->d_lut, e->d_cseed);
     HIP_TRY(hipGetLastError());
     e->cseed_valid = true;
@@ -7930,7 +7835,7 @@ int ensure_finals(dmx_engine* e, const double** out) {
   // what it saves is ~2 ms per 1e8 covered pairs (cfg3, 5e8 pairs: 13 ms STRICT, 7 ms FAST)
   if (e->P < 100000000 && !e->cfin_valid && !e->knob("DMX_FINALS_ANY_DEPTH")) return DMX_OK;
   if (!e->cfin_valid) {
-    if (!e->d_cfin) HIP_TRY(hipMalloc((void**)&e->d_cfin, sizeof(double) * kCFinStride * (size_t)kCFinN));
+    if (!e->d_cfin) if (int rc = e->d_cfin.alloc(sizeof(double) * kCFinStride * (size_t)kCFinN)) return rc;
     hipLaunchKernelGGL(k_build_certify_finals, dim3((unsigned)((kCFinN + 255) / 256)), dim3(256), 0, e->stream, e->d_lut, e->d_cfin);
     HIP_TRY(hipGetLastError());
     e->cfin_valid = true;
@@ -7981,14 +7886,13 @@ int launch_singlet(dmx_engine* e) {
       const bool lean = can && V <= 16 && e->nrd_width == 1 && e->reads_padded && e->off32 && (uint64_t)e->S * 64 < (1ull << 32) && !e->knob("DMX_K1_NO_LEAN");
       if (lean) {
         if (!e->snprec_valid) {
-          if (e->d_snprec) { (void)hipFree(e->d_snprec); e->d_snprec = nullptr; }
-          HIP_TRY(hipMalloc((void**)&e->d_snprec, kSnpRecBytes * (size_t)std::max(e->S, 1)));
+          if (int rc = e->d_snprec.alloc(kSnpRecBytes * (size_t)std::max(e->S, 1))) return rc;
           hipLaunchKernelGGL(k_build_snprec, dim3((unsigned)((e->S + 255) / 256)), dim3(256), 0, e->stream, e->d_gp0, e->d_ids, e->d_oth, e->S, V, e->d_snprec);
           HIP_TRY(hipGetLastError());
           e->snprec_valid = true;
         }
         if (!e->ctab_valid) {
-          if (!e->d_ctab) HIP_TRY(hipMalloc((void**)&e->d_ctab, sizeof(double) * 8 * (size_t)kCtN));
+          if (!e->d_ctab) if (int rc = e->d_ctab.alloc(sizeof(double) * 8 * (size_t)kCtN)) return rc;
           hipLaunchKernelGGL(k_build_ctab, dim3((unsigned)((kCtN + 255) / 256)), dim3(256), 0, e->stream, e->d_lut, (double)e->can_hi, (double)e->can_lo, e->d_ctab);
           HIP_TRY(hipGetLastError());
           e->ctab_valid = true;
@@ -8003,9 +7907,8 @@ int launch_singlet(dmx_engine* e) {
         // read-byte loads: 2.31 and 2.71 ms; touching those lines 4 / 8 / 16 tiles ahead from the consumer's spare lanes: 3.44-3.50 ms, no help) — DESIGN 11.
         if (!oth && V <= 8 && e->pv.pair_snp == nullptr && e->knob("DMX_K1_CANP") && !e->knob("DMX_K1_NO_CANP") && !e->knob("DMX_K1_CW")) {
           if (!e->clsb_valid) {
-            if (e->d_clsb) { (void)hipFree(e->d_clsb); e->d_clsb = nullptr; }
             e->clsb_stride = (uint32_t)(((int64_t)e->S + 63) / 64 * 64 + 64);
-            HIP_TRY(hipMalloc((void**)&e->d_clsb, (size_t)9 * e->clsb_stride));
+            if (int rc = e->d_clsb.alloc((size_t)9 * e->clsb_stride)) return rc;
             hipLaunchKernelGGL(k_build_clsb, dim3((unsigned)(((size_t)9 * e->clsb_stride + 255) / 256)), dim3(256), 0, e->stream, e->d_ids, e->S, V, e->clsb_stride, e->d_clsb);
             HIP_TRY(hipGetLastError());
             e->clsb_valid = true;
@@ -8030,7 +7933,7 @@ int launch_singlet(dmx_engine* e) {
         return DMX_OK;
       }
       if (can && !e->ltab_valid) {
-        if (!e->d_ltab) HIP_TRY(hipMalloc((void**)&e->d_ltab, sizeof(double) * 4 * (size_t)kCanN));
+        if (!e->d_ltab) if (int rc = e->d_ltab.alloc(sizeof(double) * 4 * (size_t)kCanN)) return rc;
         hipLaunchKernelGGL(k_build_canon_logs, dim3((unsigned)((kCanN + 255) / 256)), dim3(256), 0, e->stream, e->d_lut, (double)e->can_hi,
                            (double)e->can_lo, e->d_ltab);
         HIP_TRY(hipGetLastError());
@@ -8108,7 +8011,7 @@ int launch_doublet_generic(dmx_engine* e) {
   const dim3 grid(FIXUP ? (unsigned)std::min(B, 256) : (unsigned)B, slabs), block(kThreads);
 #define DMX_K2(NN)                                                                                                   \
   DMX_LAUNCH_IF(!FIXUP, k2_fn, (k_doublet_generic<NRD, NN, FIXUP>), grid, block, 0, e->stream, e->pv, e->d_g, e->d_gp0, e->d_lut, \
-                     e->d_alpha, e->d_sched, V, A, A_pad, TP, e->d_grid, e->d_l00, e->d_flag)
+                     e->d_alpha, e->d_sched, V, A, A_pad, TP, e->d_grid, e->d_l00, e->d_flag())
   if (per <= 1) DMX_K2(1);
   else if (per <= 2) DMX_K2(2);
   else if (per <= 4) DMX_K2(4);
@@ -8148,7 +8051,7 @@ int launch_doublet(dmx_engine* e) {
     const int VS = (V + 15) & ~15;
     size_t cb = (size_t)32 * AP * 9 * 8 + (size_t)32 * 16 * AP * 8 + (size_t)AP * 34 * 8 + 32 * (4 + 4 + 8) + (size_t)32 * 12 * 4 + (size_t)32 * VS;
     cb = (cb + 15) & ~(size_t)15;
-    HIP_TRY(hipMemsetAsync(e->d_flag - kFlagHead, 0, (size_t)B + kFlagHead, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
     auto slabs = [&](int tpc, int nk) { const int kb = (V + nk - 1) / nk, js = tpc / kb; return (unsigned)((V + js - 1) / js); };
 #define DMX_K2CN(NK, APP)                                                                                              \
   do {                                                                                                                 \
@@ -8156,7 +8059,7 @@ int launch_doublet(dmx_engine* e) {
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)cb));              \
     DMX_LAUNCH(k2_fn, (k_doublet_clsn<256, NK, APP>), dim3((unsigned)B, slabs(256, NK)), dim3(kThreads), cb, e->stream, \
                        e->pv, e->nrd_width, e->d_rows, e->d_ids, e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, A, VS,   \
-                       e->d_grid, e->d_l00, e->d_flag);                                                                  \
+                       e->d_grid, e->d_l00, e->d_flag());                                                                  \
   } while (0)
     if (AP == 4) { if (V <= 16) DMX_K2CN(1, 4); else if (V <= 32) DMX_K2CN(4, 4); else DMX_K2CN(8, 4); }
     else         { if (V <= 16) DMX_K2CN(1, 8); else DMX_K2CN(4, 8); }
@@ -8170,7 +8073,7 @@ int launch_doublet(dmx_engine* e) {
     // bilinear form
     const int AP = A <= 2 ? 2 : (A <= 4 ? 4 : 8);
     const int GS = (V * 3 + 3) & ~3;
-    HIP_TRY(hipMemsetAsync(e->d_flag - kFlagHead, 0, (size_t)B + kFlagHead, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
     const dim3 block(kThreads);
     auto slabs = [&](int tpc, int nk) { const int kb = (V + nk - 1) / nk, js = tpc / kb; return (unsigned)((V + js - 1) / js); };
 #define DMX_K2NF_(TPC, NK, APP, VUS, SUBP, MINW, CHK)                                                                  \
@@ -8183,7 +8086,7 @@ int launch_doublet(dmx_engine* e) {
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
     DMX_LAUNCH(k2_fn, (k_doublet_anf<TPC, NK, APP, VUS, SUBP, MINW, CHK>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs(TPC, NK)), \
                        block, lds, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut,                            \
-                       e->d_alpha, e->d_sched, V, A, GS, e->d_grid, e->d_l00, e->d_flag);                                \
+                       e->d_alpha, e->d_sched, V, A, GS, e->d_grid, e->d_l00, e->d_flag());                                \
   } while (0)
 #define DMX_K2NF(TPC, NK, APP, VUS, SUBP, MINW) do { if (e->geno_safe) DMX_K2NF_(TPC, NK, APP, VUS, SUBP, MINW, false); else DMX_K2NF_(TPC, NK, APP, VUS, SUBP, MINW, true); } while (0)
     // u rows: V entries plus the slack a k-block may read past the panel's end (NK - 1), even; pairs per sub-tile by the LDS they need
@@ -8209,7 +8112,7 @@ int launch_doublet(dmx_engine* e) {
     const int AP = A <= 4 ? 4 : 8;
     const int GS = (V * 3 + 3) & ~3;
     const size_t cell_bytes = (size_t)32 * AP * 9 * 8 + (size_t)32 * GS * 4 + (size_t)AP * 34 * 8 + 32 * (4 + 4 + 8);
-    HIP_TRY(hipMemsetAsync(e->d_flag - kFlagHead, 0, (size_t)B + kFlagHead, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
     const dim3 block(kThreads);
     auto slabs = [&](int tpc, int nk) { const int kb = (V + nk - 1) / nk, js = tpc / kb; return (unsigned)((V + js - 1) / js); };
     // gfx950 lets one workgroup use all 160 KB of a CU's LDS; above the traditional 64 KB the limit is raised explicitly
@@ -8220,7 +8123,7 @@ int launch_doublet(dmx_engine* e) {
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
     DMX_LAUNCH(k2_fn, (k_doublet_an<TPC, NK, APP>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs(TPC, NK)), \
                        block, lds, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut,                            \
-                       e->d_alpha, e->d_sched, V, A, GS, e->d_grid, e->d_l00, e->d_flag);                                \
+                       e->d_alpha, e->d_sched, V, A, GS, e->d_grid, e->d_l00, e->d_flag());                                \
   } while (0)
     if (AP == 4) {
       if (V <= 8) DMX_K2N(64, 1, 4);
@@ -8243,7 +8146,7 @@ int launch_doublet(dmx_engine* e) {
   // (round 4: the general A = 2 kernel itself runs up to kA2MaxV = 1024 samples — one workgroup may use all 160 KB of a gfx950 CU's LDS, and the
   // tile shortens from 32 to 16 or 8 pairs as the rows grow; beyond, the generic kernel)
   if (A != 2 || force_generic || (V > (use_cls ? 1024 : kA2MaxV) && !sym_wide)) {
-    HIP_TRY(hipMemsetAsync(e->d_flag - kFlagHead, 0, (size_t)B + kFlagHead, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
     if (int rc = launch_doublet_generic_w<false>(e)) return rc;
     HIP_TRY(hipGetLastError());
     return launch_doublet_generic_w<true>(e);
@@ -8252,11 +8155,11 @@ int launch_doublet(dmx_engine* e) {
   if (use_cls && e->mode == DMX_MODE_FAST && e->alpha[0] == 0.0 && e->alpha[1] == 0.5 && V <= 64 && !e->knob("DMX_NO_SYM")) {
     if (V > 32 && !e->knob("DMX_FAST_NO_PROD")) {
       // 33..64 samples: the producer / consumer kernel over the printed entries (round 4; k_doublet_clsym<33,2> ran 2 wavefronts per SIMD)
-      HIP_TRY(hipMemsetAsync(e->d_flag - kFlagHead, 0, (size_t)B + kFlagHead, e->stream));
+      HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
       const size_t lds = (size_t)2 * 32 * 32 * 8 + (size_t)2 * 32 * 64 + (size_t)32 * 18 * 8 + 2 * 34 * 8 + 2 * 32 * (8 + 4 + 4) +
                          (size_t)32 * 12 * 4;
       DMX_LAUNCH(k2_fn, (k_doublet_clsp<3, true>), dim3((unsigned)B), dim3(kThreads), lds, e->stream, e->pv, e->nrd_width, e->d_rows, e->d_ids,
-                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, 0, e->d_grid, e->d_l00, e->d_flag);
+                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, 0, e->d_grid, e->d_l00, e->d_flag());
       HIP_TRY(hipGetLastError());
       return launch_doublet_generic_w<true>(e);
     }
@@ -8271,12 +8174,12 @@ int launch_doublet(dmx_engine* e) {
     if (NS == 2 && (D + Q - 1) / Q <= 33) NS = 1;
     if (const char* env = e->knob("DMX_CLSYM_NED")) NS = (D + Q * atoi(env) - 1) / (Q * atoi(env));   // kernel experiments only
     const int need = (D + Q * NS - 1) / (Q * NS);
-    HIP_TRY(hipMemsetAsync(e->d_flag - kFlagHead, 0, (size_t)B + kFlagHead, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
     constexpr size_t cb = ((size_t)8 * 32 * 8 + 32 * 6 * 8 + 32 * 4 * 8 + 2 * 34 * 8 + 32 * 16 + 32 * 12 * 4 + 32 * 10 * 4 + 63) & ~(size_t)63;
     static_assert(cb % 64 == 0, "a barcode's LDS block keeps its class table 64-byte aligned (k_doublet_clsym ORs the class offset in)");
 #define DMX_K2CS(NED, MINW)                                                                                            \
   DMX_LAUNCH(k2_fn, (k_doublet_clsym<NED, MINW>), dim3((unsigned)((B + 3) / 4), (unsigned)NS), dim3(kThreads), cb * 4, e->stream, e->pv, \
-                     e->nrd_width, e->d_rows, e->d_idd, e->nwd2, e->d_gp0, e->d_lut, e->d_sched, V, e->d_grid, e->d_l00, e->d_flag)
+                     e->nrd_width, e->d_rows, e->d_idd, e->nwd2, e->d_gp0, e->d_lut, e->d_sched, V, e->d_grid, e->d_l00, e->d_flag())
     if (need <= 1) DMX_K2CS(1, 4); else if (need <= 2) DMX_K2CS(2, 4); else if (need <= 3) DMX_K2CS(3, 4); else if (need <= 5) DMX_K2CS(5, 4);
     else if (need <= 7) DMX_K2CS(7, 3); else if (need <= 9) DMX_K2CS(9, 3); else if (need <= 11) DMX_K2CS(11, 3);
     else if (need <= 13) DMX_K2CS(13, 3); else if (need <= 15) DMX_K2CS(15, 3); else if (need <= 17) DMX_K2CS(17, 3);
@@ -8290,12 +8193,12 @@ int launch_doublet(dmx_engine* e) {
     size_t cb = (size_t)32 * 18 * 8 + (size_t)32 * 32 * 8 + 2 * 34 * 8 + 32 * (4 + 4 + 8) + (size_t)32 * 12 * 4 + (size_t)32 * VS;
     if (V > 32) cb += 32 * 16;                      // the pipelined form's second header buffer
     cb = (cb + 15) & ~(size_t)15;
-    HIP_TRY(hipMemsetAsync(e->d_flag - kFlagHead, 0, (size_t)B + kFlagHead, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
     const dim3 blk(kThreads);
 #define DMX_K2C(TPC, NK, ...)                                                                                        \
   DMX_LAUNCH(k2_fn, (k_doublet_cls<TPC, NK, ##__VA_ARGS__>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs_of(TPC, NK)), blk,   \
                      cb * (kThreads / TPC), e->stream, e->pv, e->nrd_width, e->d_rows, e->d_ids, e->d_gp0, e->d_lut,   \
-                     e->d_alpha, e->d_sched, V, VS, e->d_grid, e->d_l00, e->d_flag)
+                     e->d_alpha, e->d_sched, V, VS, e->d_grid, e->d_l00, e->d_flag())
     if (V <= 8) DMX_K2C(64, 1);
     else if (V <= 16) DMX_K2C(64, 4);
     else if (V <= 32) DMX_K2C(256, 4);
@@ -8306,7 +8209,7 @@ int launch_doublet(dmx_engine* e) {
       const size_t lds = (size_t)2 * 32 * 32 * 8 + (size_t)2 * 32 * 64 + (size_t)32 * 18 * 8 + 2 * 34 * 8 + 2 * 32 * (8 + 4 + 4) +
                          (size_t)32 * 12 * 4;
       DMX_LAUNCH(k2_fn, (k_doublet_clsp<3>), dim3((unsigned)B), dim3(kThreads), lds, e->stream, e->pv, e->nrd_width, e->d_rows, e->d_ids, e->d_gp0,
-                         e->d_lut, e->d_alpha, e->d_sched, V, VS, e->d_grid, e->d_l00, e->d_flag);
+                         e->d_lut, e->d_alpha, e->d_sched, V, VS, e->d_grid, e->d_l00, e->d_flag());
     }
     else if (V <= 64 && !e->knob("DMX_CLS_NO_UJ")) DMX_K2C(256, 16, 2, true);   // uniform-j form (a wavefront's 16 samples j share their class per pair)
     else DMX_K2C(256, 16);
@@ -8316,7 +8219,7 @@ int launch_doublet(dmx_engine* e) {
   }
   const int GS = (V * 3 + 3) & ~3;               // LDS row stride of a genotype row (floats), 16-byte multiple
   const size_t cell_bytes = (size_t)32 * 18 * 8 + (size_t)32 * GS * 4 + 2 * 34 * 8 + 32 * (4 + 4 + 8);
-  HIP_TRY(hipMemsetAsync(e->d_flag - kFlagHead, 0, (size_t)B + kFlagHead, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
   const dim3 block(kThreads);
   // k_doublet_a2's phase 1 on the default grid {0, 0.5}: finished values of pairs of up to three tabled reads from the table (round 6; shallow pileups only,
   // ensure_finals; DMX_A2_NO_FINALS=1: the read loop everywhere) — other grids have other mixing weights and keep the loop
@@ -8330,11 +8233,11 @@ int launch_doublet(dmx_engine* e) {
     if (e->geno_safe)                                                                                                 \
       DMX_LAUNCH(k2_fn, (k_doublet_a2<TPC, NK, 1, false, false>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs_of(TPC, NK)), block,  \
                          cell_bytes * (kThreads / TPC), e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut,    \
-                         e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);                               \
+                         e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);                               \
     else                                                                                                              \
   DMX_LAUNCH(k2_fn, (k_doublet_a2<TPC, NK>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs_of(TPC, NK)), block,  \
                      cell_bytes * (kThreads / TPC), e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut,        \
-                     e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);                                   \
+                     e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);                                   \
   } while (0)
   if (fast_soft && e->alpha[0] == 0.0 && e->alpha[1] == 0.5 && (V <= 128 || sym_wide) && !e->knob("DMX_NO_SYM")) {
     // demuxlet's default grid {0, 0.5}: only the printed entries (singlet column + one evaluation per unordered pair)
@@ -8356,11 +8259,11 @@ int launch_doublet(dmx_engine* e) {
     if (e->geno_safe)                                                                                                  \
       DMX_LAUNCH(k2_fn, (k_doublet_sym<TPC, VMAX, SUB, FIX, 3, 0, false>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC))), \
                          block, lds, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched, V | sym_flags,         \
-                         e->d_grid, e->d_l00, e->d_flag, pfin, pseed);                                                              \
+                         e->d_grid, e->d_l00, e->d_flag(), pfin, pseed);                                                              \
     else                                                                                                               \
     DMX_LAUNCH(k2_fn, (k_doublet_sym<TPC, VMAX, SUB, FIX>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC))), \
                        block, lds, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched, V | sym_flags,           \
-                       e->d_grid, e->d_l00, e->d_flag, pfin, pseed);                                                                \
+                       e->d_grid, e->d_l00, e->d_flag(), pfin, pseed);                                                                \
   } while (0)
 #define DMX_K2SV(TPC, VMAX, SUB, FIX, MINW)                                                                            \
   do { e->k2_sym = true;                                                                                                                \
@@ -8371,7 +8274,7 @@ int launch_doublet(dmx_engine* e) {
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));          \
     DMX_LAUNCH(k2_fn, (k_doublet_sym<TPC, VMAX, SUB, FIX, MINW>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC))), \
                        block, lds, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched, V | sym_flags,           \
-                       e->d_grid, e->d_l00, e->d_flag, pfin, pseed);                                                                \
+                       e->d_grid, e->d_l00, e->d_flag(), pfin, pseed);                                                                \
   } while (0)
     const int32_t sym_flags = (e->knob("DMX_SYM_NO_DMA") ? (1 << 16) : 0) | (e->knob("DMX_SYM_ABLATE_P1") ? (1 << 17) : 0) |
                               (e->knob("DMX_SYM_ABLATE_P2") ? (1 << 18) : 0) | (e->knob("DMX_SYM_ABLATE_U") ? (1 << 19) : 0) |
@@ -8406,10 +8309,10 @@ int launch_doublet(dmx_engine* e) {
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)cb_));                               \
     if (e->geno_safe)                                                                                                  \
       DMX_LAUNCH(k2_fn, (k_doublet_sym<256, VMAX, SUB, FIX, 3, 9, false>), dim3((unsigned)B, ns), block, cb_, e->stream, e->pv, \
-                         e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched, V | sym_flags, e->d_grid, e->d_l00, e->d_flag, pfin, pseed);      \
+                         e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched, V | sym_flags, e->d_grid, e->d_l00, e->d_flag(), pfin, pseed);      \
     else                                                                                                               \
     DMX_LAUNCH(k2_fn, (k_doublet_sym<256, VMAX, SUB, FIX, 3, 9>), dim3((unsigned)B, ns), block, cb_, e->stream, e->pv, \
-                       e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched, V | sym_flags, e->d_grid, e->d_l00, e->d_flag, pfin, pseed);        \
+                       e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched, V | sym_flags, e->d_grid, e->d_l00, e->d_flag(), pfin, pseed);        \
   } while (0)
       if (V <= 96) DMX_K2SS(96, 8, false); else if (V == 128) DMX_K2SS(128, 8, true); else if (V < 128) DMX_K2SS(128, 8, false);
       else if (V <= 192) DMX_K2SS(192, 4, false); else if (V <= 256) DMX_K2SS(256, 4, false);        // (sub-tiles of 4 pairs: 40 / 53 KB of LDS per workgroup)
@@ -8431,7 +8334,7 @@ int launch_doublet(dmx_engine* e) {
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));          \
     DMX_LAUNCH(k2_fn, (k_doublet_a2f<TPC, NK>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs_of(TPC, NK)), \
                        block, lds, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS,           \
-                       e->d_grid, e->d_l00, e->d_flag);                                                              \
+                       e->d_grid, e->d_l00, e->d_flag());                                                              \
   } while (0)
     if (V <= 8) DMX_K2F(64, 1);
     else if (V <= 16) DMX_K2F(64, 4);
@@ -8446,7 +8349,7 @@ int launch_doublet(dmx_engine* e) {
     // the products they share once — and the 64 diagonal accumulators of a barcode on one wavefront behind it (DMX_A2_NO_SYMU=1: k_doublet_a2)
     const size_t cbd = (size_t)32 * 18 * 8 + (size_t)32 * GS * 8 + 2 * 34 * 8 + 32 * (4 + 4 + 8);
     DMX_LAUNCH(k2_fn, (k_doublet_a2u<4>), dim3((unsigned)B, 1), block, cbd, e->stream, e->pv, e->nrd_width, e->d_g,
-                       e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);
+                       e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
     if (e->knob("DMX_A2U_DIAG_WAVE"))             // kernel experiments only: the diagonal on one wavefront per barcode (the first form)
       hipLaunchKernelGGL((k_doublet_a2s<4, 4, 0>), dim3((unsigned)((B + 3) / 4), 1), block, 0, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched,
                          e->d_grid, e->d_l00, pfin_a2);
@@ -8470,7 +8373,7 @@ int launch_doublet(dmx_engine* e) {
   else if (V == 16 && pfin_a2_grid && e->geno_safe && !e->knob("DMX_A2_NO_SYMU")) {
     // 16 soft-field samples on the default grid (cfg5): the same — unordered pairs on k_doublet_a2<64,4>'s kernel, the diagonal on 16 lanes per barcode behind it
     DMX_LAUNCH(k2_fn, (k_doublet_a2u16), dim3((unsigned)((B + 3) / 4), 1), block, cell_bytes * 4, e->stream, e->pv, e->nrd_width, e->d_g,
-                       e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);
+                       e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
     hipLaunchKernelGGL((k_doublet_diag<5, 16>), dim3((unsigned)((B + 15) / 16)), block, 0, e->stream, e->pv, e->nrd_width, e->d_g, e->d_lut, e->d_sched, e->d_grid, pfin_a2, pseed_a2);
   }
   else if (V <= 8) DMX_K2A(64, 1);
@@ -8481,13 +8384,13 @@ int launch_doublet(dmx_engine* e) {
       const size_t cbd = (size_t)32 * 18 * 8 + (size_t)32 * GS * 8 + 2 * 34 * 8 + 32 * (4 + 4 + 8);
       if (e->geno_safe)
         DMX_LAUNCH(k2_fn, (k_doublet_a2<256, 4, 4, true, false>), dim3((unsigned)B, slabs_of(256, 4)), block, cbd, e->stream, e->pv, e->nrd_width, e->d_g,
-                           e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);
+                           e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
       else
       DMX_LAUNCH(k2_fn, (k_doublet_a2<256, 4, 4, true>), dim3((unsigned)B, slabs_of(256, 4)), block, cbd, e->stream, e->pv, e->nrd_width, e->d_g,
-                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);
+                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
     } else if (!e->knob("DMX_A2_MINW1"))
       DMX_LAUNCH(k2_fn, (k_doublet_a2<256, 4, 4>), dim3((unsigned)B, slabs_of(256, 4)), block, cell_bytes, e->stream, e->pv, e->nrd_width, e->d_g,
-                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);
+                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
     else DMX_K2A(256, 4);
   }
   else if (V <= 128) DMX_K2A(256, 16);            // <= 55 KB of LDS
@@ -8509,12 +8412,12 @@ int launch_doublet(dmx_engine* e) {
       if (lds > 60 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_doublet_a2<256, 16, 1, false, false, TPP>),  \
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
       DMX_LAUNCH(k2_fn, (k_doublet_a2<256, 16, 1, false, false, TPP>), dim3((unsigned)B, slabs_of(256, 16)), block, lds, e->stream, e->pv,  \
-                         e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);  \
+                         e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);  \
     } else {                                                                                                          \
       if (lds > 60 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_doublet_a2<256, 16, 1, false, true, TPP>),   \
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));        \
       DMX_LAUNCH(k2_fn, (k_doublet_a2<256, 16, 1, false, true, TPP>), dim3((unsigned)B, slabs_of(256, 16)), block, lds, e->stream, e->pv,   \
-                         e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag, pfin_a2, pseed_a2);  \
+                         e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);  \
     }                                                                                                                 \
   } while (0)
     if (tp == 32) DMX_K2AW(32); else if (tp == 16) DMX_K2AW(16); else DMX_K2AW(8);
@@ -8539,7 +8442,7 @@ int launch_certify(dmx_engine* e) {
   const int n_launch = blk ? (e->blk_n + bstride - 1) / bstride : 1;
   double* park = nullptr;
   if (blk) {
-    if (int rc = ensure_dev((void**)&e->d_park, &e->park_cap, sizeof(double) * kPark * (size_t)std::max(B, 1))) return rc;
+    if (int rc = e->d_park.ensure(sizeof(double) * kPark * (size_t)std::max(B, 1))) return rc;
     park = e->d_park;
   }
   const float* gT = (!e->pv.pair_snp && e->have_gT && !e->knob("DMX_CERTIFY_NO_GT")) ? e->d_gT : nullptr;   // dense pileups: SNP-minor columns
@@ -8566,7 +8469,7 @@ extern "C" int dmx_engine_run_singlet(dmx_engine* e) {
   if (!e->have_pileup || !e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_run_singlet: set genotypes and pileup first");
   HIP_TRY(hipSetDevice(e->device));
   if (e->pv.B == 0) { e->have_sing = true; return DMX_OK; }
-  hipEvent_t* rs = e->ring_s[e->n_ring_s % dmx_engine::kRing];
+  Event* rs = e->ring_s[e->n_ring_s % dmx_engine::kRing];
   e->k1_fn = nullptr;                              // dmx_engine_kernel_names: what THIS call launches, never an earlier call's choice
   HIP_TRY(hipEventRecord(e->ev[2], e->stream));
   HIP_TRY(hipEventRecord(rs[0], e->stream));
@@ -8617,21 +8520,20 @@ int run_doublet_impl(dmx_engine* e, bool with_singlet) {
   HIP_TRY(hipSetDevice(e->device));
   const int32_t B = e->pv.B;
   const size_t nAB = (size_t)e->V * e->V * e->A;
-  if (!e->d_grid || e->grid_cap < B) {
-    if (e->d_grid) { (void)hipFree(e->d_grid); (void)hipFree(e->d_l00); (void)hipFree(e->d_sum); if (e->d_flag) (void)hipFree(e->d_flag - kFlagHead); (void)hipFree(e->d_sing); }
-    e->d_grid = e->d_l00 = e->d_sing = nullptr; e->d_sum = nullptr; e->d_flag = nullptr;
-    const size_t cap = (size_t)e->out_cap;       // the singlet buffers' capacity (>= B)
-    HIP_TRY(hipMalloc((void**)&e->d_grid, std::max<size_t>(sizeof(double) * nAB * cap, 16)));
-    HIP_TRY(hipMalloc((void**)&e->d_l00, std::max<size_t>(sizeof(double) * (size_t)e->A * cap, 16)));
-    HIP_TRY(hipMalloc((void**)&e->d_sum, std::max<size_t>(sizeof(dmx_cell_summary) * cap, 16)));
-    { uint8_t* fb = nullptr; HIP_TRY(hipMalloc((void**)&fb, cap + 2 * kFlagHead)); e->d_flag = fb + kFlagHead; }
-    HIP_TRY(hipMalloc((void**)&e->d_sing, std::max<size_t>(sizeof(double) * cap * e->V, 16)));
-    e->grid_cap = (int32_t)cap;
+  if (!e->d_grid || e->grid_cells < B) {
+    e->d_grid.reset(); e->d_l00.reset(); e->d_sum.reset(); e->d_flag_base.reset(); e->d_sing.reset();
+    const size_t cap = (size_t)e->out_cells;       // the singlet buffers' capacity (>= B)
+    if (int rc = e->d_grid.alloc(std::max<size_t>(sizeof(double) * nAB * cap, 16))) return rc;
+    if (int rc = e->d_l00.alloc(std::max<size_t>(sizeof(double) * (size_t)e->A * cap, 16))) return rc;
+    if (int rc = e->d_sum.alloc(std::max<size_t>(sizeof(dmx_cell_summary) * cap, 16))) return rc;
+    if (int rc = e->d_flag_base.alloc(cap + 2 * kFlagHead)) return rc;
+    if (int rc = e->d_sing.alloc(std::max<size_t>(sizeof(double) * cap * e->V, 16))) return rc;
+    e->grid_cells = (int32_t)cap;
   }
   e->k2_fn = e->k3b_fn = nullptr;                  // (dmx_engine_kernel_names reports this call's launches; a run without K3b leaves `certify` empty)
   if (with_singlet) e->k1_fn = nullptr;
   if (B == 0) { e->have_grid = true; if (with_singlet) e->have_sing = true; return DMX_OK; }
-  hipEvent_t* rd = e->ring_d[e->n_ring_d % dmx_engine::kRing];
+  Event* rd = e->ring_d[e->n_ring_d % dmx_engine::kRing];
   if (with_singlet) HIP_TRY(hipEventRecord(e->ev_fork, e->stream));       // (K1 must not start before what precedes this call on the stream)
   HIP_TRY(hipEventRecord(e->ev[4], e->stream));
   HIP_TRY(hipEventRecord(rd[0], e->stream));
@@ -8641,7 +8543,7 @@ int run_doublet_impl(dmx_engine* e, bool with_singlet) {
   HIP_TRY(hipEventRecord(rd[1], e->stream));
   if (with_singlet) {                            // K1, enqueued after K2, on the low-priority stream
     hipStream_t main_stream = e->stream;
-    hipEvent_t* rs = e->ring_s[e->n_ring_s % dmx_engine::kRing];
+    Event* rs = e->ring_s[e->n_ring_s % dmx_engine::kRing];
     // K1 beside K2 — or, where K2 leaves it no room (k_doublet_clsp: three issuing wavefronts per SIMD), beside K3 + K3b, which like K1
     // issue on about half of their cycles: K1 then starts when K2 has finished (DMX_FORCE_OVERLAP=1: beside K2 anyway)
     // The same holds for k_doublet_sym under ONE long K1 launch (round 5): its workgroups fill the CU's LDS three deep (46-53 KB each); a K1
@@ -8847,7 +8749,7 @@ extern "C" int dmx_engine_refine_genotypes(dmx_engine* e, const dmx_refine_reque
     return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: assign_memory %d", rq->assign_memory);
   if (!(rq->floor >= 0.0) || !std::isfinite(rq->floor)) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: floor %g", rq->floor);
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->rev[0]) for (hipEvent_t& ev : e->rev) HIP_TRY(hipEventCreate(&ev));
+  for (Event& ev : e->rev) if (int rc = ev.create()) return rc;
 
   // ---- chunk plan: samp_chunk[V + 1] | chunk_beg[n_chunks + 1] | members[n_assigned] (cell ids by sample, ascending within a sample)
   std::vector<int32_t> a((size_t)B);
@@ -8878,12 +8780,12 @@ extern "C" int dmx_engine_refine_genotypes(dmx_engine* e, const dmx_refine_reque
   for (int32_t b = 0; b < B; ++b) if (a[(size_t)b] >= 0) plan[o_mem + (size_t)cnt[(size_t)a[(size_t)b]]++] = b;   // stable: ascending cell id
 
   const size_t rows = (size_t)S * V;
-  if (int rc = ensure_dev((void**)&e->d_rplan, &e->rplan_cap, sizeof(int32_t) * plan.size())) return rc;
-  if (int rc = ensure_dev((void**)&e->d_rprior, &e->rprior_cap, sizeof(float) * rows * 3)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_rll, &e->rll_cap, sizeof(double) * rows * 3)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_rcnt, &e->rcnt_cap, sizeof(int32_t) * rows * 3)) return rc;
+  if (int rc = e->d_rplan.ensure(sizeof(int32_t) * plan.size())) return rc;
+  if (int rc = e->d_rprior.ensure(sizeof(float) * rows * 3)) return rc;
+  if (int rc = e->d_rll.ensure(sizeof(double) * rows * 3)) return rc;
+  if (int rc = e->d_rcnt.ensure(sizeof(int32_t) * rows * 3)) return rc;
   const int nxt = e->d_g == e->d_rgp[0] ? 1 : 0;                      // never the buffer the engine's genotype matrix is
-  if (int rc = ensure_dev((void**)&e->d_rgp[nxt], &e->rgp_cap[nxt], sizeof(float) * rows * 3)) return rc;
+  if (int rc = e->d_rgp[nxt].ensure(sizeof(float) * rows * 3)) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_rplan, plan.data(), sizeof(int32_t) * plan.size(), hipMemcpyHostToDevice, e->stream));
   if (rows) HIP_TRY(hipMemcpyAsync(e->d_rprior, rq->prior, sizeof(float) * rows * 3, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemsetAsync(e->d_rll, 0, sizeof(double) * rows * 3, e->stream));
@@ -8894,7 +8796,7 @@ extern "C" int dmx_engine_refine_genotypes(dmx_engine* e, const dmx_refine_reque
   const bool build_blk = !e->rblk_valid || e->rblk_S != S;
   HIP_TRY(hipEventRecord(e->rev[0], e->stream));
   if (build_blk && B > 0) {
-    if (int rc = ensure_dev((void**)&e->d_rblk, &e->rblk_cap, sizeof(int64_t) * 2 * (size_t)B * ((size_t)nblk + 1))) return rc;
+    if (int rc = e->d_rblk.ensure(sizeof(int64_t) * 2 * (size_t)B * ((size_t)nblk + 1))) return rc;
     hipLaunchKernelGGL(k_snp_blocks, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, kRefSlabShift, nblk, e->d_rblk);
     HIP_TRY(hipGetLastError());
   }
@@ -8909,16 +8811,16 @@ extern "C" int dmx_engine_refine_genotypes(dmx_engine* e, const dmx_refine_reque
   const int32_t cpw = (int32_t)std::max<size_t>(1, std::min<size_t>({per_chunk ? budget / per_chunk : (size_t)65535, (size_t)65535, (size_t)std::max(nch, 1)}));
   int32_t n_waves = 0;
   if (nch > 0 && S > 0) {
-    if (int rc = ensure_dev(&e->d_rpart, &e->rpart_cap, per_chunk * (size_t)cpw)) return rc;
+    if (int rc = e->d_rpart.ensure(per_chunk * (size_t)cpw)) return rc;
     const int32_t* d_samp = e->d_rplan;
     const int32_t* d_beg = e->d_rplan + o_beg;
     const int32_t* d_mem = e->d_rplan + o_mem;
     for (int32_t c0 = 0; c0 < nch; c0 += cpw, ++n_waves) {
       const int32_t nc = std::min(cpw, nch - c0);
       hipLaunchKernelGGL(k_refine_partial, dim3((unsigned)nblk, (unsigned)nc), dim3(64), 0, e->stream, e->pv, e->nrd_width, (const double*)e->d_lut,
-                         (const int64_t*)e->d_rblk, nblk, d_mem, d_beg, c0, (RefPartial*)e->d_rpart);
+                         (const int64_t*)e->d_rblk, nblk, d_mem, d_beg, c0, e->d_rpart.get());
       HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_refine_fold, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream, (const RefPartial*)e->d_rpart, S, V, d_samp, c0,
+      hipLaunchKernelGGL(k_refine_fold, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream, (const RefPartial*)e->d_rpart.get(), S, V, d_samp, c0,
                          c0 + nc, e->d_rll, e->d_rcnt);
       HIP_TRY(hipGetLastError());
     }
@@ -8979,7 +8881,6 @@ extern "C" int dmx_engine_cluster_stage(dmx_engine* e) {
   if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_stage: no pileup staged (dmx_engine_set_pileup first)");
   const int32_t B = e->pv.B, S = e->pv.S;
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->cev[0]) for (hipEvent_t& ev : e->cev) HIP_TRY(hipEventCreate(&ev));
   int64_t po[2] = {0, 0};
   if (B > 0) {
     HIP_TRY(hipMemcpyAsync(&po[0], e->pv.cell_pair_off, sizeof(int64_t), hipMemcpyDeviceToHost, e->stream));
@@ -8999,25 +8900,23 @@ extern "C" int dmx_engine_cluster_stage(dmx_engine* e) {
   if (!dense && P > 0 && ng > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_stage: %d cells exceed this build's limit", B);
   const size_t cache_b = sizeof(int64_t) * ((size_t)S + 1) + (size_t)P * (sizeof(int32_t) + 3 * sizeof(double) + sizeof(uint32_t));
   const size_t scratch_b = (!dense && P > 0) ? 16 * (size_t)B * ((size_t)nblk + 1) + sizeof(int32_t) * ((size_t)ng * S + S + (size_t)P) : 0;
-  for (void** p : {(void**)&e->d_coff, (void**)&e->d_ccell, (void**)&e->d_clgl, (void**)&e->d_ccnt}) if (*p) { (void)hipFree(*p); *p = nullptr; }
-  e->coff_cap = e->ccell_cap = e->clgl_cap = e->ccnt_cap = 0;
+  e->d_coff.reset(); e->d_ccell.reset(); e->d_clgl.reset(); e->d_ccnt.reset();
   e->have_cstage = false;
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
   if ((double)(cache_b + scratch_b) > 0.9 * (double)free_b)
     return set_error(DMX_ERR_NOMEM, "dmx_engine_cluster_stage: the cache of %lld pairs needs %.2f GB (+%.2f GB scratch), %.2f GB of device memory are free",
                      (long long)P, cache_b / 1e9, scratch_b / 1e9, free_b / 1e9);
-  if (int rc = ensure_dev((void**)&e->d_coff, &e->coff_cap, sizeof(int64_t) * ((size_t)S + 1))) return rc;
-  if (int rc = ensure_dev((void**)&e->d_ccell, &e->ccell_cap, sizeof(int32_t) * (size_t)P)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_clgl, &e->clgl_cap, 3 * sizeof(double) * (size_t)P)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_ccnt, &e->ccnt_cap, sizeof(uint32_t) * (size_t)P)) return rc;
-  int32_t* d_deep = nullptr;
-  HIP_TRY(hipMalloc((void**)&d_deep, sizeof(int32_t)));
-  HIP_TRY(hipMemsetAsync(d_deep, 0, sizeof(int32_t), e->stream));
-  HIP_TRY(hipEventRecord(e->cev[0], e->stream));
-  int64_t* d_sblk = nullptr; int32_t *d_M = nullptr, *d_tot = nullptr, *d_dst = nullptr;
-  int rc = DMX_OK;
+  if (int rc = e->d_coff.ensure(sizeof(int64_t) * ((size_t)S + 1))) return rc;
+  if (int rc = e->d_ccell.ensure(sizeof(int32_t) * (size_t)P)) return rc;
+  if (int rc = e->d_clgl.ensure(3 * sizeof(double) * (size_t)P)) return rc;
+  if (int rc = e->d_ccnt.ensure(sizeof(uint32_t) * (size_t)P)) return rc;
   std::vector<int64_t> off((size_t)S + 1, 0);
+  DevBuf<int32_t> d_deep, d_M, d_tot, d_dst;     // the call's own scratch: freed on every return
+  DevBuf<int64_t> d_sblk;
+  if (int rc = d_deep.alloc(sizeof(int32_t))) return rc;
+  HIP_TRY(hipMemsetAsync(d_deep, 0, sizeof(int32_t), e->stream));
+  if (int rc = e->cev.record_start(e->stream)) return rc;
   if (dense) {
     const int64_t sp = B > 0 ? P / B : 0;                       // pairs per barcode (set_pileup checked that every barcode has them)
     for (int32_t t = 0; t <= S; ++t) off[(size_t)t] = std::min<int64_t>(t, sp) * B;
@@ -9026,47 +8925,36 @@ extern "C" int dmx_engine_cluster_stage(dmx_engine* e) {
     HIP_TRY(hipMemsetAsync(e->d_coff, 0, sizeof(int64_t) * ((size_t)S + 1), e->stream));
   } else {
     std::vector<int32_t> tot((size_t)S);
-    hipError_t he = hipMalloc((void**)&d_sblk, 16 * (size_t)B * ((size_t)nblk + 1));
-    if (he == hipSuccess) he = hipMalloc((void**)&d_M, sizeof(int32_t) * (size_t)ng * S);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_tot, sizeof(int32_t) * (size_t)S);
-    if (he == hipSuccess) he = hipMalloc((void**)&d_dst, sizeof(int32_t) * (size_t)P);
-    if (he == hipSuccess) {
-      hipLaunchKernelGGL(k_snp_blocks, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, kClSlabShift, nblk, d_sblk);
-      hipLaunchKernelGGL(k_cluster_slots<false>, dim3((unsigned)nblk, (unsigned)ng), dim3(64), 0, e->stream, e->pv, (const int64_t*)d_sblk, nblk, gsz, p_base,
-                         d_M, (const int64_t*)nullptr, (int32_t*)nullptr);
-      hipLaunchKernelGGL(k_cluster_colscan, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, e->stream, d_M, ng, S, d_tot);
-      he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(tot.data(), d_tot, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, e->stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he == hipSuccess) {
-      for (int32_t t = 0; t < S; ++t) off[(size_t)t + 1] = off[(size_t)t] + tot[(size_t)t];
-      if (off[(size_t)S] != P) rc = set_error(DMX_ERR_STATE, "dmx_engine_cluster_stage: %lld pairs placed of %lld", (long long)off[(size_t)S], (long long)P);
-    }
-    if (he == hipSuccess && rc == DMX_OK) he = hipMemcpyAsync(e->d_coff, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, e->stream);
-    if (he == hipSuccess && rc == DMX_OK) {
-      hipLaunchKernelGGL(k_cluster_slots<true>, dim3((unsigned)nblk, (unsigned)ng), dim3(64), 0, e->stream, e->pv, (const int64_t*)d_sblk, nblk, gsz, p_base,
-                         d_M, (const int64_t*)e->d_coff, d_dst);
-      he = hipGetLastError();
-    }
-    if (he != hipSuccess && rc == DMX_OK) rc = set_error(DMX_ERR_HIP, "dmx_engine_cluster_stage: placement: %s", hipGetErrorString(he));
+    if (int rc = d_sblk.alloc(16 * (size_t)B * ((size_t)nblk + 1))) return rc;
+    if (int rc = d_M.alloc(sizeof(int32_t) * (size_t)ng * S)) return rc;
+    if (int rc = d_tot.alloc(sizeof(int32_t) * (size_t)S)) return rc;
+    if (int rc = d_dst.alloc(sizeof(int32_t) * (size_t)P)) return rc;
+    hipLaunchKernelGGL(k_snp_blocks, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, kClSlabShift, nblk, d_sblk);
+    hipLaunchKernelGGL(k_cluster_slots<false>, dim3((unsigned)nblk, (unsigned)ng), dim3(64), 0, e->stream, e->pv, (const int64_t*)d_sblk, nblk, gsz, p_base,
+                       d_M, (const int64_t*)nullptr, (int32_t*)nullptr);
+    hipLaunchKernelGGL(k_cluster_colscan, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, e->stream, d_M, ng, S, d_tot);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(tot.data(), d_tot, sizeof(int32_t) * (size_t)S, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    for (int32_t t = 0; t < S; ++t) off[(size_t)t + 1] = off[(size_t)t] + tot[(size_t)t];
+    if (off[(size_t)S] != P) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_stage: %lld pairs placed of %lld", (long long)off[(size_t)S], (long long)P);
+    HIP_TRY(hipMemcpyAsync(e->d_coff, off.data(), sizeof(int64_t) * off.size(), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_cluster_slots<true>, dim3((unsigned)nblk, (unsigned)ng), dim3(64), 0, e->stream, e->pv, (const int64_t*)d_sblk, nblk, gsz, p_base,
+                       d_M, (const int64_t*)e->d_coff, d_dst);
+    HIP_TRY(hipGetLastError());
   }
-  if (rc == DMX_OK && B > 0) {
+  if (B > 0) {
     hipLaunchKernelGGL(k_cluster_lgl, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, (const double*)e->d_lut, p_base,
                        (const int32_t*)d_dst, e->d_clgl, e->d_ccnt, e->d_ccell, d_deep);
-    const hipError_t he = hipGetLastError();
-    if (he != hipSuccess) rc = set_error(DMX_ERR_HIP, "dmx_engine_cluster_stage: k_cluster_lgl: %s", hipGetErrorString(he));
+    HIP_TRY(hipGetLastError());
   }
-  if (rc == DMX_OK) { const hipError_t he = hipEventRecord(e->cev[1], e->stream); if (he != hipSuccess) rc = set_error(DMX_ERR_HIP, "hipEventRecord: %s", hipGetErrorString(he)); }
-  const hipError_t hs = hipStreamSynchronize(e->stream);
-  if (rc == DMX_OK && hs != hipSuccess) rc = set_error(DMX_ERR_HIP, "dmx_engine_cluster_stage: %s", hipGetErrorString(hs));
+  if (int rc = e->cev.record_stop(e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
   int32_t deep = 0;
-  if (rc == DMX_OK) { const hipError_t he = hipMemcpy(&deep, d_deep, sizeof(int32_t), hipMemcpyDeviceToHost); if (he != hipSuccess) rc = set_error(DMX_ERR_HIP, "hipMemcpy: %s", hipGetErrorString(he)); }
-  for (void* p : {(void*)d_sblk, (void*)d_M, (void*)d_tot, (void*)d_dst, (void*)d_deep}) if (p) (void)hipFree(p);
-  if (rc != DMX_OK) return rc;
+  HIP_TRY(hipMemcpy(&deep, d_deep, sizeof(int32_t), hipMemcpyDeviceToHost));
   if (deep) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_stage: a pair has more than 65 535 stored reads");
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->cev[0], e->cev[1]));
+  if (int rc = e->cev.elapsed_ms(&ms)) return rc;
   dmx_cluster_info& inf = e->cl_info;
   std::memset(&inf, 0, sizeof inf);
   inf.stage_ms = ms; inf.cache_bytes = (int64_t)cache_b; inf.n_pairs = P; inf.n_cells = B; inf.n_snps = S; inf.sorted = !dense && P > 0;
@@ -9075,6 +8963,66 @@ extern "C" int dmx_engine_cluster_stage(dmx_engine* e) {
   e->have_cm = false; e->have_cw = false; e->have_ckw = false;
   return DMX_OK;
 }
+
+namespace {
+
+// Where an M-step takes its weights [B][C] from: the last E-step's (which must have had C columns), or the caller's, a host copy of
+// which goes through d_cwh.  `last_estep` ends the message of the state error; `who` is the entry point.
+int mstep_weights(dmx_engine* e, const char* who, const char* last_estep, int32_t memory, const double* weights, size_t nw, int32_t C, const double** w) {
+  if (memory == DMX_CLUSTER_LAST_ESTEP) {
+    if (!e->have_cw || e->cw_C != C) return set_error(DMX_ERR_STATE, "%s: no E-step weights of %s", who, last_estep);
+    *w = e->d_cw;
+  } else if (memory == DMX_MEM_HOST || memory == DMX_MEM_DEVICE) {
+    if (nw > 0 && !weights) return set_error(DMX_ERR_ARG, "%s: missing weights", who);
+    if (memory == DMX_MEM_HOST) {
+      if (int rc = e->d_cwh.ensure(sizeof(double) * nw)) return rc;
+      if (nw) HIP_TRY(hipMemcpyAsync(e->d_cwh, weights, sizeof(double) * nw, hipMemcpyHostToDevice, e->stream));
+      *w = e->d_cwh;
+    } else {
+      *w = weights;
+    }
+  } else {
+    return set_error(DMX_ERR_ARG, "%s: weights_memory %d", who, memory);
+  }
+  return DMX_OK;
+}
+
+// What the four E-steps share once their arguments are checked and their own inputs are on the device.  `launch(d_mask)` enqueues the
+// variant's kernel, which fills d_cw (B x cw_cols), d_clse (B x R) and whatever else the variant keeps; the column sums of `w` (B x C:
+// d_cw, or the known-column E-step's d_ckw), the log likelihoods of the R restarts and, with `dm`, the doublet masses then go
+// through k_cluster_epart / k_cluster_efold and come back to the host.
+struct EstepSums { double *col_sum, *ll, *dbl_mass; };
+template <typename Launch>
+int cluster_estep_run(dmx_engine* e, EventPair& ev, int32_t B, int32_t R, int32_t C, int32_t cw_cols, const DevBuf<double>& w, const DevBuf<double>* dm,
+                      const uint8_t* mask, const EstepSums& sums, float* ms, Launch&& launch) {
+  const int32_t nch = (B + kEChunk - 1) / kEChunk, ncol = C + (dm ? 2 : 1) * R;
+  if (int rc = e->d_cw.ensure(sizeof(double) * (size_t)B * cw_cols)) return rc;
+  if (int rc = e->d_clse.ensure(sizeof(double) * (size_t)B * R)) return rc;
+  if (int rc = e->d_cpart.ensure(sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
+  if (mask) if (int rc = e->d_cmask.ensure((size_t)B)) return rc;
+  if (mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
+  double* d_out = e->d_cpart + (size_t)nch * ncol;   // (a view: the row behind the chunks' partials)
+  if (int rc = ev.record_start(e->stream)) return rc;
+  if (B > 0) {
+    launch(mask ? (const uint8_t*)e->d_cmask : nullptr);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)w,
+                       (const double*)e->d_clse, dm ? (const double*)*dm : nullptr, B, C, R, e->d_cpart);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
+  HIP_TRY(hipGetLastError());
+  if (int rc = ev.record_stop(e->stream)) return rc;
+  std::vector<double> out((size_t)ncol);
+  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (sums.col_sum) std::memcpy(sums.col_sum, out.data(), sizeof(double) * (size_t)C);
+  if (sums.ll) std::memcpy(sums.ll, out.data() + C, sizeof(double) * (size_t)R);
+  if (dm && sums.dbl_mass) std::memcpy(sums.dbl_mass, out.data() + C + R, sizeof(double) * (size_t)R);
+  return ev.elapsed_ms(ms);
+}
+
+}  // namespace
 
 extern "C" int dmx_engine_cluster_mstep(dmx_engine* e, const dmx_cluster_mstep_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: null argument");
@@ -9087,38 +9035,23 @@ extern "C" int dmx_engine_cluster_mstep(dmx_engine* e, const dmx_cluster_mstep_r
   HIP_TRY(hipSetDevice(e->device));
   const size_t nw = (size_t)B * C, rows = (size_t)S * C;
   const double* w = nullptr;
-  if (rq->weights_memory == DMX_CLUSTER_LAST_ESTEP) {
-    if (!e->have_cw || e->cw_C != C) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_mstep: no E-step weights of this cache (dmx_engine_cluster_estep first)");
-    w = e->d_cw;
-  } else if (rq->weights_memory == DMX_MEM_HOST || rq->weights_memory == DMX_MEM_DEVICE) {
-    if (nw > 0 && !rq->weights) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: missing weights");
-    if (rq->weights_memory == DMX_MEM_HOST) {
-      if (int rc = ensure_dev((void**)&e->d_cwh, &e->cwh_cap, sizeof(double) * nw)) return rc;
-      if (nw) HIP_TRY(hipMemcpyAsync(e->d_cwh, rq->weights, sizeof(double) * nw, hipMemcpyHostToDevice, e->stream));
-      w = e->d_cwh;
-    } else {
-      w = rq->weights;
-    }
-  } else {
-    return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep: weights_memory %d", rq->weights_memory);
-  }
-  if (!e->cev[0]) for (hipEvent_t& ev : e->cev) HIP_TRY(hipEventCreate(&ev));
-  if (int rc = ensure_dev((void**)&e->d_cq, &e->cq_cap, sizeof(float) * 3 * (size_t)S)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cll, &e->cll_cap, sizeof(double) * 3 * rows)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cW, &e->cW_cap, sizeof(double) * rows)) return rc;
+  if (int rc = mstep_weights(e, "dmx_engine_cluster_mstep", "this cache (dmx_engine_cluster_estep first)", rq->weights_memory, rq->weights, nw, C, &w)) return rc;
+  if (int rc = e->d_cq.ensure(sizeof(float) * 3 * (size_t)S)) return rc;
+  if (int rc = e->d_cll.ensure(sizeof(double) * 3 * rows)) return rc;
+  if (int rc = e->d_cW.ensure(sizeof(double) * rows)) return rc;
   const int nxt = e->d_g == e->d_cgp[0] ? 1 : 0;                      // never the buffer the engine's genotype matrix is
-  if (int rc = ensure_dev((void**)&e->d_cgp[nxt], &e->cgp_cap[nxt], sizeof(float) * 3 * rows)) return rc;
+  if (int rc = e->d_cgp[nxt].ensure(sizeof(float) * 3 * rows)) return rc;
   if (S) HIP_TRY(hipMemcpyAsync(e->d_cq, rq->prior, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipEventRecord(e->cev[0], e->stream));
+  if (int rc = e->cev.record_start(e->stream)) return rc;
   if (rows) {
     hipLaunchKernelGGL(k_cluster_mstep, dim3((unsigned)((S + 3) / 4), (unsigned)((C + 63) / 64)), dim3(256), 0, e->stream, (const int64_t*)e->d_coff,
                        (const int32_t*)e->d_ccell, (const double*)e->d_clgl, w, S, C, (const float*)e->d_cq, rq->floor, e->d_cll, e->d_cW, e->d_cgp[nxt]);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(e->cev[1], e->stream));
+  if (int rc = e->cev.record_stop(e->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's prior / weights may go away after return
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->cev[0], e->cev[1]));
+  if (int rc = e->cev.elapsed_ms(&ms)) return rc;
   e->cl_info.mstep_ms = ms; e->cl_info.n_cols = C;
   e->cgp_cur = nxt; e->cm_S = S; e->cm_C = C; e->cgp_C = C; e->have_cm = true;
   return DMX_OK;
@@ -9136,35 +9069,13 @@ extern "C" int dmx_engine_cluster_estep(dmx_engine* e, const dmx_cluster_estep_r
   const int32_t nch = (B + kEChunk - 1) / kEChunk;
   if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep: %d cells exceed this build's limit", B);
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->cev[0]) for (hipEvent_t& ev : e->cev) HIP_TRY(hipEventCreate(&ev));
-  const int32_t ncol = C + R;
-  if (int rc = ensure_dev((void**)&e->d_cw, &e->cw_cap, sizeof(double) * (size_t)B * C)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_clse, &e->clse_cap, sizeof(double) * (size_t)B * R)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cpart, &e->cpart_cap, sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cpi, &e->cpi_cap, sizeof(double) * (size_t)C)) return rc;
-  if (rq->mask) if (int rc = ensure_dev((void**)&e->d_cmask, &e->cmask_cap, (size_t)B)) return rc;
+  if (int rc = e->d_cpi.ensure(sizeof(double) * (size_t)C)) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_cpi, rq->log_pi, sizeof(double) * (size_t)C, hipMemcpyHostToDevice, e->stream));
-  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
-  double* d_out = e->d_cpart + (size_t)nch * ncol;
-  HIP_TRY(hipEventRecord(e->cev[0], e->stream));
-  if (B > 0) {
-    hipLaunchKernelGGL(k_cluster_estep, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R, K,
-                       (const double*)e->d_cpi, 1.0 / rq->temperature, rq->mask ? (const uint8_t*)e->d_cmask : nullptr, e->d_cw, e->d_clse);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_cw,
-                       (const double*)e->d_clse, (const double*)nullptr, B, C, R, e->d_cpart);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->cev[1], e->stream));
-  std::vector<double> out((size_t)ncol);
-  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (rq->col_sum) std::memcpy(rq->col_sum, out.data(), sizeof(double) * (size_t)C);
-  if (rq->ll) std::memcpy(rq->ll, out.data() + C, sizeof(double) * (size_t)R);
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->cev[0], e->cev[1]));
+  if (int rc = cluster_estep_run(e, e->cev, B, R, C, C, e->d_cw, nullptr, rq->mask, {rq->col_sum, rq->ll, nullptr}, &ms, [&](const uint8_t* d_mask) {
+        hipLaunchKernelGGL(k_cluster_estep, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R, K,
+                           (const double*)e->d_cpi, 1.0 / rq->temperature, d_mask, e->d_cw, e->d_clse);
+      })) return rc;
   e->cl_info.estep_ms = ms;
   e->cw_C = C; e->have_cw = true;
   return DMX_OK;
@@ -9230,32 +9141,31 @@ extern "C" int dmx_engine_cluster_doublet(dmx_engine* e, int32_t n_restarts, int
   const int64_t n_units = (int64_t)B * n_cblk;
   if ((n_units + kDblWaves - 1) / kDblWaves > INT32_MAX) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: %d cells x %lld pair-columns exceed this build's limit", B, (long long)ncols);
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->dev_[0]) for (hipEvent_t& ev : e->dev_) HIP_TRY(hipEventCreate(&ev));
   const size_t lld_b = sizeof(double) * ((size_t)B * (size_t)ncols + (size_t)B), pairs_b = sizeof(uint32_t) * (size_t)P;   // LLD, then lsc[B]
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  const size_t need = (lld_b > e->clld_cap ? lld_b : 0) + (pairs_b > e->cpairs_cap ? pairs_b : 0);
+  const size_t need = (lld_b > e->d_clld.cap() ? lld_b : 0) + (pairs_b > e->d_cpairs.cap() ? pairs_b : 0);
   if (need > 0 && (double)need > 0.9 * (double)free_b)
     return set_error(DMX_ERR_NOMEM, "dmx_engine_cluster_doublet: LLD of %d cells x %d restarts x %lld pairs needs %.2f GB (+%.2f MB pair table), %.2f GB of device memory are free",
                      B, R, (long long)P, lld_b / 1e9, pairs_b / 1e6, free_b / 1e9);
   e->have_cdbl = false;
-  if (int rc = ensure_dev((void**)&e->d_clld, &e->clld_cap, lld_b)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cpairs, &e->cpairs_cap, pairs_b)) return rc;
+  if (int rc = e->d_clld.ensure(lld_b)) return rc;
+  if (int rc = e->d_cpairs.ensure(pairs_b)) return rc;
   std::vector<uint32_t> pr((size_t)P);
   for (int32_t k = 0, p = 0; k < K; ++k)
     for (int32_t l = k + 1; l < K; ++l) pr[(size_t)p++] = (uint32_t)k | ((uint32_t)l << 16);
   HIP_TRY(hipMemcpyAsync(e->d_cpairs, pr.data(), pairs_b, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipEventRecord(e->dev_[0], e->stream));
+  if (int rc = e->dev_.record_start(e->stream)) return rc;
   if (n_units > 0) {
     hipLaunchKernelGGL(k_cluster_dbl, dim3((unsigned)((n_units + kDblWaves - 1) / kDblWaves)), dim3(64 * kDblWaves), 0, e->stream, e->pv, e->nrd_width,
                        (const double*)e->d_lut, (const float*)e->d_g, V, K, (int32_t)P, (const uint32_t*)e->d_cpairs, (int32_t)ncols, n_cblk, n_units,
                        e->d_clld, e->d_clld + (size_t)B * ncols);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(e->dev_[1], e->stream));
+  if (int rc = e->dev_.record_stop(e->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->dev_[0], e->dev_[1]));
+  if (int rc = e->dev_.elapsed_ms(&ms)) return rc;
   dmx_cluster_doublet_info& inf = e->cd_info;
   std::memset(&inf, 0, sizeof inf);
   inf.doublet_ms = ms; inf.lld_bytes = (int64_t)lld_b; inf.n_cells = B; inf.n_restarts = R; inf.n_clusters = K; inf.n_pairs = (int32_t)P;
@@ -9305,38 +9215,15 @@ extern "C" int dmx_engine_cluster_estep_doublet(dmx_engine* e, const dmx_cluster
         lpd[(size_t)r * P + p] = (ld == -INFINITY || !(s2 < 1.0)) ? -INFINITY : ld + M_LN2 + pi[k] + pi[l] - lden;
   }
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->dev_[0]) for (hipEvent_t& ev : e->dev_) HIP_TRY(hipEventCreate(&ev));
-  const int32_t ncol = C + 2 * R;
-  if (int rc = ensure_dev((void**)&e->d_cw, &e->cw_cap, sizeof(double) * (size_t)B * C)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_clse, &e->clse_cap, sizeof(double) * (size_t)B * R)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cdm, &e->cdm_cap, sizeof(double) * (size_t)B * R)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cpart, &e->cpart_cap, sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_clp, &e->clp_cap, sizeof(double) * lp.size())) return rc;
-  if (rq->mask) if (int rc = ensure_dev((void**)&e->d_cmask, &e->cmask_cap, (size_t)B)) return rc;
+  if (int rc = e->d_cdm.ensure(sizeof(double) * (size_t)B * R)) return rc;
+  if (int rc = e->d_clp.ensure(sizeof(double) * lp.size())) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_clp, lp.data(), sizeof(double) * lp.size(), hipMemcpyHostToDevice, e->stream));
-  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
-  double* d_out = e->d_cpart + (size_t)nch * ncol;
-  HIP_TRY(hipEventRecord(e->dev_[0], e->stream));
-  if (B > 0) {
-    hipLaunchKernelGGL(k_cluster_estep_dbl, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks,
-                       (const double*)e->d_clld, (const double*)(e->d_clld + (size_t)B * R * P), B, R, K, (int32_t)P, (const double*)e->d_clp, (const double*)(e->d_clp + C), 1.0 / rq->temperature,
-                       rq->mask ? (const uint8_t*)e->d_cmask : nullptr, e->d_cw, e->d_clse, e->d_cdm);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_cw,
-                       (const double*)e->d_clse, (const double*)e->d_cdm, B, C, R, e->d_cpart);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->dev_[1], e->stream));
-  std::vector<double> out((size_t)ncol);
-  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (rq->col_sum) std::memcpy(rq->col_sum, out.data(), sizeof(double) * (size_t)C);
-  if (rq->ll) std::memcpy(rq->ll, out.data() + C, sizeof(double) * (size_t)R);
-  if (rq->dbl_mass) std::memcpy(rq->dbl_mass, out.data() + C + R, sizeof(double) * (size_t)R);
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->dev_[0], e->dev_[1]));
+  if (int rc = cluster_estep_run(e, e->dev_, B, R, C, C, e->d_cw, &e->d_cdm, rq->mask, {rq->col_sum, rq->ll, rq->dbl_mass}, &ms, [&](const uint8_t* d_mask) {
+        hipLaunchKernelGGL(k_cluster_estep_dbl, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks,
+                           (const double*)e->d_clld, (const double*)(e->d_clld + (size_t)B * R * P), B, R, K, (int32_t)P, (const double*)e->d_clp, (const double*)(e->d_clp + C), 1.0 / rq->temperature,
+                           d_mask, e->d_cw, e->d_clse, e->d_cdm);
+      })) return rc;
   e->cd_info.estep_ms = ms;
   e->cw_C = C; e->have_cw = true;
   return DMX_OK;
@@ -9365,16 +9252,15 @@ extern "C" int dmx_engine_cluster_merge_score(dmx_engine* e, int32_t n_restarts,
   const int32_t P = K * (K - 1) / 2, nch = (S + kSmChunk - 1) / kSmChunk;
   const size_t rows = (size_t)S * C, nout = (size_t)R * P, npart = (size_t)R * nch * P;
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->sev[0]) for (hipEvent_t& ev : e->sev) HIP_TRY(hipEventCreate(&ev));
-  if (int rc = ensure_dev((void**)&e->d_smA, &e->smA_cap, sizeof(double) * rows)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_smF, &e->smF_cap, rows)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_smq, &e->smq_cap, sizeof(float) * 3 * (size_t)S)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_smpart, &e->smpart_cap, sizeof(double) * npart)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_smnpart, &e->smnpart_cap, sizeof(int32_t) * npart)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_smout, &e->smout_cap, sizeof(double) * nout)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_smnout, &e->smnout_cap, sizeof(int32_t) * nout)) return rc;
+  if (int rc = e->d_smA.ensure(sizeof(double) * rows)) return rc;
+  if (int rc = e->d_smF.ensure(rows)) return rc;
+  if (int rc = e->d_smq.ensure(sizeof(float) * 3 * (size_t)S)) return rc;
+  if (int rc = e->d_smpart.ensure(sizeof(double) * npart)) return rc;
+  if (int rc = e->d_smnpart.ensure(sizeof(int32_t) * npart)) return rc;
+  if (int rc = e->d_smout.ensure(sizeof(double) * nout)) return rc;
+  if (int rc = e->d_smnout.ensure(sizeof(int32_t) * nout)) return rc;
   if (S) HIP_TRY(hipMemcpyAsync(e->d_smq, prior, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipEventRecord(e->sev[0], e->stream));
+  if (int rc = e->sev.record_start(e->stream)) return rc;
   if (rows) {
     hipLaunchKernelGGL(k_cluster_marg, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cll, (const double*)e->d_cW,
                        (const float*)e->d_smq, floor_, S, C, e->d_smA, e->d_smF);
@@ -9386,12 +9272,12 @@ extern "C" int dmx_engine_cluster_merge_score(dmx_engine* e, int32_t n_restarts,
   hipLaunchKernelGGL(k_cluster_merge_fold, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_smpart,
                      (const int32_t*)e->d_smnpart, nch, R, P, e->d_smout, e->d_smnout);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->sev[1], e->stream));
+  if (int rc = e->sev.record_stop(e->stream)) return rc;
   if (bf) HIP_TRY(hipMemcpyAsync(bf, e->d_smout, sizeof(double) * nout, hipMemcpyDeviceToHost, e->stream));
   if (n_shared) HIP_TRY(hipMemcpyAsync(n_shared, e->d_smnout, sizeof(int32_t) * nout, hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->sev[0], e->sev[1]));
+  if (int rc = e->sev.elapsed_ms(&ms)) return rc;
   e->sm_info.merge_ms = ms; e->sm_info.n_restarts = R; e->sm_info.n_clusters = K; e->sm_info.n_pairs = P; e->sm_info.n_chunks = nch;
   return DMX_OK;
 }
@@ -9414,38 +9300,15 @@ extern "C" int dmx_engine_cluster_estep_grouped(dmx_engine* e, const dmx_cluster
   const int32_t nch = (B + kEChunk - 1) / kEChunk;
   if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_grouped: %d cells exceed this build's limit", B);
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->sev[0]) for (hipEvent_t& ev : e->sev) HIP_TRY(hipEventCreate(&ev));
-  const int32_t ncol = C + R;
-  if (int rc = ensure_dev((void**)&e->d_cw, &e->cw_cap, sizeof(double) * (size_t)B * C)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_clse, &e->clse_cap, sizeof(double) * (size_t)B * R)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cpart, &e->cpart_cap, sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cpi, &e->cpi_cap, sizeof(double) * (size_t)C)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cgrp, &e->cgrp_cap, sizeof(int32_t) * (size_t)B)) return rc;
-  if (rq->mask) if (int rc = ensure_dev((void**)&e->d_cmask, &e->cmask_cap, (size_t)B)) return rc;
+  if (int rc = e->d_cpi.ensure(sizeof(double) * (size_t)C)) return rc;
+  if (int rc = e->d_cgrp.ensure(sizeof(int32_t) * (size_t)B)) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_cpi, rq->log_pi, sizeof(double) * (size_t)C, hipMemcpyHostToDevice, e->stream));
   if (B) HIP_TRY(hipMemcpyAsync(e->d_cgrp, rq->group, sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, e->stream));
-  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
-  double* d_out = e->d_cpart + (size_t)nch * ncol;
-  HIP_TRY(hipEventRecord(e->sev[0], e->stream));
-  if (B > 0) {
-    hipLaunchKernelGGL(k_cluster_estep_grp, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R, K,
-                       (const double*)e->d_cpi, 1.0 / rq->temperature, rq->mask ? (const uint8_t*)e->d_cmask : nullptr, (const int32_t*)e->d_cgrp, Rs,
-                       e->d_cw, e->d_clse);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_cw,
-                       (const double*)e->d_clse, (const double*)nullptr, B, C, R, e->d_cpart);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->sev[1], e->stream));
-  std::vector<double> out((size_t)ncol);
-  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (rq->col_sum) std::memcpy(rq->col_sum, out.data(), sizeof(double) * (size_t)C);
-  if (rq->ll) std::memcpy(rq->ll, out.data() + C, sizeof(double) * (size_t)R);
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->sev[0], e->sev[1]));
+  if (int rc = cluster_estep_run(e, e->sev, B, R, C, C, e->d_cw, nullptr, rq->mask, {rq->col_sum, rq->ll, nullptr}, &ms, [&](const uint8_t* d_mask) {
+        hipLaunchKernelGGL(k_cluster_estep_grp, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R, K,
+                           (const double*)e->d_cpi, 1.0 / rq->temperature, d_mask, (const int32_t*)e->d_cgrp, Rs, e->d_cw, e->d_clse);
+      })) return rc;
   e->sm_info.grouped_estep_ms = ms;
   e->cw_C = C; e->have_cw = true;
   return DMX_OK;
@@ -9469,7 +9332,7 @@ extern "C" int dmx_engine_cluster_set_known(dmx_engine* e, int32_t n_snps, int32
   const size_t n = (size_t)n_snps * n_known * 3;
   if (n && !g) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_set_known: missing rows");
   HIP_TRY(hipSetDevice(e->device));
-  if (int rc = ensure_dev((void**)&e->d_ckn, &e->ckn_cap, sizeof(float) * n)) return rc;
+  if (int rc = e->d_ckn.ensure(sizeof(float) * n)) return rc;
   if (n) HIP_TRY(hipMemcpyAsync(e->d_ckn, g, sizeof(float) * n, memory == DMX_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
   e->ckn_S = n_snps; e->ckn_Vk = n_known; e->have_ckn = true;
@@ -9488,37 +9351,16 @@ extern "C" int dmx_engine_cluster_estep_known(dmx_engine* e, const dmx_cluster_e
   if (!(rq->temperature > 0.0) || !std::isfinite(rq->temperature)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_known: temperature %g", rq->temperature);
   const int32_t nch = (B + kEChunk - 1) / kEChunk;
   if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_estep_known: %d cells exceed this build's limit", B);
-  const int32_t K = Vk + M, CK = R * K, CF = R * M, ncol = CK + R;
+  const int32_t K = Vk + M, CK = R * K, CF = R * M;
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->kev[0]) for (hipEvent_t& ev : e->kev) HIP_TRY(hipEventCreate(&ev));
-  if (int rc = ensure_dev((void**)&e->d_ckw, &e->ckw_cap, sizeof(double) * (size_t)B * CK)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cw, &e->cw_cap, sizeof(double) * (size_t)B * CF)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_clse, &e->clse_cap, sizeof(double) * (size_t)B * R)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cpart, &e->cpart_cap, sizeof(double) * ((size_t)nch + 1) * ncol)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cpi, &e->cpi_cap, sizeof(double) * (size_t)CK)) return rc;
-  if (rq->mask) if (int rc = ensure_dev((void**)&e->d_cmask, &e->cmask_cap, (size_t)B)) return rc;
+  if (int rc = e->d_ckw.ensure(sizeof(double) * (size_t)B * CK)) return rc;
+  if (int rc = e->d_cpi.ensure(sizeof(double) * (size_t)CK)) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_cpi, rq->log_pi, sizeof(double) * (size_t)CK, hipMemcpyHostToDevice, e->stream));
-  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_cmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
-  double* d_out = e->d_cpart + (size_t)nch * ncol;
-  HIP_TRY(hipEventRecord(e->kev[0], e->stream));
-  if (B > 0) {
-    hipLaunchKernelGGL(k_cluster_estep_known, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R,
-                       Vk, M, (const double*)e->d_cpi, 1.0 / rq->temperature, rq->mask ? (const uint8_t*)e->d_cmask : nullptr, e->d_ckw, e->d_cw, e->d_clse);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cluster_epart, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_ckw,
-                       (const double*)e->d_clse, (const double*)nullptr, B, CK, R, e->d_cpart);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_cluster_efold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cpart, nch, ncol, d_out);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e->kev[1], e->stream));
-  std::vector<double> out((size_t)ncol);
-  HIP_TRY(hipMemcpyAsync(out.data(), d_out, sizeof(double) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
-  HIP_TRY(hipStreamSynchronize(e->stream));
-  if (rq->col_sum) std::memcpy(rq->col_sum, out.data(), sizeof(double) * (size_t)CK);
-  if (rq->ll) std::memcpy(rq->ll, out.data() + CK, sizeof(double) * (size_t)R);
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->kev[0], e->kev[1]));
+  if (int rc = cluster_estep_run(e, e->kev, B, R, CK, CF, e->d_ckw, nullptr, rq->mask, {rq->col_sum, rq->ll, nullptr}, &ms, [&](const uint8_t* d_mask) {
+        hipLaunchKernelGGL(k_cluster_estep_known, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_llks, B, R,
+                           Vk, M, (const double*)e->d_cpi, 1.0 / rq->temperature, d_mask, e->d_ckw, e->d_cw, e->d_clse);
+      })) return rc;
   e->kn_info.estep_ms = ms; e->kn_info.n_cells = B; e->kn_info.n_known = Vk; e->kn_info.n_restarts = R; e->kn_info.n_free = M;
   e->cw_C = CF; e->have_cw = true;
   e->ckw_B = B; e->ckw_R = R; e->ckw_K = K; e->have_ckw = true;
@@ -9540,29 +9382,15 @@ extern "C" int dmx_engine_cluster_mstep_window(dmx_engine* e, const dmx_cluster_
   const int32_t C = R * M;
   const size_t nw = (size_t)B * C, rows = (size_t)S * C;
   const double* w = nullptr;
-  if (rq->weights_memory == DMX_CLUSTER_LAST_ESTEP) {
-    if (!e->have_cw || e->cw_C != C) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_mstep_window: no E-step weights of %d free columns (dmx_engine_cluster_estep_known first)", C);
-    w = e->d_cw;
-  } else if (rq->weights_memory == DMX_MEM_HOST || rq->weights_memory == DMX_MEM_DEVICE) {
-    if (nw > 0 && !rq->weights) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: missing weights");
-    if (rq->weights_memory == DMX_MEM_HOST) {
-      if (int rc = ensure_dev((void**)&e->d_cwh, &e->cwh_cap, sizeof(double) * nw)) return rc;
-      if (nw) HIP_TRY(hipMemcpyAsync(e->d_cwh, rq->weights, sizeof(double) * nw, hipMemcpyHostToDevice, e->stream));
-      w = e->d_cwh;
-    } else {
-      w = rq->weights;
-    }
-  } else {
-    return set_error(DMX_ERR_ARG, "dmx_engine_cluster_mstep_window: weights_memory %d", rq->weights_memory);
-  }
-  if (!e->kev[0]) for (hipEvent_t& ev : e->kev) HIP_TRY(hipEventCreate(&ev));
-  if (int rc = ensure_dev((void**)&e->d_cq, &e->cq_cap, sizeof(float) * 3 * (size_t)S)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cll, &e->cll_cap, sizeof(double) * 3 * rows)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_cW, &e->cW_cap, sizeof(double) * rows)) return rc;
+  const std::string last = std::to_string(C) + " free columns (dmx_engine_cluster_estep_known first)";
+  if (int rc = mstep_weights(e, "dmx_engine_cluster_mstep_window", last.c_str(), rq->weights_memory, rq->weights, nw, C, &w)) return rc;
+  if (int rc = e->d_cq.ensure(sizeof(float) * 3 * (size_t)S)) return rc;
+  if (int rc = e->d_cll.ensure(sizeof(double) * 3 * rows)) return rc;
+  if (int rc = e->d_cW.ensure(sizeof(double) * rows)) return rc;
   const int nxt = e->d_g == e->d_cgp[0] ? 1 : 0;                      // never the buffer the engine's genotype matrix is
-  if (int rc = ensure_dev((void**)&e->d_cgp[nxt], &e->cgp_cap[nxt], sizeof(float) * 3 * (size_t)S * V)) return rc;
+  if (int rc = e->d_cgp[nxt].ensure(sizeof(float) * 3 * (size_t)S * V)) return rc;
   if (S) HIP_TRY(hipMemcpyAsync(e->d_cq, rq->prior, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, e->stream));
-  HIP_TRY(hipEventRecord(e->kev[0], e->stream));
+  if (int rc = e->kev.record_start(e->stream)) return rc;
   if (S && Vk)
     HIP_TRY(hipMemcpy2DAsync(e->d_cgp[nxt], sizeof(float) * 3 * (size_t)V, e->d_ckn, sizeof(float) * 3 * (size_t)Vk, sizeof(float) * 3 * (size_t)Vk,
                              (size_t)S, hipMemcpyDeviceToDevice, e->stream));
@@ -9571,10 +9399,10 @@ extern "C" int dmx_engine_cluster_mstep_window(dmx_engine* e, const dmx_cluster_
                        (const int32_t*)e->d_ccell, (const double*)e->d_clgl, w, S, C, (const float*)e->d_cq, rq->floor, e->d_cll, e->d_cW, e->d_cgp[nxt], Vk);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(e->kev[1], e->stream));
+  if (int rc = e->kev.record_stop(e->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's prior / weights may go away after return
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->kev[0], e->kev[1]));
+  if (int rc = e->kev.elapsed_ms(&ms)) return rc;
   e->kn_info.mstep_ms = ms; e->kn_info.n_known = Vk; e->kn_info.n_restarts = R; e->kn_info.n_free = M;
   e->cgp_cur = nxt; e->cm_S = S; e->cm_C = C; e->cgp_C = V; e->have_cm = true;
   return DMX_OK;
@@ -9620,7 +9448,6 @@ extern "C" int dmx_engine_ambient(dmx_engine* e, const dmx_ambient_request* rq) 
   for (int32_t i = 0; i < S; ++i)
     if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->aev[0]) for (hipEvent_t& ev : e->aev) HIP_TRY(hipEventCreate(&ev));
   std::vector<int32_t> a((size_t)B);
   if (B > 0) {
     if (rq->assign_memory == DMX_MEM_DEVICE) {
@@ -9638,29 +9465,29 @@ extern "C" int dmx_engine_ambient(dmx_engine* e, const dmx_ambient_request* rq) 
   const size_t prof = sizeof(double) * (size_t)B * (size_t)Q;
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  if (prof > e->all_cap && prof + prof / 16 > free_b)
+  if (prof > e->d_all.cap() && prof + prof / 16 > free_b)
     return set_error(DMX_ERR_NOMEM, "dmx_engine_ambient: the %d x %d profile needs %zu bytes, %zu are free", B, Q, prof, free_b);
-  if (int rc = ensure_dev((void**)&e->d_all, &e->all_cap, prof)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_acnt, &e->acnt_cap, sizeof(int32_t) * 2 * (size_t)B)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_aasg, &e->aasg_cap, sizeof(int32_t) * (size_t)B)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_aamb, &e->aamb_cap, sizeof(double) * (size_t)S)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_agrid, &e->agrid_cap, sizeof(double) * (size_t)Q)) return rc;
+  if (int rc = e->d_all.ensure(prof)) return rc;
+  if (int rc = e->d_acnt.ensure(sizeof(int32_t) * 2 * (size_t)B)) return rc;
+  if (int rc = e->d_aasg.ensure(sizeof(int32_t) * (size_t)B)) return rc;
+  if (int rc = e->d_aamb.ensure(sizeof(double) * (size_t)S)) return rc;
+  if (int rc = e->d_agrid.ensure(sizeof(double) * (size_t)Q)) return rc;
   if (B > 0) HIP_TRY(hipMemcpyAsync(e->d_aasg, a.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, e->stream));
   if (S > 0) HIP_TRY(hipMemcpyAsync(e->d_aamb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_agrid, rq->grid, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, e->stream));
   const int32_t n_qblk = (Q + 63) / 64;
   const int64_t n_units = (int64_t)B * n_qblk;
-  HIP_TRY(hipEventRecord(e->aev[0], e->stream));
+  if (int rc = e->aev.record_start(e->stream)) return rc;
   if (n_units > 0) {
     hipLaunchKernelGGL(k_ambient, dim3((unsigned)((n_units + kAmbWaves - 1) / kAmbWaves)), dim3(64 * kAmbWaves), 0, e->stream, e->pv, e->nrd_width,
                        (const double*)e->d_lut, e->d_g, V, (const int32_t*)e->d_aasg, (const double*)e->d_aamb, (const double*)e->d_agrid, Q, n_qblk,
                        n_units, e->d_all, e->d_acnt, e->d_acnt + B);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(e->aev[1], e->stream));
+  if (int rc = e->aev.record_stop(e->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->aev[0], e->aev[1]));
+  if (int rc = e->aev.elapsed_ms(&ms)) return rc;
   dmx_ambient_info& inf = e->amb_info;
   std::memset(&inf, 0, sizeof inf);
   inf.kernel_ms = ms; inf.profile_bytes = (int64_t)prof; inf.n_cells = B; inf.n_grid = Q; inf.n_assigned = n_asg;
@@ -9732,7 +9559,6 @@ extern "C" int dmx_engine_ambient_doublet(dmx_engine* e, const dmx_ambient_doubl
     if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0))
       return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
   HIP_TRY(hipSetDevice(e->device));
-  if (!e->dbev[0]) for (hipEvent_t& ev : e->dbev) HIP_TRY(hipEventCreate(&ev));
   const size_t n_slot = (size_t)B * (size_t)C;
   std::vector<int32_t> cd(n_slot * 2);
   if (n_slot > 0) {
@@ -9755,20 +9581,20 @@ extern "C" int dmx_engine_ambient_doublet(dmx_engine* e, const dmx_ambient_doubl
   const size_t prof = sizeof(double) * n_slot * (size_t)A * (size_t)Q;
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-  if (prof > e->dll_cap && prof + prof / 16 > free_b)
+  if (prof > e->d_dll.cap() && prof + prof / 16 > free_b)
     return set_error(DMX_ERR_NOMEM, "dmx_engine_ambient_doublet: the %d x %d x %d x %d profile needs %zu bytes, %zu are free", B, C, A, Q, prof, free_b);
-  if (int rc = ensure_dev((void**)&e->d_dll, &e->dll_cap, prof)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_dcnt, &e->dcnt_cap, sizeof(int32_t) * 2 * n_slot)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_dcand, &e->dcand_cap, sizeof(int32_t) * 2 * n_slot)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_damb, &e->damb_cap, sizeof(double) * (size_t)S)) return rc;
-  if (int rc = ensure_dev((void**)&e->d_dgrid, &e->dgrid_cap, sizeof(double) * (size_t)(Q + A))) return rc;
+  if (int rc = e->d_dll.ensure(prof)) return rc;
+  if (int rc = e->d_dcnt.ensure(sizeof(int32_t) * 2 * n_slot)) return rc;
+  if (int rc = e->d_dcand.ensure(sizeof(int32_t) * 2 * n_slot)) return rc;
+  if (int rc = e->d_damb.ensure(sizeof(double) * (size_t)S)) return rc;
+  if (int rc = e->d_dgrid.ensure(sizeof(double) * (size_t)(Q + A))) return rc;
   if (n_slot > 0) HIP_TRY(hipMemcpyAsync(e->d_dcand, cd.data(), sizeof(int32_t) * 2 * n_slot, hipMemcpyHostToDevice, e->stream));
   if (S > 0) HIP_TRY(hipMemcpyAsync(e->d_damb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_dgrid, rq->grid, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_dgrid + Q, rq->alpha, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, e->stream));
   const int32_t n_qblk = (Q + 63) / 64;
   const int64_t n_units = (int64_t)B * A * n_qblk;
-  HIP_TRY(hipEventRecord(e->dbev[0], e->stream));
+  if (int rc = e->dbev.record_start(e->stream)) return rc;
   if (n_units > 0) {
     if (C == 1) launch_ambient_dbl<1, 64>(e, C, A, Q, n_qblk, n_units);
     else if (C == 2) launch_ambient_dbl<2, 64>(e, C, A, Q, n_qblk, n_units);
@@ -9776,10 +9602,10 @@ extern "C" int dmx_engine_ambient_doublet(dmx_engine* e, const dmx_ambient_doubl
     else launch_ambient_dbl<8, 32>(e, C, A, Q, n_qblk, n_units);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipEventRecord(e->dbev[1], e->stream));
+  if (int rc = e->dbev.record_stop(e->stream)) return rc;
   HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return; cd is pageable host memory
   float ms = 0.f;
-  HIP_TRY(hipEventElapsedTime(&ms, e->dbev[0], e->dbev[1]));
+  if (int rc = e->dbev.elapsed_ms(&ms)) return rc;
   dmx_ambient_doublet_info& inf = e->adbl_info;
   std::memset(&inf, 0, sizeof inf);
   inf.kernel_ms = ms; inf.profile_bytes = (int64_t)prof; inf.n_used = n_used;
@@ -9859,29 +9685,26 @@ extern "C" int dmx_debug_log_rate(int32_t which, int32_t iters, int32_t device, 
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return set_error(DMX_ERR_NOGPU, "dmx_debug_log_rate: no such HIP device");
   HIP_TRY(hipSetDevice(device));
   const int blocks = 256 * 8, threads = 256;                  // 8 workgroups (32 wavefronts) per CU
-  double *dt = nullptr, *ds = nullptr;
-  HIP_TRY(hipMalloc((void**)&dt, sizeof(double) * DMX_LOG2_TABLE_DOUBLES));
-  HIP_TRY(hipMalloc((void**)&ds, sizeof(double) * (size_t)blocks * threads));
+  DevBuf<double> dt, ds;
+  if (int rc = dt.alloc(sizeof(double) * DMX_LOG2_TABLE_DOUBLES)) return rc;
+  if (int rc = ds.alloc(sizeof(double) * (size_t)blocks * threads)) return rc;
   if (which == 2) HIP_TRY(hipMemcpy(dt, dmx_log2_table_host, sizeof(double) * DMX_LOG2_TABLE_DOUBLES, hipMemcpyHostToDevice));
   else HIP_TRY(hipMemcpy(dt, dmx_log_table_host, sizeof(double) * DMX_LOG_TABLE_DOUBLES, hipMemcpyHostToDevice));
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+  EventPair ev;
   iters &= ~3;
   float best = 1e30f;
   for (int rep = 0; rep < 4; ++rep) {                          // first pass warms up; keep the fastest
-    HIP_TRY(hipEventRecord(e0, 0));
+    if (int rc = ev.record_start(0)) return rc;
     if (which == 0) hipLaunchKernelGGL((k_log_rate<0>), dim3(blocks), dim3(threads), 0, 0, iters, dt, ds);
     else if (which == 2) hipLaunchKernelGGL((k_log_rate<2>), dim3(blocks), dim3(threads), 0, 0, iters, dt, ds);
     else            hipLaunchKernelGGL((k_log_rate<1>), dim3(blocks), dim3(threads), 0, 0, iters, dt, ds);
-    HIP_TRY(hipEventRecord(e1, 0));
-    HIP_TRY(hipEventSynchronize(e1));
+    if (int rc = ev.record_stop(0)) return rc;
+    HIP_TRY(hipEventSynchronize(ev.stop));
     HIP_TRY(hipGetLastError());
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    if (int rc = ev.elapsed_ms(&ms)) return rc;
     if (rep > 0 && ms < best) best = ms;
   }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(dt); (void)hipFree(ds);
   *logs_per_second = (double)blocks * threads * iters / (best * 1e-3);
   return DMX_OK;
 }
@@ -9891,15 +9714,14 @@ extern "C" int dmx_debug_device_div(const double* a, const double* b, double* q,
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return set_error(DMX_ERR_NOGPU, "dmx_debug_device_div: no such HIP device");
   HIP_TRY(hipSetDevice(device));
-  double *da = nullptr, *db = nullptr, *dq = nullptr;
+  DevBuf<double> da, db, dq;
   const size_t bytes = std::max<size_t>(sizeof(double) * (size_t)n, 16);
-  HIP_TRY(hipMalloc((void**)&da, bytes)); HIP_TRY(hipMalloc((void**)&db, bytes)); HIP_TRY(hipMalloc((void**)&dq, bytes));
+  for (DevBuf<double>* d : {&da, &db, &dq}) if (int rc = d->alloc(bytes)) return rc;
   HIP_TRY(hipMemcpy(da, a, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(db, b, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_debug_div, dim3(1024), dim3(256), 0, 0, da, db, dq, n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(q, dq, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  (void)hipFree(da); (void)hipFree(db); (void)hipFree(dq);
   return DMX_OK;
 }
 
@@ -9909,10 +9731,10 @@ int debug_device_log(int which, const double* x, double* y, int64_t n, int32_t d
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return set_error(DMX_ERR_NOGPU, "dmx_debug_device_log: no such HIP device");
   HIP_TRY(hipSetDevice(device));
-  double *dx = nullptr, *dy = nullptr, *dt = nullptr;
-  HIP_TRY(hipMalloc((void**)&dx, std::max<size_t>(sizeof(double) * (size_t)n, 16)));
-  HIP_TRY(hipMalloc((void**)&dy, std::max<size_t>(sizeof(double) * (size_t)n, 16)));
-  HIP_TRY(hipMalloc((void**)&dt, sizeof(double) * DMX_LOG2_TABLE_DOUBLES));
+  DevBuf<double> dx, dy, dt;
+  if (int rc = dx.alloc(std::max<size_t>(sizeof(double) * (size_t)n, 16))) return rc;
+  if (int rc = dy.alloc(std::max<size_t>(sizeof(double) * (size_t)n, 16))) return rc;
+  if (int rc = dt.alloc(sizeof(double) * DMX_LOG2_TABLE_DOUBLES)) return rc;
   HIP_TRY(hipMemcpy(dx, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
   if (which == 4) HIP_TRY(hipMemcpy(dt, dmx_log32_table_host, sizeof(double) * DMX_LOG32_TABLE_DOUBLES, hipMemcpyHostToDevice));
   else if (which >= 2) HIP_TRY(hipMemcpy(dt, dmx_log2_table_host, sizeof(double) * DMX_LOG2_TABLE_DOUBLES, hipMemcpyHostToDevice));
@@ -9923,7 +9745,6 @@ int debug_device_log(int which, const double* x, double* y, int64_t n, int32_t d
   else hipLaunchKernelGGL((k_debug_log<0>), dim3(1024), dim3(256), 0, 0, dx, dy, n, dt);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(y, dy, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(dt);
   return DMX_OK;
 }
 }  // namespace
@@ -9938,7 +9759,7 @@ extern "C" int dmx_debug_device_log2_lite32(const double* x, double* y, int64_t 
 
 struct dmx_pair_text {
   int device = 0;
-  char* d_text = nullptr;
+  DevBuf<char> d_text;
   int64_t n_bytes = 0;
   std::vector<int64_t> cell_off;
   std::vector<uint8_t> cell_flag;
@@ -9948,7 +9769,7 @@ struct dmx_pair_text {
 
 extern "C" void dmx_pair_text_free(dmx_pair_text* t) {
   if (!t) return;
-  if (t->d_text) { (void)hipSetDevice(t->device); (void)hipFree(t->d_text); }
+  (void)hipSetDevice(t->device);
   delete t;
 }
 
@@ -10018,14 +9839,12 @@ extern "C" int dmx_engine_format_pair(dmx_engine* e, const dmx_pair_request* rq,
   std::vector<double> pow10(310);
   for (int n = 0; n < 310; ++n) { char b[16]; std::snprintf(b, sizeof b, "1e%d", n); pow10[(size_t)n] = std::strtod(b, nullptr); }   // correctly rounded
   // ---- device copies (small; per call)
-  struct Dev {
-    std::vector<void*> p;
-    ~Dev() { for (void* x : p) if (x) (void)hipFree(x); }
-  } dev;
+  std::deque<DevBuf<void>> dev;
   hipStream_t st = e->stream;
   auto up = [&](const void* src, size_t bytes, void** d) -> int {
-    HIP_TRY(hipMalloc(d, std::max<size_t>(bytes, 16)));
-    dev.p.push_back(*d);
+    dev.emplace_back();
+    if (int rc = dev.back().alloc(std::max<size_t>(bytes, 16))) return rc;
+    *d = dev.back();
     if (bytes && src) HIP_TRY(hipMemcpyAsync(*d, src, bytes, hipMemcpyHostToDevice, st));
     return DMX_OK;
   };
@@ -10056,12 +9875,10 @@ extern "C" int dmx_engine_format_pair(dmx_engine* e, const dmx_pair_request* rq,
   t->device = e->device;
   t->cell_off.assign((size_t)n_out + 1, 0);
   t->cell_flag.assign((size_t)n_out, 0);
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  HIP_TRY(hipEventCreate(&ev0)); HIP_TRY(hipEventCreate(&ev1));
-  struct Evs { hipEvent_t a, b; ~Evs() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } evs{ev0, ev1};
+  EventPair ev;
   if (n_out > 0) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&dmx_fmt::k_pair_write), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipEventRecord(ev0, st));
+    if (int rc = ev.record_start(st)) return rc;
     hipLaunchKernelGGL(dmx_fmt::k_pair_lengths, dim3((unsigned)n_out), dim3(dmx_fmt::kFmtThreads), 0, st, c);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(dmx_fmt::k_pair_scan, dim3(1), dim3(1024), 0, st, d_len, d_np, n_out, d_off, d_poff);
@@ -10073,17 +9890,17 @@ extern "C" int dmx_engine_format_pair(dmx_engine* e, const dmx_pair_request* rq,
     HIP_TRY(hipStreamSynchronize(st));
     t->n_bytes = t->cell_off[(size_t)n_out];
     t->patches.resize(n_patch);
-    HIP_TRY(hipMalloc((void**)&t->d_text, (size_t)std::max<int64_t>(t->n_bytes, 16)));
+    if (int rc = t->d_text.alloc((size_t)std::max<int64_t>(t->n_bytes, 16))) return rc;
     dmx_pair_patch* d_patch = nullptr;
     if (int rc = up(nullptr, sizeof(dmx_pair_patch) * (size_t)std::max<uint32_t>(n_patch, 1), (void**)&d_patch)) return rc;
     c.text = t->d_text; c.patches = d_patch;
     hipLaunchKernelGGL(dmx_fmt::k_pair_write, dim3((unsigned)n_out), dim3(dmx_fmt::kFmtThreads), lds, st, c);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev1, st));
+    if (int rc = ev.record_stop(st)) return rc;
     if (n_patch) HIP_TRY(hipMemcpyAsync(t->patches.data(), d_patch, sizeof(dmx_pair_patch) * n_patch, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    if (int rc = ev.elapsed_ms(&ms)) return rc;
     t->format_ms = ms;
   }
   *out = t.release();
@@ -10418,9 +10235,8 @@ extern "C" int dmx_demuxlet_run(const dmx_job* job) {
   // write(2) as it is; where the device left a POSTPRB field to the host (dmx_pair_patch: the denormal range, a digit next to a rounding boundary) the
   // field is computed here with the host libm — the expression of :780 / :792 on the barcode's K3 record — and spliced in; barcodes left to the host
   // formatter (cell_flag != 0) have their rows (pair_rows, from write_doublet_core) inserted at their place.
-  void* pair_stage = nullptr;
+  PinnedBuf pair_stage;
   constexpr int64_t kPairStage = (int64_t)32 << 20;
-  struct StageGuard { void** p; ~StageGuard() { if (*p) (void)hipHostFree(*p); } } stage_guard{&pair_stage};
   auto stream_pair = [&](Range& x, const std::vector<std::string>& pair_rows, bool append) -> int {
     dmx_pair_text_info pi{};
     if (int rc = dmx_pair_text_get_info(x.ptext, &pi)) return rc;
@@ -10428,8 +10244,8 @@ extern "C" int dmx_demuxlet_run(const dmx_job* job) {
     if (!f) return set_error(DMX_ERR_IO, "Cannot create %s.single, %s.pair files", job->out_prefix, job->out_prefix);     // :535-536
     struct Closer { FILE* f; ~Closer() { if (f) fclose(f); } } closer{f};
     if (!append) fputs("BARCODE\tSM1.ID\tSM2.ID\tLLK12\tPOSTPRB\n", f);                                               // :570
-    if (!pair_stage) HIP_TRY(hipHostMalloc(&pair_stage, (size_t)kPairStage, hipHostMallocDefault));
-    char* buf = (char*)pair_stage;
+    if (int rc = pair_stage.ensure((size_t)kPairStage)) return rc;
+    char* buf = (char*)pair_stage.get();
     int64_t wbeg = 0, wend = 0;                  // the piece of the text the buffer holds
     bool ok = true;
     auto put = [&](int64_t a, int64_t b) -> int {     // text bytes [a, b)

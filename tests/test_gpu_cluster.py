@@ -262,6 +262,51 @@ def test_no_interference(m):
         assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
 
 
+def test_buffers_grow_then_serve_a_smaller_pileup(m):
+    """One engine stages 64, then 300, then 64 barcodes again: its device buffers grow for the second round and are reused below their
+    capacity in the third.  Every round equals, bit for bit, the same calls on a fresh engine — once through the clustering calls, once
+    through ambient_profile (whose out-of-memory check reads the profile buffer's capacity)."""
+    eng = m["engine"]
+    rng = np.random.default_rng(31)
+    S, R, K = 200, 2, 3
+    V = R * K
+    raw = m["synth"].make_raw_genotypes(rng, S, V)
+    g = np.stack([eng.geno_from_gt(raw.alleles[s], 0.01) for s in range(S)])
+    pls = {B: host_pileup(m, m["synth"].make_pileup(rng, raw.alleles, B, 0.2, 1.5, dense_layout=False, doublet_rate=0.1)) for B in (64, 300)}
+    q = m["cluster"].hwe_prior(np.zeros(S), np.zeros(S))
+    log_pi = np.full((R, K), -np.log(K))
+    assign = {B: rng.integers(-1, V, B).astype(np.int32) for B in pls}
+    soup, grid = rng.random(S), np.array([0.0, 0.1, 0.3])
+
+    def cluster_round(e, B):
+        e.set_pileup(pls[B]); e.cluster_stage(); e.run_singlet()
+        return [*e.get_singlet(), *e.cluster_estep(R, K, log_pi), *e.cluster_mstep(None, q)]
+
+    def ambient_round(e, B):
+        e.set_pileup(pls[B])
+        return list(e.ambient_profile(assign[B], soup, grid))
+
+    for one_round in (cluster_round, ambient_round):
+        fresh = {}
+        for B in pls:
+            e = eng.Engine(V, (0.0, 0.5), 0.5)
+            try:
+                e.set_genotypes(g)
+                fresh[B] = one_round(e, B)
+            finally:
+                e.close()
+        e = eng.Engine(V, (0.0, 0.5), 0.5)
+        try:
+            e.set_genotypes(g)
+            for B in (64, 300, 64):
+                got = one_round(e, B)
+                assert len(got) == len(fresh[B])
+                for x, y in zip(got, fresh[B]):
+                    assert x.shape == y.shape and np.array_equal(x.view(np.uint8), y.view(np.uint8)), (one_round.__name__, B)
+        finally:
+            e.close()
+
+
 def synth_case(m, K, seed, B=4000, S=10000, delta=0.1, rbar=1.25):
     rng = np.random.default_rng(seed)
     raw, sp = make_sp(m, rng, S, K, B, delta, rbar)
