@@ -12,11 +12,10 @@ import numpy as np
 import pytest
 
 from golden_util import printed_mask
-from quality_mix import genotypes, host_pileup, mixed_depth_pileup, oracle_run
+from quality_mix import A2, FAMILIES, family_problem, genotypes, host_pileup, mixed_depth_pileup, oracle_run
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
-A2, A3 = (0.0, 0.5), (0.0, 0.25, 0.5)
 SWITCHES = ("DMX_K1_CANP", "DMX_A2_NO_SYMU", "DMX_A2_SYM", "DMX_NO_ANF", "DMX_K2_GENERIC", "DMX_FINALS_ANY_DEPTH", "DMX_SYM_NO_FINALS",
             "DMX_A2_NO_FINALS", "DMX_SYM_NO_SEEDS", "DMX_A2_NO_SEEDS", "DMX_CERTIFY_NO_FINALS", "DMX_CERTIFY_NO_SEEDS", "DMX_NO_CLASSES",
             "DMX_K1_NO_CANP", "DMX_K1_NO_LEAN", "DMX_K1_NO_OWN")
@@ -62,48 +61,6 @@ def max_diffs(out, ref, alphas, mode):
              grid=np.abs(out["grid"] - ref.llksAB)[mask].max() if mask.any() else 0.0,
              l00=np.abs(out["l00"][proc] - ref.llks00[proc]).max() if proc.any() else 0.0)
     return d
-
-
-# (case id, field, V, alphas, mode, switches, K1 name prefix, K2 name prefix, dense, u16 pairs).  Which V / field / switch picks a family:
-# launch_singlet and launch_doublet in dmx_engine.hip.  k_singlet_can(p) need one-byte read counts, so their cases have no u16 pairs.
-FAMILIES = [
-    # K1
-    ("k1_singlet", "GP", 8, A2, "strict", {}, "k_singlet<", "k_doublet_a2<", False, 3),
-    ("k1_singlet_own", "GP", 16, A2, "strict", {}, "k_singlet_own<", "k_doublet_a2u16", False, 3),
-    ("k1_singlet_cls", "GT", 18, A2, "strict", {}, "k_singlet_cls<", "k_doublet_cls<", False, 3),
-    ("k1_singlet_can", "GT", 8, A2, "strict", {}, "k_singlet_can<", "k_doublet_cls<", False, 0),
-    ("k1_singlet_canp", "GT", 8, A2, "strict", {"DMX_K1_CANP": "1"}, "k_singlet_canp<", "k_doublet_cls<", True, 0),
-    ("k1_singlet_clsw", "GT", 40, A2, "strict", {}, "k_singlet_clsw<", "k_doublet_clsp<", False, 3),
-    ("k1_wide_v129_gp", "GP", 129, A2, "strict", {}, "k_singlet<", "k_doublet_a2<", False, 2),
-    ("k1_wide_v129_gt", "GT", 129, A2, "strict", {}, "k_singlet_clsw<", "k_doublet_cls<", False, 2),
-    # K2
-    ("k2_cls_v24", "GT", 24, A2, "strict", {}, "k_singlet_clsw<", "k_doublet_cls<", False, 3),
-    ("k2_clsp_fast", "GT", 40, A2, "fast", {}, "k_singlet_clsw<", "k_doublet_clsp<", False, 3),
-    ("k2_clsym", "GT", 8, A2, "fast", {}, "k_singlet_cls<", "k_doublet_clsym<", False, 3),
-    ("k2_clsym_v24", "GT", 24, A2, "fast", {}, "k_singlet_clsw<", "k_doublet_clsym<", False, 3),
-    ("k2_clsn", "GT", 16, A3, "strict", {}, "k_singlet_cls<", "k_doublet_clsn<", False, 3),
-    ("k2_a2u16", "GP", 16, A2, "strict", {}, "k_singlet_own<", "k_doublet_a2u16", False, 3),
-    ("k2_a2u", "GP", 32, A2, "strict", {}, "k_singlet_own<", "k_doublet_a2u<", False, 3),
-    ("k2_a2", "GP", 32, A2, "strict", {"DMX_A2_NO_SYMU": "1"}, "k_singlet_own<", "k_doublet_a2<", True, 0),
-    ("k2_a2s", "GP", 32, A2, "strict", {"DMX_A2_SYM": "1"}, "k_singlet_own<", "k_doublet_a2s<", False, 3),
-    ("k2_sym_v8", "GP", 8, A2, "fast", {}, "k_singlet<", "k_doublet_sym<", False, 3),
-    ("k2_sym_v32", "PL", 32, A2, "fast", {}, "k_singlet_own<", "k_doublet_sym<", True, 0),
-    ("k2_an", "PL", 16, A3, "strict", {}, "k_singlet_own<", "k_doublet_an<", False, 3),
-    ("k2_anf", "GP", 16, A3, "fast", {}, "k_singlet_own<", "k_doublet_anf<", False, 3),
-    ("k2_a2f", "GP", 16, (0.0, 0.25), "fast", {"DMX_NO_ANF": "1"}, "k_singlet_own<", "k_doublet_a2f<", False, 3),
-    ("k2_generic", "GP", 8, A2, "strict", {"DMX_K2_GENERIC": "1"}, "k_singlet<", "k_doublet_generic<", False, 3),
-]
-
-
-def family_problem(eng, case, field, V, dense, deep, quals):
-    from demuxlet_amd import synth
-    seed = 31000 + 7 * V + sum(map(ord, case)) + {"full": 0, "edges": 1, "max": 2}[quals]
-    rng = np.random.default_rng(seed)
-    S, B = (131, 11) if dense else ((220, 12) if V > 64 else (300, 24))
-    raw = synth.make_raw_genotypes(rng, S, V)
-    g = genotypes(eng, rng, raw.alleles, field)
-    sp = mixed_depth_pileup(rng, raw.alleles, B, 0.3, quals=quals, dense=dense, deep=deep)
-    return g, sp
 
 
 @pytest.mark.parametrize("quals", ["full", "edges", "max"])
