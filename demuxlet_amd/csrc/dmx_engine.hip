@@ -157,34 +157,35 @@ __device__ __forceinline__ GlSeed gl_seed(const double* __restrict__ tabs, uint3
   sd.r0 = n < 2 ? n : (three ? 3u : (two ? 2u : 1u));
   return sd;
 }
-// reads beyond the tables: continue the reference's loop from read r0, then the +1e-6 renormalisation
+// reads beyond a table's state (g0, g1, g2 after the pair's first r0 reads): continue the reference's loop from read r0, then the +1e-6 renormalisation
+__device__ __forceinline__ void gl_continue(uint32_t r0, uint32_t n, uint32_t rd4, const uint8_t* __restrict__ reads, int64_t off,
+                                            const double* __restrict__ lut, double& g0, double& g1, double& g2) {
+  const bool safe = n <= kSafeReads;
+  for (uint32_t r = r0; r < n; ++r) {
+    const uint32_t byte = (r < 4) ? ((rd4 >> (8 * r)) & 0xFFu) : (uint32_t)reads[off + r];
+    const uint32_t bq = byte & 127u;
+    const bool alt = (byte >> 7) != 0;
+    const double m = lut[bq], e3 = lut[128 + bq], h = lut[256 + bq];
+    g0 *= alt ? e3 : m;                                                      // :437
+    g1 *= h;                                                                 // :438
+    g2 *= alt ? m : e3;                                                      // :439
+    const double tmp = g0 + g1 + g2;                                         // :440
+    if (safe) {
+      const double y = rcp_refined(tmp);
+      g0 = div_by(g0, tmp, y); g1 = div_by(g1, tmp, y); g2 = div_by(g2, tmp, y);   // :441-443
+    } else {
+      g0 /= tmp; g1 /= tmp; g2 /= tmp;
+    }
+  }
+  g0 += 1e-6; g1 += 1e-6; g2 += 1e-6;                                        // :446-448
+  const double tmp = g0 + g1 + g2;
+  const double y = rcp_refined(tmp);
+  g0 = div_by(g0, tmp, y); g1 = div_by(g1, tmp, y); g2 = div_by(g2, tmp, y);         // :449-452
+}
 __device__ __forceinline__ void gl_finish(const GlSeed& sd, uint32_t n, uint32_t rd4, const uint8_t* __restrict__ reads, int64_t off,
                                           const double* __restrict__ lut, double& G0, double& G1, double& G2) {
   G0 = sd.g0; G1 = sd.g1; G2 = sd.g2;
-  if (sd.r0 < n) {
-    double g0_ = G0, g1_ = G1, g2_ = G2;
-    const bool safe = n <= kSafeReads;
-    for (uint32_t r = sd.r0; r < n; ++r) {
-      const uint32_t byte = (r < 4) ? ((rd4 >> (8 * r)) & 0xFFu) : (uint32_t)reads[off + r];
-      const uint32_t bq = byte & 127u;
-      const bool alt = (byte >> 7) != 0;
-      const double m = lut[bq], e3 = lut[128 + bq], h = lut[256 + bq];
-      g0_ *= alt ? e3 : m;                                                   // :437
-      g1_ *= h;                                                              // :438
-      g2_ *= alt ? m : e3;                                                   // :439
-      const double tmp = g0_ + g1_ + g2_;                                    // :440
-      if (safe) {
-        const double y = rcp_refined(tmp);
-        g0_ = div_by(g0_, tmp, y); g1_ = div_by(g1_, tmp, y); g2_ = div_by(g2_, tmp, y);   // :441-443
-      } else {
-        g0_ /= tmp; g1_ /= tmp; g2_ /= tmp;
-      }
-    }
-    g0_ += 1e-6; g1_ += 1e-6; g2_ += 1e-6;                                   // :446-448
-    const double tmp = g0_ + g1_ + g2_;
-    const double y = rcp_refined(tmp);
-    G0 = div_by(g0_, tmp, y); G1 = div_by(g1_, tmp, y); G2 = div_by(g2_, tmp, y);          // :449-452
-  }
+  if (sd.r0 < n) gl_continue(sd.r0, n, rd4, reads, off, lut, G0, G1, G2);
 }
 
 
@@ -412,12 +413,35 @@ __global__ void k_build_certify_finals(const double* __restrict__ tabs, double* 
 // at 1.25 reads per pair it used to run max(cnt) ~ 2.6 times per tile of 32 pairs with most lanes idle, now 0.6 times.
 constexpr int kCSeedStride = 6;                  // doubles per (entry, alpha lane): five values + pad (16-byte aligned loads)
 constexpr int64_t kCSeedN = 256 + 128 * 128;
-template <int NV, bool HAND = true>            // HAND: k_certify's hand-over at the end (both lanes of a pair leave with the alpha = 0.5 lane's values); false: each lane keeps its own
-__device__ __forceinline__ void certify_pair_values(const PileupView& pv, uint32_t cnt, int64_t off, uint32_t rd4, const double* s_tab,
-                                                    const double (&wA)[NV], const double (&wR)[NV], int n1, double (&v)[NV],
-                                                    const double* __restrict__ cseed = nullptr) {
-  double pG[NV];
+// One maximum across the AW lanes that hold the alphas of one pair (AW = 2: the neighbour by DPP; 4, 8: a butterfly; 0: a butterfly of run-time width aw).
+template <int AW>
+__device__ __forceinline__ double alpha_group_max(double mx, int aw = AW) {
+  if constexpr (AW == 2) {
+    const double o = shfl_xor1(mx);
+    return fmax(mx, o);
+  } else if constexpr (AW == 0) {
+    for (int d = 1; d < aw; d <<= 1) { const double o = __shfl_xor(mx, d); mx = fmax(mx, o); }
+    return mx;
+  } else {
 #pragma unroll
+    for (int d = 1; d < AW; d <<= 1) { const double o = __shfl_xor(mx, d); mx = fmax(mx, o); }
+    return mx;
+  }
+}
+// Phase 1 of every doublet kernel and of k_certify for one (pair, alpha) lane, up to the last division: pG after the read loop of :597-639 and the
+// +1e-6 of :649, and (returned) the maximum of :650-655 across the pair's AW alpha lanes.  Callers that fuse the final division into their gp00 loop
+// take these; the others call certify_pair_values.
+//   AW    lanes of the max (alpha_group_max); n_ok = false marks a padding alpha of a grid narrower than AW: it skips the update but takes part in the shuffles
+//   DIVI  the plain division of a pair deeper than kSafeReads inline (`/`) instead of through div_slow: both are the IEEE division, same bits — the
+//         nine-value STRICT kernels were tuned with the inline form and the five-value FAST ones with the call, and each keeps its registers that way
+//   RD4   the first four reads come from rd4 (load_rd4); false: every read is loaded from pv.reads (the alpha-grid kernels, whose lanes hold no rd4)
+//   W     the mixing weights of :613 (wA: p, wR: 1 - p): register arrays, or pointers into LDS (k_doublet_clsp keeps them there)
+template <int NV, int AW = 2, bool DIVI = false, bool RD4 = true, class W>
+__device__ __forceinline__ double pair_values_open(const PileupView& pv, uint32_t cnt, int64_t off, uint32_t rd4, const double* s_tab,
+                                                   const W& wA, const W& wR, int n1, double (&out)[NV],
+                                                   const double* __restrict__ cseed = nullptr, bool n_ok = true, int aw = AW) {
+  double pG[NV];                                                          // (a local, copied out at the end: worked on through `out` the callers' kernels
+#pragma unroll                                                            //  take other registers — the array is then promoted element by element, not as a vector)
   for (int i = 0; i < NV; ++i) pG[i] = 1.0;                               // :597
   uint32_t r_start = 0;
   if (NV == 5 && cseed) {
@@ -435,8 +459,10 @@ __device__ __forceinline__ void certify_pair_values(const PileupView& pv, uint32
   uint32_t r = 0;
   if (NV == 5 && cseed) r = __any(r_start == 0 && cnt > 0) ? 0u : (__any(r_start <= 1 && cnt > 1) ? 1u : 2u);
   for (; __any(r < cnt); ++r) {
-    const bool live = r >= r_start && r < cnt;
-    const uint32_t byte = live ? (r < 4 ? (rd4 >> (8 * r)) & 0xFFu : (uint32_t)pv.reads[off + r]) : 0u;
+    const bool has = r >= r_start && r < cnt, live = has && n_ok;
+    uint32_t byte;
+    if constexpr (RD4) byte = live ? (r < 4 ? (rd4 >> (8 * r)) & 0xFFu : (uint32_t)pv.reads[off + r]) : 0u;
+    else byte = has ? pv.reads[off + r] : 0u;
     const uint32_t bq = byte & 127u;
     const bool alt = (byte >> 7) != 0;
     const double pR = alt ? s_tab[128 + bq] : s_tab[bq];                // :606
@@ -449,10 +475,7 @@ __device__ __forceinline__ void certify_pair_values(const PileupView& pv, uint32
         mx = fmax(mx, pG[i]);                                 // :626-627
       }
     }
-    {
-      const double o = shfl_xor1(mx);                               // one max across both alphas of the pair
-      mx = fmax(mx, o);
-    }
+    mx = alpha_group_max<AW>(mx, aw);                                   // one max across all alphas of the pair
     if (live) {
       if (cnt <= kSafeReads) {
         const double y = rcp_refined(mx);
@@ -460,22 +483,32 @@ __device__ __forceinline__ void certify_pair_values(const PileupView& pv, uint32
         for (int i = 0; i < NV; ++i) pG[i] = div_by(pG[i], mx, y);      // :632-639
       } else {
 #pragma unroll
-        for (int i = 0; i < NV; ++i) pG[i] = div_slow(pG[i], mx);
+        for (int i = 0; i < NV; ++i) pG[i] = DIVI ? pG[i] / mx : div_slow(pG[i], mx);
       }
     }
   }
   double mx = 0.0;
+  if (n_ok) {
 #pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    pG[i] += 1e-6;                                                       // :649
-    mx = fmax(mx, pG[i]);
+    for (int i = 0; i < NV; ++i) {
+      pG[i] += 1e-6;                                                     // :649
+      mx = fmax(mx, pG[i]);
+    }
   }
-  {
-    const double o = shfl_xor1(mx);
-    mx = fmax(mx, o);
-  }
-  // the alpha = 0.5 lane finishes its values (:656-663) and hands a copy to its alpha = 0 neighbour (which only had to contribute
-  // to the shared maxima): the two lanes of a pair then take one accumulator each
+#pragma unroll
+  for (int i = 0; i < NV; ++i) out[i] = pG[i];
+  (void)n1;
+  return alpha_group_max<AW>(mx, aw);
+}
+// ... and finished (:656-663; numerators >= 1e-6, the maximum in [1e-6, 1 + 1e-6]).  HAND: k_certify's hand-over at the end — the alpha = 0.5 lane hands a
+// copy of its values to its alpha = 0 neighbour (which only had to contribute to the shared maxima), and the two lanes of a pair then take one
+// accumulator each; false: each lane keeps its own.
+template <int NV, bool HAND = true, int AW = 2, bool DIVI = false>
+__device__ __forceinline__ void certify_pair_values(const PileupView& pv, uint32_t cnt, int64_t off, uint32_t rd4, const double* s_tab,
+                                                    const double (&wA)[NV], const double (&wR)[NV], int n1, double (&v)[NV],
+                                                    const double* __restrict__ cseed = nullptr) {
+  double pG[NV];
+  const double mx = pair_values_open<NV, AW, DIVI>(pv, cnt, off, rd4, s_tab, wA, wR, n1, pG, cseed);
   const double y = rcp_refined(mx);
 #pragma unroll
   for (int i = 0; i < NV; ++i) v[i] = div_by(pG[i], mx, y);
@@ -483,9 +516,60 @@ __device__ __forceinline__ void certify_pair_values(const PileupView& pv, uint32
 #pragma unroll
     for (int i = 0; i < NV; ++i) v[i] = shfl_odd(v[i]);   // (the alpha = 0.5 lane is the odd one: n1 == lane & 1)
   }
-  (void)n1;
 }
 
+// The pair headers of one tile of TP covered pairs -> LDS, by the first TP lanes of the cell (tid): read count n, first read byte (a segmented
+// scan of the counts from rd_base) and SNP id sn.  The barrier and the rd_base update (s_off[tp - 1] + s_cnt[tp - 1], by every lane) stay with the caller.
+template <int TP>
+__device__ __forceinline__ void publish_tile_headers(uint32_t n, int32_t sn, int tid, int64_t rd_base, uint32_t* s_cnt, int64_t* s_off, int32_t* s_snp) {
+  const uint32_t incl = seg_scan_incl<TP>(n);
+  s_cnt[tid] = n;
+  s_off[tid] = rd_base + (int64_t)(incl - n);
+  s_snp[tid] = sn;
+}
+// ... loaded here (the kernels that prefetch a tile's header while the one before it is computed publish what they hold in registers)
+template <int TP>
+__device__ __forceinline__ void load_tile_headers(const PileupView& pv, int nrd_width, int64_t p_beg, int64_t tbase, int tp, int tid, int64_t rd_base,
+                                                  uint32_t* s_cnt, int64_t* s_off, int32_t* s_snp) {
+  if (tid < TP) {
+    const bool v = tid < tp;
+    const uint32_t n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
+    const int32_t sn = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
+    publish_tile_headers<TP>(n, sn, tid, rd_base, s_cnt, s_off, s_snp);
+  }
+}
+// The genotype rows of the tile's SNPs -> LDS as G (float32 as stored, or widened to binary64), coalesced along the row, by the cell's TPC threads.
+template <int TPC, typename G>
+__device__ __forceinline__ void stage_geno_rows(const float* __restrict__ g, const int32_t* s_snp, int tp, int tid, int row_len, int GS, G* s_g) {
+  int r = tid % row_len, ti = tid / row_len;
+  const int dr = TPC % row_len, dt = TPC / row_len;
+  while (ti < tp) {
+    s_g[ti * GS + r] = (G)g[(size_t)s_snp[ti] * row_len + r];
+    r += dr; ti += dt;
+    if (r >= row_len) { r -= row_len; ++ti; }
+  }
+}
+// The llks00 term of one (pair, alpha) lane: the sum of the pair's nine phase-1 values value(l, m) weighted by gp00 = gp0s[l] gp0s[m] (qq: the SNP's
+// gp0s; :555), in the reference's l-major order (:702-705), and the log term of :708-709 -> *t00.  Returns whether the sum was a normal positive
+// number (the fast log's domain; k_doublet_a2s ignores it).  value() is called once per (l, m), in order: the kernels finish (div_by) and store
+// their pG in it.
+template <class F>
+__device__ __forceinline__ bool llks00_term(const double (&qq)[3], F&& value, const double* s_log, double* t00) {
+  double sum = 0.0;
+#pragma unroll
+  for (int l = 0; l < 3; ++l)
+#pragma unroll
+    for (int m = 0; m < 3; ++m) sum += ((qq[l] * qq[m]) * value(l, m));
+  *t00 = dmx_log2_fast(sum, s_log);
+  return __builtin_amdgcn_class(sum, 0x100);
+}
+template <class F>
+__device__ __forceinline__ bool llks00_term(const double* __restrict__ gp0, int32_t snp, F&& value, const double* s_log, double* t00) {
+  const double* g0 = gp0 + (size_t)snp * 3;
+  const double q0 = g0[0], q1 = g0[1], q2 = g0[2];
+  const double qq[3] = {q0, q1, q2};
+  return llks00_term(qq, value, s_log, t00);
+}
 // The seeds of certify_pair_values<5>: one thread per read code (256 one-read codes, then 128 x 128 two-read codes of base quality < 64) runs the
 // loop of :597-639 for BOTH alpha lanes (0 and 0.5: the maximum of :626-627 runs across them) — the same operations on the same operands as the
 // two lanes of k_certify, hence the same bits.
@@ -659,28 +743,8 @@ __global__ __launch_bounds__(kThreads, 4) void k_singlet(PileupView pv, int nrd_
       G0 = f[0]; G1 = f[1]; G2 = f[2];
       if (n >= 2 && !(ablate & 1)) {
         const double* f1 = s_first + 3 * b0;
-        double g0 = f1[0], g1 = f1[1], g2 = f1[2];
-        const bool safe = n <= kSafeReads;
-        for (uint32_t r = 1; r < n; ++r) {
-          const uint32_t byte = (r < 4) ? ((cur.rd4 >> (8 * r)) & 0xFFu) : (uint32_t)pv.reads[cur.off + r];
-          const uint32_t bq = byte & 127u;
-          const bool alt = (byte >> 7) != 0;
-          const double m = s_tab[bq], e3 = s_tab[128 + bq], h = s_tab[256 + bq];
-          g0 *= alt ? e3 : m;                                                // :437
-          g1 *= h;                                                           // :438
-          g2 *= alt ? m : e3;                                                // :439
-          const double tmp = g0 + g1 + g2;                                   // :440
-          if (safe) {
-            const double y = rcp_refined(tmp);
-            g0 = div_by(g0, tmp, y); g1 = div_by(g1, tmp, y); g2 = div_by(g2, tmp, y);   // :441-443
-          } else {
-            g0 /= tmp; g1 /= tmp; g2 /= tmp;
-          }
-        }
-        g0 += 1e-6; g1 += 1e-6; g2 += 1e-6;                                  // :446-448
-        const double tmp = g0 + g1 + g2;
-        const double y = rcp_refined(tmp);
-        G0 = div_by(g0, tmp, y); G1 = div_by(g1, tmp, y); G2 = div_by(g2, tmp, y);       // :449-452
+        G0 = f1[0]; G1 = f1[1]; G2 = f1[2];
+        gl_continue(1u, n, cur.rd4, pv.reads, cur.off, s_tab, G0, G1, G2);
       }
     }
     // dense: uniform plane base per row element + this lane's SNP index (scalar base, 32-bit lane offset, no per-load
@@ -868,28 +932,8 @@ __global__ __launch_bounds__(kThreads, 5) void k_singlet_own(PileupView pv, int 
       G0 = f[0]; G1 = f[1]; G2 = f[2];
       if (n >= 2) {
         const double* f1 = s_first + 3 * b0;
-        double g0 = f1[0], g1 = f1[1], g2 = f1[2];
-        const bool safe = n <= kSafeReads;
-        for (uint32_t r = 1; r < n; ++r) {
-          const uint32_t byte = (r < 4) ? ((cur.rd4 >> (8 * r)) & 0xFFu) : (uint32_t)pv.reads[cur.off + r];
-          const uint32_t bq = byte & 127u;
-          const bool alt = (byte >> 7) != 0;
-          const double m = s_tab[bq], e3 = s_tab[128 + bq], h = s_tab[256 + bq];
-          g0 *= alt ? e3 : m;                                                // :437
-          g1 *= h;                                                           // :438
-          g2 *= alt ? m : e3;                                                // :439
-          const double tmp = g0 + g1 + g2;                                   // :440
-          if (safe) {
-            const double y = rcp_refined(tmp);
-            g0 = div_by(g0, tmp, y); g1 = div_by(g1, tmp, y); g2 = div_by(g2, tmp, y);   // :441-443
-          } else {
-            g0 /= tmp; g1 /= tmp; g2 /= tmp;
-          }
-        }
-        g0 += 1e-6; g1 += 1e-6; g2 += 1e-6;                                  // :446-448
-        const double tmp = g0 + g1 + g2;
-        const double y = rcp_refined(tmp);
-        G0 = div_by(g0, tmp, y); G1 = div_by(g1, tmp, y); G2 = div_by(g2, tmp, y);       // :449-452
+        G0 = f1[0]; G1 = f1[1]; G2 = f1[2];
+        gl_continue(1u, n, cur.rd4, pv.reads, cur.off, s_tab, G0, G1, G2);
       }
     }
     {
@@ -1800,28 +1844,8 @@ __global__ __launch_bounds__(kThreads, MINW) void k_singlet_clsw(PileupView pv, 
       G0 = f[0]; G1 = f[1]; G2 = f[2];
       if (n >= 2) {
         const double* f1 = s_first + 3 * b0;
-        double g0_ = f1[0], g1_ = f1[1], g2_ = f1[2];
-        const bool safe = n <= kSafeReads;
-        for (uint32_t r = 1; r < n; ++r) {
-          const uint32_t byte = (r < 4) ? ((cur.rd4 >> (8 * r)) & 0xFFu) : (uint32_t)pv.reads[cur.off + r];
-          const uint32_t bq = byte & 127u;
-          const bool alt = (byte >> 7) != 0;
-          const double m = s_tab[bq], e3 = s_tab[128 + bq], h = s_tab[256 + bq];
-          g0_ *= alt ? e3 : m;
-          g1_ *= h;
-          g2_ *= alt ? m : e3;
-          const double tmp = g0_ + g1_ + g2_;
-          if (safe) {
-            const double y = rcp_refined(tmp);
-            g0_ = div_by(g0_, tmp, y); g1_ = div_by(g1_, tmp, y); g2_ = div_by(g2_, tmp, y);
-          } else {
-            g0_ /= tmp; g1_ /= tmp; g2_ /= tmp;
-          }
-        }
-        g0_ += 1e-6; g1_ += 1e-6; g2_ += 1e-6;
-        const double tmp = g0_ + g1_ + g2_;
-        const double y = rcp_refined(tmp);
-        G0 = div_by(g0_, tmp, y); G1 = div_by(g1_, tmp, y); G2 = div_by(g2_, tmp, y);
+        G0 = f1[0]; G1 = f1[1]; G2 = f1[2];
+        gl_continue(1u, n, cur.rd4, pv.reads, cur.off, s_tab, G0, G1, G2);
       }
     }
     if (valid) {
@@ -3023,50 +3047,7 @@ __global__ __launch_bounds__(kThreads) void k_doublet_generic(PileupView pv, con
       const int64_t off = on ? s_off[ti1] : 0;
       const uint32_t rd4 = load_rd4(pv, off, cnt);       // the first four read bytes in one load (one dependent latency instead of four)
       double pG[9];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) pG[i] = 1.0;                              // :597
-      for (uint32_t r = 0; __any(r < cnt); ++r) {
-        const bool live = r < cnt;
-        const uint32_t byte = live ? (r < 4 ? (rd4 >> (8 * r)) & 0xFFu : (uint32_t)pv.reads[off + r]) : 0u;
-        const uint32_t bq = byte & 127u;
-        const bool alt = (byte >> 7) != 0;
-        const double pR = alt ? s_lut[128 + bq] : s_lut[bq];               // :606
-        const double pA = alt ? s_lut[bq] : s_lut[128 + bq];               // :607
-        double mx = 0.0;
-        if (live) {
-#pragma unroll
-          for (int i = 0; i < 9; ++i) {
-            pG[i] *= (pR * wR[i] + pA * wA[i]);                            // :625
-            mx = fmax(mx, pG[i]);                                // :626-627
-          }
-        }
-        for (int d = 1; d < A_pad; d <<= 1) {                              // one max across ALL alphas of the pair
-          const double o = __shfl_xor(mx, d);
-          mx = fmax(mx, o);
-        }
-        if (live) {
-          if (cnt <= kSafeReads) {
-            const double y = rcp_refined(mx);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] = div_by(pG[i], mx, y);      // :632-639
-          } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] /= mx;
-          }
-        }
-      }
-      double mx = 0.0;
-      if (on) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-          pG[i] += 1e-6;                                                    // :649
-          mx = fmax(mx, pG[i]);
-        }
-      }
-      for (int d = 1; d < A_pad; d <<= 1) {
-        const double o = __shfl_xor(mx, d);
-        mx = fmax(mx, o);
-      }
+      const double mx = pair_values_open<9, 0, true>(pv, cnt, off, rd4, s_lut, wA, wR, n1, pG, nullptr, on, A_pad);
       if (on) {
         const double y = rcp_refined(mx);                                   // numerators >= 1e-6, mx in [1e-6, 1+1e-6]
 #pragma unroll
@@ -3218,26 +3199,11 @@ __device__ __forceinline__ void a2_body(PileupView pv, int nrd_width, const floa
   for (int64_t tbase = 0; tbase < np; tbase += TP) {
     const int tp = (int)min((int64_t)TP, np - tbase);
     // ---- headers of the tile's pairs (first 32 lanes of the cell)
-    if (tid < TP) {
-      const bool v = tid < tp;
-      const uint32_t n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
-      const uint32_t incl = seg_scan_incl<TP>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
-    }
+    load_tile_headers<TP>(pv, nrd_width, p_beg, tbase, tp, tid, rd_base, s_cnt, s_off, s_snp);
     DMX_K2_SYNC();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
     // ---- genotype rows -> LDS (coalesced along the row)
-    {
-      int r = tid % row_len, ti = tid / row_len;
-      const int dr = TPC % row_len, dt = TPC / row_len;
-      while (ti < tp) {
-        s_g[ti * GS + r] = (g_t)g[(size_t)s_snp[ti] * row_len + r];
-        r += dr; ti += dt;
-        if (r >= row_len) { r -= row_len; ++ti; }
-      }
-    }
+    stage_geno_rows<TPC>(g, s_snp, tp, tid, row_len, GS, s_g);
     // ---- phase 1
     if (tid < 2 * TP) {
       const bool on = ti1 < tp;
@@ -3273,71 +3239,14 @@ __device__ __forceinline__ void a2_body(PileupView pv, int nrd_width, const floa
 #pragma unroll
           for (int m = 0; m < 3; ++m) vf[l * 3 + m] = n1 ? q5[l + m] : q5[l];
       } else {
-      double pG[9], wA[9], wR[9];
+        double wA[9], wR[9];
 #pragma unroll
-      for (int i = 0; i < 9; ++i) { pG[i] = 1.0; wA[i] = s_w[n1][i]; wR[i] = s_w[n1][9 + i]; }   // :597
-      for (uint32_t r = 0; __any(r < cnt); ++r) {
-        const bool live = r < cnt;
-        const uint32_t byte = live ? (r < 4 ? (rd4 >> (8 * r)) & 0xFFu : (uint32_t)pv.reads[off + r]) : 0u;
-        const uint32_t bq = byte & 127u;
-        const bool alt = (byte >> 7) != 0;
-        const double pR = alt ? s_tab[128 + bq] : s_tab[bq];                // :606
-        const double pA = alt ? s_tab[bq] : s_tab[128 + bq];                // :607
-        double mx = 0.0;
-        if (live) {
-#pragma unroll
-          for (int i = 0; i < 9; ++i) {
-            pG[i] *= (pR * wR[i] + pA * wA[i]);                             // :625
-            mx = fmax(mx, pG[i]);                                 // :626-627
-          }
-        }
-        {
-          const double o = shfl_xor1(mx);                               // one max across both alphas of the pair
-          mx = fmax(mx, o);
-        }
-        if (live) {
-          if (cnt <= kSafeReads) {
-            const double y = rcp_refined(mx);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] = div_by(pG[i], mx, y);       // :632-639
-          } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] /= mx;
-          }
-        }
+        for (int i = 0; i < 9; ++i) { wA[i] = s_w[n1][i]; wR[i] = s_w[n1][9 + i]; }
+        certify_pair_values<9, false, 2, true>(pv, cnt, off, rd4, s_tab, wA, wR, n1, vf);
       }
-      double mx = 0.0;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        pG[i] += 1e-6;                                                       // :649
-        mx = fmax(mx, pG[i]);
-      }
-      {
-        const double o = shfl_xor1(mx);
-        mx = fmax(mx, o);
-      }
-      {
-        const double y = rcp_refined(mx);                                    // numerators >= 1e-6, mx in [1e-6, 1+1e-6]
-#pragma unroll
-        for (int i = 0; i < 9; ++i) vf[i] = div_by(pG[i], mx, y);            // :656-663
-      }
-      }
-      if (on) {
-        const double* g0 = gp0 + (size_t)s_snp[ti1] * 3;
-        const double q0 = g0[0], q1 = g0[1], q2 = g0[2];
-        const double qq[3] = {q0, q1, q2};
-        double sum = 0.0;
-#pragma unroll
-        for (int l = 0; l < 3; ++l)
-#pragma unroll
-          for (int m = 0; m < 3; ++m) {
-            const double v = vf[l * 3 + m];
-            s_pG[(ti1 * 2 + n1) * 9 + l * 3 + m] = v;
-            sum += ((qq[l] * qq[m]) * v);                                    // gp00 (:555) then :702-705
-          }
-        ok &= __builtin_amdgcn_class(sum, 0x100);
-        s_t00[n1 * T00 + ti1] = dmx_log2_fast(sum, s_log);                    // :708-709 term
-      }
+      if (on)
+        ok &= llks00_term(gp0, s_snp[ti1], [&](int l, int m) { const double v = vf[l * 3 + m]; s_pG[(ti1 * 2 + n1) * 9 + l * 3 + m] = v; return v; },
+                    s_log, &s_t00[n1 * T00 + ti1]);
     }
     DMX_K2_SYNC();
     // ---- llks00: lane n < 2 of the cell adds its alpha's terms in pair order
@@ -3575,26 +3484,11 @@ __global__ __launch_bounds__(kThreads, 3) void k_doublet_a2f(PileupView pv, int 
   for (int64_t tbase = 0; tbase < np; tbase += TP) {
     const int tp = (int)min((int64_t)TP, np - tbase);
     // ---- headers of the tile's pairs (first 32 lanes of the cell)
-    if (tid < TP) {
-      const bool v = tid < tp;
-      const uint32_t n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
-      const uint32_t incl = seg_scan_incl<32>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
-    }
+    load_tile_headers<TP>(pv, nrd_width, p_beg, tbase, tp, tid, rd_base, s_cnt, s_off, s_snp);
     DMX_K2_SYNC();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
     // ---- genotype rows -> LDS (coalesced along the row)
-    {
-      int r = tid % row_len, ti = tid / row_len;
-      const int dr = TPC % row_len, dt = TPC / row_len;
-      while (ti < tp) {
-        s_g[ti * GS + r] = g[(size_t)s_snp[ti] * row_len + r];
-        r += dr; ti += dt;
-        if (r >= row_len) { r -= row_len; ++ti; }
-      }
-    }
+    stage_geno_rows<TPC>(g, s_snp, tp, tid, row_len, GS, s_g);
     // ---- phase 1
     if (tid < 64) {
       const bool on = ti1 < tp;
@@ -3602,64 +3496,11 @@ __global__ __launch_bounds__(kThreads, 3) void k_doublet_a2f(PileupView pv, int 
       const int64_t off = on ? s_off[ti1] : 0;
       const uint32_t rd4 = load_rd4(pv, off, cnt);       // the first four read bytes in one load (one dependent latency instead of four)
       double pG[9];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) pG[i] = 1.0;                               // :597
-      for (uint32_t r = 0; __any(r < cnt); ++r) {
-        const bool live = r < cnt;
-        const uint32_t byte = live ? (r < 4 ? (rd4 >> (8 * r)) & 0xFFu : (uint32_t)pv.reads[off + r]) : 0u;
-        const uint32_t bq = byte & 127u;
-        const bool alt = (byte >> 7) != 0;
-        const double pR = alt ? s_tab[128 + bq] : s_tab[bq];                // :606
-        const double pA = alt ? s_tab[bq] : s_tab[128 + bq];                // :607
-        double mx = 0.0;
-        if (live) {
-#pragma unroll
-          for (int i = 0; i < 9; ++i) {
-            pG[i] *= (pR * wR[i] + pA * wA[i]);                             // :625
-            mx = fmax(mx, pG[i]);                                 // :626-627
-          }
-        }
-        {
-          const double o = shfl_xor1(mx);                               // one max across both alphas of the pair
-          mx = fmax(mx, o);
-        }
-        if (live) {
-          if (cnt <= kSafeReads) {
-            const double y = rcp_refined(mx);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] = div_by(pG[i], mx, y);       // :632-639
-          } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] /= mx;
-          }
-        }
-      }
-      double mx = 0.0;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) {
-        pG[i] += 1e-6;                                                       // :649
-        mx = fmax(mx, pG[i]);
-      }
-      {
-        const double o = shfl_xor1(mx);
-        mx = fmax(mx, o);
-      }
+      const double mx = pair_values_open<9, 2, true>(pv, cnt, off, rd4, s_tab, wA, wR, n1, pG);
       if (on) {
         const double y = rcp_refined(mx);                                    // numerators >= 1e-6, mx in [1e-6, 1+1e-6]
-        const double* g0 = gp0 + (size_t)s_snp[ti1] * 3;
-        const double q0 = g0[0], q1 = g0[1], q2 = g0[2];
-        const double qq[3] = {q0, q1, q2};
-        double sum = 0.0;
-#pragma unroll
-        for (int l = 0; l < 3; ++l)
-#pragma unroll
-          for (int m = 0; m < 3; ++m) {
-            const double v = div_by(pG[l * 3 + m], mx, y);                   // :656-663
-            s_pG[(ti1 * 2 + n1) * 9 + l * 3 + m] = v;
-            sum += ((qq[l] * qq[m]) * v);                                    // gp00 (:555) then :702-705
-          }
-        ok &= __builtin_amdgcn_class(sum, 0x100);
-        s_t00[n1 * T00 + ti1] = dmx_log2_fast(sum, s_log);                    // :708-709 term
+        ok &= llks00_term(gp0, s_snp[ti1], [&](int l, int m) { const double v = div_by(pG[l * 3 + m], mx, y); s_pG[(ti1 * 2 + n1) * 9 + l * 3 + m] = v; return v; },
+                    s_log, &s_t00[n1 * T00 + ti1]);                      // :656-663 into the llks00 term
       }
     }
     DMX_K2_SYNC();
@@ -3944,10 +3785,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_sym(PileupView pv, i
         n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
         sn = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
       }
-      const uint32_t incl = seg_scan_incl<TP>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = sn;
+      publish_tile_headers<TP>(n, sn, tid, rd_base, s_cnt, s_off, s_snp);
     }
     DMX_K2_SYNC();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
@@ -3994,7 +3832,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_sym(PileupView pv, i
         for (int l = 0; l < 3; ++l)
 #pragma unroll
           for (int m = 0; m < 3; ++m) {
-            const double v = n1 ? q[l + m] : q[l];                           // pG[n][l][m]
+            const double v = n1 ? q[l + m] : q[l];                           // pG[n][l][m] (not llks00_term: the call selects q[] with fewer instructions, another kernel)
             sum += ((qq[l] * qq[m]) * v);                                    // gp00 (:555) then :702-705
           }
         ok &= __builtin_amdgcn_class(sum, 0x100);
@@ -4317,19 +4155,11 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_a2s(PileupView pv, i
   };
   for (int64_t tbase = 0; tbase < np; tbase += TP) {
     const int tp = (int)min((int64_t)TP, np - tbase);
-    if (tid < TP) {
-      const bool v = tid < tp;
-      const uint32_t n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
-      const int32_t sn = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
-      const uint32_t incl = seg_scan_incl<TP>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = sn;
-    }
+    load_tile_headers<TP>(pv, nrd_width, p_beg, tbase, tp, tid, rd_base, s_cnt, s_off, s_snp);
     DMX_WAVE_LDS_ORDER();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
     request_rows(0, 0);                            // sub-tile 0's rows travel while phase 1 runs
-    // ---- phase 1 (:597-663), k_doublet_sym's: lane (pair ti1, alpha n1), five distinct values
+    // ---- phase 1 (:597-663): lane (pair ti1, alpha n1), five distinct values
     {
       const bool on = ti1 < tp;
       const uint32_t cnt = on ? s_cnt[ti1] : 0u;
@@ -4343,6 +4173,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_a2s(PileupView pv, i
         q[0] = fp[0]; q[1] = fp[1]; q[2] = fp[2];
         q[3] = n1 ? fp[3] : 0.0; q[4] = n1 ? fp[4] : 0.0;
       } else {
+        // (its own copy of certify_pair_values<5, false>: through the call k_doublet_a2s<4, 3, 4> spills 77 registers instead of 129: another kernel)
         double wA[5], wR[5];
 #pragma unroll
         for (int i = 0; i < 5; ++i) { q[i] = 1.0; wA[i] = s_w[n1][i]; wR[i] = s_w[n1][5 + i]; }   // :597
@@ -4398,7 +4229,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_a2s(PileupView pv, i
         for (int l = 0; l < 3; ++l)
 #pragma unroll
           for (int m = 0; m < 3; ++m) {
-            const double v = n1 ? q[l + m] : q[l];                           // pG[n][l][m]
+            const double v = n1 ? q[l + m] : q[l];                           // pG[n][l][m] (not llks00_term: the call selects q[] with fewer instructions, another kernel)
             sum += ((qq[l] * qq[m]) * v);                                    // gp00 (:555) then :702-705
           }
         s_t00[n1 * T00 + ti1] = dmx_log2_fast(sum, s_log);                    // :708-709 term
@@ -4569,18 +4400,10 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_diag(PileupView pv, 
   const int ti1 = tid >> 1, n1 = tid & 1;
   for (int64_t tbase = 0; tbase < np_w; tbase += TP) {
     const int tp = (int)max((int64_t)0, min((int64_t)TP, np - tbase));
-    if (tid < TP) {
-      const bool v = tid < tp;
-      const uint32_t n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
-      const int32_t sn = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
-      const uint32_t incl = seg_scan_incl<TP>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = sn;
-    }
+    load_tile_headers<TP>(pv, nrd_width, p_beg, tbase, tp, tid, rd_base, s_cnt, s_off, s_snp);
     DMX_WAVE_LDS_ORDER();
     if (tp > 0) rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
-    // ---- phase 1 (:597-663), k_doublet_sym's: lane (pair ti1, alpha n1), five distinct values
+    // ---- phase 1 (:597-663): lane (pair ti1, alpha n1), five distinct values
     {
       const bool on = ti1 < tp;
       const uint32_t cnt = on ? s_cnt[ti1] : 0u;
@@ -4722,25 +4545,10 @@ __global__ __launch_bounds__(kThreads) void k_doublet_an(PileupView pv, int nrd_
 
   for (int64_t tbase = 0; tbase < np; tbase += TP) {
     const int tp = (int)min((int64_t)TP, np - tbase);
-    if (tid < TP) {
-      const bool v = tid < tp;
-      const uint32_t n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
-      const uint32_t incl = seg_scan_incl<32>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
-    }
+    load_tile_headers<TP>(pv, nrd_width, p_beg, tbase, tp, tid, rd_base, s_cnt, s_off, s_snp);
     DMX_K2_SYNC();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
-    {
-      int r = tid % row_len, ti = tid / row_len;
-      const int dr = TPC % row_len, dt = TPC / row_len;
-      while (ti < tp) {
-        s_g[ti * GS + r] = g[(size_t)s_snp[ti] * row_len + r];
-        r += dr; ti += dt;
-        if (r >= row_len) { r -= row_len; ++ti; }
-      }
-    }
+    stage_geno_rows<TPC>(g, s_snp, tp, tid, row_len, GS, s_g);
     // ---- phase 1: lane u = (pair u / AP, alpha u % AP)
 #pragma unroll
     for (int pass = 0; pass < NPASS; ++pass) {
@@ -4751,67 +4559,11 @@ __global__ __launch_bounds__(kThreads) void k_doublet_an(PileupView pv, int nrd_
       const uint32_t cnt = (ti1 < tp) ? s_cnt[ti1] : 0u;
       const int64_t off = (ti1 < tp) ? s_off[ti1] : 0;
       double pG[9];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) pG[i] = 1.0;                               // :597
-      for (uint32_t r = 0; __any(r < cnt); ++r) {
-        const bool live = r < cnt && n_ok;
-        const uint32_t byte = (r < cnt) ? pv.reads[off + r] : 0u;
-        const uint32_t bq = byte & 127u;
-        const bool alt = (byte >> 7) != 0;
-        const double pR = alt ? s_tab[128 + bq] : s_tab[bq];                // :606
-        const double pA = alt ? s_tab[bq] : s_tab[128 + bq];                // :607
-        double mx = 0.0;
-        if (live) {
-#pragma unroll
-          for (int i = 0; i < 9; ++i) {
-            pG[i] *= (pR * wR[i] + pA * wA[i]);                             // :625
-            mx = fmax(mx, pG[i]);                                 // :626-627
-          }
-        }
-#pragma unroll
-        for (int d = 1; d < AP; d <<= 1) {                                  // one max across ALL alphas of the pair
-          const double o = __shfl_xor(mx, d);
-          mx = fmax(mx, o);
-        }
-        if (live) {
-          if (cnt <= kSafeReads) {
-            const double y = rcp_refined(mx);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] = div_by(pG[i], mx, y);       // :632-639
-          } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] /= mx;
-          }
-        }
-      }
-      double mx = 0.0;
-      if (n_ok) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-          pG[i] += 1e-6;                                                     // :649
-          mx = fmax(mx, pG[i]);
-        }
-      }
-#pragma unroll
-      for (int d = 1; d < AP; d <<= 1) {
-        const double o = __shfl_xor(mx, d);
-        mx = fmax(mx, o);
-      }
+      const double mx = pair_values_open<9, AP, true, false>(pv, cnt, off, 0u, s_tab, wA, wR, n1, pG, nullptr, n_ok);
       if (on) {
-        const double y = rcp_refined(mx);
-        const double* g0 = gp0 + (size_t)s_snp[ti1] * 3;
-        const double qq[3] = {g0[0], g0[1], g0[2]};
-        double sum = 0.0;
-#pragma unroll
-        for (int l = 0; l < 3; ++l)
-#pragma unroll
-          for (int m = 0; m < 3; ++m) {
-            const double v = div_by(pG[l * 3 + m], mx, y);                   // :656-663
-            s_pG[(ti1 * AP + n1) * 9 + l * 3 + m] = v;
-            sum += ((qq[l] * qq[m]) * v);                                    // gp00 (:555) then :702-705
-          }
-        ok &= __builtin_amdgcn_class(sum, 0x100);
-        s_t00[n1 * T00 + ti1] = dmx_log2_fast(sum, s_log);                    // :708-709 term
+        const double y = rcp_refined(mx);                                    // numerators >= 1e-6, mx in [1e-6, 1+1e-6]
+        ok &= llks00_term(gp0, s_snp[ti1], [&](int l, int m) { const double v = div_by(pG[l * 3 + m], mx, y); s_pG[(ti1 * AP + n1) * 9 + l * 3 + m] = v; return v; },
+                    s_log, &s_t00[n1 * T00 + ti1]);                      // :656-663 into the llks00 term
       }
     }
     DMX_K2_SYNC();
@@ -4969,6 +4721,8 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_anf(PileupView pv, i
       }
   }
 
+  // (this kernel keeps its own copies of load_tile_headers, stage_geno_rows, pair_values_open and llks00_term: through the calls its AP = 8 forms
+  //  spill a few registers more or fewer than before)
   for (int64_t tbase = 0; tbase < np; tbase += TP) {
     const int tp = (int)min((int64_t)TP, np - tbase);
     if (tid < TP) {
@@ -5433,14 +5187,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_cls(PileupView pv, i
       DMX_K2_SYNC();
       request_next();
     } else {
-    if (tid < TP) {
-      const bool v = tid < tp;
-      const uint32_t n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
-      const uint32_t incl = seg_scan_incl<32>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
-    }
+    load_tile_headers<TP>(pv, nrd_width, p_beg, tbase, tp, tid, rd_base, s_cnt, s_off, s_snp);
     DMX_K2_SYNC();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
     // ---- class rows and ids -> LDS
@@ -5455,12 +5202,13 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_cls(PileupView pv, i
       }
     }
     }
-    // ---- phase 1 (identical to k_doublet_a2)
+    // ---- phase 1
     if (tid < 64 && !(ablate & 4096)) {
       const bool on = ti1 < tp;
       const uint32_t cnt = on ? s_cnt[ti1] : 0u;
       const int64_t off = on ? s_off[ti1] : 0;
       const uint32_t rd4 = PF ? rd4_cur : load_rd4(pv, off, cnt);   // the first four read bytes in one load (one dependent latency instead of four)
+      // (its own copy of pair_values_open and llks00_term: through the calls k_doublet_cls<256, 16, 1, false> takes 253 registers instead of 252)
       double pG[9], wA[9], wR[9];
 #pragma unroll
       for (int i = 0; i < 9; ++i) { pG[i] = 1.0; wA[i] = s_w[n1][i]; wR[i] = s_w[n1][9 + i]; }
@@ -5524,7 +5272,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_cls(PileupView pv, i
     DMX_K2_SYNC();
     if (tid < 2) {
       const double* row = &s_t00[tid * T00];
-      if (tp == TP) {
+      if (tp == TP) {                              // loads first (LDS latency paid once), then the ordered adds
         double2 v[TP / 2];
 #pragma unroll
         for (int i = 0; i < TP / 2; ++i) v[i] = *reinterpret_cast<const double2*>(&row[2 * i]);
@@ -5906,75 +5654,25 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_clsp(PileupView pv, 
       publish_next();
       load_hdr(tbase + 2 * TP);
       DMX_WAVE_LDS_ORDER();
-      // ---- phase 1 (identical to k_doublet_a2 / k_doublet_cls)
+      // ---- phase 1
       {
         const bool on = ti1 < tp;
         const uint32_t cnt = on ? s_cnt[ti1] : 0u;
         const int64_t off = on ? s_off[ti1] : 0;
         double pG[9];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) pG[i] = 1.0;
-        for (uint32_t r = 0; __any(r < cnt); ++r) {
-          const bool live = r < cnt;
-          const uint32_t byte = live ? (r < 4 ? (rd4 >> (8 * r)) & 0xFFu : (uint32_t)pv.reads[off + r]) : 0u;
-          const uint32_t bq = byte & 127u;
-          const bool alt = (byte >> 7) != 0;
-          const double pR = alt ? s_tab[128 + bq] : s_tab[bq];
-          const double pA = alt ? s_tab[bq] : s_tab[128 + bq];
-          double mx = 0.0;
-          if (live) {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) {
-              pG[i] *= (pR * s_w[n1][9 + i] + pA * s_w[n1][i]);
-              mx = fmax(mx, pG[i]);
-            }
-          }
-          {
-            const double o = shfl_xor1(mx);
-            mx = fmax(mx, o);
-          }
-          if (live) {
-            if (cnt <= kSafeReads) {
-              const double y = rcp_refined(mx);
-#pragma unroll
-              for (int i = 0; i < 9; ++i) pG[i] = div_by(pG[i], mx, y);
-            } else {
-#pragma unroll
-              for (int i = 0; i < 9; ++i) pG[i] /= mx;
-            }
-          }
-        }
-        double mx = 0.0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-          pG[i] += 1e-6;
-          mx = fmax(mx, pG[i]);
-        }
-        {
-          const double o = shfl_xor1(mx);
-          mx = fmax(mx, o);
-        }
+        const double mx = pair_values_open<9, 2, true>(pv, cnt, off, rd4, s_tab, &s_w[n1][0], &s_w[n1][9], n1, pG);   // (the weights stay in LDS)
         if (on) {
           const double y = rcp_refined(mx);
-          double sum = 0.0;
-#pragma unroll
-          for (int l = 0; l < 3; ++l)
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-              const double v = div_by(pG[l * 3 + m], mx, y);
-              s_pG[(ti1 * 2 + n1) * 9 + l * 3 + m] = v;
-              sum += ((qq[l] * qq[m]) * v);
-            }
-          ok &= __builtin_amdgcn_class(sum, 0x100);
-          s_t00[n1 * T00 + ti1] = dmx_log2_fast(sum, s_log);
+          ok &= llks00_term(qq, [&](int l, int m) { const double v = div_by(pG[l * 3 + m], mx, y); s_pG[(ti1 * 2 + n1) * 9 + l * 3 + m] = v; return v; },
+                      s_log, &s_t00[n1 * T00 + ti1]);
         }
       }
       DMX_WAVE_LDS_ORDER();
       request_next();                                              // (after phase 1: its registers are free again; phase 1b, this wavefront's
                                                                    //  phase 2 and the barrier cover the loads' latency)
-      if (lane < 2) {                                              // llks00[n] += the tile's terms, ascending SNP order (:688-704)
+      if (lane < 2) {
         const double* row = &s_t00[lane * T00];
-        if (tp == TP) {
+        if (tp == TP) {                              // loads first (LDS latency paid once), then the ordered adds
           double2 v[TP / 2];
 #pragma unroll
           for (int i = 0; i < TP / 2; ++i) v[i] = *reinterpret_cast<const double2*>(&row[2 * i]);
@@ -6321,10 +6019,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_clsym(PileupView pv,
       const int64_t nx = tbase + TP + tid;
       hd_n = 0u; hd_s = 0;
       if (nx < np) { hd_n = load_nrd(pv.pair_nrd, p_beg + nx, nrd_width); hd_s = pv.pair_snp ? pv.pair_snp[p_beg + nx] : (int32_t)nx; }
-      const uint32_t incl = seg_scan_incl<32>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = sn;
+      publish_tile_headers<TP>(n, sn, tid, rd_base, s_cnt, s_off, s_snp);
     }
     DMX_WAVE_LDS_ORDER();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
@@ -6335,7 +6030,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_clsym(PileupView pv,
       s_pk[e] = w < nwd2 ? idd[(size_t)s_snp[ti] * nwd2 + w] : 0u;
     }
     }
-    // ---- phase 1 (k_doublet_sym's: five distinct values per alpha lane)
+    // ---- phase 1 (five distinct values per alpha lane)
     {
       const bool on = ti1 < tp;
       const uint32_t cnt = on ? s_cnt[ti1] : 0u;
@@ -6344,47 +6039,8 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_clsym(PileupView pv,
       const int32_t snp1 = on ? s_snp[ti1] : 0;
       double qv[5], wA[5], wR[5];
 #pragma unroll
-      for (int i = 0; i < 5; ++i) { qv[i] = 1.0; wA[i] = s_w[n1][i]; wR[i] = s_w[n1][5 + i]; }   // :597
-      for (uint32_t r = 0; __any(r < cnt); ++r) {
-        const bool live = r < cnt;
-        const uint32_t byte = live ? (r < 4 ? (rd4 >> (8 * r)) & 0xFFu : (uint32_t)pv.reads[off + r]) : 0u;
-        const uint32_t bq = byte & 127u;
-        const bool alt = (byte >> 7) != 0;
-        const double pR = alt ? s_tab[128 + bq] : s_tab[bq];                // :606
-        const double pA = alt ? s_tab[bq] : s_tab[128 + bq];                // :607
-        double mx = 0.0;
-        if (live) {
-#pragma unroll
-          for (int i = 0; i < 5; ++i) {
-            qv[i] *= (pR * wR[i] + pA * wA[i]);                             // :625
-            mx = fmax(mx, qv[i]);                                 // :626-627
-          }
-        }
-        {
-          const double o = shfl_xor1(mx);
-          mx = fmax(mx, o);
-        }
-        if (live) {
-          if (cnt <= kSafeReads) {
-            const double y = rcp_refined(mx);
-#pragma unroll
-            for (int i = 0; i < 5; ++i) qv[i] = div_by(qv[i], mx, y);       // :632-639
-          } else {
-#pragma unroll
-            for (int i = 0; i < 5; ++i) qv[i] = div_slow(qv[i], mx);
-          }
-        }
-      }
-      double mx = 0.0;
-#pragma unroll
-      for (int i = 0; i < 5; ++i) {
-        qv[i] += 1e-6;                                                       // :649
-        mx = fmax(mx, qv[i]);
-      }
-      {
-        const double o = shfl_xor1(mx);
-        mx = fmax(mx, o);
-      }
+      for (int i = 0; i < 5; ++i) { wA[i] = s_w[n1][i]; wR[i] = s_w[n1][5 + i]; }
+      const double mx = pair_values_open<5>(pv, cnt, off, rd4, s_tab, wA, wR, n1, qv);
       if (on) {
         const double y = rcp_refined(mx);
 #pragma unroll
@@ -6396,7 +6052,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_clsym(PileupView pv,
         for (int l = 0; l < 3; ++l)
 #pragma unroll
           for (int m = 0; m < 3; ++m) {
-            const double v = n1 ? qv[l + m] : qv[l];                         // pG[n][l][m]
+            const double v = n1 ? qv[l + m] : qv[l];                         // pG[n][l][m] (not llks00_term: see k_doublet_sym)
             sum += ((qq[l] * qq[m]) * v);                                    // :555, :702-705
           }
         ok &= __builtin_amdgcn_class(sum, 0x100);
@@ -6603,14 +6259,7 @@ __global__ __launch_bounds__(kThreads) void k_doublet_clsn(PileupView pv, int nr
 
   for (int64_t tbase = 0; tbase < np; tbase += TP) {
     const int tp = (int)min((int64_t)TP, np - tbase);
-    if (tid < TP) {
-      const bool v = tid < tp;
-      const uint32_t n = v ? load_nrd(pv.pair_nrd, p_beg + tbase + tid, nrd_width) : 0u;
-      const uint32_t incl = seg_scan_incl<32>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = v ? (pv.pair_snp ? pv.pair_snp[p_beg + tbase + tid] : (int32_t)(tbase + tid)) : 0;
-    }
+    load_tile_headers<TP>(pv, nrd_width, p_beg, tbase, tp, tid, rd_base, s_cnt, s_off, s_snp);
     DMX_K2_SYNC();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
     for (int e = tid; e < tp * 12; e += TPC) s_rows[e] = rows[(size_t)s_snp[e / 12] * 12 + (e % 12)];
@@ -6634,67 +6283,11 @@ __global__ __launch_bounds__(kThreads) void k_doublet_clsn(PileupView pv, int nr
       const uint32_t cnt = (ti1 < tp) ? s_cnt[ti1] : 0u;
       const int64_t off = (ti1 < tp) ? s_off[ti1] : 0;
       double pG[9];
-#pragma unroll
-      for (int i = 0; i < 9; ++i) pG[i] = 1.0;                               // :597
-      for (uint32_t r = 0; __any(r < cnt); ++r) {
-        const bool live = r < cnt && n_ok;
-        const uint32_t byte = (r < cnt) ? pv.reads[off + r] : 0u;
-        const uint32_t bq = byte & 127u;
-        const bool alt = (byte >> 7) != 0;
-        const double pR = alt ? s_tab[128 + bq] : s_tab[bq];                // :606
-        const double pA = alt ? s_tab[bq] : s_tab[128 + bq];                // :607
-        double mx = 0.0;
-        if (live) {
-#pragma unroll
-          for (int i = 0; i < 9; ++i) {
-            pG[i] *= (pR * wR[i] + pA * wA[i]);                             // :625
-            mx = fmax(mx, pG[i]);                                 // :626-627
-          }
-        }
-#pragma unroll
-        for (int d = 1; d < AP; d <<= 1) {                                  // one max across ALL alphas of the pair
-          const double o = __shfl_xor(mx, d);
-          mx = fmax(mx, o);
-        }
-        if (live) {
-          if (cnt <= kSafeReads) {
-            const double y = rcp_refined(mx);
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] = div_by(pG[i], mx, y);       // :632-639
-          } else {
-#pragma unroll
-            for (int i = 0; i < 9; ++i) pG[i] /= mx;
-          }
-        }
-      }
-      double mx = 0.0;
-      if (n_ok) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
-          pG[i] += 1e-6;                                                     // :649
-          mx = fmax(mx, pG[i]);
-        }
-      }
-#pragma unroll
-      for (int d = 1; d < AP; d <<= 1) {
-        const double o = __shfl_xor(mx, d);
-        mx = fmax(mx, o);
-      }
+      const double mx = pair_values_open<9, AP, true, false>(pv, cnt, off, 0u, s_tab, wA, wR, n1, pG, nullptr, n_ok);
       if (on) {
-        const double y = rcp_refined(mx);
-        const double* g0 = gp0 + (size_t)s_snp[ti1] * 3;
-        const double qq[3] = {g0[0], g0[1], g0[2]};
-        double sum = 0.0;
-#pragma unroll
-        for (int l = 0; l < 3; ++l)
-#pragma unroll
-          for (int m = 0; m < 3; ++m) {
-            const double v = div_by(pG[l * 3 + m], mx, y);                   // :656-663
-            s_pG[(ti1 * AP + n1) * 9 + l * 3 + m] = v;
-            sum += ((qq[l] * qq[m]) * v);                                    // gp00 (:555) then :702-705
-          }
-        ok &= __builtin_amdgcn_class(sum, 0x100);
-        s_t00[n1 * T00 + ti1] = dmx_log2_fast(sum, s_log);                    // :708-709 term
+        const double y = rcp_refined(mx);                                    // numerators >= 1e-6, mx in [1e-6, 1+1e-6]
+        ok &= llks00_term(gp0, s_snp[ti1], [&](int l, int m) { const double v = div_by(pG[l * 3 + m], mx, y); s_pG[(ti1 * AP + n1) * 9 + l * 3 + m] = v; return v; },
+                    s_log, &s_t00[n1 * T00 + ti1]);                      // :656-663 into the llks00 term
       }
     }
     DMX_K2_SYNC();
@@ -7011,10 +6604,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_certify(PileupView pv, int n
       const int64_t nx = tbase + TP + tid;
       hd_n = 0u; hd_s = 0;
       if (nx < np) { hd_n = load_nrd(pv.pair_nrd, p_beg + nx, nrd_width); hd_s = pv.pair_snp ? pv.pair_snp[p_beg + nx] : (int32_t)nx; }
-      const uint32_t incl = seg_scan_incl<32>(n);
-      s_cnt[tid] = n;
-      s_off[tid] = rd_base + (int64_t)(incl - n);
-      s_snp[tid] = sn;
+      publish_tile_headers<TP>(n, sn, tid, rd_base, s_cnt, s_off, s_snp);
     }
     DMX_WAVE_LDS_ORDER();
     rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
@@ -8044,6 +7634,8 @@ int launch_doublet(dmx_engine* e) {
   const bool fast_soft = e->mode == DMX_MODE_FAST && (e->max_cell_pairs <= kLiteLogMaxPairs || e->knob("DMX_LITE_LOG_ANY_DEPTH"));
   const bool force_generic = e->knob("DMX_K2_GENERIC") != nullptr;      // kernel experiments only
   const bool use_cls = e->n_classes > 0 && !e->knob("DMX_NO_CLASSES");
+  // j-slabs of a kernel that owns JS = tpc / ceil(V / nk) rows of the grid per workgroup (blockIdx.y)
+  auto slabs_of = [&](int tpc, int nk) { const int kb = (V + nk - 1) / nk, js = tpc / kb; return (unsigned)((V + js - 1) / js); };
   if (A >= 3 && A <= 8 && use_cls && V <= 1024 && !force_generic) {
     // GT inputs, longer alpha grids: the class kernel with AP alphas per pair.  One cell per workgroup (the class table is
     // 4 x 4 x AP doubles per pair: 16-32 KB a tile); the k-block width follows the panel.
@@ -8052,12 +7644,11 @@ int launch_doublet(dmx_engine* e) {
     size_t cb = (size_t)32 * AP * 9 * 8 + (size_t)32 * 16 * AP * 8 + (size_t)AP * 34 * 8 + 32 * (4 + 4 + 8) + (size_t)32 * 12 * 4 + (size_t)32 * VS;
     cb = (cb + 15) & ~(size_t)15;
     HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
-    auto slabs = [&](int tpc, int nk) { const int kb = (V + nk - 1) / nk, js = tpc / kb; return (unsigned)((V + js - 1) / js); };
 #define DMX_K2CN(NK, APP)                                                                                              \
   do {                                                                                                                 \
     if (cb > 60 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_doublet_clsn<256, NK, APP>),       \
                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)cb));              \
-    DMX_LAUNCH(k2_fn, (k_doublet_clsn<256, NK, APP>), dim3((unsigned)B, slabs(256, NK)), dim3(kThreads), cb, e->stream, \
+    DMX_LAUNCH(k2_fn, (k_doublet_clsn<256, NK, APP>), dim3((unsigned)B, slabs_of(256, NK)), dim3(kThreads), cb, e->stream, \
                        e->pv, e->nrd_width, e->d_rows, e->d_ids, e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, A, VS,   \
                        e->d_grid, e->d_l00, e->d_flag());                                                                  \
   } while (0)
@@ -8075,7 +7666,6 @@ int launch_doublet(dmx_engine* e) {
     const int GS = (V * 3 + 3) & ~3;
     HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
     const dim3 block(kThreads);
-    auto slabs = [&](int tpc, int nk) { const int kb = (V + nk - 1) / nk, js = tpc / kb; return (unsigned)((V + js - 1) / js); };
 #define DMX_K2NF_(TPC, NK, APP, VUS, SUBP, MINW, CHK)                                                                  \
   do {                                                                                                                 \
     const int NU = (A - 1) * 3 * VUS + 4;                                                                              \
@@ -8084,7 +7674,7 @@ int launch_doublet(dmx_engine* e) {
     const size_t lds = cell_bytes * (kThreads / TPC);                                                                  \
     if (lds > 60 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_doublet_anf<TPC, NK, APP, VUS, SUBP, MINW, CHK>),  \
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
-    DMX_LAUNCH(k2_fn, (k_doublet_anf<TPC, NK, APP, VUS, SUBP, MINW, CHK>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs(TPC, NK)), \
+    DMX_LAUNCH(k2_fn, (k_doublet_anf<TPC, NK, APP, VUS, SUBP, MINW, CHK>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs_of(TPC, NK)), \
                        block, lds, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut,                            \
                        e->d_alpha, e->d_sched, V, A, GS, e->d_grid, e->d_l00, e->d_flag());                                \
   } while (0)
@@ -8114,14 +7704,13 @@ int launch_doublet(dmx_engine* e) {
     const size_t cell_bytes = (size_t)32 * AP * 9 * 8 + (size_t)32 * GS * 4 + (size_t)AP * 34 * 8 + 32 * (4 + 4 + 8);
     HIP_TRY(hipMemsetAsync(e->d_flag_base, 0, (size_t)B + kFlagHead, e->stream));
     const dim3 block(kThreads);
-    auto slabs = [&](int tpc, int nk) { const int kb = (V + nk - 1) / nk, js = tpc / kb; return (unsigned)((V + js - 1) / js); };
     // gfx950 lets one workgroup use all 160 KB of a CU's LDS; above the traditional 64 KB the limit is raised explicitly
 #define DMX_K2N(TPC, NK, APP)                                                                                          \
   do {                                                                                                                 \
     const size_t lds = cell_bytes * (kThreads / TPC);                                                                  \
     if (lds > 60 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_doublet_an<TPC, NK, APP>),        \
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));            \
-    DMX_LAUNCH(k2_fn, (k_doublet_an<TPC, NK, APP>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs(TPC, NK)), \
+    DMX_LAUNCH(k2_fn, (k_doublet_an<TPC, NK, APP>), dim3((unsigned)((B + (kThreads / TPC) - 1) / (kThreads / TPC)), slabs_of(TPC, NK)), \
                        block, lds, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut,                            \
                        e->d_alpha, e->d_sched, V, A, GS, e->d_grid, e->d_l00, e->d_flag());                                \
   } while (0)
@@ -8151,7 +7740,6 @@ int launch_doublet(dmx_engine* e) {
     HIP_TRY(hipGetLastError());
     return launch_doublet_generic_w<true>(e);
   }
-  auto slabs_of = [&](int tpc, int nk) { const int kb = (V + nk - 1) / nk, js = tpc / kb; return (unsigned)((V + js - 1) / js); };
   if (use_cls && e->mode == DMX_MODE_FAST && e->alpha[0] == 0.0 && e->alpha[1] == 0.5 && V <= 64 && !e->knob("DMX_NO_SYM")) {
     if (V > 32 && !e->knob("DMX_FAST_NO_PROD")) {
       // 33..64 samples: the producer / consumer kernel over the printed entries (round 4; k_doublet_clsym<33,2> ran 2 wavefronts per SIMD)

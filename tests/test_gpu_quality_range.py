@@ -12,19 +12,10 @@ import numpy as np
 import pytest
 
 from golden_util import printed_mask
-from quality_mix import A2, FAMILIES, family_problem, genotypes, host_pileup, mixed_depth_pileup, oracle_run
+from quality_mix import A2, FAMILIES, TABLES, family_problem, genotypes, mixed_depth_pileup, oracle_run, run_with_env
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
-SWITCHES = ("DMX_K1_CANP", "DMX_A2_NO_SYMU", "DMX_A2_SYM", "DMX_NO_ANF", "DMX_K2_GENERIC", "DMX_FINALS_ANY_DEPTH", "DMX_SYM_NO_FINALS",
-            "DMX_A2_NO_FINALS", "DMX_SYM_NO_SEEDS", "DMX_A2_NO_SEEDS", "DMX_CERTIFY_NO_FINALS", "DMX_CERTIFY_NO_SEEDS", "DMX_NO_CLASSES",
-            "DMX_K1_NO_CANP", "DMX_K1_NO_LEAN", "DMX_K1_NO_OWN")
-TABLES = {
-    "tables_default": {},
-    "tables_off": {k: "1" for k in ("DMX_SYM_NO_FINALS", "DMX_A2_NO_FINALS", "DMX_SYM_NO_SEEDS", "DMX_A2_NO_SEEDS", "DMX_CERTIFY_NO_FINALS",
-                                    "DMX_CERTIFY_NO_SEEDS")},
-    "tables_any_depth": {"DMX_FINALS_ANY_DEPTH": "1"},
-}
 
 
 @pytest.fixture(scope="module")
@@ -35,22 +26,6 @@ def eng():
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     capi.load()
     return engine
-
-
-def run_with_env(eng, monkeypatch, g, sp, alphas, mode, env):
-    from demuxlet_amd import capi
-    monkeypatch.setenv("DMX_EXPERIMENTS", "1")
-    for k in SWITCHES:
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    e = eng.Engine(g.shape[1], alphas, 0.5, mode=capi.DMX_MODE_FAST if mode == "fast" else capi.DMX_MODE_STRICT)
-    e.set_genotypes(g); e.set_pileup(host_pileup(eng, sp)); e.run(); e.sync()
-    names = e.kernel_names()
-    llks, llk0s = e.get_singlet()
-    grid, l00, summ = e.get_doublet()
-    e.close()
-    return dict(llks=llks, llk0s=llk0s, grid=grid, l00=l00, summ=summ, names=names)
 
 
 def max_diffs(out, ref, alphas, mode):
