@@ -43,6 +43,7 @@ SYMBOLS = [
     "dmx_engine_cluster_known_info",
     "dmx_engine_ambient", "dmx_engine_get_ambient", "dmx_engine_ambient_info",
     "dmx_engine_ambient_doublet", "dmx_engine_get_ambient_doublet", "dmx_engine_ambient_doublet_info",
+    "dmx_engine_triplet", "dmx_engine_get_triplet", "dmx_engine_triplet_info",
 ]
 
 
@@ -148,6 +149,16 @@ class AmbientDoubletRequest(C.Structure):  # dmx_ambient_doublet_request
 class AmbientDoubletInfo(C.Structure):   # dmx_ambient_doublet_info
     _fields_ = [("kernel_ms", C.c_double), ("profile_bytes", C.c_int64), ("n_used", C.c_int64), ("n_cells", C.c_int32), ("n_cand", C.c_int32),
                 ("n_alpha", C.c_int32), ("n_grid", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class TripletRequest(C.Structure):     # dmx_triplet_request
+    _fields_ = [("n_cells", C.c_int32), ("base_memory", C.c_int32), ("base", C.c_void_p), ("n_base", C.c_int32), ("n_shares", C.c_int32),
+                ("n_snps", C.c_int32), ("reserved0", C.c_int32), ("shares", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class TripletInfo(C.Structure):        # dmx_triplet_info
+    _fields_ = [("kernel_ms", C.c_double), ("profile_bytes", C.c_int64), ("n_used", C.c_int64), ("n_cells", C.c_int32), ("n_base", C.c_int32),
+                ("n_shares", C.c_int32), ("n_samples", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class DmxError(RuntimeError):
@@ -288,6 +299,7 @@ def load() -> C.CDLL:
         "dmx_engine_cluster_mstep_window": [vp, vp], "dmx_engine_get_cluster_known": [vp, vp], "dmx_engine_cluster_known_info": [vp, vp],
         "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],
         "dmx_engine_ambient_doublet": [vp, vp], "dmx_engine_get_ambient_doublet": [vp, vp, vp, vp], "dmx_engine_ambient_doublet_info": [vp, vp],
+        "dmx_engine_triplet": [vp, vp], "dmx_engine_get_triplet": [vp, vp, vp, vp], "dmx_engine_triplet_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

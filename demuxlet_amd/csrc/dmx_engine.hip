@@ -2928,6 +2928,198 @@ __global__ __launch_bounds__(64 * kAmbDblWaves) void k_ambient_dbl(PileupView pv
   }
 }
 
+// ---- triplet profile (dmx_engine_triplet) -------------------------------------------------------------------------
+// For a barcode b, a base pair (v1, v2), a share triple (w1, w2, w3) and EVERY sample c of the pool as the third donor:
+//   p_lmn = 0.5 (w1 l + w2 m + w3 n),   f_lmn = product over the pair's stored reads of pR (1 - p_lmn) + pA p_lmn,
+//   u_n = sum_l sum_m gp[i][v1][l] gp[i][v2][m] f_lmn (l-major, m-minor),   L_c = sum_n gp[i][c][n] u_n,
+//   LL[b][s][t][c] = sum over b's pairs, in stored (ascending SNP) order, of log(L_c).
+// One wavefront per (barcode, slot, share triple, block of 64 NACC columns); kTripPT pair headers staged in LDS per trip, then three steps:
+//   phase 1   lane (h, k), h = lane / 32, k = lane % 32 < 27: entry k = (l, m, n) of pair 2 i + h, i = 0 .. kTripPT / 2 - 1: the read loop with
+//             the entry's own exponent, then the weighted entry gp[v1][l] gp[v2][m] f_lmn (float32 x float32: exact) and its exponent go to LDS;
+//   fold      lane (j, n) < 3 kTripPT: u_n of pair j, nine terms in the contract's order, and its exponent, to LDS;
+//   phase 2   one lane per third donor c: per pair three float32 of g[snp][c] (lanes 12 bytes apart), three multiply-adds on the
+//             broadcast u_n, one log, into the lane's own accumulator (NACC of them: columns c0 + 64 a + lane).
+// Range (section 18's scheme): a pair of fewer than 8 reads keeps every exponent 0.  A deeper pair scales an f_lmn below 2^-300 to
+// [0.5, 1) every 8 reads and keeps the exponent per entry; u_n takes E_n = max over its entries with a non-zero weight and sums
+// t 2^(E_lmn - E_n), L_c takes E = max E_n over the n with gp[c][n] != 0 and sums gp u_n 2^(E_n - E) (exact shifts; a term more than
+// ~700 binades below the largest adds nothing), and the log gets E ln 2.  With every exponent 0 the shifts are by 0, so both depths
+// run the same sums.  Nothing depends on what else is in the call: an entry's bits follow from b's data, (v1, v2), the share triple, c
+// and V (which picks NACC and the column block) only.
+constexpr int kTripWaves = 4, kTripPT = 16;
+constexpr int kTripMaxSlot = 8, kTripMaxShare = 8, kTripMaxAcc = 4;
+constexpr int32_t kTripNoExp = INT32_MIN / 2;                     // the exponent of an entry that is 0 or carries no weight
+struct TripPair { int64_t off; uint32_t n, rd4; int32_t snp; float gp[6]; uint32_t pad; };   // n = 0: skipped; gp = rows v1, v2
+
+template <int NACC>
+__global__ __launch_bounds__(64 * kTripWaves) void k_triplet(PileupView pv, int nrd_width, const double* __restrict__ tabs, const float* __restrict__ g,
+                                                           int32_t V, const int32_t* __restrict__ base, int32_t C, const double* __restrict__ shares,
+                                                           int32_t T, int32_t n_vblk, int64_t n_units, double* __restrict__ ll,
+                                                           int32_t* __restrict__ n_snp, int32_t* __restrict__ n_read) {
+  static_assert(NACC >= 1 && NACC <= kTripMaxAcc && kTripPT % 2 == 0 && 3 * kTripPT <= 64, "accumulators per lane / staged headers per trip");
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_pra[256][2];               // by read byte (allele << 7 | bq): {pR, pA}
+  __shared__ TripPair s_hdr[kTripWaves][kTripPT];
+  __shared__ double s_t[kTripWaves][kTripPT][27];    // weighted entries
+  __shared__ int32_t s_te[kTripWaves][kTripPT][27];  // their exponents
+  __shared__ double s_u[kTripWaves][kTripPT][3];
+  __shared__ int32_t s_ue[kTripWaves][kTripPT][3];
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += 64 * kTripWaves) s_log[i] = tabs[kLut + i];
+  for (int i = threadIdx.x; i < 256; i += 64 * kTripWaves) {
+    const double mat = tabs[i & 127], e3 = tabs[128 + (i & 127)];
+    s_pra[i][0] = (i >> 7) ? e3 : mat;
+    s_pra[i][1] = (i >> 7) ? mat : e3;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t unit = (int64_t)blockIdx.x * kTripWaves + wave;
+  if (unit >= n_units) return;
+  const int32_t vb = (int32_t)(unit % n_vblk), ti = (int32_t)((unit / n_vblk) % T);
+  const int64_t slot = unit / ((int64_t)n_vblk * T);               // cell * C + s
+  const int32_t cell = (int32_t)(slot / C);
+  const int32_t c0 = vb * (64 * NACC) + lane;
+  const int32_t v1 = __builtin_amdgcn_readfirstlane(base[slot * 2]), v2 = __builtin_amdgcn_readfirstlane(base[slot * 2 + 1]);
+  double acc[NACC];
+  int32_t ns[NACC], nr[NACC];
+#pragma unroll
+  for (int a = 0; a < NACC; ++a) { acc[a] = 0.0; ns[a] = 0; nr[a] = 0; }
+  if (v1 >= 0) {
+    TripPair* hdr = s_hdr[wave];
+    double (*st)[27] = s_t[wave];
+    int32_t (*ste)[27] = s_te[wave];
+    double (*su)[3] = s_u[wave];
+    int32_t (*sue)[3] = s_ue[wave];
+    // phase 1's entry of this lane
+    const int h = lane >> 5, k = lane & 31;
+    const bool ent = k < 27;
+    const int el = ent ? k / 9 : 0, em = ent ? (k / 3) % 3 : 0, en = ent ? k % 3 : 0;
+    const double w1 = shares[3 * ti], w2 = shares[3 * ti + 1], w3 = shares[3 * ti + 2];
+    const double pk = 0.5 * (w1 * (double)el + w2 * (double)em + w3 * (double)en), qk = 1.0 - pk;
+    // the fold's (pair, n) of this lane
+    const int fj = lane / 3, fn = lane - 3 * fj;
+    const DmxLogPins lk = dmx_log_pins();
+    const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+    int64_t rd_base = pv.cell_read_off[cell];
+    for (int64_t p0 = p_beg; p0 < p_end; p0 += kTripPT) {
+      const int64_t p = p0 + lane;
+      const bool in = lane < kTripPT && p < p_end;
+      const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+      const uint32_t incl = seg_scan_incl<64>(n);
+      const int64_t off = rd_base + (int64_t)(incl - n);
+      rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      if (lane < kTripPT) {
+        TripPair& hd = hdr[lane];
+        bool both = false;
+        int32_t snp = 0;
+        if (n > 0) {
+          snp = pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg);
+          const float* gs = g + (size_t)snp * V * 3;
+          const float* r1 = gs + (size_t)v1 * 3;
+          const float* r2 = gs + (size_t)v2 * 3;
+          const float x0 = r1[0], x1 = r1[1], x2 = r1[2], y0 = r2[0], y1 = r2[1], y2 = r2[2];
+          hd.gp[0] = x0; hd.gp[1] = x1; hd.gp[2] = x2; hd.gp[3] = y0; hd.gp[4] = y1; hd.gp[5] = y2;
+          both = (x0 != 0.f || x1 != 0.f || x2 != 0.f) && (y0 != 0.f || y1 != 0.f || y2 != 0.f);
+          hd.rd4 = load_rd4(pv, off, n);
+        }
+        hd.off = off;
+        hd.snp = snp;
+        hd.n = both ? n : 0u;
+      }
+      DMX_WAVE_LDS_ORDER();
+      const int cnt = (int)min<int64_t>(kTripPT, p_end - p0);
+      // phase 1: two pairs side by side
+      for (int jj = 0; jj < cnt; jj += 2) {
+        const int j = jj + h;
+        const uint32_t nj = (ent && j < cnt) ? hdr[j].n : 0u;
+        if (nj > 0) {
+          const int64_t roff = hdr[j].off;
+          uint32_t w = hdr[j].rd4;
+          double f = s_pra[w & 0xFF][0] * qk + s_pra[w & 0xFF][1] * pk;
+          int32_t E = 0;
+          const bool deep = nj >= 8;
+          for (uint32_t r = 1; r < nj; ++r) {
+            if ((r & 3) == 0) w = load_rd4(pv, roff + r, nj - r);
+            const uint32_t byte = (w >> (8 * (r & 3))) & 0xFF;
+            f *= s_pra[byte][0] * qk + s_pra[byte][1] * pk;
+            if (deep && (r & 7) == 7 && f < kAmbRescaleBelow && f > 0.0) {
+              int e;
+              (void)frexp(f, &e);
+              f = ldexp(f, -e);
+              E += e;
+            }
+          }
+          const double wk = (double)hdr[j].gp[el] * (double)hdr[j].gp[3 + em];   // float32 x float32: exact in float64
+          const double t = wk * f;
+          st[j][k] = t;
+          ste[j][k] = t > 0.0 ? E : kTripNoExp;
+        }
+      }
+      DMX_WAVE_LDS_ORDER();
+      // fold: u_n of pair fj
+      if (fj < cnt && hdr[fj].n > 0) {
+        int32_t En = kTripNoExp;
+#pragma unroll
+        for (int x = 0; x < 9; ++x) En = max(En, ste[fj][3 * x + fn]);
+        if (En == kTripNoExp) En = 0;
+        double u = 0.0;
+#pragma unroll
+        for (int x = 0; x < 9; ++x) {
+          const double t = ldexp(st[fj][3 * x + fn], max(ste[fj][3 * x + fn] - En, -1100));
+          u = x == 0 ? t : u + t;
+        }
+        su[fj][fn] = u;
+        sue[fj][fn] = u > 0.0 ? En : kTripNoExp;
+      }
+      DMX_WAVE_LDS_ORDER();
+      // phase 2: every third donor of this unit's columns
+      for (int j = 0; j < cnt; ++j) {
+        const uint32_t nj = (uint32_t)__builtin_amdgcn_readfirstlane((int)hdr[j].n);
+        if (nj == 0) continue;
+        const int32_t snp = __builtin_amdgcn_readfirstlane(hdr[j].snp);
+        const double u0 = amb_uniform(su[j][0]), u1 = amb_uniform(su[j][1]), u2 = amb_uniform(su[j][2]);
+        const int32_t e0 = __builtin_amdgcn_readfirstlane(sue[j][0]), e1 = __builtin_amdgcn_readfirstlane(sue[j][1]),
+                      e2 = __builtin_amdgcn_readfirstlane(sue[j][2]);
+        const float* gs = g + (size_t)snp * V * 3;
+#pragma unroll
+        for (int a = 0; a < NACC; ++a) {
+          const int32_t c = c0 + 64 * a;
+          const float* gr = gs + (size_t)(c < V ? c : 0) * 3;    // lanes past V run along and write nothing
+          const float g0 = gr[0], g1 = gr[1], g2 = gr[2];
+          const bool nz = g0 != 0.f || g1 != 0.f || g2 != 0.f;
+          double L;
+          int32_t E = 0;
+          if (nj < 8) {
+            L = (double)g0 * u0 + (double)g1 * u1 + (double)g2 * u2;
+          } else {
+            E = kTripNoExp;
+            if (g0 != 0.f) E = max(E, e0);
+            if (g1 != 0.f) E = max(E, e1);
+            if (g2 != 0.f) E = max(E, e2);
+            if (E == kTripNoExp) E = 0;
+            // (a u_n that carries no weight may sit far ABOVE the scale: its term is 0, not 0 x inf)
+            const double t0 = g0 != 0.f ? (double)g0 * ldexp(u0, max(e0 - E, -1100)) : 0.0;
+            const double t1 = g1 != 0.f ? (double)g1 * ldexp(u1, max(e1 - E, -1100)) : 0.0;
+            const double t2 = g2 != 0.f ? (double)g2 * ldexp(u2, max(e2 - E, -1100)) : 0.0;
+            L = t0 + t1 + t2;
+          }
+          if (!nz) L = 1.0;
+          double lg = dmx_log_is_special(L) ? log(L) : dmx_log_fast_pinned(L, s_log, lk);
+          if (E != 0) lg = __builtin_fma((double)E, DMX_LOG_LN2HI, __builtin_fma((double)E, DMX_LOG_LN2LO, lg));
+          if (nz) { acc[a] += lg; ns[a] += 1; nr[a] += (int32_t)nj; }
+        }
+      }
+      DMX_WAVE_LDS_ORDER();
+    }
+  }
+#pragma unroll
+  for (int a = 0; a < NACC; ++a) {
+    const int32_t c = c0 + 64 * a;
+    if (c >= V) continue;
+    ll[((size_t)slot * T + ti) * V + c] = acc[a];
+    if (ti == 0) { n_snp[(size_t)slot * V + c] = ns[a]; n_read[(size_t)slot * V + c] = nr[a]; }
+  }
+}
+
 // SNP-minor copies for dense pileups: gT[r][s] = g[s][r] (r = k*3+l, float32 as stored) and g0T[l][s] = gp0s[s][l].
 __global__ void k_transpose_geno(const float* __restrict__ g, const double* __restrict__ gp0, int32_t S, int32_t V,
                                  float* __restrict__ gT, double* __restrict__ g0T) {
@@ -6864,6 +7056,14 @@ struct dmx_engine {
   int32_t adbl_B = 0, adbl_C = 0, adbl_A = 0, adbl_Q = 0; bool have_adbl = false;
   EventPair dbev;
   dmx_ambient_doublet_info adbl_info{};
+  // triplet profile (dmx_engine_triplet): buffers of its own, so that the ambient profiles stay
+  DevBuf<int32_t> d_tbase;
+  DevBuf<double> d_tshare;                       // shares[T][3]
+  DevBuf<double> d_tll;
+  DevBuf<int32_t> d_tcnt;                        // n_snp[B][C][V], then n_read[B][C][V]
+  int32_t trip_B = 0, trip_C = 0, trip_T = 0, trip_V = 0; bool have_trip = false;
+  EventPair tev;
+  dmx_triplet_info trip_info{};
 };
 
 namespace {
@@ -7392,6 +7592,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   }
   e->have_sing = e->have_grid = false;
   e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_adbl = false; e->have_cdbl = false;
+  e->have_trip = false;
   e->have_pileup = true;
   e->k1_fn = e->k2_fn = e->k3b_fn = nullptr; e->k1_placement = 0;      // nothing has run on this pileup yet
   return DMX_OK;
@@ -9219,6 +9420,119 @@ extern "C" int dmx_engine_ambient_doublet_info(dmx_engine* e, dmx_ambient_double
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet_info: null argument");
   if (!e->have_adbl) return set_error(DMX_ERR_STATE, "dmx_engine_ambient_doublet_info: no profile on the staged pileup (dmx_engine_ambient_doublet first)");
   *out = e->adbl_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Triplet profile: the arguments are checked on the host (base and the shares are small), then one launch of
+// k_triplet over B x C x T x ceil(V / (64 NACC)) wavefronts, NACC = 1 / 2 / 4 accumulators per lane by V alone.  Every buffer is the
+// call's own.
+namespace {
+template <int NACC>
+void launch_triplet(dmx_engine* e, int32_t C, int32_t T, int32_t n_vblk, int64_t n_units) {
+  hipLaunchKernelGGL((k_triplet<NACC>), dim3((unsigned)((n_units + kTripWaves - 1) / kTripWaves)), dim3(64 * kTripWaves), 0, e->stream,
+                     e->pv, e->nrd_width, (const double*)e->d_lut, e->d_g, e->V, (const int32_t*)e->d_tbase, C, (const double*)e->d_tshare, T,
+                     n_vblk, n_units, e->d_tll, e->d_tcnt, e->d_tcnt + (size_t)e->pv.B * C * e->V);
+}
+}  // namespace
+
+extern "C" int dmx_engine_triplet(dmx_engine* e, const dmx_triplet_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_triplet: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_triplet: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S, C = rq->n_base, T = rq->n_shares;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_triplet: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (C < 1 || C > kTripMaxSlot) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: n_base %d is not in [1, %d]", C, kTripMaxSlot);
+  if (T < 1 || T > kTripMaxShare) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: n_shares %d is not in [1, %d]", T, kTripMaxShare);
+  if (!rq->shares || (B > 0 && !rq->base)) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: missing base / shares");
+  if (rq->base_memory != DMX_MEM_HOST && rq->base_memory != DMX_MEM_DEVICE)
+    return set_error(DMX_ERR_ARG, "dmx_engine_triplet: base_memory %d", rq->base_memory);
+  for (int32_t t = 0; t < T; ++t) {
+    const double* w = rq->shares + 3 * t;
+    for (int k = 0; k < 3; ++k)
+      if (!(w[k] >= 0.0 && w[k] <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: shares[%d][%d] = %g is not in [0, 1]", t, k, w[k]);
+    if (!(std::fabs(w[0] + w[1] + w[2] - 1.0) <= 1e-12))
+      return set_error(DMX_ERR_ARG, "dmx_engine_triplet: shares[%d] = (%g, %g, %g) do not sum to 1", t, w[0], w[1], w[2]);
+    for (int32_t u = 0; u < t; ++u) {
+      const double* x = rq->shares + 3 * u;
+      if (x[0] == w[0] && x[1] == w[1] && x[2] == w[2]) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: shares[%d] repeats shares[%d]", t, u);
+    }
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t n_slot = (size_t)B * (size_t)C;
+  std::vector<int32_t> bs(n_slot * 2);
+  if (n_slot > 0) {
+    if (rq->base_memory == DMX_MEM_DEVICE) {
+      HIP_TRY(hipMemcpyAsync(bs.data(), rq->base, sizeof(int32_t) * 2 * n_slot, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+      std::memcpy(bs.data(), rq->base, sizeof(int32_t) * 2 * n_slot);
+    }
+  }
+  int64_t n_used = 0;
+  for (size_t k = 0; k < n_slot; ++k) {
+    const int32_t v1 = bs[2 * k], v2 = bs[2 * k + 1];
+    if (v1 == -1) continue;
+    if (v1 < 0 || v1 >= V || v2 < 0 || v2 >= V || v1 == v2)
+      return set_error(DMX_ERR_ARG, "dmx_engine_triplet: base[%zu][%zu] = (%d, %d) is not -1 or two different samples in [0, %d)",
+                       k / (size_t)C, k % (size_t)C, v1, v2, V);
+    ++n_used;
+  }
+  const size_t n_col = n_slot * (size_t)V;
+  const size_t prof = sizeof(double) * n_col * (size_t)T, cnts = sizeof(int32_t) * 2 * n_col;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const size_t need = (prof > e->d_tll.cap() ? prof + prof / 16 : 0) + (cnts > e->d_tcnt.cap() ? cnts + cnts / 16 : 0);
+  if (need > free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_triplet: the %d x %d x %d x %d profile needs %zu bytes, %zu are free", B, C, T, V, prof + cnts, free_b);
+  if (int rc = e->d_tll.ensure(prof)) return rc;
+  if (int rc = e->d_tcnt.ensure(cnts)) return rc;
+  if (int rc = e->d_tbase.ensure(sizeof(int32_t) * 2 * n_slot)) return rc;
+  if (int rc = e->d_tshare.ensure(sizeof(double) * 3 * (size_t)T)) return rc;
+  if (n_slot > 0) HIP_TRY(hipMemcpyAsync(e->d_tbase, bs.data(), sizeof(int32_t) * 2 * n_slot, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_tshare, rq->shares, sizeof(double) * 3 * (size_t)T, hipMemcpyHostToDevice, e->stream));
+  const int nacc = V <= 64 ? 1 : V <= 128 ? 2 : kTripMaxAcc;
+  const int32_t n_vblk = (V + 64 * nacc - 1) / (64 * nacc);
+  const int64_t n_units = (int64_t)n_slot * T * n_vblk;
+  if (int rc = e->tev.record_start(e->stream)) return rc;
+  if (n_units > 0) {
+    if (nacc == 1) launch_triplet<1>(e, C, T, n_vblk, n_units);
+    else if (nacc == 2) launch_triplet<2>(e, C, T, n_vblk, n_units);
+    else launch_triplet<kTripMaxAcc>(e, C, T, n_vblk, n_units);
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->tev.record_stop(e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return; bs is pageable host memory
+  float ms = 0.f;
+  if (int rc = e->tev.elapsed_ms(&ms)) return rc;
+  dmx_triplet_info& inf = e->trip_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.kernel_ms = ms; inf.profile_bytes = (int64_t)prof; inf.n_used = n_used;
+  inf.n_cells = B; inf.n_base = C; inf.n_shares = T; inf.n_samples = V;
+  e->trip_B = B; e->trip_C = C; e->trip_T = T; e->trip_V = V; e->have_trip = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_triplet(dmx_engine* e, double* ll, int32_t* n_snp, int32_t* n_read) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_triplet: null engine");
+  if (!e->have_trip) return set_error(DMX_ERR_STATE, "dmx_engine_get_triplet: no profile on the staged pileup (dmx_engine_triplet first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t n_col = (size_t)e->trip_B * (size_t)e->trip_C * (size_t)e->trip_V;
+  if (!n_col) return DMX_OK;
+  if (ll) HIP_TRY(hipMemcpy(ll, e->d_tll, sizeof(double) * n_col * (size_t)e->trip_T, hipMemcpyDeviceToHost));
+  if (n_snp) HIP_TRY(hipMemcpy(n_snp, e->d_tcnt, sizeof(int32_t) * n_col, hipMemcpyDeviceToHost));
+  if (n_read) HIP_TRY(hipMemcpy(n_read, e->d_tcnt + n_col, sizeof(int32_t) * n_col, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_triplet_info(dmx_engine* e, dmx_triplet_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_triplet_info: null argument");
+  if (!e->have_trip) return set_error(DMX_ERR_STATE, "dmx_engine_triplet_info: no profile on the staged pileup (dmx_engine_triplet first)");
+  *out = e->trip_info;
   return DMX_OK;
 }
 

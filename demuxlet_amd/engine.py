@@ -165,6 +165,7 @@ class Engine:
         self._h = h
         self._keep = []
         self.B = 0
+        self.S = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -197,11 +198,13 @@ class Engine:
         self._keep = [pl]
         check(self._L.dmx_engine_set_pileup(self._h, C.byref(st)))
         self.B = pl.n_cells
+        self.S = pl.n_snps
 
     def set_pileup_struct(self, st: capi.Pileup, keep=None) -> None:
         self._keep = [keep]
         check(self._L.dmx_engine_set_pileup(self._h, C.byref(st)))
         self.B = st.n_cells
+        self.S = st.n_snps
 
     def run_singlet(self) -> None: check(self._L.dmx_engine_run_singlet(self._h))
     def run_doublet(self) -> None: check(self._L.dmx_engine_run_doublet(self._h))
@@ -586,6 +589,38 @@ class Engine:
         r = capi.AmbientDoubletInfo()
         check(self._L.dmx_engine_ambient_doublet_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.AmbientDoubletInfo._fields_ if n != "reserved"}
+
+    def triplet_profile(self, base, shares, n_base=None):
+        """dmx_engine_triplet over the staged pileup: LL[b][s][t][c] of barcode b as a triplet of the base pair base[b][s] = (v1, v2)
+        (v1 = -1: slot not used) and the third donor c, with the read shares shares[t] = (w1, w2, w3) of v1, v2 and c.  `base` is a host
+        array [B][C][2], or a device pointer (int) to B x n_base x 2 int32.
+        Returns (ll[B][C][T][V] f64, n_snp[B][C][V] i32, n_read[B][C][V] i32)."""
+        sh = np.ascontiguousarray(shares, dtype=np.float64)
+        if sh.ndim != 2 or sh.shape[1] != 3:
+            raise ValueError("shares must be [T][3]")
+        if isinstance(base, int):
+            if n_base is None:
+                raise ValueError("a device base needs n_base=")
+            bs, mem, ptr, Cn = None, capi.DMX_MEM_DEVICE, base, int(n_base)
+        else:
+            bs = np.ascontiguousarray(base, dtype=np.int32)
+            if bs.ndim != 3 or bs.shape[0] != self.B or bs.shape[2] != 2:
+                raise ValueError(f"base must be [{self.B}][C][2]")
+            mem, ptr, Cn = capi.DMX_MEM_HOST, (bs.ctypes.data if bs.size else None), bs.shape[1]
+        T = sh.shape[0]
+        rq = capi.TripletRequest(self.B, mem, ptr, Cn, T, self.S, 0, sh.ctypes.data if sh.size else None)
+        check(self._L.dmx_engine_triplet(self._h, C.byref(rq)))
+        ll = np.zeros((self.B, Cn, T, self.V))
+        n_snp = np.zeros((self.B, Cn, self.V), dtype=np.int32)
+        n_read = np.zeros((self.B, Cn, self.V), dtype=np.int32)
+        check(self._L.dmx_engine_get_triplet(self._h, ll.ctypes.data, n_snp.ctypes.data, n_read.ctypes.data))
+        return ll, n_snp, n_read
+
+    def triplet_info(self) -> dict:
+        """HIP-event time (ms) of the last triplet profile and its size (dmx_engine_triplet_info)."""
+        r = capi.TripletInfo()
+        check(self._L.dmx_engine_triplet_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.TripletInfo._fields_ if not n.startswith("reserved")}
 
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()

@@ -256,6 +256,73 @@ def make_ambient_mixed_pileup(rng: np.random.Generator, alleles: np.ndarray, B: 
     return sp, rho, alpha, a
 
 
+def make_multiplet_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: float, rbar: float, kinds, shares,
+                          dense_layout: bool = False, quals: Optional[str] = None, chunk_cells: int = 256
+                          ) -> Tuple[SynthPileup, np.ndarray, np.ndarray]:
+    """Singlets, doublets and triplets.  kinds[c] in {1, 2, 3} is the number of donors of cell c (a scalar or [B]): the first is sample
+    c mod V, the others are drawn different from it and from each other.  shares[c] = (w1, w2, w3) (one row or [B][3]) are the donors'
+    read shares; the entries of the donors a cell does not have are dropped and the rest scaled to sum 1.  Each read's source is drawn
+    by these shares (ALT w.p. its dosage / 2); then sequencing error as in make_pileup.  Returns (pileup, truth3[B][3],
+    true_shares[B][3]) with -1 / 0 in the unused donor slots; pileup.truth holds the first two donors."""
+    S, V, _ = alleles.shape
+    dosage = np.clip(alleles, 0, 1).sum(axis=2).astype(np.float64)      # [S][V]
+    kinds = np.broadcast_to(np.asarray(kinds, dtype=np.int64), (B,))
+    if B and (kinds.min() < 1 or kinds.max() > 3 or kinds.max() > V):
+        raise ValueError(f"kinds: 1, 2 or 3 donors per cell, at most the pool's {V}")
+    w = np.broadcast_to(np.asarray(shares, dtype=np.float64), (B, 3)).copy()
+    w[np.arange(3)[None, :] >= kinds[:, None]] = 0.0
+    if B and (np.any(w < 0.0) or np.any(w.sum(axis=1) <= 0.0)):
+        raise ValueError("shares: non-negative, with a positive share among each cell's donors")
+    w /= w.sum(axis=1, keepdims=True)
+    cum = np.cumsum(w, axis=1)
+    cell_pair_off = np.zeros(B + 1, dtype=np.int64)
+    cell_read_off = np.zeros(B + 1, dtype=np.int64)
+    snp_chunks, nrd_chunks, rd_chunks = [], [], []
+    totl = np.zeros(B, dtype=np.int32)
+    truth3 = np.full((B, 3), -1, dtype=np.int32)
+    for c0 in range(0, B, chunk_cells):
+        c1 = min(B, c0 + chunk_cells)
+        nc = c1 - c0
+        s1 = (np.arange(c0, c1) % V).astype(np.int32)
+        s2 = ((s1 + 1 + rng.integers(0, max(V - 1, 1), size=nc)) % V).astype(np.int32)
+        k3 = rng.integers(0, max(V - 2, 1), size=nc)                    # the k3-th sample, in cyclic order after s1, that is not s2
+        d2 = (s2 - s1) % V
+        s3 = ((s1 + 1 + k3 + (1 + k3 >= d2)) % V).astype(np.int32)
+        don = np.stack([s1, s2, s3], axis=1)
+        truth3[c0:c1] = np.where(np.arange(3)[None, :] < kinds[c0:c1, None], don, -1)
+        cov = np.ones((nc, S), dtype=bool) if delta >= 1.0 else rng.random((nc, S)) < delta
+        cc, ss = np.nonzero(cov)
+        npairs = len(cc)
+        nreads = 1 + rng.poisson(max(rbar - 1.0, 0.0), size=npairs)
+        pair_of_read = np.repeat(np.arange(npairs), nreads)
+        rc, rs = cc[pair_of_read], ss[pair_of_read]
+        x = rng.random(len(rc))
+        which = np.minimum((x >= cum[c0 + rc, 0]).astype(np.int64) + (x >= cum[c0 + rc, 1]), kinds[c0 + rc] - 1)
+        src = don[rc, which]
+        alt = rng.random(len(rc)) < dosage[rs, src] / 2.0
+        bq = draw_bq(rng, len(rc), quals)
+        e = rng.random(len(rc)) < ERR_OF_BQ[bq]
+        u = rng.integers(0, 3, size=len(rc))
+        allele = np.where(e, np.where(u == 0, 1 - alt.astype(np.int32), 2), alt.astype(np.int32)).astype(np.uint8)
+        keep = allele != 2
+        cell_pair_off[c0 + 1:c1 + 1] = np.bincount(cc, minlength=nc)
+        cell_read_off[c0 + 1:c1 + 1] = np.bincount(rc[keep], minlength=nc)
+        totl[c0:c1] = np.bincount(rc, minlength=nc)
+        snp_chunks.append(ss.astype(np.int32))
+        nrd_chunks.append(np.bincount(pair_of_read[keep], minlength=npairs))
+        rd_chunks.append(((allele[keep] << 7) | bq[keep]).astype(np.uint8))
+    np.cumsum(cell_pair_off, out=cell_pair_off)
+    np.cumsum(cell_read_off, out=cell_read_off)
+    nrd = np.concatenate(nrd_chunks) if nrd_chunks else np.zeros(0, dtype=np.int64)
+    nrd = nrd.astype(np.uint8 if (len(nrd) == 0 or nrd.max() <= 255) else np.uint16)
+    pair_snp = np.concatenate(snp_chunks) if snp_chunks else np.zeros(0, dtype=np.int32)
+    reads = np.concatenate(rd_chunks) if rd_chunks else np.zeros(0, dtype=np.uint8)
+    use_dense = dense_layout and delta >= 1.0
+    sp = SynthPileup(B, S, cell_pair_off, cell_read_off, None if use_dense else pair_snp, nrd, reads, totl, totl.copy(), totl.copy(),
+                     truth3[:, :2].copy())
+    return sp, truth3, w
+
+
 def barcode_name(i: int) -> str:
     """Deterministic 16-mer barcode whose byte-wise sort order is NOT the id order (exercises the sorted-output rule)."""
     x = (i * 2654435761 + 12345) & 0xFFFFFFFF

@@ -35,7 +35,8 @@ extern "C" {
                                _cluster_estep_grouped / _cluster_sm_info (split-merge moves); dmx_engine_cluster_set_known /
                                _cluster_estep_known / _cluster_mstep_window / _get_cluster_known / _cluster_known_info (partly
                                genotyped pools); dmx_engine_ambient_doublet / _get_ambient_doublet / _ambient_doublet_info (doublet
-                               likelihood with a soup term, to tell soupy singlets from doublets).  Additions only. */
+                               likelihood with a soup term, to tell soupy singlets from doublets); dmx_engine_triplet / _get_triplet /
+                               _triplet_info (a base pair with every sample as a third donor).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -609,6 +610,53 @@ int dmx_engine_ambient_doublet(dmx_engine*, const dmx_ambient_doublet_request*);
 /* Device->host copies of the last profile (any pointer may be NULL): ll[B][C][A][Q] f64, n_snp[B][C] / n_read[B][C] i32. */
 int dmx_engine_get_ambient_doublet(dmx_engine*, double* ll, int32_t* n_snp, int32_t* n_read);
 int dmx_engine_ambient_doublet_info(dmx_engine*, dmx_ambient_doublet_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Triplet profile (no counterpart in the reference): a barcode's base pair of donors with every sample of the pool
+ * as a third donor, on the scale of dmx_engine_ambient / dmx_engine_ambient_doublet at rho = 0.  For up to C base slots per barcode,
+ * base[b][s] = (v1, v2) with v1 = -1 = slot not used and otherwise 0 <= v1, v2 < V, v1 != v2, and share triples shares[t] = (w1, w2, w3),
+ * t < T, over the staged pileup, the phred tables and the engine's genotype matrix gp (float32), for every barcode b, used slot s, t
+ * and sample c in [0, V):
+ *   p_lmn     = 0.5 (w1 l + w2 m + w3 n)  for l, m, n = 0, 1, 2, evaluated in that order in float64: the reference's ALT fraction
+ *               (cmd_cram_demuxlet.cpp:613) with a third genome;
+ *   f_lmn     = product over the pair's stored reads, in stored order, of pR (1 - p_lmn) + pA p_lmn (pR / pA as for dmx_engine_ambient);
+ *   u_n       = sum_l sum_m gp[i][v1][l] gp[i][v2][m] f_lmn, the float32 entries widened to float64 (their product is exact), l-major, m-minor;
+ *   L_c       = sum_n gp[i][c][n] u_n, n ascending;
+ *   LL[b][s][t][c] = sum over b's pairs in ascending SNP order of log(L_c), the log being dmx_log.
+ * No per-read renormalisation and no 1e-6 floor.  A pair with no stored read, or where the gp row of v1 or v2 is all zero, contributes
+ * nothing to any c; a pair where the row of c is all zero contributes nothing to that c; n_snp[b][s][c] / n_read[b][s][c] count the
+ * pairs / reads that did.  c = v1 and c = v2 are computed like any other column (a pair with one donor counted twice).  f_lmn is kept
+ * in range by exact power-of-two rescaling, one exponent per entry, carried through u_n and L_c into the log (entries of zero weight do
+ * not drive the scale): pairs of hundreds of reads give the finite value of the log-space sum.  Each (b, s, t, c) is one serial sum
+ * with no floating-point atomics and no cross-lane step that depends on the rest of the call: its bits depend on b's data, (v1, v2),
+ * the share triple, c and V only — not on C, T, the slot, the other slots, where `base` lives or what ran before.  Unused slots get
+ * zero rows.  The call runs on the engine's stream, synchronises it before returning (host inputs may be freed then), uses buffers of
+ * its own and leaves every other result of the engine, the ambient profiles included, as it was.
+ * DMX_ERR_ARG: C or T outside [1, 8], a share outside [0, 1], a row with |w1 + w2 + w3 - 1| > 1e-12, two equal rows, a slot that is
+ * neither unused nor two different samples in [0, V), n_cells / n_snps that do not match the staged pileup / the genotype matrix.
+ * DMX_ERR_STATE: no pileup or no genotypes yet.  DMX_ERR_NOMEM: the B x C x T x V profile does not fit the free device memory. */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t base_memory;         /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `base` lives */
+  const int32_t* base;         /* [n_cells][n_base][2] */
+  int32_t n_base;              /* C, 1..8 */
+  int32_t n_shares;            /* T, 1..8 */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t reserved0;           /* 0 */
+  const double* shares;        /* [n_shares][3] float64 in [0, 1], rows summing to 1 and pairwise different, HOST */
+  int32_t reserved[4];         /* 0 */
+} dmx_triplet_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the last call's k_triplet */
+  int64_t profile_bytes;       /* device bytes of the B x C x T x V profile */
+  int64_t n_used;              /* base slots in use */
+  int32_t n_cells, n_base, n_shares, n_samples;
+  int32_t reserved[4];
+} dmx_triplet_info;
+int dmx_engine_triplet(dmx_engine*, const dmx_triplet_request*);
+/* Device->host copies of the last profile (any pointer may be NULL): ll[B][C][T][V] f64, n_snp[B][C][V] / n_read[B][C][V] i32. */
+int dmx_engine_get_triplet(dmx_engine*, double* ll, int32_t* n_snp, int32_t* n_read);
+int dmx_engine_triplet_info(dmx_engine*, dmx_triplet_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * a6,a10..a14  finaliser and writers — replaces cmd_cram_demuxlet.cpp:465-527 (.single), :713-875 (.sing2/.pair/.best).
