@@ -39,6 +39,8 @@ SYMBOLS = [
     "dmx_engine_cluster_device_ptr", "dmx_engine_cluster_info",
     "dmx_engine_cluster_doublet", "dmx_engine_get_cluster_doublet", "dmx_engine_cluster_estep_doublet", "dmx_engine_cluster_doublet_info",
     "dmx_engine_cluster_merge_score", "dmx_engine_cluster_estep_grouped", "dmx_engine_cluster_sm_info",
+    "dmx_engine_cluster_evidence", "dmx_engine_cluster_hard", "dmx_engine_get_cluster_hard", "dmx_engine_cluster_hard_device_ptr", "dmx_engine_cluster_merge_columns",
+    "dmx_engine_cluster_k_info",
     "dmx_engine_cluster_set_known", "dmx_engine_cluster_estep_known", "dmx_engine_cluster_mstep_window", "dmx_engine_get_cluster_known",
     "dmx_engine_cluster_known_info",
     "dmx_engine_ambient", "dmx_engine_get_ambient", "dmx_engine_ambient_info",
@@ -113,6 +115,17 @@ class ClusterEstepGroupedRequest(C.Structure):   # dmx_cluster_estep_grouped_req
 class ClusterSmInfo(C.Structure):         # dmx_cluster_sm_info
     _fields_ = [("merge_ms", C.c_double), ("grouped_estep_ms", C.c_double), ("n_restarts", C.c_int32), ("n_clusters", C.c_int32),
                 ("n_pairs", C.c_int32), ("n_chunks", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class ClusterHardRequest(C.Structure):    # dmx_cluster_hard_request
+    _fields_ = [("n_restarts", C.c_int32), ("n_clusters", C.c_int32), ("doublets", C.c_int32), ("reserved0", C.c_int32), ("active", C.c_void_p),
+                ("mask", C.c_void_p), ("label", C.c_void_p), ("n_sing", C.c_void_p), ("n_dbl", C.c_void_p), ("dbl_score", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class ClusterKInfo(C.Structure):          # dmx_cluster_k_info
+    _fields_ = [("evidence_ms", C.c_double), ("hard_ms", C.c_double), ("merge_columns_ms", C.c_double), ("n_restarts", C.c_int32),
+                ("n_clusters", C.c_int32), ("n_chunks", C.c_int32), ("n_cells", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class ClusterEstepKnownRequest(C.Structure):   # dmx_cluster_estep_known_request
@@ -295,6 +308,10 @@ def load() -> C.CDLL:
         "dmx_engine_cluster_doublet_info": [vp, vp],
         "dmx_engine_cluster_merge_score": [vp, i32, i32, vp, C.c_double, vp, vp], "dmx_engine_cluster_estep_grouped": [vp, vp],
         "dmx_engine_cluster_sm_info": [vp, vp],
+        "dmx_engine_cluster_evidence": [vp, i32, i32, vp, C.c_double, vp, vp], "dmx_engine_cluster_hard": [vp, vp],
+        "dmx_engine_get_cluster_hard": [vp, vp, vp, vp, vp],
+        "dmx_engine_cluster_hard_device_ptr": [vp, vp], "dmx_engine_cluster_merge_columns": [vp, i32, i32, vp, vp],
+        "dmx_engine_cluster_k_info": [vp, vp],
         "dmx_engine_cluster_set_known": [vp, i32, i32, vp, i32], "dmx_engine_cluster_estep_known": [vp, vp],
         "dmx_engine_cluster_mstep_window": [vp, vp], "dmx_engine_get_cluster_known": [vp, vp], "dmx_engine_cluster_known_info": [vp, vp],
         "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],

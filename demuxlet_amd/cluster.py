@@ -17,14 +17,22 @@ With split_merge (--split-merge) the winning restart then 
 pair of its clusters (cluster_merge_score), a 2-component sub-EM inside every cluster (cluster_estep_grouped), and candidate restarts
 that merge one pair and split one cluster into the freed column; the best candidate replaces the winner when its converged LL is higher.
 
+With auto_k (--auto-k) n_clusters is an upper bound K_max: after the EM at K_max every restart walks a merge path
+down to k_min clusters.  Each state is turned into hard labels on the device (cluster_hard), an M-step on their one-hot matrix gives the
+pooled genotype likelihoods, and the state's score is the model evidence of those labels (cluster_evidence, path_score); the pair of
+highest merge score (cluster_merge_score) is then merged (cluster_merge_columns), its column goes inactive (log pi = -inf) and the EM
+converges again.  The (state, restart) of highest score gives K and the genotype columns; <prefix>.kpath.tsv records the path.
+
     python -m demuxlet_amd.cluster --pileup <x>.pileup.txt --n-clusters K --out <prefix> [--restarts R] [--seed S] [--max-iter N]
-        [--tol T] [--floor F] [--min-snp M] [--alpha A ...] [--rounds N] [--match] [--em-doublets] [--split-merge] [--fast] [--gpu G]
+        [--tol T] [--floor F] [--min-snp M] [--alpha A ...] [--rounds N] [--match] [--em-doublets] [--split-merge] [--auto-k [--k-min M]]
+        [--fast] [--gpu G]
 
 reads the dump that `demuxlet --pileup-only` writes; its genotype matrix is ignored unless --match is given."""
 from __future__ import annotations
 
 import argparse
 import sys
+from math import lgamma
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -46,6 +54,8 @@ MATCH_HEADER = "CLUST\tSM_ID\tN.CELL\tSUM.LLK\tBEST\n"
 SM_CANDIDATES = (3, 3)
 SM_SPLIT_RESTARTS = 4
 SM_MAX_K = 64               # dmx_engine_cluster_merge_score stages K columns per SNP in LDS
+AUTO_K_MAX = SM_MAX_K         # the merge path scores pairs with dmx_engine_cluster_merge_score
+KPATH_HEADER = "STEP\tRESTART\tK\tLLK\tSCORE\tEVIDENCE\tDBL.SCORE\tLABEL.TERM\tN.SNG\tN.DBL\tSIZES\tMERGE_K\tMERGE_L\tBF\tCHOSEN\n"
 MOVES_HEADER = "MOVE\tCAND\tMERGE_K\tMERGE_L\tSPLIT\tBF\tSPLIT_GAIN\tLLK_BEFORE\tLLK_AFTER\tITER\tACCEPTED\n"
 
 
@@ -80,6 +90,16 @@ def check_sm_args(n_clusters: int, candidates: Sequence[int], split_restarts: in
         raise ValueError(f"{a} x {b} candidates or {split_restarts} split restarts of {n_clusters} clusters exceed {MAX_COLUMNS} columns")
     if max_moves is not None and max_moves < 0:
         raise ValueError(f"--sm-max-moves {max_moves}: at least 0")
+
+
+def check_auto_k_args(n_clusters: int, k_min: int, split_merge: bool) -> None:
+    """The error paths of auto_k=True, before any device work: 2 <= k_min <= K_max <= AUTO_K_MAX, and no split-merge moves."""
+    if split_merge:
+        raise ValueError("--auto-k and --split-merge do not go together (run split-merge at the chosen K afterwards, from init_labels)")
+    if n_clusters > AUTO_K_MAX:
+        raise ValueError(f"--auto-k walks down from at most {AUTO_K_MAX} clusters, not {n_clusters}")
+    if k_min < 2 or k_min > n_clusters:
+        raise ValueError(f"--k-min {k_min}: must be in [2, --n-clusters {n_clusters}]")
 
 
 def check_init_labels(labels, n_cells: int, n_clusters: int) -> np.ndarray:
@@ -128,6 +148,21 @@ def update_log_pi(col_sum: np.ndarray, restarts: int, n_clusters: int) -> np.nda
     pi = np.maximum(pi, PI_FLOOR)
     pi /= pi.sum(axis=1, keepdims=True)
     return np.log(pi)
+
+
+def update_log_pi_active(col_sum: np.ndarray, active: np.ndarray) -> np.ndarray:
+    """update_log_pi over the active columns only (active [R][K], at least one per restart): an inactive column keeps log pi = -inf,
+    the active ones get pi = sum / mass of the active sums, at least PI_FLOOR, renormalised to sum to 1."""
+    act = np.asarray(active, dtype=bool)
+    R, K = act.shape
+    cs = np.where(act, np.asarray(col_sum, dtype=np.float64).reshape(R, K), 0.0)
+    n_act = act.sum(axis=1, keepdims=True)
+    mass = cs.sum(axis=1, keepdims=True)
+    pi = np.where(mass > 0, cs / np.where(mass > 0, mass, 1.0), 1.0 / n_act)
+    pi = np.where(act, np.maximum(pi, PI_FLOOR), 0.0)
+    pi /= pi.sum(axis=1, keepdims=True)
+    with np.errstate(divide="ignore"):
+        return np.log(pi)
 
 
 def pair_index(n_clusters: int) -> np.ndarray:
@@ -204,6 +239,54 @@ def match_labels(truth: np.ndarray, pred: np.ndarray, n_truth: int, n_pred: int)
             break
         out[k], used_t[t] = t, True
     return out
+
+
+# ---- choosing K by a merge path: pure functions the CPU tests reach ---------------------------------------------
+def path_score(ev: np.ndarray, n_sing: np.ndarray, n_dbl: int, dbl_score: float, active: np.ndarray) -> Tuple[float, float, float]:
+    """The score of one restart's hard-labelled state, (score, evidence, label_term) with score = evidence + dbl_score + label_term:
+      evidence    the sum over the active columns k of ev[k], the log marginal likelihood of the reads of the barcodes labelled k;
+      dbl_score   the doublet-labelled barcodes' log-likelihoods at the plug-in genotypes;
+      label_term  lgamma(Ka) + sum over active k of lgamma(n_k + 1) - lgamma(N_s + Ka): the labels of the N_s singlets among the Ka
+                  active clusters, mixing weights integrated out under a flat Dirichlet; + lgamma(n_dbl + 1) + lgamma(N_s + 1)
+                  - lgamma(N_s + n_dbl + 2): which barcodes are doublets, their share integrated out under a flat Beta."""
+    act = np.asarray(active, dtype=bool)
+    n = np.asarray(n_sing, dtype=np.int64)[act]
+    ka, ns, nd = int(act.sum()), int(n.sum()), int(n_dbl)
+    evidence = float(np.sum(np.asarray(ev, dtype=np.float64)[act]))
+    label = lgamma(ka) + sum(lgamma(int(x) + 1) for x in n) - lgamma(ns + ka) + lgamma(nd + 1) + lgamma(ns + 1) - lgamma(ns + nd + 2)
+    return evidence + float(dbl_score) + label, evidence, label
+
+
+def best_active_pair(bf: np.ndarray, active: np.ndarray) -> Tuple[int, int, float]:
+    """(k, l, BF) of the pair k < l of two active columns with the largest merge score bf[P] (pair_index order); the lowest pair index
+    on a tie.  An emptied column has BF exactly 0 against every column, above the negative scores of distinct donors, so it goes first."""
+    act = np.asarray(active, dtype=bool)
+    pairs = pair_index(act.shape[0])
+    ok = np.flatnonzero(act[pairs[:, 0]] & act[pairs[:, 1]])
+    if ok.size == 0:
+        raise ValueError("best_active_pair: fewer than two active columns")
+    b = np.asarray(bf, dtype=np.float64)[ok]
+    p = int(ok[np.flatnonzero(b == b.max())[0]])
+    return int(pairs[p][0]), int(pairs[p][1]), float(bf[p])
+
+
+def path_winner(rows: Sequence[dict]) -> int:
+    """The index of the winning row of a merge path: the highest score; on a tie the smaller K, then the lower restart."""
+    return max(range(len(rows)), key=lambda i: (rows[i]["score"], -rows[i]["k"], -rows[i]["restart"]))
+
+
+def write_kpath_tsv(path: str, rows: Sequence[dict]) -> None:
+    """<prefix>.kpath.tsv: one row per (step, restart) of the merge path (KPATH_HEADER).  K active clusters; LLK the converged EM's
+    log-likelihood there; SCORE = EVIDENCE + DBL.SCORE + LABEL.TERM (path_score); N.SNG / N.DBL the singlet- / doublet-labelled barcodes,
+    SIZES the active clusters' singlets in column order; MERGE_K < MERGE_L the pair merged next and BF its merge score (-1, -1 and NA at
+    the last step); CHOSEN 1 on the one row whose state the run goes on with."""
+    with open(path, "w") as f:
+        f.write(KPATH_HEADER)
+        for r in rows:
+            bf = "NA" if r["merge_k"] < 0 else f"{r['bf']:.6f}"
+            f.write(f"{r['step']}\t{r['restart']}\t{r['k']}\t{r['llk']:.6f}\t{r['score']:.6f}\t{r['evidence']:.6f}\t{r['dbl_score']:.6f}\t"
+                    f"{r['label_term']:.6f}\t{r['n_sng']}\t{r['n_dbl']}\t" + ",".join(str(int(x)) for x in r["sizes"]) +
+                    f"\t{r['merge_k']}\t{r['merge_l']}\t{bf}\t{int(r['chosen'])}\n")
 
 
 # ---- split-merge moves (DESIGN.md section 16): pure functions the CPU tests reach ---------------------------------------------------------
@@ -311,14 +394,16 @@ def write_moves_tsv(path: str, rows: Sequence[dict]) -> None:
 
 
 def em_loop(eng, pl, S: int, R: int, K: int, q: np.ndarray, floor: float, log_pi: np.ndarray, delta: np.ndarray, mask, n_mask: int,
-            max_iter: int, tol: float, temperature: float, em_doublets: bool, em_rows: Optional[list] = None):
+            max_iter: int, tol: float, temperature: float, em_doublets: bool, em_rows: Optional[list] = None,
+            active: Optional[np.ndarray] = None, it0: int = 0):
     """The EM iterations of R restarts x K clusters after a first M-step (module docstring): returns (ll[R] of the last E-step, log_pi and
-    delta after it, iterations).  The engine ends with the M-step of the last E-step's weights."""
+    delta after it, iterations).  The engine ends with the M-step of the last E-step's weights.  With `active` ([R][K]; the merge path)
+    the inactive columns come with log_pi = -inf and keep it (update_log_pi_active); iterations are numbered from it0 + 1."""
     dense = pl.pair_snp is None
     prev = None
-    it = 0
+    it = it0
     ll = None
-    for it in range(1, max_iter + 1):
+    for it in range(it0 + 1, it0 + max_iter + 1):
         eng.set_genotypes_device(eng.cluster_device_ptr(), S)
         if dense:
             eng.set_pileup(pl)          # a dense pileup's SNP-minor copy of the matrix is made when it is staged
@@ -333,12 +418,62 @@ def em_loop(eng, pl, S: int, R: int, K: int, q: np.ndarray, floor: float, log_pi
             ll, cs = eng.cluster_estep(R, K, log_pi, temperature, mask)
             if em_rows is not None:
                 em_rows += [(it, r, float(ll[r]), np.exp(log_pi[r])) for r in range(R)]
-        log_pi = update_log_pi(cs, R, K)
+        log_pi = update_log_pi(cs, R, K) if active is None else update_log_pi_active(cs, active)
         eng.cluster_mstep(None, q, floor, fetch=False)
         if converged(prev, ll, tol):
             break
         prev = ll
     return ll, log_pi, delta, it
+
+
+def merge_path(eng, pl, S: int, R: int, K: int, q: np.ndarray, floor: float, ll: np.ndarray, log_pi: np.ndarray, delta: np.ndarray, mask,
+               n_mask: int, max_iter: int, tol: float, temperature: float, em_doublets: bool, k_min: int, em_rows: Optional[list], it: int):
+    """The merge path of auto_k (module docstring) from the converged EM at K clusters in `eng`, all R restarts stepping together.  Returns
+    (rows of .kpath.tsv with the winner marked; gp[S][K*][3], the winner's hard M-step genotypes of its active columns in ascending
+    column order; ll[R], delta[R] and the iteration count at the winner's step)."""
+    active = np.ones((R, K), dtype=np.uint8)
+    rows: List[dict] = []
+    best, g_best, at_best = None, None, None
+    # LLD is on the doublet kernel's max-normalised scale, the evidence on K1's sum-normalised one: lsc[b] (a function of the barcode's
+    # reads alone) takes a doublet-labelled barcode's LLD to the evidence's scale, as in the doublet E-step
+    lsc = eng.cluster_doublet_scale() if em_doublets else None
+    for step in range(K - k_min + 1):
+        label, n_sing, n_dbl, dsc = eng.cluster_hard(R, K, active, mask, doublets=em_doublets)
+        if em_doublets:
+            dsc = dsc - np.array([lsc[label[:, r] <= -2].sum() for r in range(R)])
+        eng.cluster_mstep(eng.cluster_hard_device_ptr(), q, floor, fetch=False)
+        ev, _ = eng.cluster_evidence(R, K, q, floor)
+        last = K - step == k_min
+        bf = None if last else eng.cluster_merge_score(R, K, q, floor)[0]
+        first = len(rows)
+        for r in range(R):
+            score, evidence, label_term = path_score(ev[r], n_sing[r], n_dbl[r], dsc[r], active[r])
+            k, l, b = (-1, -1, float("nan")) if last else best_active_pair(bf[r], active[r])
+            rows.append(dict(step=step, restart=r, k=K - step, llk=float(ll[r]), score=score, evidence=evidence, dbl_score=float(dsc[r]),
+                             label_term=label_term, n_sng=int(n_sing[r][active[r] > 0].sum()), n_dbl=int(n_dbl[r]),
+                             sizes=n_sing[r][active[r] > 0].tolist(), merge_k=k, merge_l=l, bf=b, chosen=False))
+        w = path_winner(rows)
+        if w >= first:                      # a state of this step is the best so far: keep its genotypes
+            best = w
+            gp = eng.cluster_genotypes(S)
+            cols = rows[w]["restart"] * K + np.flatnonzero(active[rows[w]["restart"]])
+            g_best = np.ascontiguousarray(gp[:, cols, :])
+            at_best = (ll, delta, it)
+        if last:
+            break
+        frm = np.array([rows[first + r]["merge_l"] for r in range(R)], dtype=np.int32)
+        into = np.array([rows[first + r]["merge_k"] for r in range(R)], dtype=np.int32)
+        eng.cluster_merge_columns(R, K, frm, into)
+        log_pi = np.array(log_pi, dtype=np.float64)
+        for r in range(R):
+            log_pi[r, into[r]] = np.logaddexp(log_pi[r, into[r]], log_pi[r, frm[r]])
+            log_pi[r, frm[r]] = -np.inf
+            active[r, frm[r]] = 0
+        eng.cluster_mstep(None, q, floor, fetch=False)
+        ll, log_pi, delta, it = em_loop(eng, pl, S, R, K, q, floor, log_pi, delta, mask, n_mask, max_iter, tol, temperature, em_doublets,
+                                        em_rows, active=active, it0=it)
+    rows[best]["chosen"] = True
+    return rows, g_best, at_best[0], at_best[1], at_best[2]
 
 
 def sub_em(eng, pl, S: int, K: int, Rs: int, q: np.ndarray, floor: float, w0: np.ndarray, group: np.ndarray, max_iter: int, tol: float):
@@ -437,15 +572,17 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
                 mode: int = capi.DMX_MODE_STRICT, doublet_prior: float = 0.5, temperature: float = 1.0,
                 snps: Optional[Sequence[Tuple]] = None, em_doublets: bool = False, init_labels: Optional[np.ndarray] = None,
                 split_merge: bool = False, sm_max_moves: Optional[int] = None, sm_candidates: Sequence[int] = SM_CANDIDATES,
-                sm_split_restarts: int = SM_SPLIT_RESTARTS) -> dict:
+                sm_split_restarts: int = SM_SPLIT_RESTARTS, auto_k: bool = False, k_min: int = 2) -> dict:
     """EM clustering of the barcodes of `store_or_pileup` (a Store, or a HostPileup with barcodes=...) into n_clusters donors, then
     the final demultiplexing pass and `rounds` hard-refine rounds (module docstring).  `match` = (g[S][NV][3], sample_ids) scores each
     cluster against genotyped samples (<prefix>.match.tsv).  `init_labels` ([R][B] int, values in [-1, K); -1 = no weight in the first
     M-step) replaces the seeded random start, e.g. to start from an earlier clustering; its R replaces `restarts`.  With split_merge the
     winning restart goes through split-merge moves (at most sm_max_moves, default K; sm_candidates = (merges, splits) per move,
-    sm_split_restarts random-half sub-restarts per split) and <prefix>.moves.tsv records every candidate.  Returns a dict: the winning
-    restart, per-restart LL, iterations, the cluster genotype matrix gp[S][K][3] and the prior q[S][3]; with em_doublets also `delta`,
-    the winning restart's doublet share; with split_merge also `moves`, the rows of .moves.tsv."""
+    sm_split_restarts random-half sub-restarts per split) and <prefix>.moves.tsv records every candidate.  With auto_k n_clusters is
+    K_max: the restarts walk a merge path down to k_min clusters and the state of highest score gives K (module docstring;
+    <prefix>.kpath.tsv); not together with split_merge.  Returns a dict: the winning restart, per-restart LL, iterations, the cluster
+    genotype matrix gp[S][K][3] and the prior q[S][3]; with em_doublets also `delta`, the winning restart's doublet share; with
+    split_merge also `moves`, the rows of .moves.tsv; with auto_k also `n_clusters`, the chosen K, and `kpath`, the rows of .kpath.tsv."""
     if isinstance(store_or_pileup, engine.HostPileup):
         pl = store_or_pileup
         if barcodes is None:
@@ -457,6 +594,8 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
         init_labels = check_init_labels(init_labels, B, K)
         R = init_labels.shape[0]
     check_args(K, R, max_iter, tol, floor, B, len(pl.pair_nrd))
+    if auto_k:
+        check_auto_k_args(K, int(k_min), split_merge)
     if split_merge:
         check_sm_args(K, sm_candidates, sm_split_restarts, sm_max_moves)
     C = R * K
@@ -464,6 +603,7 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
     kw = dict(barcodes=barcodes, doublet_prior=doublet_prior, device=device, mode=mode, min_snp=min_snp)
     eng = engine.Engine(C, alphas, doublet_prior, device=device, mode=mode)
     moves: List[dict] = []
+    kpath: List[dict] = []
     em_rows = []
     try:
         # prior: pooled REF / ALT counts of every barcode (one refinement with all barcodes in column 0)
@@ -482,9 +622,15 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
         n_mask = B if mask is None else int(np.count_nonzero(mask))
         ll, log_pi, delta, it = em_loop(eng, pl, S, R, K, q, floor, log_pi, delta, mask, n_mask, max_iter, tol, temperature, em_doublets,
                                         em_rows)
-        win = best_restart(ll)
-        _, _, gp = eng.get_cluster(S)
-        g = np.ascontiguousarray(gp[:, win * K:(win + 1) * K, :])
+        if auto_k:
+            kpath, g, ll, delta, it = merge_path(eng, pl, S, R, K, q, floor, ll, log_pi, delta, mask, n_mask, max_iter, tol, temperature,
+                                                 em_doublets, int(k_min), em_rows, it)
+            win = next(row["restart"] for row in kpath if row["chosen"])
+            K = g.shape[1]                  # K*: everything below runs at the chosen K
+        else:
+            win = best_restart(ll)
+            _, _, gp = eng.get_cluster(S)
+            g = np.ascontiguousarray(gp[:, win * K:(win + 1) * K, :])
         if split_merge:
             g_sm, moves = split_merge_moves(eng, win, R, float(ll[win]), float(delta[win]), pl, S, K, q, floor, mask, n_mask, max_iter, tol,
                                             temperature, em_doublets, seed, K if sm_max_moves is None else int(sm_max_moves), sm_candidates,
@@ -496,6 +642,8 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
     write_em_tsv(out_prefix + ".em.tsv", em_rows, doublets=em_doublets)
     if split_merge:
         write_moves_tsv(out_prefix + ".moves.tsv", moves)
+    if auto_k:
+        write_kpath_tsv(out_prefix + ".kpath.tsv", kpath)
     ids = cluster_ids(K)
     engine.demuxlet_run(pl, g, ids, alphas, out_prefix, **kw)
     # hard-refine rounds: the previous round's singlets only, prior q for every cluster
@@ -536,6 +684,8 @@ def cluster_run(store_or_pileup, n_clusters: int, out_prefix: str, restarts: int
         res["delta"] = float(delta[win])
     if split_merge:
         res["moves"] = moves
+    if auto_k:
+        res["n_clusters"], res["kpath"] = K, kpath
     return res
 
 
@@ -562,6 +712,10 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--sm-candidates", type=int, nargs=2, default=list(SM_CANDIDATES), metavar=("MERGES", "SPLITS"),
                     help="top merges x top splits evaluated per move (default 3 3)")
     ap.add_argument("--sm-split-restarts", type=int, default=SM_SPLIT_RESTARTS, help="random-half sub-restarts per split (default 4)")
+    ap.add_argument("--auto-k", action="store_true",
+                    help="choose the number of donors: --n-clusters is an upper bound K_max (about twice the expected number), a merge "
+                         "path down to --k-min is scored by model evidence (DESIGN.md section 20); writes <out>.kpath.tsv")
+    ap.add_argument("--k-min", type=int, default=None, help="with --auto-k: the smallest number of clusters the path reaches (default 2)")
     ap.add_argument("--fast", action="store_true", help="DMX_MODE_FAST for every pass")
     ap.add_argument("--gpu", type=int, default=0)
     a = ap.parse_args(argv)
@@ -569,6 +723,14 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         ap.error("--n-clusters must be at least 2")
     if a.restarts < 1 or a.n_clusters * a.restarts > MAX_COLUMNS:
         ap.error(f"--restarts x --n-clusters must be in [1, {MAX_COLUMNS}]")
+    if a.k_min is not None and not a.auto_k:
+        ap.error("--k-min needs --auto-k")
+    if a.auto_k:
+        a.k_min = 2 if a.k_min is None else a.k_min
+        try:
+            check_auto_k_args(a.n_clusters, a.k_min, a.split_merge)
+        except ValueError as e:
+            ap.error(str(e))
     return a
 
 
@@ -584,7 +746,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 min_snp=a.min_snp, alphas=a.alpha, rounds=a.rounds, match=match, barcodes=d.barcodes, device=a.gpu,
                 mode=capi.DMX_MODE_FAST if a.fast else capi.DMX_MODE_STRICT, doublet_prior=a.doublet_prior, snps=d.snps,
                 em_doublets=a.em_doublets, split_merge=a.split_merge, sm_max_moves=a.sm_max_moves, sm_candidates=tuple(a.sm_candidates),
-                sm_split_restarts=a.sm_split_restarts)
+                sm_split_restarts=a.sm_split_restarts, auto_k=a.auto_k, k_min=2 if a.k_min is None else a.k_min)
     return 0
 
 

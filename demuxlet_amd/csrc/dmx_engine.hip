@@ -2534,6 +2534,119 @@ __global__ __launch_bounds__(256) void k_cluster_estep_grp(const double* __restr
   cluster_estep_one(llks, b, r, R, K, log_pi, inv_t, (!mask || mask[b]) && group[b] == r / rpg, w, lse);
 }
 
+// ---- choosing the number of clusters (dmx_engine_cluster_evidence / _hard / _merge_columns) ---------------------
+// Evidence of every column of the last M-step from k_cluster_marg's A[S][C] and flags F[S][C]: one thread per (chunk of kSmChunk SNPs,
+// column c) adds A[i][c] of the SNPs with F[i][c] set, serially from 0 in ascending order, and counts them; k_cluster_ev_fold then adds
+// the chunks in ascending order.  The chunk size is the merge score's, and part of the contract.  A column's bits depend on its own
+// LL and W only: not on the grid, R, the column's position or what ran before.  A SNP with W = 0 is skipped, not added as a zero.
+__global__ __launch_bounds__(256) void k_cluster_ev_part(const double* __restrict__ A, const uint8_t* __restrict__ F, int32_t S, int32_t C,
+                                                         double* __restrict__ part, int32_t* __restrict__ npart) {
+  const int32_t c = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
+  if (c >= C) return;
+  const int32_t i0 = ch * kSmChunk, i1 = min(S, i0 + kSmChunk);
+  double acc = 0.0;
+  int32_t n = 0;
+  for (int32_t i = i0; i < i1; ++i) {
+    const size_t o = (size_t)i * C + c;
+    if (F[o]) { acc += A[o]; n += 1; }
+  }
+  part[(size_t)ch * C + c] = acc; npart[(size_t)ch * C + c] = n;
+}
+__global__ __launch_bounds__(256) void k_cluster_ev_fold(const double* __restrict__ part, const int32_t* __restrict__ npart, int32_t n_chunks, int32_t C,
+                                                         double* __restrict__ ev, int32_t* __restrict__ ncov) {
+  const int32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  double a = 0.0;
+  int32_t n = 0;
+  for (int32_t ch = 0; ch < n_chunks; ++ch) { a += part[(size_t)ch * C + c]; n += npart[(size_t)ch * C + c]; }
+  ev[c] = a; ncov[c] = n;
+}
+
+// Hard labels.  One thread per (barcode b, restart r) over the E-step's weights w[B][R K], the active flags act[R K] and, with dm (the
+// doublet E-step's mass [B][R]), LLD[B][R][P]:
+//   outside the mask                label = -1
+//   dm != NULL and dm[b][r] >= 0.5  label = -2 - p, p the pair (k, l), both active, of the highest LLD[b][r][p] (the lowest p on a tie);
+//                                   dsc[b][r] = that LLD
+//   otherwise                       label = the active k of the highest w[b][rK + k] (the lowest k on a tie)
+// dsc is 0.0 unless the label is a doublet's.  hot[b][rK + k] = 1.0 at a singlet label's column, else 0.0: every entry of the row is
+// written, and w is only read.  The host has checked that every restart has an active column (with dm: an active pair).
+__global__ __launch_bounds__(256) void k_cluster_hard(const double* __restrict__ w, const double* __restrict__ dm, const double* __restrict__ lld,
+                                                      const uint8_t* __restrict__ act, const uint8_t* __restrict__ mask, int32_t B, int32_t R, int32_t K,
+                                                      int32_t P, int32_t* __restrict__ label, double* __restrict__ dsc, double* __restrict__ hot) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)B * R) return;
+  const int32_t b = (int32_t)(t / R), r = (int32_t)(t % R);
+  const size_t o = (size_t)b * R * K + (size_t)r * K;
+  const uint8_t* a = act + (size_t)r * K;
+  int32_t lab = -1;
+  double sc = 0.0;
+  if (!(mask && !mask[b])) {
+    if (dm && dm[t] >= 0.5) {
+      const double* ld = lld + (size_t)t * P;
+      int32_t best = -1, p = 0;
+      for (int32_t k = 0; k < K; ++k)
+        for (int32_t l = k + 1; l < K; ++l, ++p)
+          if (a[k] && a[l] && (best < 0 || ld[p] > sc)) { best = p; sc = ld[p]; }
+      lab = -2 - best;
+    } else {
+      double top = 0.0;
+      for (int32_t k = 0; k < K; ++k)
+        if (a[k] && (lab < 0 || w[o + k] > top)) { lab = k; top = w[o + k]; }
+    }
+  }
+  label[t] = lab; dsc[t] = sc;
+  for (int32_t k = 0; k < K; ++k) hot[o + k] = k == lab ? 1.0 : 0.0;
+}
+
+// The hard labels' sums in the E-step's order: chunk partials over kEChunk consecutive barcodes (one thread per output column, serial
+// over the chunk's barcodes), then k_cluster_hard_fold adds the chunks in ascending order.  Columns 0 .. C-1: barcodes labelled k of
+// restart r (c = rK + k); C .. C+R-1: doublet-labelled barcodes of restart r, whose doublet scores go to dpart[ch][r] beside them.
+__global__ __launch_bounds__(256) void k_cluster_hard_part(const int32_t* __restrict__ label, const double* __restrict__ dsc, int32_t B, int32_t R, int32_t K,
+                                                           int32_t* __restrict__ ipart, double* __restrict__ dpart) {
+  const int32_t col = blockIdx.x * blockDim.x + threadIdx.x, ch = blockIdx.y;
+  const int32_t C = R * K, ncol = C + R;
+  if (col >= ncol) return;
+  const int32_t b0 = ch * kEChunk, b1 = min(B, b0 + kEChunk);
+  int32_t n = 0;
+  if (col < C) {
+    const int32_t r = col / K, k = col - r * K;
+    for (int32_t b = b0; b < b1; ++b) n += label[(size_t)b * R + r] == k;
+  } else {
+    const int32_t r = col - C;
+    double acc = 0.0;
+    for (int32_t b = b0; b < b1; ++b)
+      if (label[(size_t)b * R + r] <= -2) { acc += dsc[(size_t)b * R + r]; n += 1; }
+    dpart[(size_t)ch * R + r] = acc;
+  }
+  ipart[(size_t)ch * ncol + col] = n;
+}
+__global__ __launch_bounds__(256) void k_cluster_hard_fold(const int32_t* __restrict__ ipart, const double* __restrict__ dpart, int32_t n_chunks, int32_t C,
+                                                           int32_t R, int32_t* __restrict__ iout, double* __restrict__ dout) {
+  const int32_t col = blockIdx.x * blockDim.x + threadIdx.x, ncol = C + R;
+  if (col >= ncol) return;
+  int32_t n = 0;
+  for (int32_t ch = 0; ch < n_chunks; ++ch) n += ipart[(size_t)ch * ncol + col];
+  iout[col] = n;
+  if (col >= C) {
+    double a = 0.0;
+    for (int32_t ch = 0; ch < n_chunks; ++ch) a += dpart[(size_t)ch * R + (col - C)];
+    dout[col - C] = a;
+  }
+}
+
+// Column merge, in place on the E-step's weights: one thread per (barcode b, restart r) with fi[r] = from >= 0 and fi[R + r] = into:
+//   w[b][rK + into] = w[b][rK + into] + w[b][rK + from] (one addition), then w[b][rK + from] = 0.0.
+__global__ __launch_bounds__(256) void k_cluster_merge_cols(double* __restrict__ w, const int32_t* __restrict__ fi, int32_t B, int32_t R, int32_t K) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)B * R) return;
+  const int32_t b = (int32_t)(t / R), r = (int32_t)(t % R);
+  const int32_t from = fi[r], into = fi[R + r];
+  if (from < 0) return;
+  const size_t o = (size_t)b * R * K + (size_t)r * K;
+  w[o + into] = w[o + into] + w[o + from];
+  w[o + from] = 0.0;
+}
+
 // ---- partly genotyped pools (dmx_engine_cluster_estep_known / _mstep_window) ------------------------------------
 // The engine's V = Vk + R M columns are [Vk known donors | restart 0's M free columns | ... | restart R-1's M], the known ones shared
 // by every restart.  E-step: one thread per (barcode b, restart r) over its Vk + M components, component k's llk at column
@@ -7031,6 +7144,18 @@ struct dmx_engine {
   DevBuf<int32_t> d_cgrp;
   EventPair sev;
   dmx_cluster_sm_info sm_info{};
+  // choosing the number of clusters (dmx_engine_cluster_evidence / _hard / _merge_columns): the evidence's partials and folded sums,
+  // the hard labels, doublet scores and one-hot matrix [B][C] (a buffer of its own: the E-step's weights are only read), the sums'
+  // partials; cdm_*: whether d_cdm holds the doublet mass of the LAST E-step (cluster_estep_run keeps it)
+  DevBuf<double> d_kepart; DevBuf<int32_t> d_kenpart;
+  DevBuf<int32_t> d_klab; DevBuf<double> d_kdsc, d_khot;
+  DevBuf<uint8_t> d_kact, d_kmask;
+  DevBuf<int32_t> d_kipart; DevBuf<double> d_kdpart;
+  DevBuf<int32_t> d_kfi;
+  int32_t khot_B = 0, khot_C = 0, khot_R = 0; bool have_khot = false, khot_dbl = false;
+  int32_t cdm_B = 0, cdm_R = 0; bool have_cdm = false;
+  EventPair kkev;
+  dmx_cluster_k_info k_info{};
   // partly genotyped pools (dmx_engine_cluster_set_known / _estep_known / _mstep_window): the known rows gk[S][Vk][3], every
   // component's weights [B][R][Vk + M] of the last known-column E-step; cgp_C is the column count of the last M-step's gp' buffer
   DevBuf<float> d_ckn; int32_t ckn_S = 0, ckn_Vk = 0; bool have_ckn = false;
@@ -8749,7 +8874,7 @@ extern "C" int dmx_engine_cluster_stage(dmx_engine* e) {
   inf.stage_ms = ms; inf.cache_bytes = (int64_t)cache_b; inf.n_pairs = P; inf.n_cells = B; inf.n_snps = S; inf.sorted = !dense && P > 0;
   inf.scratch_bytes = (int64_t)scratch_b;
   e->cl_P = P; e->cl_B = B; e->cl_S = S; e->have_cstage = true;
-  e->have_cm = false; e->have_cw = false; e->have_ckw = false;
+  e->have_cm = false; e->have_cw = false; e->have_ckw = false; e->have_khot = false; e->have_cdm = false;
   return DMX_OK;
 }
 
@@ -8808,6 +8933,7 @@ int cluster_estep_run(dmx_engine* e, EventPair& ev, int32_t B, int32_t R, int32_
   if (sums.col_sum) std::memcpy(sums.col_sum, out.data(), sizeof(double) * (size_t)C);
   if (sums.ll) std::memcpy(sums.ll, out.data() + C, sizeof(double) * (size_t)R);
   if (dm && sums.dbl_mass) std::memcpy(sums.dbl_mass, out.data() + C + R, sizeof(double) * (size_t)R);
+  e->have_cdm = dm != nullptr; e->cdm_B = B; e->cdm_R = R;   // (d_cdm is the last E-step's only after a doublet E-step)
   return ev.elapsed_ms(ms);
 }
 
@@ -9106,6 +9232,171 @@ extern "C" int dmx_engine_cluster_estep_grouped(dmx_engine* e, const dmx_cluster
 extern "C" int dmx_engine_cluster_sm_info(dmx_engine* e, dmx_cluster_sm_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_sm_info: null argument");
   *out = e->sm_info;
+  return DMX_OK;
+}
+
+// Choosing the number of clusters: the evidence of the last M-step's columns (k_cluster_marg, shared with the
+// merge score and writing its d_smA / d_smF, then k_cluster_ev_part over ceil(S / kSmChunk) x ceil(C / 256) workgroups and
+// k_cluster_ev_fold), the hard labels of the last E-step's weights with their ordered sums, and the in-place column merge.
+extern "C" int dmx_engine_cluster_evidence(dmx_engine* e, int32_t n_restarts, int32_t n_clusters, const float* prior, double floor_, double* ev,
+                                           int32_t* n_cov) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_evidence: null engine");
+  if (!e->have_cstage || !e->have_cm) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_evidence: no M-step on this stage cache (dmx_engine_cluster_mstep first)");
+  const int32_t R = n_restarts, K = n_clusters, S = e->cm_S, C = e->cm_C;
+  if (K < 1 || K > kSmMaxK) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_evidence: %d clusters; the evidence needs 1 .. %d", K, kSmMaxK);
+  if (R < 1 || (int64_t)R * K != C) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_evidence: %d restarts x %d clusters, the last M-step has %d columns", R, K, C);
+  if (S > 0 && !prior) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_evidence: missing prior");
+  if (!(floor_ >= 0.0) || !std::isfinite(floor_)) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_evidence: floor %g", floor_);
+  const int32_t nch = (S + kSmChunk - 1) / kSmChunk;
+  if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_evidence: %d SNPs exceed this build's limit", S);
+  const size_t rows = (size_t)S * C, npart = ((size_t)nch + 1) * C;      // (the folded sums are the row behind the chunks' partials)
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = e->d_smA.ensure(sizeof(double) * rows)) return rc;
+  if (int rc = e->d_smF.ensure(rows)) return rc;
+  if (int rc = e->d_smq.ensure(sizeof(float) * 3 * (size_t)S)) return rc;
+  if (int rc = e->d_kepart.ensure(sizeof(double) * npart)) return rc;
+  if (int rc = e->d_kenpart.ensure(sizeof(int32_t) * npart)) return rc;
+  double* d_ev = e->d_kepart + (size_t)nch * C;
+  int32_t* d_nc = e->d_kenpart + (size_t)nch * C;
+  if (S) HIP_TRY(hipMemcpyAsync(e->d_smq, prior, sizeof(float) * 3 * (size_t)S, hipMemcpyHostToDevice, e->stream));
+  if (int rc = e->kkev.record_start(e->stream)) return rc;
+  if (rows) {
+    hipLaunchKernelGGL(k_cluster_marg, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cll, (const double*)e->d_cW,
+                       (const float*)e->d_smq, floor_, S, C, e->d_smA, e->d_smF);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cluster_ev_part, dim3((unsigned)((C + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const double*)e->d_smA,
+                       (const uint8_t*)e->d_smF, S, C, e->d_kepart, e->d_kenpart);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cluster_ev_fold, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_kepart,
+                     (const int32_t*)e->d_kenpart, nch, C, d_ev, d_nc);
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->kkev.record_stop(e->stream)) return rc;
+  if (ev) HIP_TRY(hipMemcpyAsync(ev, d_ev, sizeof(double) * (size_t)C, hipMemcpyDeviceToHost, e->stream));
+  if (n_cov) HIP_TRY(hipMemcpyAsync(n_cov, d_nc, sizeof(int32_t) * (size_t)C, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  float ms = 0.f;
+  if (int rc = e->kkev.elapsed_ms(&ms)) return rc;
+  e->k_info.evidence_ms = ms; e->k_info.n_restarts = R; e->k_info.n_clusters = K; e->k_info.n_chunks = nch;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_hard(dmx_engine* e, const dmx_cluster_hard_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_hard: null argument");
+  if (!e->have_cstage || !e->have_cw) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_hard: no E-step weights on this stage cache (an E-step first)");
+  const int32_t B = e->cl_B, R = rq->n_restarts, K = rq->n_clusters, C = e->cw_C;
+  const bool dbl = rq->doublets != 0;
+  if (R < 1 || K < 1 || (int64_t)R * K != C) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_hard: %d restarts x %d clusters, the last E-step's weights have %d columns", R, K, C);
+  if (!rq->active) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_hard: missing active");
+  for (int32_t r = 0; r < R; ++r) {
+    int32_t n = 0;
+    for (int32_t k = 0; k < K; ++k) n += rq->active[(size_t)r * K + k] != 0;
+    if (n < (dbl ? 2 : 1))
+      return set_error(DMX_ERR_ARG, "dmx_engine_cluster_hard: restart %d has %d active columns; %s", r, n, dbl ? "doublet labels need two" : "labels need one");
+  }
+  if (dbl && (!e->have_cdbl || e->cd_B != B || e->cd_R != R || e->cd_K != K))
+    return set_error(DMX_ERR_STATE, "dmx_engine_cluster_hard: no doublet likelihoods of %d restarts x %d clusters (dmx_engine_cluster_doublet first)", R, K);
+  if (dbl && (!e->have_cdm || e->cdm_B != B || e->cdm_R != R))
+    return set_error(DMX_ERR_STATE, "dmx_engine_cluster_hard: the last E-step left no doublet mass (dmx_engine_cluster_estep_doublet first)");
+  const int32_t nch = (B + kEChunk - 1) / kEChunk, ncol = C + R;
+  if (nch > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_hard: %d cells exceed this build's limit", B);
+  const int64_t P = (int64_t)K * (K - 1) / 2;
+  HIP_TRY(hipSetDevice(e->device));
+  e->have_khot = false;
+  if (int rc = e->d_khot.ensure(sizeof(double) * (size_t)B * C)) return rc;
+  if (int rc = e->d_klab.ensure(sizeof(int32_t) * (size_t)B * R)) return rc;
+  if (int rc = e->d_kdsc.ensure(sizeof(double) * (size_t)B * R)) return rc;
+  if (int rc = e->d_kact.ensure((size_t)C)) return rc;
+  if (int rc = e->d_kipart.ensure(sizeof(int32_t) * ((size_t)nch + 1) * ncol)) return rc;
+  if (int rc = e->d_kdpart.ensure(sizeof(double) * ((size_t)nch + 1) * R)) return rc;
+  if (rq->mask) if (int rc = e->d_kmask.ensure((size_t)B)) return rc;
+  std::vector<uint8_t> act((size_t)C);
+  for (int32_t c = 0; c < C; ++c) act[(size_t)c] = rq->active[c] != 0;
+  HIP_TRY(hipMemcpyAsync(e->d_kact, act.data(), (size_t)C, hipMemcpyHostToDevice, e->stream));
+  if (rq->mask && B) HIP_TRY(hipMemcpyAsync(e->d_kmask, rq->mask, (size_t)B, hipMemcpyHostToDevice, e->stream));
+  int32_t* d_iout = e->d_kipart + (size_t)nch * ncol;
+  double* d_dout = e->d_kdpart + (size_t)nch * R;
+  if (int rc = e->kkev.record_start(e->stream)) return rc;
+  if (B > 0) {
+    hipLaunchKernelGGL(k_cluster_hard, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_cw,
+                       dbl ? (const double*)e->d_cdm : nullptr, dbl ? (const double*)e->d_clld : nullptr, (const uint8_t*)e->d_kact,
+                       rq->mask ? (const uint8_t*)e->d_kmask : nullptr, B, R, K, (int32_t)P, e->d_klab, e->d_kdsc, e->d_khot);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_cluster_hard_part, dim3((unsigned)((ncol + 255) / 256), (unsigned)nch), dim3(256), 0, e->stream, (const int32_t*)e->d_klab,
+                       (const double*)e->d_kdsc, B, R, K, e->d_kipart, e->d_kdpart);
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_cluster_hard_fold, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, e->stream, (const int32_t*)e->d_kipart,
+                     (const double*)e->d_kdpart, nch, C, R, d_iout, d_dout);
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->kkev.record_stop(e->stream)) return rc;
+  std::vector<int32_t> iout((size_t)ncol);
+  HIP_TRY(hipMemcpyAsync(iout.data(), d_iout, sizeof(int32_t) * (size_t)ncol, hipMemcpyDeviceToHost, e->stream));
+  if (rq->dbl_score) HIP_TRY(hipMemcpyAsync(rq->dbl_score, d_dout, sizeof(double) * (size_t)R, hipMemcpyDeviceToHost, e->stream));
+  if (rq->label && B) HIP_TRY(hipMemcpyAsync(rq->label, e->d_klab, sizeof(int32_t) * (size_t)B * R, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (rq->n_sing) std::memcpy(rq->n_sing, iout.data(), sizeof(int32_t) * (size_t)C);
+  if (rq->n_dbl) std::memcpy(rq->n_dbl, iout.data() + C, sizeof(int32_t) * (size_t)R);
+  float ms = 0.f;
+  if (int rc = e->kkev.elapsed_ms(&ms)) return rc;
+  e->k_info.hard_ms = ms; e->k_info.n_cells = B;
+  e->khot_B = B; e->khot_C = C; e->khot_R = R; e->khot_dbl = dbl; e->have_khot = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_cluster_hard(dmx_engine* e, int32_t* label, double* score, double* hot, double* dbl_mass) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_cluster_hard: null engine");
+  if (!e->have_khot) return set_error(DMX_ERR_STATE, "dmx_engine_get_cluster_hard: no hard labels on this stage cache (dmx_engine_cluster_hard first)");
+  if (dbl_mass && !e->khot_dbl) return set_error(DMX_ERR_STATE, "dmx_engine_get_cluster_hard: the last hard labels read no doublet mass (doublets = 1 first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t B = (size_t)e->khot_B, C = (size_t)e->khot_C, R = (size_t)e->khot_R;
+  if (label && B) HIP_TRY(hipMemcpy(label, e->d_klab, sizeof(int32_t) * B * R, hipMemcpyDeviceToHost));
+  if (score && B) HIP_TRY(hipMemcpy(score, e->d_kdsc, sizeof(double) * B * R, hipMemcpyDeviceToHost));
+  if (hot && B) HIP_TRY(hipMemcpy(hot, e->d_khot, sizeof(double) * B * C, hipMemcpyDeviceToHost));
+  if (dbl_mass && B) HIP_TRY(hipMemcpy(dbl_mass, e->d_cdm, sizeof(double) * B * R, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_hard_device_ptr(dmx_engine* e, const double** out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_hard_device_ptr: null argument");
+  if (!e->have_khot) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_hard_device_ptr: no hard labels on this stage cache (dmx_engine_cluster_hard first)");
+  *out = e->d_khot;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_merge_columns(dmx_engine* e, int32_t n_restarts, int32_t n_clusters, const int32_t* from, const int32_t* into) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_columns: null engine");
+  if (!e->have_cstage || !e->have_cw) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_merge_columns: no E-step weights on this stage cache (an E-step first)");
+  const int32_t B = e->cl_B, R = n_restarts, K = n_clusters, C = e->cw_C;
+  if (R < 1 || K < 1 || (int64_t)R * K != C) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_columns: %d restarts x %d clusters, the last E-step's weights have %d columns", R, K, C);
+  if (!from || !into) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_columns: missing from / into");
+  std::vector<int32_t> fi((size_t)2 * R);
+  for (int32_t r = 0; r < R; ++r) {
+    if (from[r] < -1 || from[r] >= K) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_columns: from[%d] = %d; columns are -1 .. %d", r, from[r], K - 1);
+    if (from[r] >= 0 && (into[r] < 0 || into[r] >= K || into[r] == from[r]))
+      return set_error(DMX_ERR_ARG, "dmx_engine_cluster_merge_columns: restart %d merges column %d into %d of %d", r, from[r], into[r], K);
+    fi[(size_t)r] = from[r]; fi[(size_t)R + r] = from[r] >= 0 ? into[r] : 0;
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  if (int rc = e->d_kfi.ensure(sizeof(int32_t) * fi.size())) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_kfi, fi.data(), sizeof(int32_t) * fi.size(), hipMemcpyHostToDevice, e->stream));
+  if (int rc = e->kkev.record_start(e->stream)) return rc;
+  if (B > 0) {
+    hipLaunchKernelGGL(k_cluster_merge_cols, dim3((unsigned)(((int64_t)B * R + 255) / 256)), dim3(256), 0, e->stream, e->d_cw.get(), (const int32_t*)e->d_kfi, B, R, K);
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->kkev.record_stop(e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));        // (fi goes away after return)
+  float ms = 0.f;
+  if (int rc = e->kkev.elapsed_ms(&ms)) return rc;
+  e->k_info.merge_columns_ms = ms;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_cluster_k_info(dmx_engine* e, dmx_cluster_k_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_k_info: null argument");
+  *out = e->k_info;
   return DMX_OK;
 }
 

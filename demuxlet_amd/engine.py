@@ -347,6 +347,12 @@ class Engine:
         check(self._L.dmx_engine_get_cluster(self._h, ll.ctypes.data, W.ctypes.data, gp.ctypes.data, None))
         return ll, W, gp
 
+    def cluster_genotypes(self, n_snps: int) -> np.ndarray:
+        """The last M-step's gp' [S][V][3] f32 alone."""
+        gp = np.zeros((n_snps, self.V, 3), dtype=np.float32)
+        check(self._L.dmx_engine_get_cluster(self._h, None, None, gp.ctypes.data, None))
+        return gp
+
     def cluster_weights(self) -> np.ndarray:
         """The last E-step's weights [B][V] f64."""
         w = np.zeros((self.B, self.V))
@@ -391,6 +397,12 @@ class Engine:
         lsc = np.zeros(inf["n_cells"])
         check(self._L.dmx_engine_get_cluster_doublet(self._h, lld.ctypes.data if lld.size else None, lsc.ctypes.data if lsc.size else None))
         return lld, lsc
+
+    def cluster_doublet_scale(self) -> np.ndarray:
+        """lsc [B] f64 of the last cluster_doublet alone (LLD stays on the device): LLD - lsc is on K1's scale."""
+        lsc = np.zeros(self.cluster_doublet_info()["n_cells"])
+        check(self._L.dmx_engine_get_cluster_doublet(self._h, None, lsc.ctypes.data if lsc.size else None))
+        return lsc
 
     def cluster_estep_doublet(self, n_restarts: int, n_clusters: int, log_pi, log_delta, temperature: float = 1.0, mask=None):
         """dmx_engine_cluster_estep_doublet on K1's llks of the last run_singlet and the last LLD: the singlet weights stay on the device;
@@ -455,6 +467,72 @@ class Engine:
         r = capi.ClusterSmInfo()
         check(self._L.dmx_engine_cluster_sm_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.ClusterSmInfo._fields_ if n != "reserved"}
+
+    def cluster_evidence(self, n_restarts: int, n_clusters: int, prior: np.ndarray, floor: float = 1e-3):
+        """dmx_engine_cluster_evidence on the last M-step: (ev[R][K] f64, the log marginal likelihood of each column's reads with the
+        genotypes integrated out; n_cov[R][K] i32, its covered SNPs)."""
+        prior = np.ascontiguousarray(prior, dtype=np.float32)
+        if prior.ndim != 2 or prior.shape[1] != 3:
+            raise ValueError("prior must be [S][3]")
+        ev = np.zeros((max(int(n_restarts), 0), max(int(n_clusters), 0)))
+        nc = np.zeros(ev.shape, dtype=np.int32)
+        check(self._L.dmx_engine_cluster_evidence(self._h, int(n_restarts), int(n_clusters), prior.ctypes.data if prior.size else None,
+                                                  float(floor), ev.ctypes.data if ev.size else None, nc.ctypes.data if nc.size else None))
+        return ev, nc
+
+    def cluster_hard(self, n_restarts: int, n_clusters: int, active, mask=None, doublets: bool = False):
+        """dmx_engine_cluster_hard on the last E-step's weights: active [R][K] (1 = the column takes part).  Returns (label[B][R] i32: the
+        cluster, -1 outside the mask, -2 - p for a doublet of pair p; n_sing[R][K] i32; n_dbl[R] i32; dbl_score[R] f64).  The one-hot
+        matrix of the singlet labels stays on the device (cluster_hard_device_ptr)."""
+        R, K = int(n_restarts), int(n_clusters)
+        act = np.ascontiguousarray(active, dtype=np.uint8).reshape(-1)
+        if act.size != max(R, 0) * max(K, 0):
+            raise ValueError("active must be [R][K]")
+        m = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint8)
+        if m is not None and m.shape != (self.B,):
+            raise ValueError(f"mask must be [{self.B}]")
+        label = np.zeros((self.B, max(R, 0)), dtype=np.int32)
+        n_sing = np.zeros((max(R, 0), max(K, 0)), dtype=np.int32)
+        n_dbl = np.zeros(max(R, 0), dtype=np.int32)
+        score = np.zeros(max(R, 0))
+        rq = capi.ClusterHardRequest(R, K, int(bool(doublets)), 0, act.ctypes.data if act.size else None,
+                                     m.ctypes.data if m is not None and m.size else None, label.ctypes.data if label.size else None,
+                                     n_sing.ctypes.data if n_sing.size else None, n_dbl.ctypes.data if n_dbl.size else None,
+                                     score.ctypes.data if score.size else None)
+        check(self._L.dmx_engine_cluster_hard(self._h, C.byref(rq)))
+        return label, n_sing, n_dbl, score
+
+    def get_cluster_hard(self, n_restarts: int, n_clusters: int, dbl_mass: bool = False):
+        """The last hard labels' device results: (label[B][R] i32, score[B][R] f64: each barcode's doublet score, hot[B][R * K] f64: the
+        one-hot matrix) and, with dbl_mass, the doublet mass [B][R] f64 they were made from."""
+        label = np.zeros((self.B, n_restarts), dtype=np.int32)
+        score = np.zeros((self.B, n_restarts))
+        hot = np.zeros((self.B, n_restarts * n_clusters))
+        dm = np.zeros((self.B, n_restarts)) if dbl_mass else None
+        check(self._L.dmx_engine_get_cluster_hard(self._h, label.ctypes.data, score.ctypes.data, hot.ctypes.data, dm.ctypes.data if dbl_mass else None))
+        return (label, score, hot, dm) if dbl_mass else (label, score, hot)
+
+    def cluster_hard_device_ptr(self) -> int:
+        """Device pointer of the last one-hot matrix [B][R * K] f64 (for cluster_mstep(weights=<int>))."""
+        p = C.c_void_p()
+        check(self._L.dmx_engine_cluster_hard_device_ptr(self._h, C.byref(p)))
+        return int(p.value)
+
+    def cluster_merge_columns(self, n_restarts: int, n_clusters: int, merge_from, merge_into) -> None:
+        """dmx_engine_cluster_merge_columns: in every restart r with merge_from[r] >= 0 the last E-step's weights of column merge_from[r]
+        are added to column merge_into[r] and zeroed, on the device (the next cluster_mstep(None, ...) reads them)."""
+        f = np.ascontiguousarray(merge_from, dtype=np.int32).reshape(-1)
+        t = np.ascontiguousarray(merge_into, dtype=np.int32).reshape(-1)
+        if f.size != n_restarts or t.size != n_restarts:
+            raise ValueError("merge_from and merge_into must be [R]")
+        check(self._L.dmx_engine_cluster_merge_columns(self._h, int(n_restarts), int(n_clusters), f.ctypes.data if f.size else None,
+                                                       t.ctypes.data if t.size else None))
+
+    def cluster_k_info(self) -> dict:
+        """HIP-event times (ms) of the last evidence / hard labels / column merge (dmx_engine_cluster_k_info)."""
+        r = capi.ClusterKInfo()
+        check(self._L.dmx_engine_cluster_k_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.ClusterKInfo._fields_ if n != "reserved"}
 
     def cluster_set_known(self, g) -> None:
         """dmx_engine_cluster_set_known: the known rows [S][Vk][3] f32 (a host array) shared by every restart of the windowed M-step."""

@@ -36,7 +36,9 @@ extern "C" {
                                _cluster_estep_known / _cluster_mstep_window / _get_cluster_known / _cluster_known_info (partly
                                genotyped pools); dmx_engine_ambient_doublet / _get_ambient_doublet / _ambient_doublet_info (doublet
                                likelihood with a soup term, to tell soupy singlets from doublets); dmx_engine_triplet / _get_triplet /
-                               _triplet_info (a base pair with every sample as a third donor).  Additions only. */
+                               _triplet_info (a base pair with every sample as a third donor); dmx_engine_cluster_evidence /
+                               _cluster_hard / _get_cluster_hard / _cluster_hard_device_ptr / _cluster_merge_columns / _cluster_k_info (choosing the number
+                               of clusters).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -465,6 +467,70 @@ typedef struct {
 int dmx_engine_cluster_merge_score(dmx_engine*, int32_t n_restarts, int32_t n_clusters, const float* prior, double floor, double* bf, int32_t* n_shared);
 int dmx_engine_cluster_estep_grouped(dmx_engine*, const dmx_cluster_estep_grouped_request*);
 int dmx_engine_cluster_sm_info(dmx_engine*, dmx_cluster_sm_info* out);
+
+/* Choosing the number of clusters (no counterpart in the reference), driven by demuxlet_amd/cluster.py: a merge
+ * path from an over-specified K downwards, every state scored by the model evidence of its hard labels.  A column that has been merged
+ * away is "inactive": the driver gives it log_pi = -inf in the E-steps above, which then give it weights of exactly 0.
+ *
+ * dmx_engine_cluster_evidence: for the last M-step's C = R * K columns, with dmx_engine_cluster_merge_score's genotype prior log pi[i][g],
+ *     ev[r][k] = sum over the SNPs i with W[i][rK + k] > 0 of A[i][rK + k],  A[i][c] = lse_g(log pi[i][g] + LL[i][c][g]),
+ *   the log marginal likelihood of the column's reads with the genotypes integrated out, and n_cov[r][k] = the number of those SNPs.
+ *   A SNP with W = 0 adds nothing, so an empty column has ev = 0.0 and n_cov = 0.  Sum order: the merge score's (the SNPs in chunks of
+ *   256 in ascending order, each chunk serially from 0, then the chunks in ascending order; no floating-point atomics), so the bits
+ *   depend neither on the launch geometry, R, the position of the restart's columns nor on what ran before, and for a pair (k, l) the
+ *   evidence of the merged column minus ev[k] and ev[l] is bf[(k, l)] up to rounding.  ev [R * K] f64 and n_cov [R * K] i32 are HOST
+ *   outputs (either may be NULL).  DMX_ERR_STATE: no M-step on the stage cache; DMX_ERR_ARG: R * K != the last M-step's columns, K
+ *   outside [1, 64], a missing prior or a bad floor.
+ *
+ * dmx_engine_cluster_hard: hard labels from the weights w[B][R * K] of the last E-step of any kind.  Per barcode b and restart r:
+ *     mask[b] = 0:                                    label = -1;
+ *     doublets and the doublet mass m_b,r >= 0.5:     label = -2 - p, p the pair (k, l) of two active columns with the highest
+ *                                                     LLD[b][r][p] (the lowest p on a tie), which is the barcode's doublet score;
+ *     otherwise:                                      label = the active k with the highest w[b][rK + k] (the lowest k on a tie).
+ *   With doublets = 1 the doublet mass is that of the last dmx_engine_cluster_estep_doublet, which must be the last E-step, and LLD that
+ *   of the last dmx_engine_cluster_doublet (same R and K).  n_sing[r][k] counts the barcodes labelled k, n_dbl[r] the doublet-labelled
+ *   ones, dbl_score[r] is the sum of their doublet scores in dmx_engine_cluster_estep's order (chunks of 256 barcodes in barcode order,
+ *   then the chunks in ascending order; other barcodes add nothing).  It is on LLD's scale: minus the sum of lsc[b] over those barcodes it
+ *   is on K1's and the evidence's (dmx_engine_cluster_doublet).  On the device the call leaves a one-hot matrix [B][R * K] f64,
+ *   1.0 at a singlet-labelled barcode's column and 0.0 elsewhere, in a buffer of its own (dmx_engine_cluster_hard_device_ptr; the
+ *   M-step takes it as DMX_MEM_DEVICE): the E-step's weights are only read.  DMX_ERR_STATE: no E-step weights, or doublets = 1 without
+ *   that doublet mass or those doublet likelihoods; DMX_ERR_ARG: R * K != the weights' columns, a missing `active`, a restart with no
+ *   active column, or doublets = 1 with fewer than two active columns in a restart.
+ *
+ * dmx_engine_cluster_merge_columns: edits the last E-step's weights in place.  For every barcode and every restart r with from[r] >= 0:
+ *   w[into[r]] = w[into[r]] + w[from[r]] (one addition), then w[from[r]] = 0.0; a restart with from[r] = -1 is untouched.  The next
+ *   M-step takes the result as DMX_CLUSTER_LAST_ESTEP.  from / into are [R] HOST.  DMX_ERR_STATE: no E-step weights; DMX_ERR_ARG:
+ *   R * K != the weights' columns, from == into, or an index outside [0, K) (from: [-1, K)). */
+typedef struct {
+  int32_t n_restarts, n_clusters;   /* R, K: R * K = the columns of the last E-step's weights */
+  int32_t doublets;            /* 1: doublet labels from the last doublet E-step's mass and the last LLD */
+  int32_t reserved0;           /* 0 */
+  const uint8_t* active;       /* [R * K] HOST: 1 = the column takes part */
+  const uint8_t* mask;         /* [B] HOST, or NULL = every barcode */
+  int32_t* label;              /* [B][R] HOST out (may be NULL) */
+  int32_t* n_sing;             /* [R * K] HOST out (may be NULL) */
+  int32_t* n_dbl;              /* [R] HOST out (may be NULL) */
+  double* dbl_score;           /* [R] HOST out (may be NULL) */
+  int32_t reserved[4];         /* 0 */
+} dmx_cluster_hard_request;
+typedef struct {
+  double  evidence_ms;         /* HIP-event times of the last evidence (k_cluster_marg + k_cluster_ev_part + k_cluster_ev_fold), */
+  double  hard_ms;             /* ... of the last hard labels (k_cluster_hard + k_cluster_hard_part + k_cluster_hard_fold), */
+  double  merge_columns_ms;    /* ... and of the last column merge (k_cluster_merge_cols) */
+  int32_t n_restarts, n_clusters, n_chunks, n_cells;   /* R, K and the SNP chunks of the last evidence; the barcodes of the last hard labels */
+  int32_t reserved[4];
+} dmx_cluster_k_info;
+int dmx_engine_cluster_evidence(dmx_engine*, int32_t n_restarts, int32_t n_clusters, const float* prior, double floor, double* ev, int32_t* n_cov);
+int dmx_engine_cluster_hard(dmx_engine*, const dmx_cluster_hard_request*);
+/* The device pointer of the last one-hot matrix [B][R * K] f64 (DMX_ERR_STATE before dmx_engine_cluster_hard); valid until the next
+ * dmx_engine_cluster_hard or dmx_engine_cluster_stage. */
+int dmx_engine_cluster_hard_device_ptr(dmx_engine*, const double** out);
+/* Device->host copies of the last hard labels (any pointer may be NULL): label[B][R] i32, score[B][R] f64 (each barcode's doublet
+ * score, 0.0 unless doublet-labelled), hot[B][R * K] f64 (the one-hot matrix), and dbl_mass[B][R] f64, the doublet mass the labels
+ * were made from (DMX_ERR_STATE when they were made with doublets = 0, or before dmx_engine_cluster_hard). */
+int dmx_engine_get_cluster_hard(dmx_engine*, int32_t* label, double* score, double* hot, double* dbl_mass);
+int dmx_engine_cluster_merge_columns(dmx_engine*, int32_t n_restarts, int32_t n_clusters, const int32_t* from, const int32_t* into);
+int dmx_engine_cluster_k_info(dmx_engine*, dmx_cluster_k_info* out);
 
 /* Partly genotyped pools (no counterpart in the reference), driven by demuxlet_amd/partial.py: Vk donors are
  * known from the VCF and M more are learned by the clustering EM in R restarts.  The engine's V = Vk + R * M columns are
