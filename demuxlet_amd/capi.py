@@ -46,6 +46,7 @@ SYMBOLS = [
     "dmx_engine_ambient", "dmx_engine_get_ambient", "dmx_engine_ambient_info",
     "dmx_engine_ambient_doublet", "dmx_engine_get_ambient_doublet", "dmx_engine_ambient_doublet_info",
     "dmx_engine_triplet", "dmx_engine_get_triplet", "dmx_engine_triplet_info",
+    "dmx_engine_compose", "dmx_engine_composed_pileup", "dmx_engine_get_composed", "dmx_engine_compose_info",
 ]
 
 
@@ -172,6 +173,17 @@ class TripletRequest(C.Structure):     # dmx_triplet_request
 class TripletInfo(C.Structure):        # dmx_triplet_info
     _fields_ = [("kernel_ms", C.c_double), ("profile_bytes", C.c_int64), ("n_used", C.c_int64), ("n_cells", C.c_int32), ("n_base", C.c_int32),
                 ("n_shares", C.c_int32), ("n_samples", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class ComposeRequest(C.Structure):     # dmx_compose_request
+    _fields_ = [("n_out", C.c_int32), ("reserved0", C.c_int32), ("index_base", C.c_int64), ("parent", C.c_void_p), ("keep", C.c_void_p),
+                ("seed", C.c_uint64), ("reserved", C.c_int32 * 4)]
+
+
+class ComposeInfo(C.Structure):        # dmx_compose_info
+    _fields_ = [("n_pairs", C.c_int64), ("n_reads", C.c_int64), ("bytes_read", C.c_int64), ("bytes_written", C.c_int64),
+                ("count_ms", C.c_double), ("scan_ms", C.c_double), ("fill_ms", C.c_double), ("n_out", C.c_int32), ("nrd_width", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
 
 
 class DmxError(RuntimeError):
@@ -317,6 +329,8 @@ def load() -> C.CDLL:
         "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],
         "dmx_engine_ambient_doublet": [vp, vp], "dmx_engine_get_ambient_doublet": [vp, vp, vp, vp], "dmx_engine_ambient_doublet_info": [vp, vp],
         "dmx_engine_triplet": [vp, vp], "dmx_engine_get_triplet": [vp, vp, vp, vp], "dmx_engine_triplet_info": [vp, vp],
+        "dmx_engine_compose": [vp, vp], "dmx_engine_composed_pileup": [vp, vp], "dmx_engine_get_composed": [vp, vp, vp, vp, vp, vp],
+        "dmx_engine_compose_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -7189,6 +7189,15 @@ struct dmx_engine {
   int32_t trip_B = 0, trip_C = 0, trip_T = 0, trip_V = 0; bool have_trip = false;
   EventPair tev;
   dmx_triplet_info trip_info{};
+  // pileup composer (dmx_engine_compose): the recipe, the count pass's numbers, and the composed pileup itself (grow-only, like own[])
+  DevBuf<int32_t> d_cmparent; DevBuf<uint64_t> d_cmkeep;
+  DevBuf<int64_t> d_cmcnt;                       // pairs[n_out] | reads[n_out] | totals[3]
+  DevBuf<uint32_t> d_cmmax;
+  DevBuf<int64_t> d_cmpoff, d_cmroff;
+  DevBuf<int32_t> d_cmsnp; DevBuf<uint8_t> d_cmnrd, d_cmreads;
+  bool have_comp = false;
+  EventPair cmev[3];
+  dmx_compose_info comp_info{};
 };
 
 namespace {
@@ -7718,6 +7727,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   e->have_sing = e->have_grid = false;
   e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_adbl = false; e->have_cdbl = false;
   e->have_trip = false;
+  e->have_comp = false;
   e->have_pileup = true;
   e->k1_fn = e->k2_fn = e->k3b_fn = nullptr; e->k1_placement = 0;      // nothing has run on this pileup yet
   return DMX_OK;
@@ -9824,6 +9834,137 @@ extern "C" int dmx_engine_triplet_info(dmx_engine* e, dmx_triplet_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_triplet_info: null argument");
   if (!e->have_trip) return set_error(DMX_ERR_STATE, "dmx_engine_triplet_info: no profile on the staged pileup (dmx_engine_triplet first)");
   *out = e->trip_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Pileup composer (csrc/dmx_compose.hpp)
+#include "dmx_compose.hpp"
+
+extern "C" int dmx_engine_compose(dmx_engine* e, const dmx_compose_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_compose: null argument");
+  if (rq->n_out < 1 || rq->n_out > dmx_cmp::kMaxOut)
+    return set_error(DMX_ERR_ARG, "dmx_engine_compose: n_out %d is not in [1, %d] (compose a longer recipe in chunks by index_base)", rq->n_out, dmx_cmp::kMaxOut);
+  if (!rq->parent || !rq->keep) return set_error(DMX_ERR_ARG, "dmx_engine_compose: missing parent / keep");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_compose: no pileup staged (dmx_engine_set_pileup first)");
+  if (e->pv.cell_pair_off == (const int64_t*)e->d_cmpoff.get() && e->d_cmpoff)
+    return set_error(DMX_ERR_STATE, "dmx_engine_compose: the staged pileup is this engine's own composed pileup (it would be overwritten)");
+  const int32_t B = e->pv.B, N = rq->n_out;
+  for (int32_t o = 0; o < N; ++o) {
+    const int32_t p0 = rq->parent[2 * (size_t)o], p1 = rq->parent[2 * (size_t)o + 1];
+    if (p0 < 0 || p0 >= B || p1 < -1 || p1 >= B)
+      return set_error(DMX_ERR_ARG, "dmx_engine_compose: parent[%d] = (%d, %d) is not a cell in [0, %d) (slot 1: or -1)", o, p0, p1, B);
+    for (int s = 0; s < 2; ++s)
+      if (rq->keep[2 * (size_t)o + s] > dmx_cmp::kKeepAll)
+        return set_error(DMX_ERR_ARG, "dmx_engine_compose: keep[%d][%d] = %llu is above 2^32", o, s, (unsigned long long)rq->keep[2 * (size_t)o + s]);
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  e->have_comp = false;
+  // the parents' sizes, from the staged offsets: an upper bound of the result (checked against the free memory) and the algorithmic bytes
+  std::vector<int64_t> h_po((size_t)B + 1), h_ro((size_t)B + 1);
+  HIP_TRY(hipMemcpyAsync(h_po.data(), e->pv.cell_pair_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(h_ro.data(), e->pv.cell_read_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  int64_t src_pairs = 0, src_reads = 0;
+  for (int32_t o = 0; o < N; ++o)
+    for (int s = 0; s < 2; ++s) {
+      const int32_t p = rq->parent[2 * (size_t)o + s];
+      if (p >= 0) { src_pairs += h_po[(size_t)p + 1] - h_po[(size_t)p]; src_reads += h_ro[(size_t)p + 1] - h_ro[(size_t)p]; }
+    }
+  {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t have = e->d_cmsnp.cap() + e->d_cmnrd.cap() + e->d_cmreads.cap();
+    const size_t worst = ((size_t)src_pairs * 8 + (size_t)src_reads + 64 * (size_t)N) * 17 / 16 + 4096;
+    if (worst > have && worst - have > free_b)
+      return set_error(DMX_ERR_NOMEM, "dmx_engine_compose: %d barcodes of up to %lld pairs and %lld reads may need %zu bytes, %zu are free",
+                       N, (long long)src_pairs, (long long)src_reads, worst, free_b);
+  }
+  if (int rc = e->d_cmparent.ensure(sizeof(int32_t) * 2 * (size_t)N)) return rc;
+  if (int rc = e->d_cmkeep.ensure(sizeof(uint64_t) * 2 * (size_t)N)) return rc;
+  if (int rc = e->d_cmcnt.ensure(sizeof(int64_t) * (2 * (size_t)N + 3))) return rc;
+  if (int rc = e->d_cmmax.ensure(sizeof(uint32_t) * (size_t)N)) return rc;
+  if (int rc = e->d_cmpoff.ensure(sizeof(int64_t) * ((size_t)N + 1))) return rc;
+  if (int rc = e->d_cmroff.ensure(sizeof(int64_t) * ((size_t)N + 1))) return rc;
+  HIP_TRY(hipMemcpyAsync(e->d_cmparent, rq->parent, sizeof(int32_t) * 2 * (size_t)N, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_cmkeep, rq->keep, sizeof(uint64_t) * 2 * (size_t)N, hipMemcpyHostToDevice, e->stream));
+  dmx_cmp::Ctx c{};
+  c.pv = e->pv; c.nrd_width = e->nrd_width; c.n_out = N; c.index_base = rq->index_base; c.seed = rq->seed;
+  c.parent = e->d_cmparent; c.keep = e->d_cmkeep;
+  c.cnt_pairs = e->d_cmcnt; c.cnt_reads = e->d_cmcnt + N; c.cnt_max = e->d_cmmax;
+  int64_t* d_totals = e->d_cmcnt + 2 * (size_t)N;
+  const dim3 grid((unsigned)((N + dmx_cmp::kWaves - 1) / dmx_cmp::kWaves)), block(64 * dmx_cmp::kWaves);
+  if (int rc = e->cmev[0].record_start(e->stream)) return rc;
+  hipLaunchKernelGGL(dmx_cmp::k_compose<false>, grid, block, 0, e->stream, c);
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->cmev[0].record_stop(e->stream)) return rc;
+  if (int rc = e->cmev[1].record_start(e->stream)) return rc;
+  hipLaunchKernelGGL(dmx_cmp::k_compose_scan, dim3(1), dim3(1024), 0, e->stream, (const int64_t*)c.cnt_pairs, (const int64_t*)c.cnt_reads,
+                     (const uint32_t*)c.cnt_max, N, e->d_cmpoff.get(), e->d_cmroff.get(), d_totals);
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->cmev[1].record_stop(e->stream)) return rc;
+  int64_t totals[3] = {0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(totals, d_totals, sizeof totals, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the sizes decide the allocation and the width; rq's arrays may go away after return
+  const int64_t P = totals[0], R = totals[1];
+  if (P < 0 || R < 0 || P > src_pairs || R > src_reads)
+    return set_error(DMX_ERR_HIP, "dmx_engine_compose: the count pass returned %lld pairs and %lld reads from %lld and %lld", (long long)P, (long long)R,
+                     (long long)src_pairs, (long long)src_reads);
+  const int need_w = totals[2] <= 0xFF ? 1 : totals[2] <= 0xFFFF ? 2 : 4;
+  const int w = std::max(e->nrd_width, need_w);
+  if (int rc = e->d_cmsnp.ensure(sizeof(int32_t) * (size_t)P + 16)) return rc;
+  if (int rc = e->d_cmnrd.ensure((size_t)P * (size_t)w + 16)) return rc;
+  if (int rc = e->d_cmreads.ensure((size_t)R + 64)) return rc;   // (slack: the lean K1 reads four bytes at a time)
+  c.o_pair_off = e->d_cmpoff; c.o_read_off = e->d_cmroff;
+  c.o_snp = e->d_cmsnp; c.o_nrd = e->d_cmnrd.get(); c.o_width = w; c.o_reads = e->d_cmreads;
+  if (int rc = e->cmev[2].record_start(e->stream)) return rc;
+  hipLaunchKernelGGL(dmx_cmp::k_compose<true>, grid, block, 0, e->stream, c);
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->cmev[2].record_stop(e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  float ms[3] = {0.f, 0.f, 0.f};
+  for (int i = 0; i < 3; ++i) if (int rc = e->cmev[i].elapsed_ms(&ms[i])) return rc;
+  dmx_compose_info& inf = e->comp_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.n_pairs = P; inf.n_reads = R; inf.n_out = N; inf.nrd_width = w;
+  inf.count_ms = ms[0]; inf.scan_ms = ms[1]; inf.fill_ms = ms[2];
+  const int64_t src_pair_bytes = (e->pv.pair_snp ? 4 : 0) + e->nrd_width;
+  inf.bytes_read = 2 * src_pairs * src_pair_bytes + R + 2 * (int64_t)N * 24 + (int64_t)N * 20 + 16 * ((int64_t)N + 1);
+  inf.bytes_written = P * (4 + w) + R + (int64_t)N * 20 + 16 * ((int64_t)N + 1);
+  e->have_comp = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_composed_pileup(dmx_engine* e, dmx_pileup* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_composed_pileup: null argument");
+  if (!e->have_comp) return set_error(DMX_ERR_STATE, "dmx_engine_composed_pileup: nothing composed on the staged pileup (dmx_engine_compose first)");
+  std::memset(out, 0, sizeof *out);
+  out->n_cells = e->comp_info.n_out; out->n_snps = e->pv.S;
+  out->n_pairs = e->comp_info.n_pairs; out->n_reads = e->comp_info.n_reads;
+  out->cell_pair_off = e->d_cmpoff; out->cell_read_off = e->d_cmroff;
+  out->pair_snp = e->d_cmsnp; out->pair_nrd = e->d_cmnrd.get(); out->nrd_width = e->comp_info.nrd_width;
+  out->memory = DMX_MEM_DEVICE; out->reads = e->d_cmreads;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_composed(dmx_engine* e, int64_t* cell_pair_off, int64_t* cell_read_off, int32_t* pair_snp, void* pair_nrd, uint8_t* reads) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_composed: null engine");
+  if (!e->have_comp) return set_error(DMX_ERR_STATE, "dmx_engine_get_composed: nothing composed on the staged pileup (dmx_engine_compose first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t N = (size_t)e->comp_info.n_out, P = (size_t)e->comp_info.n_pairs, R = (size_t)e->comp_info.n_reads, w = (size_t)e->comp_info.nrd_width;
+  if (cell_pair_off) HIP_TRY(hipMemcpy(cell_pair_off, e->d_cmpoff, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost));
+  if (cell_read_off) HIP_TRY(hipMemcpy(cell_read_off, e->d_cmroff, sizeof(int64_t) * (N + 1), hipMemcpyDeviceToHost));
+  if (pair_snp && P) HIP_TRY(hipMemcpy(pair_snp, e->d_cmsnp, sizeof(int32_t) * P, hipMemcpyDeviceToHost));
+  if (pair_nrd && P) HIP_TRY(hipMemcpy(pair_nrd, e->d_cmnrd, P * w, hipMemcpyDeviceToHost));
+  if (reads && R) HIP_TRY(hipMemcpy(reads, e->d_cmreads, R, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_compose_info(dmx_engine* e, dmx_compose_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_compose_info: null argument");
+  if (!e->have_comp) return set_error(DMX_ERR_STATE, "dmx_engine_compose_info: nothing composed on the staged pileup (dmx_engine_compose first)");
+  *out = e->comp_info;
   return DMX_OK;
 }
 

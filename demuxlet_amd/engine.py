@@ -700,6 +700,54 @@ class Engine:
         check(self._L.dmx_engine_triplet_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.TripletInfo._fields_ if not n.startswith("reserved")}
 
+    def compose(self, parent, keep, seed: int, index_base: int = 0) -> dict:
+        """dmx_engine_compose over the staged pileup: output barcode o takes the reads of cells parent[o][0] and parent[o][1] (-1 = none),
+        each read kept iff its 32-bit hash is below keep[o][slot] (0 .. 2^32; 2^32 keeps all); output o is hashed as id index_base + o,
+        so that a recipe composed in chunks gives the same barcodes.  Returns the info dict (compose_info)."""
+        pr = np.ascontiguousarray(parent, dtype=np.int32)
+        kp = np.ascontiguousarray(keep, dtype=np.uint64)
+        if pr.ndim != 2 or pr.shape[1] != 2 or kp.shape != pr.shape:
+            raise ValueError("parent and keep must both be [n_out][2]")
+        rq = capi.ComposeRequest(pr.shape[0], 0, int(index_base), pr.ctypes.data if pr.size else None, kp.ctypes.data if kp.size else None,
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF)
+        check(self._L.dmx_engine_compose(self._h, C.byref(rq)))
+        return self.compose_info()
+
+    def compose_info(self) -> dict:
+        """Sizes, algorithmic bytes and HIP-event times (ms) of the last compose (dmx_engine_compose_info)."""
+        r = capi.ComposeInfo()
+        check(self._L.dmx_engine_compose_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.ComposeInfo._fields_ if n != "reserved"}
+
+    def composed_pileup(self) -> capi.Pileup:
+        """The composed pileup as a device-resident dmx_pileup (dmx_engine_composed_pileup) for another engine's set_pileup_struct or for
+        demuxlet_run; the rd_* counters are NULL (a caller that needs them attaches host arrays).  Owned by this engine: valid until its
+        next compose / set_pileup / close."""
+        st = capi.Pileup()
+        check(self._L.dmx_engine_composed_pileup(self._h, C.byref(st)))
+        return st
+
+    def composed_offsets(self):
+        """(cell_pair_off, cell_read_off) of the composed pileup alone: N.SNP and the kept reads of every output barcode."""
+        N = self.compose_info()["n_out"]
+        po = np.zeros(N + 1, dtype=np.int64); ro = np.zeros(N + 1, dtype=np.int64)
+        check(self._L.dmx_engine_get_composed(self._h, po.ctypes.data, ro.ctypes.data, None, None, None))
+        return po, ro
+
+    def get_composed(self) -> HostPileup:
+        """The composed pileup copied to the host (dmx_engine_get_composed).  Its rd_totl = rd_pass = rd_uniq are SYNTHETIC: the kept reads
+        of each barcode — a composed barcode has no scan behind it, so there is no count of reads that failed a filter or repeated a UMI."""
+        inf = self.compose_info()
+        N, P, R = inf["n_out"], inf["n_pairs"], inf["n_reads"]
+        po = np.zeros(N + 1, dtype=np.int64); ro = np.zeros(N + 1, dtype=np.int64)
+        snp = np.zeros(P, dtype=np.int32)
+        nrd = np.zeros(P, dtype={1: np.uint8, 2: np.uint16, 4: np.uint32}[inf["nrd_width"]])
+        reads = np.zeros(R, dtype=np.uint8)
+        check(self._L.dmx_engine_get_composed(self._h, po.ctypes.data, ro.ctypes.data, snp.ctypes.data if P else None,
+                                              nrd.ctypes.data if P else None, reads.ctypes.data if R else None))
+        kept = np.diff(ro).astype(np.int32)
+        return HostPileup(N, self.S, po, ro, snp, nrd, reads, kept, kept.copy(), kept.copy())
+
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()
         check(self._L.dmx_engine_device_view(self._h, C.byref(v)))

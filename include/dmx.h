@@ -38,7 +38,8 @@ extern "C" {
                                likelihood with a soup term, to tell soupy singlets from doublets); dmx_engine_triplet / _get_triplet /
                                _triplet_info (a base pair with every sample as a third donor); dmx_engine_cluster_evidence /
                                _cluster_hard / _get_cluster_hard / _cluster_hard_device_ptr / _cluster_merge_columns / _cluster_k_info (choosing the number
-                               of clusters).  Additions only. */
+                               of clusters); dmx_engine_compose / _composed_pileup / _get_composed / _compose_info (barcodes composed on
+                               the device from other barcodes' reads).  Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -723,6 +724,51 @@ int dmx_engine_triplet(dmx_engine*, const dmx_triplet_request*);
 /* Device->host copies of the last profile (any pointer may be NULL): ll[B][C][T][V] f64, n_snp[B][C][V] / n_read[B][C][V] i32. */
 int dmx_engine_get_triplet(dmx_engine*, double* ll, int32_t* n_snp, int32_t* n_read);
 int dmx_engine_triplet_info(dmx_engine*, dmx_triplet_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Pileup composer (no counterpart in the reference): new barcodes made on the device from the reads of one or two
+ * barcodes of the staged pileup, each read kept or dropped by a hash — in-silico doublets and thinned barcodes for power curves
+ * (demuxlet_amd/simulate.py).  All integer; the result is defined bit for bit:
+ *   mix64(z):  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) * 0x94D049BB133111EB;  return z ^ z >> 31   (mod 2^64)
+ *   for output o (id i = index_base + o), slot s in {0, 1}, SNP id n and read index r within the parent's pair:
+ *     u = mix64(mix64(seed + 0x9E3779B97F4A7C15 * (2 i + s + 1)) + (n << 32 | r)) >> 32;   the read is kept iff u < keep[o][s].
+ *   The hash sees the SNP id and the in-pair index only, so the result depends neither on the source's layout (dense or sparse) or
+ *   nrd_width nor on the other rows of the recipe: a recipe composed in chunks (index_base) gives the same barcodes.
+ *   A parent pair with stored reads survives iff it keeps at least one; a pair without stored reads (allele-2-only, see dmx_pileup)
+ *   is decided as if it held one read of index 0.  Output o's pairs are the ascending union of the SNPs of both slots' surviving
+ *   pairs; a pair's reads are slot 0's kept reads in stored order, then slot 1's.  parent[o][0] == parent[o][1] is allowed.
+ *   The output is always sparse; its nrd_width is the source's, widened to the smallest of {1, 2, 4} that holds every merged count.
+ * Three kernels (count, scan, fill), plain vector stores, no atomics: the bits do not depend on scheduling.  The call runs on the
+ * engine's stream, synchronises it before returning and leaves every other result of the engine as it was.
+ * DMX_ERR_ARG: a parent outside [0, n_cells) (slot 1: or -1 = none), keep > 2^32, n_out < 1 or > 2^24 (a longer recipe is composed in
+ * chunks by index_base), a null array.  DMX_ERR_STATE: no staged
+ * pileup, the staged pileup is this engine's own composed one, or _composed_pileup / _get_composed / _compose_info before a compose.
+ * DMX_ERR_NOMEM: the composed pileup does not fit the free device memory. */
+typedef struct {
+  int32_t n_out;            /* output barcodes, 1 .. 2^24 */
+  int32_t reserved0;        /* 0 */
+  int64_t index_base;       /* output o is hashed as id index_base + o */
+  const int32_t*  parent;   /* [n_out][2] cells of the staged pileup; slot 1 may be -1 (one parent); HOST */
+  const uint64_t* keep;     /* [n_out][2] thresholds in [0, 2^32]: a read is kept iff its 32-bit hash < keep; 2^32 keeps all; HOST */
+  uint64_t seed;
+  int32_t reserved[4];      /* 0 */
+} dmx_compose_request;
+typedef struct {
+  int64_t n_pairs, n_reads;           /* of the composed pileup */
+  int64_t bytes_read, bytes_written;  /* algorithmic device bytes of the three kernels: the parents' pair_snp / pair_nrd twice (count and
+                                         fill), the kept read bytes, the recipe and the counts; the composed arrays and the counts */
+  double  count_ms, scan_ms, fill_ms; /* HIP-event times of k_compose<count>, k_compose_scan, k_compose<fill> */
+  int32_t n_out, nrd_width;
+  int32_t reserved[4];
+} dmx_compose_info;
+int dmx_engine_compose(dmx_engine*, const dmx_compose_request*);
+/* The composed pileup as a DMX_MEM_DEVICE view owned by the engine (rd_* NULL: the caller attaches host counters where a consumer
+ * needs them), for dmx_engine_set_pileup of ANOTHER engine or dmx_job.pileup; valid until the next compose / set_pileup / destroy. */
+int dmx_engine_composed_pileup(dmx_engine*, dmx_pileup* out);
+/* Device->host copies (any pointer may be NULL): cell_pair_off / cell_read_off [n_out + 1], pair_snp [n_pairs], pair_nrd [n_pairs] of
+ * nrd_width bytes, reads [n_reads]. */
+int dmx_engine_get_composed(dmx_engine*, int64_t* cell_pair_off, int64_t* cell_read_off, int32_t* pair_snp, void* pair_nrd, uint8_t* reads);
+int dmx_engine_compose_info(dmx_engine*, dmx_compose_info* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * a6,a10..a14  finaliser and writers — replaces cmd_cram_demuxlet.cpp:465-527 (.single), :713-875 (.sing2/.pair/.best).
