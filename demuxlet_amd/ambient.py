@@ -12,7 +12,7 @@ RHO is the grid point of the highest LL (the lowest one on ties), RHO.LO / RHO.H
 1.92 (half the 95 % chi-square quantile of one degree of freedom) of that maximum, LLK.0 the LL at rho = 0 and LLR = LLK.RHO - LLK.0.
 A doublet called as a singlet also looks like a high-rho singlet: a high RHO is a QC signal, not a proof of soup.
 
-    python -m demuxlet_amd.ambient --pileup <x>.pileup.txt --out <prefix> [--best <x>.best] [--min-prb P] [--ambient reads|genotypes]
+    python -m demuxlet_amd.ambient --pileup <x>.pileup.txt --out <prefix> [--best <x>.best] [--min-prb P] [--ambient reads|genotypes|census]
         [--grid-max 0.5] [--grid-step 0.01 | --grid R ...] [--alpha A ...] [--doublets [--dbl-alpha A ...]] [--fast] [--gpu G]
 
 reads the dump that `demuxlet --pileup-only` writes.  Without --best, the unchanged demultiplexing pass runs first and writes
@@ -115,6 +115,24 @@ def ambient_from_reads(eng: engine.Engine, g: np.ndarray) -> np.ndarray:
     return ambient_from_counts(n_ref[:, 0], n_alt[:, 0])
 
 
+def ambient_from_census(eng: engine.Engine, g: np.ndarray) -> np.ndarray:
+    """a_i = sum over v of w_v d_iv with w the maximum-likelihood donor shares of ALL barcodes' reads (Engine.census with one group;
+    census.py): the shares follow the reads, so RNA content and which donor's cells lysed are in them, and the
+    profile has the variance of V estimated shares at every SNP, however few reads it has.  0.5 at a SNP where a donor's genotype
+    row is all zero (the census leaves such SNPs out)."""
+    from . import census
+    w = eng.census(np.zeros(eng.B, dtype=np.int32), n_groups=1)["w"][0]
+    return np.clip(np.nan_to_num(census.ambient_profile(w, g), nan=0.5), 0.0, 1.0)
+
+
+def _ambient_builder(ambient: str, eng: engine.Engine, g: np.ndarray, assign_fn) -> np.ndarray:
+    if ambient == "reads":
+        return ambient_from_reads(eng, g)
+    if ambient == "census":
+        return ambient_from_census(eng, g)
+    return ambient_from_genotypes(g, assign_fn())
+
+
 @dataclass
 class Summary:
     """Per-barcode estimates from a profile ll[B][Q] (rows of unassigned barcodes are meaningless)."""
@@ -175,13 +193,13 @@ def ambient_run(store_or_pileup, g: np.ndarray, sample_ids: Sequence[str], out_p
                 grid=None, min_prb: float = 0.0, alphas: Sequence[float] = (0.0, 0.5), barcodes: Optional[Sequence[str]] = None,
                 device: int = 0, mode: int = capi.DMX_MODE_STRICT, **demuxlet_run_kwargs):
     """Profile the singlets of `best` (a `.best` path) against genotype matrix g.  Without `best`, the unchanged demuxlet_run writes
-    <out_prefix>.best/.single/.sing2 first and its `.best` is used.  `ambient` is "reads", "genotypes" or an array of n_snps frequencies.
+    <out_prefix>.best/.single/.sing2 first and its `.best` is used.  `ambient` is "reads", "genotypes", "census" or an array of n_snps frequencies.
     `store_or_pileup` is a Store, or a HostPileup with barcodes=... as for demuxlet_run.  Writes <out_prefix>.ambient.tsv and
     .ambient_pool.tsv; returns a dict with the profile, counts, summary, pool profile and pool estimate."""
     g = np.ascontiguousarray(g, dtype=np.float32)
     grid = default_grid() if grid is None else check_grid(grid)
-    if isinstance(ambient, str) and ambient not in ("reads", "genotypes"):
-        raise ValueError(f"ambient: 'reads', 'genotypes' or an array, not {ambient!r}")
+    if isinstance(ambient, str) and ambient not in ("reads", "genotypes", "census"):
+        raise ValueError(f"ambient: 'reads', 'genotypes', 'census' or an array, not {ambient!r}")
     if isinstance(store_or_pileup, engine.HostPileup):
         pl = store_or_pileup
         if barcodes is None:
@@ -201,7 +219,7 @@ def ambient_run(store_or_pileup, g: np.ndarray, sample_ids: Sequence[str], out_p
         eng.set_genotypes(g)
         eng.set_pileup(pl)
         if isinstance(ambient, str):
-            a = ambient_from_reads(eng, g) if ambient == "reads" else ambient_from_genotypes(g, assign)
+            a = _ambient_builder(ambient, eng, g, lambda: assign)
         else:
             a = ambient
         ll, n_snp, n_read = eng.ambient_profile(assign, a, grid)
@@ -367,8 +385,8 @@ def ambient_calls_run(store_or_pileup, g: np.ndarray, sample_ids: Sequence[str],
     g = np.ascontiguousarray(g, dtype=np.float32)
     grid = default_grid() if grid is None else check_grid(grid)
     dal = dbl_alphas_from_run(alphas) if dbl_alphas is None else check_dbl_alphas(dbl_alphas)
-    if isinstance(ambient, str) and ambient not in ("reads", "genotypes"):
-        raise ValueError(f"ambient: 'reads', 'genotypes' or an array, not {ambient!r}")
+    if isinstance(ambient, str) and ambient not in ("reads", "genotypes", "census"):
+        raise ValueError(f"ambient: 'reads', 'genotypes', 'census' or an array, not {ambient!r}")
     if isinstance(store_or_pileup, engine.HostPileup):
         pl = store_or_pileup
         if barcodes is None:
@@ -389,8 +407,7 @@ def ambient_calls_run(store_or_pileup, g: np.ndarray, sample_ids: Sequence[str],
         eng.set_genotypes(g)
         eng.set_pileup(pl)
         if isinstance(ambient, str):
-            a = ambient_from_reads(eng, g) if ambient == "reads" else \
-                ambient_from_genotypes(g, refine.assignments_from_best(best, sample_ids, barcodes))
+            a = _ambient_builder(ambient, eng, g, lambda: refine.assignments_from_best(best, sample_ids, barcodes))
         else:
             a = ambient
         ll1, n_snp, n_read = eng.ambient_profile(rows.sng1, a, grid)
@@ -410,8 +427,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--out", required=True, help="output prefix: <out>.ambient.tsv, <out>.ambient_pool.tsv (and <out>.best/... without --best)")
     ap.add_argument("--best", help="a .best of this pileup: its singlets are profiled (default: run the demultiplexing pass first)")
     ap.add_argument("--min-prb", type=float, default=0.0, help="use only singlets with PRB.SNG1 >= this (default: all SNG- calls)")
-    ap.add_argument("--ambient", choices=("reads", "genotypes"), default="reads",
-                    help="soup ALT frequency: pooled reads of every barcode (default) or the singlet-weighted genotype mean")
+    ap.add_argument("--ambient", choices=("reads", "genotypes", "census"), default="reads",
+                    help="soup ALT frequency: pooled reads of every barcode (default), the singlet-weighted genotype mean, or the genotype "
+                         "mean weighted by the donor shares of all barcodes' reads (census.py)")
     ap.add_argument("--grid-max", type=float, default=0.5, help="largest contamination fraction of the default grid (default 0.5)")
     ap.add_argument("--grid-step", type=float, default=0.01, help="step of the default grid (default 0.01)")
     ap.add_argument("--grid", type=float, nargs="+", help="explicit grid of contamination fractions (replaces --grid-max / --grid-step)")

@@ -47,6 +47,7 @@ SYMBOLS = [
     "dmx_engine_ambient_doublet", "dmx_engine_get_ambient_doublet", "dmx_engine_ambient_doublet_info",
     "dmx_engine_triplet", "dmx_engine_get_triplet", "dmx_engine_triplet_info",
     "dmx_engine_compose", "dmx_engine_composed_pileup", "dmx_engine_get_composed", "dmx_engine_compose_info",
+    "dmx_engine_census_step", "dmx_engine_census", "dmx_engine_get_census", "dmx_engine_census_info",
 ]
 
 
@@ -184,6 +185,23 @@ class ComposeInfo(C.Structure):        # dmx_compose_info
     _fields_ = [("n_pairs", C.c_int64), ("n_reads", C.c_int64), ("bytes_read", C.c_int64), ("bytes_written", C.c_int64),
                 ("count_ms", C.c_double), ("scan_ms", C.c_double), ("fill_ms", C.c_double), ("n_out", C.c_int32), ("nrd_width", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
+
+
+class CensusStepRequest(C.Structure):  # dmx_census_step_request
+    _fields_ = [("n_cells", C.c_int32), ("group_memory", C.c_int32), ("group", C.c_void_p), ("n_groups", C.c_int32), ("n_samples", C.c_int32),
+                ("w", C.c_void_p), ("acc", C.c_void_p), ("ll", C.c_void_p), ("gap", C.c_void_p), ("n_read", C.c_void_p), ("n_pair", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class CensusRequest(C.Structure):      # dmx_census_request
+    _fields_ = [("n_cells", C.c_int32), ("group_memory", C.c_int32), ("group", C.c_void_p), ("n_groups", C.c_int32), ("n_samples", C.c_int32),
+                ("w0", C.c_void_p), ("tol", C.c_double), ("max_steps", C.c_int32), ("accelerate", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class CensusInfo(C.Structure):         # dmx_census_info
+    _fields_ = [("kernel_ms", C.c_double), ("dosage_ms", C.c_double), ("dosage_bytes", C.c_int64), ("partial_bytes", C.c_int64),
+                ("n_steps", C.c_int32), ("n_invalid_snps", C.c_int32), ("n_groups", C.c_int32), ("n_chunks", C.c_int32), ("n_cells", C.c_int32),
+                ("n_samples", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class DmxError(RuntimeError):
@@ -331,6 +349,8 @@ def load() -> C.CDLL:
         "dmx_engine_triplet": [vp, vp], "dmx_engine_get_triplet": [vp, vp, vp, vp], "dmx_engine_triplet_info": [vp, vp],
         "dmx_engine_compose": [vp, vp], "dmx_engine_composed_pileup": [vp, vp], "dmx_engine_get_composed": [vp, vp, vp, vp, vp, vp],
         "dmx_engine_compose_info": [vp, vp],
+        "dmx_engine_census_step": [vp, vp], "dmx_engine_census": [vp, vp], "dmx_engine_get_census": [vp, vp, vp, vp, vp, vp, vp, vp],
+        "dmx_engine_census_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

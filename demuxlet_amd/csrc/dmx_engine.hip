@@ -2846,6 +2846,200 @@ __global__ __launch_bounds__(64 * kAmbWaves) void k_ambient(PileupView pv, int n
   if (qb == 0 && lane == 0) { n_snp[cell] = ns; n_read[cell] = nr; }
 }
 
+// ---- donor shares of a read pool (dmx_engine_census_step / dmx_engine_census) -----------------------------------
+// Every stored read of a group of barcodes is a draw from a mixture of the V donors with shares w.  One pass at w gives, per group,
+//   acc[v] = sum over pairs of (1 - d[i][v]) sR + d[i][v] sA,  sR = sum over the pair's reads of pR / P_r,  sA = sum of pA / P_r,
+//   LL = sum of log P_r,  P_r = pR (1 - A_i) + pA A_i,  A_i = sum over v, ascending, of w[v] d[i][v]
+// (every product and sum rounded on its own: the build has no contraction).  The summation plan depends on the pileup, the group's own
+// members and V only: a group's barcodes in ascending cell id are cut into chunks of kCenChunk; one wavefront walks a chunk's barcodes in
+// that order and each barcode's pairs in stored order, 64 pairs (a tile) at a time.
+//   Phase 1, lane = pair: read count and read offset by a DPP scan, the serial V-long dot product A_i with w in LDS, then the pair's
+//   reads: two divisions and one dmx_log per read; a lane keeps a running LL and its counts; sR, sA and the SNP go to the tile in LDS.
+//   Phase 2, lane = donor (blocks of 64 up to V): the lane adds the tile's pairs in order to its donor's sum, which lives in LDS
+//   between tiles.  A pair without stored reads or at an invalid SNP has sR = sA = 0 and adds +0.  For V <= 32 the 64 lanes form
+//   nsub = 64 / Vq sets of Vq lanes (Vq the power of two >= V); set s adds the tile's pairs s, s + nsub, ... and the sets' sums are
+//   added in set order at the end of the chunk.
+// At the end of the chunk the 64 lanes' LL are added serially in lane order.  k_census_fold adds a group's chunk partials: chunk c goes
+// to accumulator c mod 8 in chunk order, then ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)).  No floating-point atomics anywhere.
+constexpr int kCenWaves = 4;                     // wavefronts (chunks) per workgroup; they share the log and read tables
+constexpr int kCenChunk = 4;                     // barcodes per chunk
+constexpr int kCenMaxV = 1024, kCenMaxG = 1024;
+struct CenChunk { int32_t g, beg, cnt, pad; };   // group, first index into the group-sorted cell list, barcodes
+struct CenPair { double sR, sA; int32_t snp, pad; };
+
+// d[i][v] = (gp1 / 2 + gp2) / (gp0 + gp1 + gp2) in float64; a row whose sum is not a positive finite number gets d = 0 and clears the
+// SNP's valid flag (every lane that clears it stores the same byte).
+__global__ __launch_bounds__(256) void k_census_dosage(const float* __restrict__ g, int64_t n, int32_t V, double* __restrict__ d,
+                                                       uint8_t* __restrict__ valid) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n) return;
+  const double g0 = g[3 * t], g1 = g[3 * t + 1], g2 = g[3 * t + 2];
+  const double den = (g0 + g1) + g2;
+  const bool ok = den > 0.0 && den < INFINITY;
+  d[t] = ok ? (g1 * 0.5 + g2) / den : 0.0;
+  if (!ok) valid[t / V] = 0;
+}
+
+__global__ __launch_bounds__(64 * kCenWaves) void k_census_step(PileupView pv, int nrd_width, const double* __restrict__ tabs,
+                                                              const double* __restrict__ d, const uint8_t* __restrict__ valid, int32_t V,
+                                                              const int32_t* __restrict__ order, const CenChunk* __restrict__ chunks,
+                                                              int32_t n_chunks, const uint8_t* __restrict__ active,
+                                                              const double* __restrict__ w, double* __restrict__ part,
+                                                              int64_t* __restrict__ pcnt) {
+  extern __shared__ double s_dyn[];              // per wavefront: w[Vp] | acc[Vp], Vp = V rounded up to 64
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_pra[256][2];               // by read byte (allele << 7 | bq): {pR, pA}
+  __shared__ CenPair s_tile[kCenWaves][64];
+  __shared__ int64_t s_cnt[kCenWaves][64][2];
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += 64 * kCenWaves) s_log[i] = tabs[kLut + i];
+  for (int i = threadIdx.x; i < 256; i += 64 * kCenWaves) {
+    const double mat = tabs[i & 127], e3 = tabs[128 + (i & 127)];
+    s_pra[i][0] = (i >> 7) ? e3 : mat;
+    s_pra[i][1] = (i >> 7) ? mat : e3;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int32_t chunk = (int32_t)blockIdx.x * kCenWaves + wave;
+  if (chunk >= n_chunks) return;
+  const int32_t grp = __builtin_amdgcn_readfirstlane(chunks[chunk].g);
+  const int32_t c_beg = __builtin_amdgcn_readfirstlane(chunks[chunk].beg), c_cnt = __builtin_amdgcn_readfirstlane(chunks[chunk].cnt);
+  if (!active[grp]) return;                      // a frozen group: its partials and results stay
+  const int32_t Vp = (V + 63) & ~63;
+  int qshift = 6;                                // V <= 32: Vq = the power of two >= V, nsub = 64 / Vq lane sets share phase 2
+  while (qshift > 0 && (1 << (qshift - 1)) >= V) --qshift;
+  const int32_t Vq = 1 << qshift, nsub = 64 >> qshift;
+  double* sw = s_dyn + (size_t)wave * 2 * Vp;
+  double* sa = sw + Vp;
+  for (int32_t v = lane; v < Vp; v += 64) { sw[v] = v < V ? w[(size_t)grp * V + v] : 0.0; sa[v] = 0.0; }
+  DMX_WAVE_LDS_ORDER();
+  CenPair* tile = s_tile[wave];
+  const DmxLogPins lk = dmx_log_pins();
+  double ll = 0.0;
+  int64_t nr = 0, np = 0;
+  for (int32_t c = 0; c < c_cnt; ++c) {
+    const int32_t cell = __builtin_amdgcn_readfirstlane(order[c_beg + c]);
+    const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+    int64_t rd_base = pv.cell_read_off[cell];
+    for (int64_t p0 = p_beg; p0 < p_end; p0 += 64) {
+      const int64_t p = p0 + lane;
+      const bool in = p < p_end;
+      const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+      const uint32_t incl = seg_scan_incl<64>(n);
+      const int64_t off = rd_base + (int64_t)(incl - n);
+      rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      const int32_t snp = in ? (pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg)) : 0;
+      const bool use = n > 0 && valid[snp];
+      const double* dr = d + (size_t)snp * V;
+      double A = 0.0;
+      for (int32_t v = 0; v < V; ++v) A = A + sw[v] * dr[v];
+      const double q = 1.0 - A;
+      double sR = 0.0, sA = 0.0;
+      if (use) {
+        uint32_t wd = 0;
+        for (uint32_t r = 0; r < n; ++r) {
+          if ((r & 3) == 0) wd = load_rd4(pv, off + r, n - r);
+          const uint32_t byte = (wd >> (8 * (r & 3))) & 0xFF;
+          const double pR = s_pra[byte][0], pA = s_pra[byte][1];
+          const double P = pR * q + pA * A;
+          sR += pR / P; sA += pA / P;
+          ll += dmx_log_is_special(P) ? log(P) : dmx_log_fast_pinned(P, s_log, lk);
+        }
+        nr += (int64_t)n; np += 1;
+      }
+      CenPair t;
+      t.sR = sR; t.sA = sA; t.snp = use ? snp : 0; t.pad = 0;
+      tile[lane] = t;
+      DMX_WAVE_LDS_ORDER();
+      const int cnt = (int)min<int64_t>(64, p_end - p0);
+      if (nsub > 1) {                              // V <= 32: nsub sets of Vq lanes, set s takes the tile's pairs s, s + nsub, ...
+        const int32_t v = lane & (Vq - 1), vv = v < V ? v : 0;
+        double a = sa[lane];
+#pragma unroll 4
+        for (int j = lane >> qshift; j < cnt; j += nsub) {
+          const double dv = d[(size_t)tile[j].snp * V + vv];
+          a += (1.0 - dv) * tile[j].sR + dv * tile[j].sA;
+        }
+        sa[lane] = a;
+      } else {
+        for (int32_t v0 = 0; v0 < Vp; v0 += 64) {
+          const int32_t v = v0 + lane, vv = v < V ? v : 0;   // lanes past V run along on donor 0; their sums are never written out
+          double a = sa[v];
+#pragma unroll 4
+          for (int j = 0; j < cnt; ++j) {
+            const double dv = d[(size_t)tile[j].snp * V + vv];
+            a += (1.0 - dv) * tile[j].sR + dv * tile[j].sA;
+          }
+          sa[v] = a;
+        }
+      }
+      DMX_WAVE_LDS_ORDER();
+    }
+  }
+  double* out = part + (size_t)chunk * ((size_t)V + 1);
+  if (nsub > 1) {
+    if (lane < V) {
+      double a = 0.0;
+      for (int s = 0; s < nsub; ++s) a += sa[s * Vq + lane];
+      out[lane] = a;
+    }
+  } else {
+    for (int32_t v = lane; v < V; v += 64) out[v] = sa[v];
+  }
+  tile[lane].sR = ll;
+  s_cnt[wave][lane][0] = nr; s_cnt[wave][lane][1] = np;
+  DMX_WAVE_LDS_ORDER();
+  if (lane == 0) {
+    double s = 0.0;
+    int64_t a = 0, b = 0;
+    for (int j = 0; j < 64; ++j) { s += tile[j].sR; a += s_cnt[wave][j][0]; b += s_cnt[wave][j][1]; }
+    out[V] = s;
+    pcnt[2 * (size_t)chunk] = a; pcnt[2 * (size_t)chunk + 1] = b;
+  }
+}
+
+// One workgroup per group: out[g] = acc[V] | LL | gap | N (as a double), cnt[g] = {reads, pairs}.  gap = N (max_v acc_v / N - 1), 0 for
+// a group without a counted read.
+__global__ __launch_bounds__(256) void k_census_fold(const double* __restrict__ part, const int64_t* __restrict__ pcnt,
+                                                     const int32_t* __restrict__ chunk_off, const uint8_t* __restrict__ active, int32_t V,
+                                                     double* __restrict__ out, int64_t* __restrict__ cnt) {
+  __shared__ double s_max[256];
+  const int32_t g = blockIdx.x, tid = threadIdx.x;
+  if (!active[g]) return;
+  const int32_t c0 = chunk_off[g], c1 = chunk_off[g + 1];
+  const size_t stride = (size_t)V + 1;
+  auto fold8 = [&](int32_t col) {
+    double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int32_t c = c0; c < c1; c += 8) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) if (c + k < c1) a[k] += part[(size_t)(c + k) * stride + col];
+    }
+    return ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  };
+  double* o = out + (size_t)g * ((size_t)V + 3);
+  double mx = 0.0;
+  for (int32_t v = tid; v < V; v += 256) {
+    const double x = fold8(v);
+    o[v] = x;
+    mx = fmax(mx, x);
+  }
+  s_max[tid] = mx;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s) s_max[tid] = fmax(s_max[tid], s_max[tid + s]);
+    __syncthreads();
+  }
+  if (tid == 0) {
+    int64_t nr = 0, np = 0;
+    for (int32_t c = c0; c < c1; ++c) { nr += pcnt[2 * (size_t)c]; np += pcnt[2 * (size_t)c + 1]; }
+    const double N = (double)nr;
+    o[V] = fold8(V);
+    o[V + 1] = nr > 0 ? N * (s_max[0] / N - 1.0) : 0.0;
+    o[V + 2] = N;
+    cnt[2 * (size_t)g] = nr; cnt[2 * (size_t)g + 1] = np;
+  }
+}
+
 // ---- ambient-aware doublet profile (dmx_engine_ambient_doublet) --------------------------------------------------
 // For a barcode b, a candidate pair (v1, v2), a mixing share alpha of v2 and a grid point rho:
 //   p_lm = (1 - rho) (0.5 l + (m - l) 0.5 alpha) + rho a_i,   f_lm = product over the pair's stored reads of pR (1 - p_lm) + pA p_lm,
@@ -7198,6 +7392,20 @@ struct dmx_engine {
   bool have_comp = false;
   EventPair cmev[3];
   dmx_compose_info comp_info{};
+  // donor shares of a read pool (dmx_engine_census_step / dmx_engine_census): the dosage table d[S][V] and the SNPs' valid flags, the
+  // group-sorted cell list and its chunks, the shares and active flags of a pass, the chunk partials and the folded results; the
+  // last driver run's results stay on the host
+  DevBuf<double> d_cnd; DevBuf<uint8_t> d_cnvalid;
+  DevBuf<int32_t> d_cnorder, d_cnoff; DevBuf<CenChunk> d_cnchunk;
+  DevBuf<double> d_cnw; DevBuf<uint8_t> d_cnact;
+  DevBuf<double> d_cnpart, d_cnout; DevBuf<int64_t> d_cnpcnt, d_cncnt;
+  EventPair cnev;
+  dmx_census_info cen_info{};
+  bool have_cen_info = false, have_census = false;
+  int32_t cn_G = 0;
+  std::vector<double> cn_w, cn_ll, cn_gap;
+  std::vector<int32_t> cn_steps, cn_conv;
+  std::vector<int64_t> cn_nread, cn_npair;
 };
 
 namespace {
@@ -7728,6 +7936,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_adbl = false; e->have_cdbl = false;
   e->have_trip = false;
   e->have_comp = false;
+  e->have_census = false; e->have_cen_info = false;
   e->have_pileup = true;
   e->k1_fn = e->k2_fn = e->k3b_fn = nullptr; e->k1_placement = 0;      // nothing has run on this pileup yet
   return DMX_OK;
@@ -9965,6 +10174,274 @@ extern "C" int dmx_engine_compose_info(dmx_engine* e, dmx_compose_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_compose_info: null argument");
   if (!e->have_comp) return set_error(DMX_ERR_STATE, "dmx_engine_compose_info: nothing composed on the staged pileup (dmx_engine_compose first)");
   *out = e->comp_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Donor shares of a read pool.  census_prepare checks the arguments, sorts the barcodes by group (ascending cell
+// id within a group), cuts each group into chunks of kCenChunk, uploads the plan and builds the dosage table; census_pass is one
+// k_census_step + k_census_fold at the given shares for the active groups, with G (V + 3) doubles copied back.
+namespace {
+
+struct CensusPlan {
+  int32_t G = 0, V = 0, n_chunks = 0;
+  std::vector<int32_t> chunk_off;                // [G + 1]
+};
+
+int census_prepare(dmx_engine* e, const char* fn, int32_t n_cells, int32_t group_memory, const int32_t* group, int32_t G, int32_t n_samples,
+                   CensusPlan* plan) {
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "%s: no pileup staged (dmx_engine_set_pileup first)", fn);
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "%s: no genotype matrix (dmx_engine_set_genotypes first)", fn);
+  const int32_t B = e->pv.B, V = e->V, S = e->S;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "%s: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", fn, S, e->pv.S);
+  if (n_cells != B) return set_error(DMX_ERR_ARG, "%s: n_cells %d, the staged pileup has %d", fn, n_cells, B);
+  if (n_samples != V) return set_error(DMX_ERR_ARG, "%s: n_samples %d, the engine has %d", fn, n_samples, V);
+  if (V > kCenMaxV) return set_error(DMX_ERR_ARG, "%s: %d samples, at most %d", fn, V, kCenMaxV);
+  if (G < 1 || G > kCenMaxG) return set_error(DMX_ERR_ARG, "%s: n_groups %d is not in [1, %d]", fn, G, kCenMaxG);
+  if (B > 0 && !group) return set_error(DMX_ERR_ARG, "%s: missing group", fn);
+  if (group_memory != DMX_MEM_HOST && group_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "%s: group_memory %d", fn, group_memory);
+  HIP_TRY(hipSetDevice(e->device));
+  std::vector<int32_t> grp((size_t)B);
+  if (B > 0) {
+    if (group_memory == DMX_MEM_DEVICE) {
+      HIP_TRY(hipMemcpyAsync(grp.data(), group, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+      std::memcpy(grp.data(), group, sizeof(int32_t) * (size_t)B);
+    }
+  }
+  std::vector<int32_t> n_in((size_t)G + 1, 0);
+  for (int32_t b = 0; b < B; ++b) {
+    if (grp[(size_t)b] < -1 || grp[(size_t)b] >= G) return set_error(DMX_ERR_ARG, "%s: group[%d] = %d is not in [-1, %d)", fn, b, grp[(size_t)b], G);
+    if (grp[(size_t)b] >= 0) n_in[(size_t)grp[(size_t)b] + 1] += 1;
+  }
+  for (int32_t g = 0; g < G; ++g) n_in[(size_t)g + 1] += n_in[(size_t)g];          // first index of each group in the sorted list
+  std::vector<int32_t> order((size_t)n_in[(size_t)G]), fill(n_in.begin(), n_in.end() - 1);
+  for (int32_t b = 0; b < B; ++b) if (grp[(size_t)b] >= 0) order[(size_t)fill[(size_t)grp[(size_t)b]]++] = b;
+  std::vector<CenChunk> chunks;
+  plan->chunk_off.assign((size_t)G + 1, 0);
+  for (int32_t g = 0; g < G; ++g) {
+    for (int32_t i = n_in[(size_t)g]; i < n_in[(size_t)g + 1]; i += kCenChunk)
+      chunks.push_back(CenChunk{g, i, std::min(kCenChunk, n_in[(size_t)g + 1] - i), 0});
+    plan->chunk_off[(size_t)g + 1] = (int32_t)chunks.size();
+  }
+  plan->G = G; plan->V = V; plan->n_chunks = (int32_t)chunks.size();
+  const size_t dos = sizeof(double) * (size_t)S * (size_t)V, par = sizeof(double) * chunks.size() * ((size_t)V + 1);
+  size_t free_b = 0, total_b = 0, need = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (dos > e->d_cnd.cap()) need += dos + dos / 16;
+  if (par > e->d_cnpart.cap()) need += par + par / 16;
+  if (need > free_b)
+    return set_error(DMX_ERR_NOMEM, "%s: the %d x %d dosage table and %zu chunk partials need %zu bytes, %zu are free", fn, S, V, chunks.size(), need, free_b);
+  if (int rc = e->d_cnd.ensure(dos)) return rc;
+  if (int rc = e->d_cnvalid.ensure((size_t)S)) return rc;
+  if (int rc = e->d_cnpart.ensure(par)) return rc;
+  if (int rc = e->d_cnpcnt.ensure(sizeof(int64_t) * 2 * chunks.size())) return rc;
+  if (int rc = e->d_cnorder.ensure(sizeof(int32_t) * order.size())) return rc;
+  if (int rc = e->d_cnchunk.ensure(sizeof(CenChunk) * chunks.size())) return rc;
+  if (int rc = e->d_cnoff.ensure(sizeof(int32_t) * ((size_t)G + 1))) return rc;
+  if (int rc = e->d_cnw.ensure(sizeof(double) * (size_t)G * V)) return rc;
+  if (int rc = e->d_cnact.ensure((size_t)G)) return rc;
+  if (int rc = e->d_cnout.ensure(sizeof(double) * (size_t)G * ((size_t)V + 3))) return rc;
+  if (int rc = e->d_cncnt.ensure(sizeof(int64_t) * 2 * (size_t)G)) return rc;
+  if (!order.empty()) HIP_TRY(hipMemcpyAsync(e->d_cnorder, order.data(), sizeof(int32_t) * order.size(), hipMemcpyHostToDevice, e->stream));
+  if (!chunks.empty()) HIP_TRY(hipMemcpyAsync(e->d_cnchunk, chunks.data(), sizeof(CenChunk) * chunks.size(), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_cnoff, plan->chunk_off.data(), sizeof(int32_t) * ((size_t)G + 1), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_cnout, 0, sizeof(double) * (size_t)G * ((size_t)V + 3), e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_cncnt, 0, sizeof(int64_t) * 2 * (size_t)G, e->stream));
+  if (S > 0) HIP_TRY(hipMemsetAsync(e->d_cnvalid, 1, (size_t)S, e->stream));
+  EventPair& ev = e->cnev;
+  if (int rc = ev.record_start(e->stream)) return rc;
+  const int64_t items = (int64_t)S * V;
+  if (items > 0) {
+    hipLaunchKernelGGL(k_census_dosage, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, e->stream, e->d_g, items, V, e->d_cnd, e->d_cnvalid);
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = ev.record_stop(e->stream)) return rc;
+  std::vector<uint8_t> valid((size_t)S);
+  if (S > 0) HIP_TRY(hipMemcpyAsync(valid.data(), e->d_cnvalid, (size_t)S, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));         // (the plan's host vectors go away on return)
+  float ms = 0.f;
+  if (int rc = ev.elapsed_ms(&ms)) return rc;
+  dmx_census_info& inf = e->cen_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.dosage_ms = ms; inf.dosage_bytes = (int64_t)dos; inf.partial_bytes = (int64_t)par;
+  for (uint8_t x : valid) inf.n_invalid_snps += x == 0;
+  inf.n_groups = G; inf.n_chunks = plan->n_chunks; inf.n_cells = B; inf.n_samples = V;
+  e->have_cen_info = true;
+  return DMX_OK;
+}
+
+int census_pass(dmx_engine* e, const CensusPlan& pl, const double* w, const uint8_t* active, double* out) {
+  const int32_t G = pl.G, V = pl.V;
+  HIP_TRY(hipMemcpyAsync(e->d_cnw, w, sizeof(double) * (size_t)G * V, hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(hipMemcpyAsync(e->d_cnact, active, (size_t)G, hipMemcpyHostToDevice, e->stream));
+  if (int rc = e->cnev.record_start(e->stream)) return rc;
+  if (pl.n_chunks > 0) {
+    const size_t lds = sizeof(double) * 2 * kCenWaves * (size_t)((V + 63) & ~63);
+    if (lds > 30 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_census_step), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_census_step, dim3((unsigned)((pl.n_chunks + kCenWaves - 1) / kCenWaves)), dim3(64 * kCenWaves), lds, e->stream, e->pv,
+                       e->nrd_width, (const double*)e->d_lut, (const double*)e->d_cnd, (const uint8_t*)e->d_cnvalid, V,
+                       (const int32_t*)e->d_cnorder, (const CenChunk*)e->d_cnchunk, pl.n_chunks, (const uint8_t*)e->d_cnact,
+                       (const double*)e->d_cnw, e->d_cnpart.get(), e->d_cnpcnt.get());
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_census_fold, dim3((unsigned)G), dim3(256), 0, e->stream, (const double*)e->d_cnpart, (const int64_t*)e->d_cnpcnt,
+                     (const int32_t*)e->d_cnoff, (const uint8_t*)e->d_cnact, V, e->d_cnout.get(), e->d_cncnt.get());
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->cnev.record_stop(e->stream)) return rc;
+  HIP_TRY(hipMemcpyAsync(out, e->d_cnout, sizeof(double) * (size_t)G * ((size_t)V + 3), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  float ms = 0.f;
+  if (int rc = e->cnev.elapsed_ms(&ms)) return rc;
+  e->cen_info.kernel_ms = ms; e->cen_info.n_steps += 1;
+  return DMX_OK;
+}
+
+int census_check_w(const char* fn, const double* w, int32_t G, int32_t V) {
+  for (int32_t g = 0; g < G; ++g) {
+    double s = 0.0;
+    for (int32_t v = 0; v < V; ++v) {
+      const double x = w[(size_t)g * V + v];
+      if (!(x >= 0.0 && x < INFINITY)) return set_error(DMX_ERR_ARG, "%s: w[%d][%d] = %g is negative or not finite", fn, g, v, x);
+      s += x;
+    }
+    if (!(std::fabs(s - 1.0) <= 1e-12)) return set_error(DMX_ERR_ARG, "%s: row %d of w sums to %.17g, not to 1 within 1e-12", fn, g, s);
+  }
+  return DMX_OK;
+}
+
+}  // namespace
+
+extern "C" int dmx_engine_census_step(dmx_engine* e, const dmx_census_step_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_census_step: null argument");
+  CensusPlan pl;
+  if (int rc = census_prepare(e, "dmx_engine_census_step", rq->n_cells, rq->group_memory, rq->group, rq->n_groups, rq->n_samples, &pl)) return rc;
+  const int32_t G = pl.G, V = pl.V;
+  if (!rq->w) return set_error(DMX_ERR_ARG, "dmx_engine_census_step: missing w");
+  if (int rc = census_check_w("dmx_engine_census_step", rq->w, G, V)) return rc;
+  std::vector<uint8_t> active((size_t)G, 1);
+  std::vector<double> out((size_t)G * ((size_t)V + 3));
+  if (int rc = census_pass(e, pl, rq->w, active.data(), out.data())) return rc;
+  std::vector<int64_t> cnt(2 * (size_t)G);
+  HIP_TRY(hipMemcpy(cnt.data(), e->d_cncnt, sizeof(int64_t) * cnt.size(), hipMemcpyDeviceToHost));
+  for (int32_t g = 0; g < G; ++g) {
+    const double* o = out.data() + (size_t)g * ((size_t)V + 3);
+    if (rq->acc) std::memcpy(rq->acc + (size_t)g * V, o, sizeof(double) * (size_t)V);
+    if (rq->ll) rq->ll[g] = o[V];
+    if (rq->gap) rq->gap[g] = o[V + 1];
+    if (rq->n_read) rq->n_read[g] = cnt[2 * (size_t)g];
+    if (rq->n_pair) rq->n_pair[g] = cnt[2 * (size_t)g + 1];
+  }
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_census(dmx_engine* e, const dmx_census_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_census: null argument");
+  CensusPlan pl;
+  if (int rc = census_prepare(e, "dmx_engine_census", rq->n_cells, rq->group_memory, rq->group, rq->n_groups, rq->n_samples, &pl)) return rc;
+  const int32_t G = pl.G, V = pl.V;
+  const size_t sv = (size_t)V;
+  if (rq->w0) if (int rc = census_check_w("dmx_engine_census", rq->w0, G, V)) return rc;
+  const double tol = rq->tol > 0.0 ? rq->tol : 1e-4;
+  const int32_t max_steps = rq->max_steps > 0 ? rq->max_steps : 2000;
+  const bool accel = rq->accelerate != 0;
+  std::vector<double> cur((size_t)G * sv), w0(cur.size()), w1(cur.size()), w2(cur.size()), ll1((size_t)G, 0.0), out((size_t)G * (sv + 3));
+  if (rq->w0) std::memcpy(cur.data(), rq->w0, sizeof(double) * cur.size());
+  else std::fill(cur.begin(), cur.end(), 1.0 / (double)V);
+  std::vector<uint8_t> active((size_t)G, 1);
+  std::vector<int32_t> phase((size_t)G, 0);
+  e->have_census = false;
+  e->cn_G = G;
+  e->cn_w.assign(cur.size(), 0.0); e->cn_ll.assign((size_t)G, 0.0); e->cn_gap.assign((size_t)G, 0.0);
+  e->cn_steps.assign((size_t)G, 0); e->cn_conv.assign((size_t)G, 0);
+  e->cn_nread.assign((size_t)G, 0); e->cn_npair.assign((size_t)G, 0);
+  int32_t n_active = G;
+  bool first = true;
+  while (n_active > 0) {
+    if (int rc = census_pass(e, pl, cur.data(), active.data(), out.data())) return rc;
+    if (first) {
+      std::vector<int64_t> cnt(2 * (size_t)G);
+      HIP_TRY(hipMemcpy(cnt.data(), e->d_cncnt, sizeof(int64_t) * cnt.size(), hipMemcpyDeviceToHost));
+      for (int32_t g = 0; g < G; ++g) { e->cn_nread[(size_t)g] = cnt[2 * (size_t)g]; e->cn_npair[(size_t)g] = cnt[2 * (size_t)g + 1]; }
+      first = false;
+    }
+    for (int32_t g = 0; g < G; ++g) {
+      if (!active[(size_t)g]) continue;
+      const double* o = out.data() + (size_t)g * (sv + 3);
+      double* x = cur.data() + (size_t)g * sv;
+      const double ll = o[V], gap = o[V + 1], N = o[V + 2];
+      const int32_t steps = ++e->cn_steps[(size_t)g];
+      const bool empty = !(N > 0.0), conv = empty || (std::isfinite(ll) && gap <= tol);
+      if (conv || steps >= max_steps) {
+        std::memcpy(e->cn_w.data() + (size_t)g * sv, x, sizeof(double) * sv);
+        e->cn_ll[(size_t)g] = empty ? 0.0 : ll; e->cn_gap[(size_t)g] = empty ? 0.0 : gap; e->cn_conv[(size_t)g] = conv ? 1 : 0;
+        active[(size_t)g] = 0; n_active -= 1;
+        continue;
+      }
+      double* a0 = w0.data() + (size_t)g * sv; double* a1 = w1.data() + (size_t)g * sv; double* a2 = w2.data() + (size_t)g * sv;
+      if (!accel) {
+        for (size_t v = 0; v < sv; ++v) x[v] = x[v] * o[v] / N;
+      } else if (phase[(size_t)g] == 0) {
+        for (size_t v = 0; v < sv; ++v) { a0[v] = x[v]; a1[v] = x[v] * o[v] / N; x[v] = a1[v]; }
+        phase[(size_t)g] = 1;
+      } else if (phase[(size_t)g] == 1) {
+        ll1[(size_t)g] = ll;
+        double rr = 0.0, uu = 0.0;
+        for (size_t v = 0; v < sv; ++v) {
+          a2[v] = x[v] * o[v] / N;
+          const double r = a1[v] - a0[v], u = (a2[v] - a1[v]) - r;
+          rr += r * r; uu += u * u;
+        }
+        double a = uu > 0.0 ? -std::sqrt(rr) / std::sqrt(uu) : -1.0;
+        if (!(a <= -1.0) || !std::isfinite(a)) a = -1.0;
+        for (;;) {
+          bool neg = false;
+          for (size_t v = 0; v < sv; ++v) {
+            const double r = a1[v] - a0[v], u = (a2[v] - a1[v]) - r;
+            x[v] = (a0[v] - 2.0 * a * r) + a * a * u;
+            neg = neg || x[v] < 0.0;
+          }
+          if (!neg || a == -1.0) break;
+          a = 0.5 * (a - 1.0);
+          if (a > -1.0 - 1e-9) a = -1.0;
+        }
+        if (a == -1.0) std::memcpy(x, a2, sizeof(double) * sv);
+        double s = 0.0;
+        for (size_t v = 0; v < sv; ++v) { if (!(x[v] > 0.0)) x[v] = 0.0; s += x[v]; }
+        for (size_t v = 0; v < sv; ++v) x[v] /= s;
+        phase[(size_t)g] = 2;
+      } else {
+        if (!std::isfinite(ll) || ll < ll1[(size_t)g]) std::memcpy(x, a2, sizeof(double) * sv);
+        else for (size_t v = 0; v < sv; ++v) x[v] = x[v] * o[v] / N;
+        phase[(size_t)g] = 0;
+      }
+    }
+  }
+  e->have_census = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_census(dmx_engine* e, double* w, double* ll, double* gap, int32_t* n_steps, int32_t* converged, int64_t* n_read,
+                                     int64_t* n_pair) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_census: null engine");
+  if (!e->have_census) return set_error(DMX_ERR_STATE, "dmx_engine_get_census: no census on the staged pileup (dmx_engine_census first)");
+  const size_t G = (size_t)e->cn_G;
+  if (w) std::memcpy(w, e->cn_w.data(), sizeof(double) * e->cn_w.size());
+  if (ll) std::memcpy(ll, e->cn_ll.data(), sizeof(double) * G);
+  if (gap) std::memcpy(gap, e->cn_gap.data(), sizeof(double) * G);
+  if (n_steps) std::memcpy(n_steps, e->cn_steps.data(), sizeof(int32_t) * G);
+  if (converged) std::memcpy(converged, e->cn_conv.data(), sizeof(int32_t) * G);
+  if (n_read) std::memcpy(n_read, e->cn_nread.data(), sizeof(int64_t) * G);
+  if (n_pair) std::memcpy(n_pair, e->cn_npair.data(), sizeof(int64_t) * G);
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_census_info(dmx_engine* e, dmx_census_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_census_info: null argument");
+  if (!e->have_cen_info) return set_error(DMX_ERR_STATE, "dmx_engine_census_info: no census pass on the staged pileup (dmx_engine_census_step or dmx_engine_census first)");
+  *out = e->cen_info;
   return DMX_OK;
 }
 

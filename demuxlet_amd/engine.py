@@ -748,6 +748,63 @@ class Engine:
         kept = np.diff(ro).astype(np.int32)
         return HostPileup(N, self.S, po, ro, snp, nrd, reads, kept, kept.copy(), kept.copy())
 
+    def _census_group(self, group, n_groups):
+        """(keep-alive array, memory, pointer, G) of a census `group`: a host array [B] or a device pointer (int) to B int32."""
+        if isinstance(group, int):
+            if n_groups is None:
+                raise ValueError("a device group needs n_groups=")
+            return None, capi.DMX_MEM_DEVICE, group, int(n_groups)
+        gr = np.ascontiguousarray(group, dtype=np.int32)
+        if gr.shape != (self.B,):
+            raise ValueError(f"group must be [{self.B}]")
+        G = int(n_groups) if n_groups is not None else (int(gr.max()) + 1 if gr.size and gr.max() >= 0 else 1)
+        return gr, capi.DMX_MEM_HOST, (gr.ctypes.data if gr.size else None), G
+
+    def census_step(self, group, w, n_groups=None):
+        """dmx_engine_census_step over the staged pileup: one pass of the mixture-proportion EM at the shares w[G][V] for the groups
+        group[b] in [-1, G) (-1 = barcode not used; a host array, or a device pointer (int) to B int32 with n_groups=).
+        Returns (acc[G][V] f64, ll[G] f64, gap[G] f64, n_read[G] i64, n_pair[G] i64); the EM image of w is w * acc / n_read."""
+        gr, mem, ptr, G = self._census_group(group, n_groups)
+        ww = np.ascontiguousarray(w, dtype=np.float64)
+        if ww.ndim == 1:
+            ww = ww[None, :]
+        if ww.shape != (G, self.V):
+            raise ValueError(f"w must be [{G}][{self.V}]")
+        acc = np.zeros((G, self.V)); ll = np.zeros(G); gap = np.zeros(G)
+        n_read = np.zeros(G, dtype=np.int64); n_pair = np.zeros(G, dtype=np.int64)
+        rq = capi.CensusStepRequest(self.B, mem, ptr, G, self.V, ww.ctypes.data, acc.ctypes.data, ll.ctypes.data, gap.ctypes.data,
+                                    n_read.ctypes.data, n_pair.ctypes.data)
+        check(self._L.dmx_engine_census_step(self._h, C.byref(rq)))
+        return acc, ll, gap, n_read, n_pair
+
+    def census(self, group, n_groups=None, w0=None, tol: float = 1e-4, max_steps: int = 2000, accelerate: bool = True) -> dict:
+        """dmx_engine_census over the staged pileup: the maximum-likelihood donor shares of every group, by SQUAREM (or plain EM with
+        accelerate=False) from w0[G][V] (None = uniform), each group stopping at duality gap <= tol or after max_steps passes.
+        Returns a dict: w[G][V], ll[G], gap[G], n_steps[G], converged[G], n_read[G], n_pair[G]."""
+        gr, mem, ptr, G = self._census_group(group, n_groups)
+        start = None
+        if w0 is not None:
+            start = np.ascontiguousarray(w0, dtype=np.float64)
+            if start.ndim == 1:
+                start = start[None, :]
+            if start.shape != (G, self.V):
+                raise ValueError(f"w0 must be [{G}][{self.V}]")
+        rq = capi.CensusRequest(self.B, mem, ptr, G, self.V, start.ctypes.data if start is not None else None, float(tol), int(max_steps),
+                                1 if accelerate else 0)
+        check(self._L.dmx_engine_census(self._h, C.byref(rq)))
+        w = np.zeros((G, self.V)); ll = np.zeros(G); gap = np.zeros(G)
+        n_steps = np.zeros(G, dtype=np.int32); conv = np.zeros(G, dtype=np.int32)
+        n_read = np.zeros(G, dtype=np.int64); n_pair = np.zeros(G, dtype=np.int64)
+        check(self._L.dmx_engine_get_census(self._h, w.ctypes.data, ll.ctypes.data, gap.ctypes.data, n_steps.ctypes.data, conv.ctypes.data,
+                                            n_read.ctypes.data, n_pair.ctypes.data))
+        return dict(w=w, ll=ll, gap=gap, n_steps=n_steps, converged=conv, n_read=n_read, n_pair=n_pair)
+
+    def census_info(self) -> dict:
+        """HIP-event times (ms) of the last census pass and dosage kernel, passes run, table sizes and invalid SNPs (dmx_engine_census_info)."""
+        r = capi.CensusInfo()
+        check(self._L.dmx_engine_census_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.CensusInfo._fields_ if n != "reserved"}
+
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()
         check(self._L.dmx_engine_device_view(self._h, C.byref(v)))

@@ -886,6 +886,92 @@ int dmx_demuxlet_run(const dmx_job*);
  * binary: the BAM x VCF scan, cmd_cram_demuxlet.cpp:195-338) calls it on a thread of its own first.  Thread-safe. */
 int dmx_device_warm_up(int32_t device, int32_t n_gpus);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Donor shares of a read pool (no counterpart in the reference; appended, DMX_ABI_VERSION stays 8).  Every stored
+ * read of a group of barcodes is an independent draw from a mixture of the V donors: which donors, in what proportions, make up the pool.
+ * Inputs: the staged pileup, the phred tables, the engine's genotype matrix gp[S][V][3] (float32), group[B] with entries in [-1, G)
+ * (-1 = barcode not used) and shares w[G][V], non-negative, each row summing to 1 within 1e-12.
+ *   d[i][v]   = (gp1 / 2 + gp2) / ((gp0 + gp1) + gp2), in float64 from the float32 entries.  A SNP where a donor's row does not sum to a
+ *               positive finite number is INVALID: its pairs are skipped for every group; dmx_census_info counts these SNPs.
+ *   A_i(w)    = sum over v, ascending, of w[v] d[i][v]; every product and sum is rounded on its own (no fused multiply-add).
+ *   P_r       = pR (1 - A_i) + pA A_i for a stored read, pR = allele 0 ? mat[bq] : err[bq] / 3, pA = allele 1 ? mat[bq] : err[bq] / 3
+ *               (as for dmx_engine_ambient).  Reads of allele 2 are not stored (see dmx_pileup): they are skipped and not counted.
+ *   LL[g]     = sum over the reads of group g of log P_r, the log being dmx_log;
+ *   acc[g][v] = sum over the pairs of group g of (1 - d[i][v]) sR + d[i][v] sA, sR = sum over the pair's reads of pR / P_r, sA = sum of
+ *               pA / P_r (IEEE divisions).  Every term is non-negative.
+ *   n_read[g] / n_pair[g] = the reads / pairs counted (pairs with a stored read at a valid SNP).
+ * The EM image of w is w'[v] = w[v] acc[v] / N, N = n_read[g]; gap[g] = N (max_v acc[v] / N - 1).  Because sum_v w[v] acc[v] = N and LL is
+ * concave in w, LL(w_MLE) - LL(w) <= gap: the gap is the stopping rule.  A group without a counted read has acc = 0, LL = 0, gap = 0.
+ * Summation plan (no floating-point atomics; it depends on the pileup, the group's own members and V only): the barcodes of a group in
+ * ascending cell id are cut into chunks of 4.  Within a chunk, barcodes in that order, pairs in stored order, 64 pairs (a tile) at a time:
+ * acc[v] adds one term per pair in that order (for V <= 32, with Vq the power of two >= V and n = 64 / Vq: n running sums, sum s taking
+ * the tile's pairs s, s + n, ..., added in order at the chunk's end); each of the tile's 64 positions keeps its own running LL over the
+ * chunk, and the 64 are added in position order at the chunk's end.  A group's chunks are folded in order into eight accumulators (chunk c into c mod 8),
+ * which are added as ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).  Therefore a repeat gives the same bits; a group evaluated alone gives
+ * the same bits as among other groups; a device `group` gives the same bits as a host one; the stream and earlier calls do not matter;
+ * nrd_width does not matter.  (The dense and the sparse layout of one pileup tile a barcode's pairs differently: same values to rounding.)
+ *
+ * dmx_engine_census_step: one device pass at w (k_census_dosage once, then k_census_step and k_census_fold); any output may be NULL.
+ * dmx_engine_census: the loop inside the library, from w0 (NULL = uniform 1 / V).  Per pass only G (V + 3) doubles cross to the host.
+ *   Plain EM (accelerate = 0): w <- w'.  SQUAREM (accelerate != 0), one cycle from w0: a pass at w0 gives w1, a pass at w1 gives w2;
+ *   r = w1 - w0, u = (w2 - w1) - r, steplength a = -|r| / |u| (Euclidean norms; -1 when |u| = 0), clamped to <= -1;
+ *   x = w0 - 2 a r + a^2 u; while a component of x is negative and a < -1, a <- (a - 1) / 2, taken as -1 once within 1e-9 of it (at a = -1, x = w2); x is clipped at 0 and
+ *   divided by its sum; a pass at x gives the stabilising step x' and LL(x); the next cycle starts from x', or from w2 when LL(x) is not
+ *   finite or below LL(w1).
+ *   After every pass, at the point just evaluated: a group stops when its LL is finite and gap <= tol (converged = 1), or when it has
+ *   taken max_steps passes (converged = 0); it returns that point with its LL and gap.  A stopped group is frozen: its wavefronts
+ *   return at once in later passes and its results stay.  A group without a counted read returns its input w, ll = 0, gap = 0,
+ *   converged = 1 after one pass.  tol <= 0 selects 1e-4 (LL units), max_steps <= 0 selects 2000.
+ * Both calls run on the engine's stream, synchronise it before returning (host inputs may be freed then), use buffers of their own and
+ * leave every other result of the engine as it was.
+ * DMX_ERR_ARG: G outside [1, 1024], V above 1024, n_samples that is not the engine's, group[b] outside [-1, G), a w entry that is negative
+ * or not finite, a row sum off 1 by more than 1e-12, n_cells that does not match the staged pileup, a null group (B > 0) or w.
+ * DMX_ERR_STATE: no pileup or no genotypes yet (or dmx_engine_get_census / _census_info before a call).  DMX_ERR_NOMEM: the S x V dosage
+ * table or the chunk partials do not fit the free device memory. */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t group_memory;        /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `group` lives */
+  const int32_t* group;        /* [n_cells], -1 = not used */
+  int32_t n_groups;            /* G, 1..1024 */
+  int32_t n_samples;           /* V = the engine's n_samples, <= 1024 */
+  const double* w;             /* [G][V] float64, HOST */
+  double*  acc;                /* out [G][V], HOST (NULL = not wanted) */
+  double*  ll;                 /* out [G] */
+  double*  gap;                /* out [G] */
+  int64_t* n_read;             /* out [G] */
+  int64_t* n_pair;             /* out [G] */
+  int32_t reserved[4];         /* 0 */
+} dmx_census_step_request;
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t group_memory;        /* DMX_MEM_HOST or DMX_MEM_DEVICE */
+  const int32_t* group;        /* [n_cells], -1 = not used */
+  int32_t n_groups;            /* G, 1..1024 */
+  int32_t n_samples;           /* V = the engine's n_samples, <= 1024 */
+  const double* w0;            /* [G][V] start, HOST; NULL = uniform */
+  double  tol;                 /* stop at gap <= tol; <= 0: 1e-4 */
+  int32_t max_steps;           /* passes per group at most; <= 0: 2000 */
+  int32_t accelerate;          /* 0 = plain EM, otherwise SQUAREM */
+  int32_t reserved[4];         /* 0 */
+} dmx_census_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the last pass: k_census_step + k_census_fold */
+  double  dosage_ms;           /* ... and of the last call's k_census_dosage */
+  int64_t dosage_bytes;        /* device bytes of d[S][V] */
+  int64_t partial_bytes;       /* device bytes of the chunk partials */
+  int32_t n_steps;             /* passes the last call ran (dmx_engine_census_step: 1) */
+  int32_t n_invalid_snps;
+  int32_t n_groups, n_chunks, n_cells, n_samples;
+  int32_t reserved[4];
+} dmx_census_info;
+int dmx_engine_census_step(dmx_engine*, const dmx_census_step_request*);
+int dmx_engine_census(dmx_engine*, const dmx_census_request*);
+/* The last dmx_engine_census result (any pointer may be NULL): w[G][V], ll[G], gap[G] f64; n_steps[G], converged[G] i32; n_read[G],
+ * n_pair[G] i64. */
+int dmx_engine_get_census(dmx_engine*, double* w, double* ll, double* gap, int32_t* n_steps, int32_t* converged, int64_t* n_read,
+                          int64_t* n_pair);
+int dmx_engine_census_info(dmx_engine*, dmx_census_info* out);
+
 #ifdef __cplusplus
 }
 #endif
