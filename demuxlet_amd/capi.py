@@ -48,6 +48,7 @@ SYMBOLS = [
     "dmx_engine_triplet", "dmx_engine_get_triplet", "dmx_engine_triplet_info",
     "dmx_engine_compose", "dmx_engine_composed_pileup", "dmx_engine_get_composed", "dmx_engine_compose_info",
     "dmx_engine_census_step", "dmx_engine_census", "dmx_engine_get_census", "dmx_engine_census_info",
+    "dmx_engine_census_fisher", "dmx_engine_census_fisher_info",
 ]
 
 
@@ -204,6 +205,18 @@ class CensusInfo(C.Structure):         # dmx_census_info
                 ("n_samples", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
+class CensusFisherRequest(C.Structure):  # dmx_census_fisher_request
+    _fields_ = [("n_cells", C.c_int32), ("group_memory", C.c_int32), ("group", C.c_void_p), ("n_groups", C.c_int32), ("n_samples", C.c_int32),
+                ("w", C.c_void_p), ("H", C.c_void_p), ("score", C.c_void_p), ("n_read_b", C.c_void_p), ("acc", C.c_void_p), ("ll", C.c_void_p),
+                ("n_read", C.c_void_p), ("n_pair", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class CensusFisherInfo(C.Structure):     # dmx_census_fisher_info
+    _fields_ = [("kernel_ms", C.c_double), ("partial_bytes", C.c_int64), ("n_groups", C.c_int32), ("n_chunks", C.c_int32),
+                ("n_blocks", C.c_int32), ("n_entries", C.c_int32), ("n_cells", C.c_int32), ("n_samples", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
 class DmxError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libdmx error {code}: {msg}")
@@ -351,6 +364,7 @@ def load() -> C.CDLL:
         "dmx_engine_compose_info": [vp, vp],
         "dmx_engine_census_step": [vp, vp], "dmx_engine_census": [vp, vp], "dmx_engine_get_census": [vp, vp, vp, vp, vp, vp, vp, vp],
         "dmx_engine_census_info": [vp, vp],
+        "dmx_engine_census_fisher": [vp, vp], "dmx_engine_census_fisher_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -8,7 +8,7 @@ Uses: the make-up of the soup (a group of empty droplets), the donors' cell or R
 donor of the VCF is in the pool at all (a share of 0).
 
     python -m demuxlet_amd.census --pileup <x>.pileup.txt --out <prefix> [--groups FILE | --max-reads N] [--tol T] [--max-steps M]
-        [--no-accel] [--gpu G]
+        [--no-accel] [--se] [--presence] [--gpu G]
 
 reads the dump that `demuxlet --pileup-only` writes.  By default every barcode goes into one group POOL; --groups names a
 BARCODE<TAB>GROUP file (barcodes not listed are left out); --max-reads N makes two groups, EMPTY (barcodes with at most N unique reads)
@@ -17,10 +17,32 @@ and CELLS.  It writes
   <prefix>.census.tsv          GROUP SM_ID SHARE READS — one row per group and donor; READS = SHARE x the group's counted reads
   <prefix>.census_groups.tsv   GROUP N.BARCODE N.SNP N.READ LLK GAP STEPS CONVERGED — N.SNP counts the (barcode, SNP) pairs that contributed
   <prefix>.census_profile.tsv  SNP GROUP A — the implied ALT frequency sum_v w_v d_iv of every SNP (NA where a donor's genotype row is
-                               all zero: such SNPs are left out of the census)"""
+                               all zero: such SNPs are left out of the census)
+
+Uncertainty.  --se makes one Engine.census_fisher call at the fitted shares: the observed information H of
+every group and the per-barcode scores.  From them `covariance` forms two standard errors per share: the model-based one (inverse
+information on the simplex), right when reads are independent draws (soup, empty droplets), and the barcode-robust sandwich, which lets
+all reads of a barcode hang together and is the only honest one for groups of cells.  It writes
+
+  <prefix>.census_se.tsv       GROUP SM_ID SHARE SE SE.ROBUST LO HI AT.BOUND — LO / HI = SHARE -/+ 1.96 SE.ROBUST clipped to [0, 1]; a donor
+                               with SHARE x N.READ <= 1 is at the bound: SE 0, AT.BOUND 1; NA where H is singular on the free donors
+                               (related or identical donors) or, for SE.ROBUST, the group has fewer than 2 |free donors| barcodes
+  <prefix>.census_cov.tsv      GROUP SM_ID1 SM_ID2 COV COV.ROBUST — free donors only, SM_ID1 before or equal to SM_ID2 in VCF order
+
+--presence tests every donor of every group: a refit from the fitted shares with that donor held at 0 (the donors at the bound stay
+at 0, the others are renormalised; the stopping rule is the duality gap on the support of the start), LLR = max(LLK.FULL - LLK.WITHOUT, 0) and P = erfc(sqrt(LLR)) / 2, the
+tail of the half-and-half mixture of chi-square 0 and chi-square 1 that a parameter on the boundary calls for.  A donor at the bound gets
+LLR 0 and P 1 without a refit.  The likelihood ratio is the independent-reads model's: for groups of cells, where reads of a barcode
+hang together, it is anti-conservative, and SHARE / SE.ROBUST of the --se table is the safer reading.  It writes
+
+  <prefix>.census_presence.tsv GROUP SM_ID SHARE LLK.FULL LLK.WITHOUT LLR P STEPS CONVERGED
+
+Both intervals and the test rest on a normal / chi-square approximation that is poor for a share near 0 or 1.  Without the two flags
+the three files above keep their bytes."""
 from __future__ import annotations
 
 import argparse
+import math
 import sys
 from typing import List, Optional, Sequence, Tuple
 
@@ -31,7 +53,11 @@ from . import engine, refine
 CENSUS_HEADER = "GROUP\tSM_ID\tSHARE\tREADS\n"
 GROUPS_HEADER = "GROUP\tN.BARCODE\tN.SNP\tN.READ\tLLK\tGAP\tSTEPS\tCONVERGED\n"
 PROFILE_HEADER = "SNP\tGROUP\tA\n"
+SE_HEADER = "GROUP\tSM_ID\tSHARE\tSE\tSE.ROBUST\tLO\tHI\tAT.BOUND\n"
+COV_HEADER = "GROUP\tSM_ID1\tSM_ID2\tCOV\tCOV.ROBUST\n"
+PRESENCE_HEADER = "GROUP\tSM_ID\tSHARE\tLLK.FULL\tLLK.WITHOUT\tLLR\tP\tSTEPS\tCONVERGED\n"
 MAX_GROUPS = 1024           # dmx_engine_census's most groups
+MAX_SE_SAMPLES = 128        # dmx_engine_census_fisher's most donors
 
 
 def dosage(g) -> Tuple[np.ndarray, np.ndarray]:
@@ -124,13 +150,175 @@ def write_profile_tsv(path: str, names: Sequence[str], profile: np.ndarray, snps
                 f.write(f"{sid}\t{name}\t{'NA' if np.isnan(a) else format(a, '.6f')}\n")
 
 
+def sum_zero_basis(f: int) -> np.ndarray:
+    """Q[f][f - 1]: orthonormal columns that each sum to zero (Helmert's), a basis of the directions that keep shares summing to 1."""
+    Q = np.zeros((f, max(f - 1, 0)))
+    for k in range(1, f):
+        Q[:k, k - 1] = 1.0 / math.sqrt(k * (k + 1.0))
+        Q[k, k - 1] = -k / math.sqrt(k * (k + 1.0))
+    return Q
+
+
+def covariance(H, w, n_read, score, n_b, min_reads: float = 1.0) -> dict:
+    """Covariances of one group's fitted shares w[V] from its observed information H[V][V] (Engine.census_fisher at w), its counted
+    reads N and its barcodes' score rows score[Bg][V] with their counted reads n_b[Bg].
+
+    A donor with w_v N <= min_reads is AT THE BOUND: SE 0, left out of the free set F.  With Q an orthonormal basis of the sum-zero
+    vectors of R^|F| and G1 = Q' H_FF Q:
+      model   C   = Q G1^-1 Q'                                  (inverse information on the simplex: reads independent);
+      robust  C_r = Bg / (Bg - 1) Q G1^-1 (Q' J Q) G1^-1 Q',    J = sum_b s_b s_b', s_b = score_b[F] - n_b 1 (the barcode's score of
+                    the log-likelihood on the simplex), the sum over the Bg barcodes with a counted read.
+    G1 singular (condition number above 1e12, or not finite): both are NaN on F.  Bg < 2 |F|: the robust one is NaN.
+    Cross-check at a converged fit (acc_v = N on F, hence H_FF w_F = N 1): C = H_FF^-1 - w_F w_F' / N.
+    Returns dict(se[V], se_robust[V], cov[V][V], cov_robust[V][V], at_bound[V] bool, free[|F|] indices, n_barcode=Bg)."""
+    H = np.asarray(H, dtype=np.float64)
+    w = np.asarray(w, dtype=np.float64)
+    V = w.shape[0]
+    if H.shape != (V, V):
+        raise ValueError(f"H {H.shape} for {V} shares")
+    score = np.asarray(score, dtype=np.float64).reshape(-1, V)
+    n_b = np.asarray(n_b, dtype=np.float64)
+    if n_b.shape != (score.shape[0],):
+        raise ValueError(f"n_b {n_b.shape} for {score.shape[0]} score rows")
+    N = float(n_read)
+    at_bound = ~(w * N > min_reads)
+    F = np.flatnonzero(~at_bound)
+    f = len(F)
+    cov = np.zeros((V, V)); cov_r = np.zeros((V, V))
+    used = n_b > 0
+    Bg = int(used.sum())
+    if f >= 2:
+        Q = sum_zero_basis(f)
+        G1 = Q.T @ H[np.ix_(F, F)] @ Q
+        ok = bool(np.isfinite(G1).all())
+        if ok:
+            sv = np.linalg.svd(G1, compute_uv=False)
+            ok = bool(sv[-1] > 0.0 and sv[0] / sv[-1] <= 1e12)
+        if ok:
+            Gi = np.linalg.inv(G1)
+            Gi = 0.5 * (Gi + Gi.T)
+            cov[np.ix_(F, F)] = Q @ Gi @ Q.T
+            if Bg >= 2 * f:
+                s = (score[used][:, F] - n_b[used][:, None]) @ Q
+                M = Gi @ (s.T @ s) @ Gi
+                cov_r[np.ix_(F, F)] = (Bg / (Bg - 1.0)) * (Q @ M @ Q.T)
+            else:
+                cov_r[np.ix_(F, F)] = np.nan
+        else:
+            cov[np.ix_(F, F)] = np.nan
+            cov_r[np.ix_(F, F)] = np.nan
+    with np.errstate(invalid="ignore"):
+        se = np.sqrt(np.maximum(np.diag(cov), 0.0))
+        se_r = np.sqrt(np.maximum(np.diag(cov_r), 0.0))
+    se = np.where(np.isnan(np.diag(cov)), np.nan, se)
+    se_r = np.where(np.isnan(np.diag(cov_r)), np.nan, se_r)
+    return dict(se=se, se_robust=se_r, cov=cov, cov_robust=cov_r, at_bound=at_bound, free=F, n_barcode=Bg)
+
+
+def _num(x: float, fmt: str) -> str:
+    return "NA" if not math.isfinite(x) else format(x, fmt)
+
+
+def write_se_tsv(path: str, names: Sequence[str], sample_ids: Sequence[str], w: np.ndarray, covs: Sequence[dict]) -> None:
+    with open(path, "w") as f:
+        f.write(SE_HEADER)
+        for k, name in enumerate(names):
+            c = covs[k]
+            for v, s in enumerate(sample_ids):
+                sr = float(c["se_robust"][v])
+                lo = min(max(w[k, v] - 1.96 * sr, 0.0), 1.0) if math.isfinite(sr) else math.nan
+                hi = min(max(w[k, v] + 1.96 * sr, 0.0), 1.0) if math.isfinite(sr) else math.nan
+                f.write(f"{name}\t{s}\t{w[k, v]:.6f}\t{_num(float(c['se'][v]), '.6f')}\t{_num(sr, '.6f')}\t{_num(lo, '.6f')}\t{_num(hi, '.6f')}\t"
+                        f"{int(c['at_bound'][v])}\n")
+
+
+def write_cov_tsv(path: str, names: Sequence[str], sample_ids: Sequence[str], covs: Sequence[dict]) -> None:
+    with open(path, "w") as f:
+        f.write(COV_HEADER)
+        for k, name in enumerate(names):
+            c = covs[k]
+            for a in c["free"]:
+                for b in c["free"]:
+                    if a <= b:
+                        f.write(f"{name}\t{sample_ids[a]}\t{sample_ids[b]}\t{_num(float(c['cov'][a, b]), '.6e')}\t"
+                                f"{_num(float(c['cov_robust'][a, b]), '.6e')}\n")
+
+
+def write_presence_tsv(path: str, names: Sequence[str], sample_ids: Sequence[str], w: np.ndarray, ll_full, pres: dict) -> None:
+    with open(path, "w") as f:
+        f.write(PRESENCE_HEADER)
+        for k, name in enumerate(names):
+            for v, s in enumerate(sample_ids):
+                f.write(f"{name}\t{s}\t{w[k, v]:.6f}\t{ll_full[k]:.5f}\t{pres['ll_without'][k, v]:.5f}\t{pres['llr'][k, v]:.5f}\t"
+                        f"{pres['p'][k, v]:.4g}\t{int(pres['n_steps'][k, v])}\t{int(pres['converged'][k, v])}\n")
+
+
+def presence_p(llr):
+    """P of the boundary likelihood-ratio test: half chi-square 0, half chi-square 1 on 2 LLR, i.e. erfc(sqrt(LLR)) / 2."""
+    return np.array([0.5 * math.erfc(math.sqrt(max(float(x), 0.0))) for x in np.ravel(llr)]).reshape(np.shape(llr))
+
+
+def presence_start(w: np.ndarray, v: int, hold=None) -> np.ndarray:
+    """w[G][V] with donor v zeroed, the entries of the mask hold[G][V] zeroed as well, and every row renormalised (a row with nothing
+    left becomes uniform over the donors other than v)."""
+    x = np.array(w, dtype=np.float64)
+    if hold is not None:
+        x[np.asarray(hold, dtype=bool)] = 0.0
+    x[:, v] = 0.0
+    s = x.sum(axis=1)
+    lone = ~(s > 0.0)
+    if lone.any():
+        x[lone] = 1.0
+        x[lone, v] = 0.0
+        s = x.sum(axis=1)
+    x = x / s[:, None]
+    return x / x.sum(axis=1)[:, None]           # (a second division brings a row sum that is an ulp off back within 1e-12)
+
+
+def presence_test(census_fn, w: np.ndarray, ll_full, n_read, min_reads: float = 1.0) -> dict:
+    """For every donor v: census_fn(w0) -> dict(w, ll, n_steps, converged) refits all groups from w0 = presence_start(w, v, bound) with
+    the gap on the start's support; LLR[g][v] = max(ll_full[g] - ll[g], 0).  A donor at the bound in a group (w N <= min_reads) gets
+    LLR 0, P 1, STEPS 0 there; a donor at the bound in every group is not refitted at all.  The donors at the bound stay at 0 in every
+    refit of their group: a share of 1e-10 left in the support creeps up by a factor acc_v / N = 1 + 1e-5 per pass once another donor
+    is taken out and keeps the gap above tol for thousands of passes; LLK.WITHOUT is then the likelihood of the free donors without v,
+    below the one with the bound donors let in by at most their part of the full fit's gap.
+    The refit for donor v runs over every group, those where v is at the bound included, and their results are not used: the engine's
+    call has no way to leave a group out.  Such a group starts from its fitted shares, which stop at once when the full fit converged;
+    where it did not, the group spends up to max_steps further passes for nothing.
+    Returns dict(ll_without, llr, p, n_steps, converged), each [G][V]."""
+    w = np.asarray(w, dtype=np.float64)
+    G, V = w.shape
+    if V < 2:
+        raise ValueError("presence: at least two donors needed")
+    ll_full = np.asarray(ll_full, dtype=np.float64)
+    bound = ~(w * np.asarray(n_read, dtype=np.float64)[:, None] > min_reads)
+    ll_wo = np.repeat(ll_full[:, None], V, axis=1)
+    steps = np.zeros((G, V), dtype=np.int64); conv = np.ones((G, V), dtype=np.int64)
+    for v in range(V):
+        if bound[:, v].all():
+            continue
+        r = census_fn(presence_start(w, v, bound))
+        free = ~bound[:, v]
+        ll_wo[free, v] = np.asarray(r["ll"])[free]
+        steps[free, v] = np.asarray(r["n_steps"])[free]
+        conv[free, v] = np.asarray(r["converged"])[free]
+    llr = np.maximum(ll_full[:, None] - ll_wo, 0.0)
+    llr[bound] = 0.0
+    p = presence_p(llr)
+    p[bound] = 1.0
+    return dict(ll_without=ll_wo, llr=llr, p=p, n_steps=steps, converged=conv)
+
+
 def census_run(store_or_pileup, g: np.ndarray, sample_ids: Sequence[str], out_prefix: Optional[str], groups=None, max_reads: Optional[int] = None,
                tol: float = 1e-4, max_steps: int = 2000, accelerate: bool = True, gpu: int = 0, barcodes: Optional[Sequence[str]] = None,
-               snps=None) -> dict:
+               snps=None, se: bool = False, presence: bool = False) -> dict:
     """The census of `store_or_pileup` (a Store, or a HostPileup) against genotype matrix g.  `groups` is None (one group POOL of every
     barcode), a BARCODE<TAB>GROUP path (needs the barcodes: a Store's own, or barcodes=), or a pair (group[B] int array, names);
     max_reads=N instead makes the groups EMPTY / CELLS.  Writes the three files unless out_prefix is None; returns a dict with the
-    engine's results (w, ll, gap, n_steps, converged, n_read, n_pair), group, names, n_barcode, profile[G][S] and info."""
+    engine's results (w, ll, gap, n_steps, converged, n_read, n_pair), group, names, n_barcode, profile[G][S] and info.
+    se=True adds one Engine.census_fisher call at the fitted shares, `covariance` per group (key "cov": a list of its dicts; "fisher":
+    the call's results) and the files .census_se.tsv / .census_cov.tsv; presence=True adds the donor presence tests (key "presence") and
+    .census_presence.tsv."""
     g = np.ascontiguousarray(g, dtype=np.float32)
     if groups is not None and max_reads is not None:
         raise ValueError("census_run: groups and max_reads exclude each other")
@@ -154,12 +342,26 @@ def census_run(store_or_pileup, g: np.ndarray, sample_ids: Sequence[str], out_pr
             raise ValueError(f"groups: {pl.n_cells} entries in [-1, {len(names)}) expected")
     if not 1 <= len(names) <= MAX_GROUPS:
         raise ValueError(f"census_run: {len(names)} groups, 1 to {MAX_GROUPS} expected")
+    if se and len(sample_ids) > MAX_SE_SAMPLES:
+        raise ValueError(f"census_run: se needs at most {MAX_SE_SAMPLES} samples, not {len(sample_ids)}")
+    if presence and len(sample_ids) < 2:
+        raise ValueError("census_run: presence needs at least two samples")
+    extra = {}
     eng = engine.Engine(len(sample_ids), device=gpu)
     try:
         eng.set_genotypes(g)
         eng.set_pileup(pl)
         r = eng.census(group, n_groups=len(names), tol=tol, max_steps=max_steps, accelerate=accelerate)
         info = eng.census_info()
+        if se:
+            fi = eng.census_fisher(group, r["w"], n_groups=len(names))
+            extra["fisher"] = fi
+            extra["cov"] = [covariance(fi["H"][k], r["w"][k], r["n_read"][k], fi["score"][group == k], fi["n_read_b"][group == k])
+                            for k in range(len(names))]
+        if presence:
+            extra["presence"] = presence_test(
+                lambda w0: eng.census(group, n_groups=len(names), w0=w0, tol=tol, max_steps=max_steps, accelerate=accelerate,
+                                      gap_on_support=True), r["w"], r["ll"], r["n_read"])
     finally:
         eng.close()
     profile = np.stack([ambient_profile(r["w"][k], g) for k in range(len(names))])
@@ -168,7 +370,12 @@ def census_run(store_or_pileup, g: np.ndarray, sample_ids: Sequence[str], out_pr
         write_census_tsv(out_prefix + ".census.tsv", names, sample_ids, r["w"], r["n_read"])
         write_groups_tsv(out_prefix + ".census_groups.tsv", names, n_bar, r)
         write_profile_tsv(out_prefix + ".census_profile.tsv", names, profile, snps)
-    return dict(r, group=group, names=names, n_barcode=n_bar, profile=profile, info=info)
+        if se:
+            write_se_tsv(out_prefix + ".census_se.tsv", names, sample_ids, r["w"], extra["cov"])
+            write_cov_tsv(out_prefix + ".census_cov.tsv", names, sample_ids, extra["cov"])
+        if presence:
+            write_presence_tsv(out_prefix + ".census_presence.tsv", names, sample_ids, r["w"], r["ll"], extra["presence"])
+    return dict(r, group=group, names=names, n_barcode=n_bar, profile=profile, info=info, **extra)
 
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
@@ -180,6 +387,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--tol", type=float, default=1e-4, help="stop a group at duality gap <= this, in log-likelihood units (default 1e-4)")
     ap.add_argument("--max-steps", type=int, default=2000, help="passes per group at most (default 2000)")
     ap.add_argument("--no-accel", action="store_true", help="plain EM instead of SQUAREM")
+    ap.add_argument("--se", action="store_true", help="standard errors of the shares, model-based and barcode-robust: <out>.census_se.tsv, "
+                    "<out>.census_cov.tsv (at most 128 samples)")
+    ap.add_argument("--presence", action="store_true", help="likelihood-ratio test of every donor's presence: <out>.census_presence.tsv")
     ap.add_argument("--gpu", type=int, default=0)
     a = ap.parse_args(argv)
     if a.groups is not None and a.max_reads is not None:
@@ -199,7 +409,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     a = parse_args(argv)
     d = refine.read_pileup_txt(a.pileup)
     r = census_run(d.pileup, d.g, d.sample_ids, a.out, groups=a.groups, max_reads=a.max_reads, tol=a.tol, max_steps=a.max_steps,
-                   accelerate=not a.no_accel, gpu=a.gpu, barcodes=d.barcodes, snps=d.snps)
+                   accelerate=not a.no_accel, gpu=a.gpu, barcodes=d.barcodes, snps=d.snps, se=a.se, presence=a.presence)
     for k, name in enumerate(r["names"]):
         top = int(np.argmax(r["w"][k]))
         print(f"{name}: {int(r['n_read'][k])} reads, {int(r['n_steps'][k])} steps, gap {r['gap'][k]:.3g}; largest share "

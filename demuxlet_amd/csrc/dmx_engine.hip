@@ -3040,6 +3040,219 @@ __global__ __launch_bounds__(256) void k_census_fold(const double* __restrict__ 
   }
 }
 
+// ---- census uncertainty: observed information and per-barcode scores (dmx_engine_census_fisher) ------------------
+// At shares w, a stored read r of pair (b, i) has the step's quotients tR = pR / P_r and tA = pA / P_r.  Per pair sRR = sum tR tR,
+// sRA = sum tR tA, sAA = sum tA tA (reads in stored order), and with e_v = 1 - d[i][v]
+//   H[g][v][u]  = sum over the pairs of group g of ((e_v e_u) sRR + (e_v d_u + d_v e_u) sRA) + (d_v d_u) sAA,  v <= u,
+//   score[b][v] = sum over the pairs of barcode b of e_v sR + d_v sA                     (the step's acc, kept per barcode),
+// every product and sum rounded on its own.  The E = V (V + 1) / 2 upper-triangle entries are numbered row-major and cut into blocks of
+// kFisBlock = 2048: one wavefront per (chunk, entry block), the chunks being census_prepare's.  A lane owns the entries
+// block * 2048 + k * 64 + lane, k < 32, and keeps their 32 running sums in registers over the whole chunk.
+//   Phase 1, lane = pair: k_census_step's phase 1 (same statements, hence the same A_i, P_r, tR, tA; no log), plus the three sums of
+//   products.  Every entry block of a chunk repeats it: phase 2b is V (V + 1) / 2 terms per pair, phase 1 a handful per read.
+//   Phase 2a, entry block 0 only, lane = donor: k_census_step's phase 2 with the sums reset at a barcode's first tile and stored at its
+//   last (for V <= 32 the lane sets' sums are added in set order there).  Lane 0 adds the 64 positions' counted reads of the barcode.
+//   Phase 2b, lane = entry: for each k the lane adds the tile's pairs in stored order to its entry's sum; the d rows come from global
+//   memory (L1 / L2: a tile touches at most 64 rows), the pair's five sums are broadcast from LDS.
+// A barcode's pairs go 64 at a time, barcodes in chunk order, so an entry's chunk partial is one serial sum.  k_census_fisher_fold adds a
+// group's chunk partials in k_census_fold's eight-accumulator order and writes both triangles.  No floating-point atomics.
+constexpr int kFisBlock = 2048, kFisPerLane = kFisBlock / 64;
+constexpr int kFisMaxV = 128;
+struct FisPair { double sR, sA, sRR, sRA, sAA; int32_t snp, pad; };
+
+// Entry e of the row-major upper triangle of a V x V matrix -> (v, u), v <= u.  Row r starts at r V - r (r - 1) / 2.
+__device__ __forceinline__ void fis_decode(int32_t e, int32_t V, int32_t& v, int32_t& u) {
+  const float t = (float)(2 * V + 1);
+  int32_t r = (int32_t)((t - sqrtf(fmaxf(t * t - 8.0f * (float)e, 0.0f))) * 0.5f);
+  r = max(0, min(r, V - 1));
+  while (r > 0 && r * V - r * (r - 1) / 2 > e) --r;
+  while (r < V - 1 && (r + 1) * V - (r + 1) * r / 2 <= e) ++r;
+  v = r; u = r + (e - (r * V - r * (r - 1) / 2));
+}
+
+__global__ __launch_bounds__(64 * kCenWaves) void k_census_fisher(PileupView pv, int nrd_width, const double* __restrict__ tabs,
+                                                                const double* __restrict__ d, const uint8_t* __restrict__ valid, int32_t V,
+                                                                const int32_t* __restrict__ order, const CenChunk* __restrict__ chunks,
+                                                                int32_t n_chunks, int32_t n_blocks, const double* __restrict__ w,
+                                                                double* __restrict__ hpart, double* __restrict__ score,
+                                                                int64_t* __restrict__ n_read_b) {
+  __shared__ double s_pra[256][2];               // by read byte (allele << 7 | bq): {pR, pA}
+  __shared__ FisPair s_tile[kCenWaves][64];
+  __shared__ double s_w[kCenWaves][kFisMaxV], s_a[kCenWaves][kFisMaxV];
+  __shared__ int64_t s_nr[kCenWaves][64];
+  for (int i = threadIdx.x; i < 256; i += 64 * kCenWaves) {
+    const double mat = tabs[i & 127], e3 = tabs[128 + (i & 127)];
+    s_pra[i][0] = (i >> 7) ? e3 : mat;
+    s_pra[i][1] = (i >> 7) ? mat : e3;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int32_t unit = (int32_t)blockIdx.x * kCenWaves + wave;          // (the host checks that n_chunks x n_blocks fits)
+  if (unit >= n_chunks * n_blocks) return;
+  const int32_t chunk = __builtin_amdgcn_readfirstlane(unit / n_blocks), eb = unit - chunk * n_blocks;
+  const int32_t grp = __builtin_amdgcn_readfirstlane(chunks[chunk].g);
+  const int32_t c_beg = __builtin_amdgcn_readfirstlane(chunks[chunk].beg), c_cnt = __builtin_amdgcn_readfirstlane(chunks[chunk].cnt);
+  const int32_t E = V * (V + 1) / 2, e0 = eb * kFisBlock;
+  const int32_t Vp = (V + 63) & ~63;
+  int qshift = 6;                                // V <= 32: Vq = the power of two >= V, nsub = 64 / Vq lane sets share phase 2a
+  while (qshift > 0 && (1 << (qshift - 1)) >= V) --qshift;
+  const int32_t Vq = 1 << qshift, nsub = 64 >> qshift;
+  double* sw = s_w[wave];
+  double* sa = s_a[wave];
+  for (int32_t v = lane; v < Vp; v += 64) sw[v] = v < V ? w[(size_t)grp * V + v] : 0.0;
+  DMX_WAVE_LDS_ORDER();
+  const int kmax = min(kFisPerLane, (E - e0 + 63) / 64);   // the k that hold an entry of this block
+  uint32_t pv8[kFisPerLane / 4], pu8[kFisPerLane / 4];     // v and u (< 128: a byte each) of this lane's entries; a lane past E runs along on entry 0
+  double hh[kFisPerLane];
+#pragma unroll
+  for (int k4 = 0; k4 < kFisPerLane / 4; ++k4) {
+    uint32_t a = 0u, b = 0u;
+#pragma unroll 1
+    for (int t = 0; t < 4; ++t) {
+      const int32_t e = e0 + (k4 * 4 + t) * 64 + lane;
+      int32_t v = 0, u = 0;
+      if (k4 * 4 + t < kmax) fis_decode(e < E ? e : 0, V, v, u);
+      a |= (uint32_t)v << (8 * t);
+      b |= (uint32_t)u << (8 * t);
+    }
+    pv8[k4] = a; pu8[k4] = b;
+  }
+#pragma unroll
+  for (int k = 0; k < kFisPerLane; ++k) hh[k] = 0.0;
+  FisPair* tile = s_tile[wave];
+  for (int32_t c = 0; c < c_cnt; ++c) {
+    const int32_t cell = __builtin_amdgcn_readfirstlane(order[c_beg + c]);
+    const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+    int64_t rd_base = pv.cell_read_off[cell];
+    int64_t nr = 0;
+    if (eb == 0) {
+      for (int32_t v = lane; v < Vp; v += 64) sa[v] = 0.0;
+      DMX_WAVE_LDS_ORDER();
+    }
+    for (int64_t p0 = p_beg; p0 < p_end; p0 += 64) {
+      const int64_t p = p0 + lane;
+      const bool in = p < p_end;
+      const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+      const uint32_t incl = seg_scan_incl<64>(n);
+      const int64_t off = rd_base + (int64_t)(incl - n);
+      rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      const int32_t snp = in ? (pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg)) : 0;
+      const bool use = n > 0 && valid[snp];
+      const double* dr = d + (size_t)snp * V;
+      double A = 0.0;
+      for (int32_t v = 0; v < V; ++v) A = A + sw[v] * dr[v];
+      const double q = 1.0 - A;
+      double sR = 0.0, sA = 0.0, sRR = 0.0, sRA = 0.0, sAA = 0.0;
+      if (use) {
+        uint32_t wd = 0;
+        for (uint32_t r = 0; r < n; ++r) {
+          if ((r & 3) == 0) wd = load_rd4(pv, off + r, n - r);
+          const uint32_t byte = (wd >> (8 * (r & 3))) & 0xFF;
+          const double pR = s_pra[byte][0], pA = s_pra[byte][1];
+          const double P = pR * q + pA * A;
+          const double tR = pR / P, tA = pA / P;
+          sR += tR; sA += tA;
+          sRR += tR * tR; sRA += tR * tA; sAA += tA * tA;
+        }
+        nr += (int64_t)n;
+      }
+      FisPair t;
+      t.sR = sR; t.sA = sA; t.sRR = sRR; t.sRA = sRA; t.sAA = sAA; t.snp = use ? snp : 0; t.pad = 0;
+      tile[lane] = t;
+      DMX_WAVE_LDS_ORDER();
+      const int cnt = (int)min<int64_t>(64, p_end - p0);
+      if (eb == 0) {                               // phase 2a: the barcode's score row
+        if (nsub > 1) {
+          const int32_t v = lane & (Vq - 1), vv = v < V ? v : 0;
+          double a = sa[lane];
+#pragma unroll 4
+          for (int j = lane >> qshift; j < cnt; j += nsub) {
+            const double dv = d[(size_t)tile[j].snp * V + vv];
+            a += (1.0 - dv) * tile[j].sR + dv * tile[j].sA;
+          }
+          sa[lane] = a;
+        } else {
+          for (int32_t v0 = 0; v0 < Vp; v0 += 64) {
+            const int32_t v = v0 + lane, vv = v < V ? v : 0;
+            double a = sa[v];
+#pragma unroll 4
+            for (int j = 0; j < cnt; ++j) {
+              const double dv = d[(size_t)tile[j].snp * V + vv];
+              a += (1.0 - dv) * tile[j].sR + dv * tile[j].sA;
+            }
+            sa[v] = a;
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kFisPerLane; ++k) {      // phase 2b: lane = entry
+        if (k < kmax) {
+          uint32_t wv = pv8[k >> 2], wu = pu8[k >> 2];
+          asm volatile("" : "+v"(wv), "+v"(wu));   // (unpacked here, per tile: 64 hoisted offsets would cost the registers the sums need)
+          const uint32_t v = (wv >> (8 * (k & 3))) & 0xFFu, u = (wu >> (8 * (k & 3))) & 0xFFu;
+          double h = hh[k];
+#pragma unroll 2
+          for (int j = 0; j < cnt; ++j) {
+            const double* row = d + (size_t)tile[j].snp * V;
+            const double dv = row[v], du = row[u];
+            const double ev = 1.0 - dv, eu = 1.0 - du;
+            h += ((ev * eu) * tile[j].sRR + (ev * du + dv * eu) * tile[j].sRA) + (dv * du) * tile[j].sAA;
+          }
+          hh[k] = h;
+        }
+      }
+      DMX_WAVE_LDS_ORDER();
+    }
+    if (eb == 0) {                                 // the barcode's last tile is done: its score row and counted reads
+      double* out = score + (size_t)cell * V;
+      if (nsub > 1) {
+        if (lane < V) {
+          double a = 0.0;
+          for (int s = 0; s < nsub; ++s) a += sa[s * Vq + lane];
+          out[lane] = a;
+        }
+      } else {
+        for (int32_t v = lane; v < V; v += 64) out[v] = sa[v];
+      }
+      s_nr[wave][lane] = nr;
+      DMX_WAVE_LDS_ORDER();
+      if (lane == 0) {
+        int64_t a = 0;
+        for (int j = 0; j < 64; ++j) a += s_nr[wave][j];
+        n_read_b[cell] = a;
+      }
+      DMX_WAVE_LDS_ORDER();
+    }
+  }
+  double* out = hpart + (size_t)chunk * (size_t)E;
+#pragma unroll
+  for (int k = 0; k < kFisPerLane; ++k) {
+    const int32_t e = e0 + k * 64 + lane;
+    if (e < E) out[e] = hh[k];
+  }
+}
+
+// One workgroup per (group, 256 entries): H[g][v][u] = H[g][u][v] = the chunk partials of entry (v, u) folded as k_census_fold does.
+__global__ __launch_bounds__(256) void k_census_fisher_fold(const double* __restrict__ hpart, const int32_t* __restrict__ chunk_off, int32_t V,
+                                                            double* __restrict__ H) {
+  const int32_t g = blockIdx.x, E = V * (V + 1) / 2;
+  const int32_t e = (int32_t)blockIdx.y * 256 + (int32_t)threadIdx.x;
+  if (e >= E) return;
+  const int32_t c0 = chunk_off[g], c1 = chunk_off[g + 1];
+  double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (int32_t c = c0; c < c1; c += 8) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (c + k < c1) a[k] += hpart[(size_t)(c + k) * (size_t)E + e];
+  }
+  const double x = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  int32_t v, u;
+  fis_decode(e, V, v, u);
+  double* Hg = H + (size_t)g * V * V;
+  Hg[(size_t)v * V + u] = x;
+  Hg[(size_t)u * V + v] = x;
+}
+
 // ---- ambient-aware doublet profile (dmx_engine_ambient_doublet) --------------------------------------------------
 // For a barcode b, a candidate pair (v1, v2), a mixing share alpha of v2 and a grid point rho:
 //   p_lm = (1 - rho) (0.5 l + (m - l) 0.5 alpha) + rho a_i,   f_lm = product over the pair's stored reads of pR (1 - p_lm) + pA p_lm,
@@ -7406,6 +7619,12 @@ struct dmx_engine {
   std::vector<double> cn_w, cn_ll, cn_gap;
   std::vector<int32_t> cn_steps, cn_conv;
   std::vector<int64_t> cn_nread, cn_npair;
+  // census uncertainty (dmx_engine_census_fisher): the chunk partials of the information's upper triangle, the folded H[G][V][V], the
+  // per-barcode score rows and counted reads
+  DevBuf<double> d_fspart, d_fsH, d_fsscore; DevBuf<int64_t> d_fsnb;
+  EventPair fsev;
+  dmx_census_fisher_info fis_info{};
+  bool have_fis_info = false;
 };
 
 namespace {
@@ -7936,7 +8155,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_adbl = false; e->have_cdbl = false;
   e->have_trip = false;
   e->have_comp = false;
-  e->have_census = false; e->have_cen_info = false;
+  e->have_census = false; e->have_cen_info = false; e->have_fis_info = false;
   e->have_pileup = true;
   e->k1_fn = e->k2_fn = e->k3b_fn = nullptr; e->k1_placement = 0;      // nothing has run on this pileup yet
   return DMX_OK;
@@ -10347,10 +10566,15 @@ extern "C" int dmx_engine_census(dmx_engine* e, const dmx_census_request* rq) {
   const double tol = rq->tol > 0.0 ? rq->tol : 1e-4;
   const int32_t max_steps = rq->max_steps > 0 ? rq->max_steps : 2000;
   const bool accel = rq->accelerate != 0;
+  const bool on_support = rq->reserved[0] != 0;    // gap_on_support: the gap's maximum runs over the donors with w0 > 0 only
   std::vector<double> cur((size_t)G * sv), w0(cur.size()), w1(cur.size()), w2(cur.size()), ll1((size_t)G, 0.0), out((size_t)G * (sv + 3));
   if (rq->w0) std::memcpy(cur.data(), rq->w0, sizeof(double) * cur.size());
   else std::fill(cur.begin(), cur.end(), 1.0 / (double)V);
-  std::vector<uint8_t> active((size_t)G, 1);
+  std::vector<uint8_t> active((size_t)G, 1), support;
+  if (on_support) {
+    support.resize(cur.size());
+    for (size_t i = 0; i < cur.size(); ++i) support[i] = cur[i] > 0.0;
+  }
   std::vector<int32_t> phase((size_t)G, 0);
   e->have_census = false;
   e->cn_G = G;
@@ -10371,7 +10595,13 @@ extern "C" int dmx_engine_census(dmx_engine* e, const dmx_census_request* rq) {
       if (!active[(size_t)g]) continue;
       const double* o = out.data() + (size_t)g * (sv + 3);
       double* x = cur.data() + (size_t)g * sv;
-      const double ll = o[V], gap = o[V + 1], N = o[V + 2];
+      const double ll = o[V], N = o[V + 2];
+      double gap = o[V + 1];
+      if (on_support && N > 0.0) {                 // EM and SQUAREM keep zeros at zero: the constrained problem's own duality gap
+        double mx = 0.0;
+        for (size_t v = 0; v < sv; ++v) if (support[(size_t)g * sv + v]) mx = std::fmax(mx, o[v]);
+        gap = N * (mx / N - 1.0);
+      }
       const int32_t steps = ++e->cn_steps[(size_t)g];
       const bool empty = !(N > 0.0), conv = empty || (std::isfinite(ll) && gap <= tol);
       if (conv || steps >= max_steps) {
@@ -10442,6 +10672,89 @@ extern "C" int dmx_engine_census_info(dmx_engine* e, dmx_census_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_census_info: null argument");
   if (!e->have_cen_info) return set_error(DMX_ERR_STATE, "dmx_engine_census_info: no census pass on the staged pileup (dmx_engine_census_step or dmx_engine_census first)");
   *out = e->cen_info;
+  return DMX_OK;
+}
+
+// Census uncertainty: census_prepare's plan and dosage table, one census_pass at w for acc, LL and the counts
+// (so they carry dmx_engine_census_step's bits), then k_census_fisher and k_census_fisher_fold into buffers of this call's own.
+extern "C" int dmx_engine_census_fisher(dmx_engine* e, const dmx_census_fisher_request* rq) {
+  const char* fn = "dmx_engine_census_fisher";
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "%s: null argument", fn);
+  const dmx_census_info keep_info = e->cen_info;   // the census calls' own info survives this call
+  const bool keep_have = e->have_cen_info;
+  struct Restore {
+    dmx_engine* e; const dmx_census_info& i; bool h;
+    ~Restore() { e->cen_info = i; e->have_cen_info = h; }
+  } restore{e, keep_info, keep_have};
+  CensusPlan pl;
+  if (int rc = census_prepare(e, fn, rq->n_cells, rq->group_memory, rq->group, rq->n_groups, rq->n_samples, &pl)) return rc;
+  const int32_t G = pl.G, V = pl.V, B = e->pv.B;
+  if (V > kFisMaxV) return set_error(DMX_ERR_ARG, "%s: %d samples, at most %d", fn, V, kFisMaxV);
+  if (!rq->w) return set_error(DMX_ERR_ARG, "%s: missing w", fn);
+  if (int rc = census_check_w(fn, rq->w, G, V)) return rc;
+  const size_t E = (size_t)V * ((size_t)V + 1) / 2;
+  const int32_t n_blocks = (int32_t)((E + kFisBlock - 1) / kFisBlock);
+  const int64_t units = (int64_t)pl.n_chunks * n_blocks;
+  if (units > INT32_MAX - kCenWaves) return set_error(DMX_ERR_ARG, "%s: %d chunks x %d entry blocks", fn, pl.n_chunks, n_blocks);
+  const size_t par = sizeof(double) * (size_t)pl.n_chunks * E, hb = sizeof(double) * (size_t)G * V * V, sb = sizeof(double) * (size_t)B * V;
+  const size_t nbb = sizeof(int64_t) * (size_t)B;
+  size_t free_b = 0, total_b = 0, need = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (par > e->d_fspart.cap()) need += par + par / 16;
+  if (hb > e->d_fsH.cap()) need += hb + hb / 16;
+  if (sb > e->d_fsscore.cap()) need += sb + sb / 16;
+  if (nbb > e->d_fsnb.cap()) need += nbb + nbb / 16;
+  if (need > free_b)
+    return set_error(DMX_ERR_NOMEM, "%s: %d chunk partials of %zu entries, H and the score rows need %zu bytes, %zu are free", fn, pl.n_chunks, E, need, free_b);
+  if (int rc = e->d_fspart.ensure(par)) return rc;
+  if (int rc = e->d_fsH.ensure(hb)) return rc;
+  if (int rc = e->d_fsscore.ensure(sb)) return rc;
+  if (int rc = e->d_fsnb.ensure(nbb)) return rc;
+  std::vector<uint8_t> active((size_t)G, 1);
+  std::vector<double> out((size_t)G * ((size_t)V + 3));
+  if (int rc = census_pass(e, pl, rq->w, active.data(), out.data())) return rc;      // (leaves w[G][V] in d_cnw)
+  std::vector<int64_t> cnt(2 * (size_t)G);
+  HIP_TRY(hipMemcpyAsync(cnt.data(), e->d_cncnt, sizeof(int64_t) * cnt.size(), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_fsH, 0, hb, e->stream));
+  if (sb) HIP_TRY(hipMemsetAsync(e->d_fsscore, 0, sb, e->stream));
+  if (B > 0) HIP_TRY(hipMemsetAsync(e->d_fsnb, 0, nbb, e->stream));
+  if (int rc = e->fsev.record_start(e->stream)) return rc;
+  if (units > 0) {
+    hipLaunchKernelGGL(k_census_fisher, dim3((unsigned)((units + kCenWaves - 1) / kCenWaves)), dim3(64 * kCenWaves), 0, e->stream, e->pv,
+                       e->nrd_width, (const double*)e->d_lut, (const double*)e->d_cnd, (const uint8_t*)e->d_cnvalid, V,
+                       (const int32_t*)e->d_cnorder, (const CenChunk*)e->d_cnchunk, pl.n_chunks, n_blocks, (const double*)e->d_cnw,
+                       e->d_fspart.get(), e->d_fsscore.get(), e->d_fsnb.get());
+    HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_census_fisher_fold, dim3((unsigned)G, (unsigned)((E + 255) / 256)), dim3(256), 0, e->stream, (const double*)e->d_fspart,
+                     (const int32_t*)e->d_cnoff, V, e->d_fsH.get());
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->fsev.record_stop(e->stream)) return rc;
+  if (rq->H) HIP_TRY(hipMemcpyAsync(rq->H, e->d_fsH, hb, hipMemcpyDeviceToHost, e->stream));
+  if (rq->score && sb) HIP_TRY(hipMemcpyAsync(rq->score, e->d_fsscore, sb, hipMemcpyDeviceToHost, e->stream));
+  if (rq->n_read_b && B > 0) HIP_TRY(hipMemcpyAsync(rq->n_read_b, e->d_fsnb, nbb, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  float ms = 0.f;
+  if (int rc = e->fsev.elapsed_ms(&ms)) return rc;
+  for (int32_t g = 0; g < G; ++g) {
+    const double* o = out.data() + (size_t)g * ((size_t)V + 3);
+    if (rq->acc) std::memcpy(rq->acc + (size_t)g * V, o, sizeof(double) * (size_t)V);
+    if (rq->ll) rq->ll[g] = o[V];
+    if (rq->n_read) rq->n_read[g] = cnt[2 * (size_t)g];
+    if (rq->n_pair) rq->n_pair[g] = cnt[2 * (size_t)g + 1];
+  }
+  dmx_census_fisher_info& inf = e->fis_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.kernel_ms = ms; inf.partial_bytes = (int64_t)par;
+  inf.n_groups = G; inf.n_chunks = pl.n_chunks; inf.n_blocks = n_blocks; inf.n_entries = (int32_t)E; inf.n_cells = B; inf.n_samples = V;
+  e->have_fis_info = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_census_fisher_info(dmx_engine* e, dmx_census_fisher_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_census_fisher_info: null argument");
+  if (!e->have_fis_info) return set_error(DMX_ERR_STATE, "dmx_engine_census_fisher_info: no call on the staged pileup (dmx_engine_census_fisher first)");
+  *out = e->fis_info;
   return DMX_OK;
 }
 

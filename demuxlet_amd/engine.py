@@ -777,9 +777,12 @@ class Engine:
         check(self._L.dmx_engine_census_step(self._h, C.byref(rq)))
         return acc, ll, gap, n_read, n_pair
 
-    def census(self, group, n_groups=None, w0=None, tol: float = 1e-4, max_steps: int = 2000, accelerate: bool = True) -> dict:
+    def census(self, group, n_groups=None, w0=None, tol: float = 1e-4, max_steps: int = 2000, accelerate: bool = True,
+               gap_on_support: bool = False) -> dict:
         """dmx_engine_census over the staged pileup: the maximum-likelihood donor shares of every group, by SQUAREM (or plain EM with
         accelerate=False) from w0[G][V] (None = uniform), each group stopping at duality gap <= tol or after max_steps passes.
+        gap_on_support=True takes the gap's maximum over the donors with w0 > 0 only (the duality gap of the problem constrained to the
+        start's support: the stopping rule of a refit with donors held at 0).
         Returns a dict: w[G][V], ll[G], gap[G], n_steps[G], converged[G], n_read[G], n_pair[G]."""
         gr, mem, ptr, G = self._census_group(group, n_groups)
         start = None
@@ -791,6 +794,8 @@ class Engine:
                 raise ValueError(f"w0 must be [{G}][{self.V}]")
         rq = capi.CensusRequest(self.B, mem, ptr, G, self.V, start.ctypes.data if start is not None else None, float(tol), int(max_steps),
                                 1 if accelerate else 0)
+        if gap_on_support:
+            rq.reserved[0] = 1
         check(self._L.dmx_engine_census(self._h, C.byref(rq)))
         w = np.zeros((G, self.V)); ll = np.zeros(G); gap = np.zeros(G)
         n_steps = np.zeros(G, dtype=np.int32); conv = np.zeros(G, dtype=np.int32)
@@ -804,6 +809,31 @@ class Engine:
         r = capi.CensusInfo()
         check(self._L.dmx_engine_census_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.CensusInfo._fields_ if n != "reserved"}
+
+    def census_fisher(self, group, w, n_groups=None) -> dict:
+        """dmx_engine_census_fisher over the staged pileup: the observed information of the shares at w[G][V] and the per-barcode
+        scores (include/dmx.h), V <= 128.  `group` as for census_step.  Returns a dict: H[G][V][V] (symmetric),
+        score[B][V] and n_read_b[B] (zero for barcodes of group -1), acc[G][V], ll[G], n_read[G], n_pair[G] (census_step's bits)."""
+        gr, mem, ptr, G = self._census_group(group, n_groups)
+        ww = np.ascontiguousarray(w, dtype=np.float64)
+        if ww.ndim == 1:
+            ww = ww[None, :]
+        if ww.shape != (G, self.V):
+            raise ValueError(f"w must be [{G}][{self.V}]")
+        H = np.zeros((G, self.V, self.V)); score = np.zeros((self.B, self.V)); n_b = np.zeros(self.B, dtype=np.int64)
+        acc = np.zeros((G, self.V)); ll = np.zeros(G)
+        n_read = np.zeros(G, dtype=np.int64); n_pair = np.zeros(G, dtype=np.int64)
+        rq = capi.CensusFisherRequest(self.B, mem, ptr, G, self.V, ww.ctypes.data, H.ctypes.data, score.ctypes.data if score.size else None,
+                                      n_b.ctypes.data if n_b.size else None, acc.ctypes.data, ll.ctypes.data, n_read.ctypes.data,
+                                      n_pair.ctypes.data)
+        check(self._L.dmx_engine_census_fisher(self._h, C.byref(rq)))
+        return dict(H=H, score=score, n_read_b=n_b, acc=acc, ll=ll, n_read=n_read, n_pair=n_pair)
+
+    def census_fisher_info(self) -> dict:
+        """HIP-event time (ms) of the last census_fisher call's kernels, partial bytes, chunks, entry blocks and entries."""
+        r = capi.CensusFisherInfo()
+        check(self._L.dmx_engine_census_fisher_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.CensusFisherInfo._fields_ if n != "reserved"}
 
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()

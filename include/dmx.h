@@ -952,7 +952,7 @@ typedef struct {
   double  tol;                 /* stop at gap <= tol; <= 0: 1e-4 */
   int32_t max_steps;           /* passes per group at most; <= 0: 2000 */
   int32_t accelerate;          /* 0 = plain EM, otherwise SQUAREM */
-  int32_t reserved[4];         /* 0 */
+  int32_t reserved[4];         /* reserved[0] = gap_on_support (see the census uncertainty block below); the others 0 */
 } dmx_census_request;
 typedef struct {
   double  kernel_ms;           /* HIP-event time of the last pass: k_census_step + k_census_fold */
@@ -971,6 +971,64 @@ int dmx_engine_census(dmx_engine*, const dmx_census_request*);
 int dmx_engine_get_census(dmx_engine*, double* w, double* ll, double* gap, int32_t* n_steps, int32_t* converged, int64_t* n_read,
                           int64_t* n_pair);
 int dmx_engine_census_info(dmx_engine*, dmx_census_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Census uncertainty: the observed information of the shares and the per-barcode scores (appended,
+ * DMX_ABI_VERSION stays 8).  Inputs as for dmx_engine_census_step.  At shares w, the step's quotients of a stored read r of pair
+ * (barcode b, SNP i) are tR = pR / P_r and tA = pA / P_r (the same IEEE divisions as in the step, on the same A_i and P_r).
+ *   Per pair: sRR = sum_r tR tR, sRA = sum_r tR tA, sAA = sum_r tA tA, reads in stored order (and the step's sR = sum tR, sA = sum tA).
+ *   With e_v = 1 - d[i][v], the observed information of group g (minus the Hessian of LL in w, unconstrained) is
+ *     H[g][v][u] = sum over the pairs of g of ((e_v e_u) sRR + (e_v d_u + d_v e_u) sRA) + (d_v d_u) sAA,  for v <= u;
+ *   every product and sum is rounded on its own, every term is non-negative, and the lower triangle is a copy of the upper.
+ *   score[b][v] = sum over the pairs of barcode b of e_v sR + d_v sA: the step's acc kept per barcode, so the barcodes of a group sum to
+ *   the group's acc (to rounding).  n_read_b[b] = the reads of b counted.  Barcodes with group -1 have a zero row and 0 reads.
+ *   Identities: sum_u H[g][v][u] w[g][u] = acc[g][v], and w' H w = N = n_read[g] (both to rounding).
+ * Summation plan: the step's chunks of 4 barcodes.  The E = V (V + 1) / 2 upper-triangle entries, numbered row-major, are cut into blocks
+ * of 2048; one wavefront per (chunk, block) adds, for each of its entries, one term per pair: barcodes in chunk order, pairs in stored
+ * order (a pair without a counted read adds +0).  A group's chunk partials are folded as the step's are: chunk c into accumulator c mod 8,
+ * then ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)).  A score row adds one term per pair of the barcode in stored order (for V <= 32 with the
+ * step's n = 64 / Vq running sums per tile position class, added in order at the barcode's end).  So a repeat, a group alone or among
+ * others, a host or a device `group`, nrd_width and earlier calls give the same bits; a barcode's score row depends on its own pairs and
+ * its w row only.  acc, ll, n_read and n_pair come from a dmx_engine_census_step pass inside the call and carry its bits.
+ * Every group given is computed (nothing is frozen).  The call runs on the engine's stream, synchronises it before returning, uses buffers of
+ * its own for H, the scores and their partials and leaves every other result of the engine, dmx_engine_get_census and
+ * dmx_engine_census_info included, as it was.
+ * DMX_ERR_ARG: as dmx_engine_census_step, and V > 128 (the chunk partials, chunks x E doubles, would not fit for a large pileup).
+ * DMX_ERR_STATE: as dmx_engine_census_step; dmx_engine_census_fisher_info before a call.  DMX_ERR_NOMEM: the partials, H and the score
+ * rows do not fit the free device memory.
+ *
+ * gap_on_support (dmx_census_request.reserved[0]): 0 keeps every bit of dmx_engine_census.  Non-zero: after each pass the driver takes
+ * gap[g] = N (max over {v : w0[g][v] > 0} of acc[v] / N - 1), computed on the host from the pass's acc, instead of the maximum over all
+ * donors.  EM and SQUAREM keep a zero share at zero, so this is the duality gap of the problem constrained to the support of the start;
+ * without it a refit with a donor held at 0 whose acc stays above N never reaches gap <= tol.  With w0 = NULL (uniform) every donor is
+ * in the support. */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t group_memory;        /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `group` lives */
+  const int32_t* group;        /* [n_cells], -1 = not used */
+  int32_t n_groups;            /* G, 1..1024 */
+  int32_t n_samples;           /* V = the engine's n_samples, <= 128 */
+  const double* w;             /* [G][V] float64, HOST */
+  double*  H;                  /* out [G][V][V], HOST (NULL = not wanted, as every output) */
+  double*  score;              /* out [n_cells][V] */
+  int64_t* n_read_b;           /* out [n_cells] */
+  double*  acc;                /* out [G][V] */
+  double*  ll;                 /* out [G] */
+  int64_t* n_read;             /* out [G] */
+  int64_t* n_pair;             /* out [G] */
+  int32_t reserved[4];         /* 0 */
+} dmx_census_fisher_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of k_census_fisher + k_census_fisher_fold */
+  int64_t partial_bytes;       /* device bytes of the chunk partials: n_chunks x n_entries doubles */
+  int32_t n_groups, n_chunks;
+  int32_t n_blocks;            /* entry blocks of 2048 per chunk: the grid is n_chunks x n_blocks wavefronts */
+  int32_t n_entries;           /* V (V + 1) / 2 */
+  int32_t n_cells, n_samples;
+  int32_t reserved[4];
+} dmx_census_fisher_info;
+int dmx_engine_census_fisher(dmx_engine*, const dmx_census_fisher_request*);
+int dmx_engine_census_fisher_info(dmx_engine*, dmx_census_fisher_info* out);
 
 #ifdef __cplusplus
 }
