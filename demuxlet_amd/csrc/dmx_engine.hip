@@ -3903,6 +3903,9 @@ __device__ __forceinline__ void a2_body(PileupView pv, int nrd_width, const floa
 #pragma unroll
     for (int su = 0; su < 2; ++su) { const int u = tid + TPC * su; uj[su] = u & (kUV - 1); uk[su] = (uj[su] + 1 + (u >> kUSh)) & (kUV - 1); }
   }
+  // SYMU: where the thread's rows start inside a staged genotype row, formed once (both units have the same j: TPC is a multiple of the panel)
+  const g_t* const ga = s_g + uj[0] * 3;
+  const g_t* const gb[2] = {s_g + uk[0] * 3, s_g + uk[1] * 3};
   // phase-1 identity (first wavefront of the cell): pair ti1, alpha n1; mixing weights of :613
   const int ti1 = tid >> 1, n1 = tid & 1;
   double acc00 = 0.0;                            // lane n1 == tid < 2 owns llks00[n]
@@ -3980,52 +3983,75 @@ __device__ __forceinline__ void a2_body(PileupView pv, int nrd_width, const floa
       // nine terms (g_k[l] g_j[m]) pG[1][l][m] of entry [k][j] are entry [j][k]'s T[l][m] = (g_j[l] g_k[m]) pG[1][l][m], transposed: the reference adds them
       // l-major for [j][k] and, seen from [j][k]'s indices, m-major for [k][j].  The owner of both forms the exact products E and the terms T once: 36
       // multiplies per unordered pair instead of 54; the 32 adds, the four logs and the four accumulator adds are the reference's, on its operands, in its order.
-      for (int ti = 0; ti < tp; ++ti) {
-        const double* P = &s_pG[ti * 18];
-        const double Q[3] = {P[0], P[3], P[6]};                              // pG[0][l][m] = q0[l]
-        const double P1[5] = {P[9], P[10], P[11], P[14], P[17]};             // pG[1][l][m] = q1[l + m]
-        const g_t* gr = &s_g[ti * GS];
+      // Order inside a pair: a unit forms its four sums, then requests the four table entries of their logs TOGETHER (dmx_log2_request_fast) and runs the four
+      // second halves behind one LDS wait (the logs one after the other left each entry's round trip exposed: ten waits per pair).  Unit 1's k row is
+      // requested behind unit 0's table entries, the next pair's values and rows once unit 1's entries are in: every other LDS read of the loop travels while
+      // logs are evaluated (three s_waitcnt lgkmcnt per pair, the one at the top of the loop for reads issued four logs earlier).
+      // The tile's pair count is workgroup-uniform (wavefront-uniform for the one-wavefront cells): a scalar loop counter.
+      const int tps = __builtin_amdgcn_readfirstlane(tp);
+      double Q[3], P1[5];
+      g_t ar[3], br[3];
+      auto load_pair = [&](int pi) {
+        const double* P = &s_pG[pi * 18];
+        Q[0] = P[0]; Q[1] = P[3]; Q[2] = P[6];                               // pG[0][l][m] = q0[l]
+        P1[0] = P[9]; P1[1] = P[10]; P1[2] = P[11]; P1[3] = P[14]; P1[4] = P[17];   // pG[1][l][m] = q1[l + m]
+        const g_t* ra = &ga[pi * GS];
+        const g_t* rb = &gb[0][pi * GS];
+        ar[0] = ra[0]; ar[1] = ra[1]; ar[2] = ra[2];
+        br[0] = rb[0]; br[1] = rb[1]; br[2] = rb[2];
+      };
+      load_pair(0);
+      for (int ti = 0; ti < tps; ++ti) {
+        const double a[3] = {(double)ar[0], (double)ar[1], (double)ar[2]};
 #pragma unroll
         for (int su = 0; su < 2; ++su) {
-          const int js = uj[su], ks = uk[su];
-          const double a[3] = {(double)gr[js * 3], (double)gr[js * 3 + 1], (double)gr[js * 3 + 2]};
-          const double b[3] = {(double)gr[ks * 3], (double)gr[ks * 3 + 1], (double)gr[ks * 3 + 2]};
+          const double b[3] = {(double)br[0], (double)br[1], (double)br[2]};
           double E[3][3];
 #pragma unroll
           for (int l = 0; l < 3; ++l)
 #pragma unroll
             for (int m = 0; m < 3; ++m) E[l][m] = a[l] * b[m];                  // :553 (exact) — shared by [j][k] and [k][j] at both alphas
-          {
-            // [j][k][0]: l-major over (l, m) of (g_j[l] g_k[m]) q0[l]; [k][j][0]: of (g_k[l] g_j[m]) q0[l] = E[m][l] q0[l] (the first product initialises the sum)
-            double s_jk0 = E[0][0] * Q[0], s_kj0 = E[0][0] * Q[0];
+          // [j][k][0]: l-major over (l, m) of (g_j[l] g_k[m]) q0[l]; [k][j][0]: of (g_k[l] g_j[m]) q0[l] = E[m][l] q0[l] (the first product initialises the sum)
+          double s_jk0 = E[0][0] * Q[0], s_kj0 = E[0][0] * Q[0];
 #pragma unroll
-            for (int l = 0; l < 3; ++l)
+          for (int l = 0; l < 3; ++l)
 #pragma unroll
-              for (int m = 0; m < 3; ++m) {
-                if (l == 0 && m == 0) continue;
-                s_jk0 += (E[l][m] * Q[l]);
-                s_kj0 += (E[m][l] * Q[l]);
-              }
-            acc[2 * su][0] += dmx_log2_fast_pinned(s_jk0, s_log, lk);          // :683
-            acc[2 * su + 1][0] += dmx_log2_fast_pinned(s_kj0, s_log, lk);
+            for (int m = 0; m < 3; ++m) {
+              if (l == 0 && m == 0) continue;
+              s_jk0 += (E[l][m] * Q[l]);
+              s_kj0 += (E[m][l] * Q[l]);
+            }
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+#pragma unroll
+            for (int m = 0; m < 3; ++m) E[l][m] = E[l][m] * P1[l + m];          // T: :677-679 at alpha 0.5 — [k][j]'s nine terms are these, transposed
+          double s_jk1 = E[0][0], s_kj1 = E[0][0];
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+              if (l == 0 && m == 0) continue;
+              s_jk1 += E[l][m];
+              s_kj1 += E[m][l];
+            }
+          const DmxLog2Req r_jk0 = dmx_log2_request_fast(s_jk0, s_log), r_kj0 = dmx_log2_request_fast(s_kj0, s_log),
+                           r_jk1 = dmx_log2_request_fast(s_jk1, s_log), r_kj1 = dmx_log2_request_fast(s_kj1, s_log);
+          if (su == 0) {
+            const g_t* rb = &gb[1][ti * GS];
+            br[0] = rb[0]; br[1] = rb[1]; br[2] = rb[2];
           }
-          {
-#pragma unroll
-            for (int l = 0; l < 3; ++l)
-#pragma unroll
-              for (int m = 0; m < 3; ++m) E[l][m] = E[l][m] * P1[l + m];        // T: :677-679 at alpha 0.5 — [k][j]'s nine terms are these, transposed
-            double s_jk1 = E[0][0], s_kj1 = E[0][0];
-#pragma unroll
-            for (int l = 0; l < 3; ++l)
-#pragma unroll
-              for (int m = 0; m < 3; ++m) {
-                if (l == 0 && m == 0) continue;
-                s_jk1 += E[l][m];
-                s_kj1 += E[m][l];
-              }
-            acc[2 * su][1] += dmx_log2_fast_pinned(s_jk1, s_log, lk);
-            acc[2 * su + 1][1] += dmx_log2_fast_pinned(s_kj1, s_log, lk);
+          __builtin_amdgcn_sched_barrier(0);                                   // requests first: nothing of the arithmetic below moves above them
+          __builtin_amdgcn_s_waitcnt(0xC07F);                                  // lgkmcnt(0): ONE wait for the unit's four entries (left alone: one per entry)
+          __builtin_amdgcn_sched_barrier(0);                                   // (the wait has no operands: without this it sinks below the arithmetic)
+          if (su == 1) {
+            load_pair(min(ti + 1, tps - 1));                                   // (the tile's last pair requests itself again: nothing reads it)
+            __builtin_amdgcn_sched_barrier(0);
           }
+          acc[2 * su][0] += dmx_log2_finish_pinned(r_jk0, lk);                 // :683
+          acc[2 * su + 1][0] += dmx_log2_finish_pinned(r_kj0, lk);
+          acc[2 * su][1] += dmx_log2_finish_pinned(r_jk1, lk);
+          acc[2 * su + 1][1] += dmx_log2_finish_pinned(r_kj1, lk);
+          __builtin_amdgcn_sched_barrier(0);                                   // one unit's logs at a time (register budget; without it: no faster)
         }
       }
     } else
