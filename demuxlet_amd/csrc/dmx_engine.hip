@@ -4147,6 +4147,258 @@ __global__ __launch_bounds__(kThreads, 3) void k_doublet_a2u16(PileupView pv, in
   a2_body<64, 4, 1, false, false, 32, true>(pv, nrd_width, g, gp0, tabs, alpha, sched, V, GS, grid, l00, flagged, pfin, pseed);
 }
 
+// k_doublet_a2u for TWO barcodes per workgroup (32 samples, STRICT, default grid, provably safe rows, DENSE pileups: cfg3 — the headline).  The exact products
+// E[l][m] = g_j[l] g_k[m] (:553) depend on the SNP and the sample pair, not on the barcode, and pair p of every barcode of a dense pileup is SNP p: two barcodes
+// that walk their pairs in lockstep need E once.  Workgroup (x, y) owns the barcodes of schedule slots 2x and 2x + 1 and slab y of the 496 unordered pairs: thread
+// tid owns ONE unit u = tid + 256 y (k_doublet_a2u's mapping: j = u % 32, d = 1 + u / 32, k = (j + d) % 32, d = 16 from j < 16 only) for BOTH barcodes — eight
+// accumulators, as there.  Everything else stays per barcode with the reference's operands in the reference's order: 209 FP64 instructions per pair where
+// k_doublet_a2u's thread spends 218 on its two units of one barcode.
+// Per tile of 32 pairs: headers of both barcodes (the first wavefront: lanes 0..31 barcode 0, 32..63 barcode 1; the SNP ids are the pair indices), the 32 rows
+// staged ONCE as binary64, phase 1 on 128 lanes (wavefront = barcode, lane = (pair, alpha); the table / loop test is per wavefront) which leaves the EIGHT values
+// phase 2 reads per (barcode, pair) — alpha 0.5's q1[0..4] | alpha 0's q0[0..2], k_doublet_diag's layout; the eighteen-value layout would not fit four
+// workgroups per CU — and, in slab 0 only, the llks00 terms.  A lone last barcode (odd B) is walked twice; the second copy stores nothing.
+// Every barcode of a dense pileup has the same pair count (checked when the pileup is set), so the tile loop and its barriers are workgroup-uniform.
+// DIAG16: slab 1's last sixteen slots (u = 496..511), which otherwise repeat units that exist, take k = j for j = 16..31: E = g_j x g_j, and the unit's l-major
+// [j][k] sums are the diagonal entries [j][j][0..1] as the reference and k_doublet_diag form them (the [k][j] sums of such a unit are dropped); k_doublet_diag_lo
+// behind the kernel then owns j = 0..15 only.
+// The kernel is a form of the unordered-pair kernel and is named so: k_doublet_a2u<k_doublet_a2u2> (the shipped form, DIAG16) and
+// k_doublet_a2u<k_doublet_a2u2_whole_diag_behind> are what dmx_engine_kernel_names and the profiler report.
+struct k_doublet_a2u2 { static constexpr bool diag16 = true; };
+struct k_doublet_a2u2_whole_diag_behind { static constexpr bool diag16 = false; };
+template <bool DIAG16>
+__device__ __forceinline__ void a2u2_body(PileupView pv, int nrd_width, const float* __restrict__ g,
+                                                         const double* __restrict__ gp0, const double* __restrict__ tabs,
+                                                         const double* __restrict__ alpha, const int32_t* __restrict__ sched,
+                                                         double* __restrict__ grid, double* __restrict__ l00,
+                                                         uint8_t* __restrict__ flagged, const double* __restrict__ pfin, const double* __restrict__ pseed) {
+  constexpr int V = 32, A = 2, TP = 32, T00 = TP + 2, GS = 3 * V, row_len = 3 * V;
+  __shared__ double s_tab[kTab2];
+  __shared__ double s_w[2][18];                  // the nine-value loop's mixing weights (a2_body's)
+  __shared__ __attribute__((aligned(16))) double s_q[2][TP][8];          // [barcode][pair]: q1[0..4] (alpha 0.5, index l + m) | q0[0..2] (alpha 0, index l)
+  __shared__ __attribute__((aligned(16))) double s_g[TP * GS];           // genotype rows of the tile's SNPs, binary64
+  __shared__ __attribute__((aligned(16))) double s_t00[2][2][T00];       // [barcode][alpha]: llks00 terms (slab 0)
+  __shared__ int64_t s_off[2][TP];
+  __shared__ int32_t s_snp[2][TP];               // (the same ids twice: each header lane group publishes its own copy)
+  __shared__ uint32_t s_cnt[2][TP];
+  const double* s_log = s_tab + kLut2;
+  const int tid = threadIdx.x;
+  stage_k2_tables(s_tab, tabs, tid, kThreads);
+  if (tid < 18) {
+    const int n = tid / 9, l = (tid % 9) / 3, m = tid % 3;
+    const double p = 0.5 * l + (m - l) * 0.5 * alpha[n];
+    s_w[n][tid % 9] = p;
+    s_w[n][9 + tid % 9] = 1.0 - p;
+  }
+  __syncthreads();
+
+  const int slot0 = 2 * (int)blockIdx.x;         // < B by the launch grid
+  const bool two = slot0 + 1 < pv.B;             // odd B: the last workgroup's second barcode does not exist — it walks the first one again and stores nothing
+  const bool slab0 = blockIdx.y == 0;
+  // header lanes (tid < 64: barcode hb, pair hl of the tile) and phase-1 lanes (tid < 128: barcode bb, pair ti1, alpha n1)
+  const int hb = (tid >> 5) & 1, hl = tid & 31;
+  const int bb = (tid >> 6) & 1, ti1 = (tid & 63) >> 1, n1 = tid & 1;
+  const int32_t cell0 = sched[slot0], cell1 = two ? sched[slot0 + 1] : cell0;
+  const int32_t cell_h = hb ? cell1 : cell0;
+  const int64_t p_beg = pv.cell_pair_off[cell_h];
+  int64_t rd_base = pv.cell_read_off[cell_h];
+  const int np = (int)(pv.cell_pair_off[cell0 + 1] - pv.cell_pair_off[cell0]);   // the pileup's common pair count: the same value in every thread
+
+  const int u = tid + kThreads * (int)blockIdx.y, uj = u & 31, ud = 1 + (u >> 5);
+  const bool udiag = DIAG16 && u >= 496;         // (j = 16..31)
+  const int uk = udiag ? uj : (uj + ud) & 31;
+  const double* const ga = s_g + uj * 3;
+  const double* const gb = s_g + uk * 3;
+  double acc[2][4];                              // [barcode]: [j][k][0], [k][j][0], [j][k][1], [k][j][1]
+#pragma unroll
+  for (int c = 0; c < 2; ++c) { acc[c][0] = 0.0; acc[c][1] = 0.0; acc[c][2] = 0.0; acc[c][3] = 0.0; }
+  bool ok = true;
+  double acc00 = 0.0;                            // slab 0, tid < 4: llks00[alpha tid & 1] of barcode tid >> 1
+  const DmxLogPins lk = dmx_log_pins();
+
+  for (int tbase = 0; tbase < np; tbase += TP) {
+    const int tp = min(TP, np - tbase);
+    // ---- headers of the tile's pairs, both barcodes
+    if (tid < 64) load_tile_headers<TP>(pv, nrd_width, p_beg, (int64_t)tbase, tp, hl, rd_base, s_cnt[hb], s_off[hb], s_snp[hb]);
+    __syncthreads();
+    if (tid < 64) rd_base = s_off[hb][tp - 1] + (int64_t)s_cnt[hb][tp - 1];
+    // ---- genotype rows -> LDS, once for both barcodes
+    stage_geno_rows<kThreads>(g, s_snp[0], tp, tid, row_len, GS, s_g);
+    // ---- phase 1
+    if (tid < 4 * TP) {
+      const bool on = ti1 < tp;
+      const uint32_t cnt = on ? s_cnt[bb][ti1] : 0u;
+      const int64_t off = on ? s_off[bb][ti1] : 0;
+      const uint32_t rd4 = load_rd4(pv, off, cnt);
+      double vf[9];                                // (a2_body's three sources, as there)
+      const int32_t fi = pfin ? certify_final_index(cnt, rd4) : -1;
+      if (!__any(fi < 0)) {
+        const double* fp = pfin + (size_t)fi * kCFinStride + (n1 ? 0 : 5);
+        const double f0 = fp[0], f1 = fp[1], f2 = fp[2], f3 = n1 ? fp[3] : 0.0, f4 = n1 ? fp[4] : 0.0;
+        const double f5[5] = {f0, f1, f2, f3, f4};
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int m = 0; m < 3; ++m) vf[l * 3 + m] = n1 ? f5[l + m] : f5[l];
+      } else if (pseed) {
+        double q5[5], wA5[5], wR5[5];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+          const int l = n1 ? (q > 2 ? 2 : q) : min(q, 2), m = n1 ? q - l : 0;
+          const double p = 0.5 * l + (m - l) * 0.5 * (n1 ? 0.5 : 0.0);
+          wA5[q] = p;
+          wR5[q] = 1.0 - p;
+        }
+        certify_pair_values<5, false>(pv, cnt, off, rd4, s_tab, wA5, wR5, n1, q5, pseed);
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int m = 0; m < 3; ++m) vf[l * 3 + m] = n1 ? q5[l + m] : q5[l];
+      } else {
+        double wA[9], wR[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) { wA[i] = s_w[n1][i]; wR[i] = s_w[n1][9 + i]; }
+        certify_pair_values<9, false, 2, true>(pv, cnt, off, rd4, s_tab, wA, wR, n1, vf);
+      }
+      if (on) {
+        double* q = &s_q[bb][ti1][0];
+        if (n1) { q[0] = vf[0]; q[1] = vf[1]; q[2] = vf[2]; q[3] = vf[5]; q[4] = vf[8]; }   // pG[1][l][m] = q1[l + m]
+        else { q[5] = vf[0]; q[6] = vf[3]; q[7] = vf[6]; }                                  // pG[0][l][m] = q0[l]
+        if (slab0)                                 // (workgroup-uniform) the llks00 term from the nine values in registers
+          ok &= llks00_term(gp0, s_snp[bb][ti1], [&](int l, int m) { return vf[l * 3 + m]; }, s_log, &s_t00[bb][n1][ti1]);
+      }
+    }
+    __syncthreads();
+    // ---- llks00 (slab 0): lane (barcode, alpha) adds its terms in pair order
+    if (slab0 && tid < 4) {
+      const double* row = &s_t00[tid >> 1][tid & 1][0];
+      if (tp == TP) {
+        double2 v[TP / 2];
+#pragma unroll
+        for (int i = 0; i < TP / 2; ++i) v[i] = *reinterpret_cast<const double2*>(&row[2 * i]);
+#pragma unroll
+        for (int i = 0; i < TP / 2; ++i) { acc00 += v[i].x; acc00 += v[i].y; }
+      } else {
+        for (int i = 0; i < tp; ++i) acc00 += row[i];
+      }
+    }
+    // ---- phase 2: the thread's unit, both barcodes.  E once; per barcode k_doublet_a2u's sums (a2_body, SYMU), logs and adds on its operands in its order.
+    // Barcode 1's alpha-0.5 terms T' go to fresh registers, barcode 0's T replace E.  The eight logs run in two batches of four (a barcode each): four table
+    // entries requested together, one wait, four second halves; the next pair's rows and q values are requested while logs are evaluated.
+    {
+      const int tps = __builtin_amdgcn_readfirstlane(tp);
+      double Q[2][3], P1[2][5], ar[3], br[3];
+      auto load_pair = [&](int pi) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          const double* q = &s_q[c][pi][0];
+          P1[c][0] = q[0]; P1[c][1] = q[1]; P1[c][2] = q[2]; P1[c][3] = q[3]; P1[c][4] = q[4];
+          Q[c][0] = q[5]; Q[c][1] = q[6]; Q[c][2] = q[7];
+        }
+        const double* ra = &ga[pi * GS];
+        const double* rb = &gb[pi * GS];
+        ar[0] = ra[0]; ar[1] = ra[1]; ar[2] = ra[2];
+        br[0] = rb[0]; br[1] = rb[1]; br[2] = rb[2];
+      };
+      load_pair(0);
+      for (int ti = 0; ti < tps; ++ti) {
+        double E[3][3], T1[3][3];
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int m = 0; m < 3; ++m) E[l][m] = ar[l] * br[m];                  // :553 (exact) — shared by [j][k] and [k][j], both alphas, BOTH barcodes
+        // [j][k][0]: l-major over (l, m) of (g_j[l] g_k[m]) q0[l]; [k][j][0]: of (g_k[l] g_j[m]) q0[l] = E[m][l] q0[l] (the first product initialises the sum)
+        double s_jk0[2], s_kj0[2], s_jk1[2], s_kj1[2];
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+          s_jk0[c] = E[0][0] * Q[c][0]; s_kj0[c] = E[0][0] * Q[c][0];
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+              if (l == 0 && m == 0) continue;
+              s_jk0[c] += (E[l][m] * Q[c][l]);
+              s_kj0[c] += (E[m][l] * Q[c][l]);
+            }
+        }
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int m = 0; m < 3; ++m) {
+            T1[l][m] = E[l][m] * P1[1][l + m];                                   // T': barcode 1's terms (:677-679 at alpha 0.5), fresh registers
+            E[l][m] = E[l][m] * P1[0][l + m];                                    // T: barcode 0's, in place
+          }
+        s_jk1[0] = E[0][0]; s_kj1[0] = E[0][0];
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int m = 0; m < 3; ++m) {
+            if (l == 0 && m == 0) continue;
+            s_jk1[0] += E[l][m];
+            s_kj1[0] += E[m][l];
+          }
+        // barcode 0's four table entries travel while barcode 1's alpha-0.5 sums are formed
+        const DmxLog2Req a_jk0 = dmx_log2_request_fast(s_jk0[0], s_log), a_kj0 = dmx_log2_request_fast(s_kj0[0], s_log),
+                         a_jk1 = dmx_log2_request_fast(s_jk1[0], s_log), a_kj1 = dmx_log2_request_fast(s_kj1[0], s_log);
+        __builtin_amdgcn_sched_barrier(0);                                     // requests first: nothing of the arithmetic below moves above them
+        s_jk1[1] = T1[0][0]; s_kj1[1] = T1[0][0];
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int m = 0; m < 3; ++m) {
+            if (l == 0 && m == 0) continue;
+            s_jk1[1] += T1[l][m];
+            s_kj1[1] += T1[m][l];
+          }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xC07F);                                    // lgkmcnt(0): ONE wait for the barcode's four entries
+        __builtin_amdgcn_sched_barrier(0);                                     // (the wait has no operands: without this it sinks below the arithmetic)
+        // barcode 1's entries, the next pair's q values and rows: every other LDS read of the pair travels while barcode 0's logs are evaluated
+        const DmxLog2Req b_jk0 = dmx_log2_request_fast(s_jk0[1], s_log), b_kj0 = dmx_log2_request_fast(s_kj0[1], s_log),
+                         b_jk1 = dmx_log2_request_fast(s_jk1[1], s_log), b_kj1 = dmx_log2_request_fast(s_kj1[1], s_log);
+        load_pair(min(ti + 1, tps - 1));                                       // (the tile's last pair requests itself again: nothing reads it)
+        __builtin_amdgcn_sched_barrier(0);
+        acc[0][0] += dmx_log2_finish_pinned(a_jk0, lk);                        // :683
+        acc[0][1] += dmx_log2_finish_pinned(a_kj0, lk);
+        acc[0][2] += dmx_log2_finish_pinned(a_jk1, lk);
+        acc[0][3] += dmx_log2_finish_pinned(a_kj1, lk);
+        asm volatile("" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]));   // barcode 0's logs stay in front of the second wait
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(0xC07F);
+        __builtin_amdgcn_sched_barrier(0);
+        acc[1][0] += dmx_log2_finish_pinned(b_jk0, lk);
+        acc[1][1] += dmx_log2_finish_pinned(b_kj0, lk);
+        acc[1][2] += dmx_log2_finish_pinned(b_jk1, lk);
+        acc[1][3] += dmx_log2_finish_pinned(b_kj1, lk);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    __syncthreads();
+  }
+  if (ud < 16 || (ud == 16 && uj < 16) || udiag) {   // d = 16 is reached from both sides: the j < 16 thread stores; slab 1's last sixteen slots repeat units that exist, or hold a diagonal entry
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      if (c == 1 && !two) break;
+      const int32_t cell = c ? cell1 : cell0;
+      double* o = grid + (((size_t)cell * V + uj) * V + uk) * A;
+      o[0] = acc[c][0]; o[1] = acc[c][2];
+      if (!udiag) {
+        double* o2 = grid + (((size_t)cell * V + uk) * V + uj) * A;
+        o2[0] = acc[c][1]; o2[1] = acc[c][3];
+      }
+    }
+  }
+  if (slab0 && tid < 4 && (tid < 2 || two)) l00[(size_t)((tid >> 1) ? cell1 : cell0) * A + (tid & 1)] = acc00;
+  if (!ok) flag_cell(flagged, bb ? cell1 : cell0);  // (phase-1 lanes of slab 0 only; a lone barcode's second copy flags the barcode itself)
+}
+template <class FORM>                            // FORM: k_doublet_a2u2 or k_doublet_a2u2_whole_diag_behind (k_doublet_a2u<MINW> above is the one-barcode kernel)
+__global__ __launch_bounds__(kThreads, 4) void k_doublet_a2u(PileupView pv, int nrd_width, const float* __restrict__ g,
+                                                         const double* __restrict__ gp0, const double* __restrict__ tabs,
+                                                         const double* __restrict__ alpha, const int32_t* __restrict__ sched,
+                                                         double* __restrict__ grid, double* __restrict__ l00,
+                                                         uint8_t* __restrict__ flagged, const double* __restrict__ pfin, const double* __restrict__ pseed) {
+  a2u2_body<FORM::diag16>(pv, nrd_width, g, gp0, tabs, alpha, sched, grid, l00, flagged, pfin, pseed);
+}
+
 // K2, A = 2, FAST mode (dmx_engine_config.mode = DMX_MODE_FAST): k_doublet_a2 with the bilinear factoring of SURVEY H3.  Not the
 // reference's operation sequence inside a term (so not STRICT), but the same accumulation order; tests bound it by 1e-9.
 template <int TPC, int NK>
@@ -5096,12 +5348,14 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_a2s(PileupView pv, i
 // (k_doublet_a2s<.., 0>, the first form, spent a 64-lane wavefront per barcode: lane (j, alpha), 62 instructions per pair; this one 83 per pair for two
 // barcodes).  Per tile of 16 pairs and barcode: headers (16 lanes), phase 1 (32 lanes = pair x alpha; k_doublet_sym's, from the final-value table where
 // every pair of the wavefront's two tiles is on it), then the lane's own three floats per pair straight from the matrix.  No workgroup barrier.
-template <int MINW, int VP = 32>                // VP: the panel — 32 samples (two barcodes per wavefront) or 16 (four)
-__global__ __launch_bounds__(kThreads, MINW) void k_doublet_diag(PileupView pv, int nrd_width, const float* __restrict__ g,
+// LN: sample lanes per barcode — the whole panel, or (k_doublet_diag_lo, behind k_doublet_a2u2, which forms the entries of j = 16..31 itself) the first 16 samples
+// of 32: four barcodes per wavefront, tiles of 8 pairs, rows still 96 floats apart.
+template <int MINW, int VP, int LN>
+__device__ __forceinline__ void diag_body(PileupView pv, int nrd_width, const float* __restrict__ g,
                                                            const double* __restrict__ tabs, const int32_t* __restrict__ sched,
                                                            double* __restrict__ grid, const double* __restrict__ pfin, const double* __restrict__ pseed) {
-  static_assert(VP == 32 || VP == 16, "panel");
-  constexpr int V = VP, A = 2, TPC = VP, TP = VP / 2, CPW = kThreads / TPC, row_len = 3 * V, PB = 8, WPC = 64 / TPC;
+  static_assert((VP == 32 || VP == 16) && (LN == VP || LN == 16), "panel");
+  constexpr int V = VP, A = 2, TPC = LN, TP = LN / 2, CPW = kThreads / TPC, row_len = 3 * V, PB = 8, WPC = 64 / TPC;
   __shared__ double s_tab[kTab2];
   __shared__ double s_w[2][10];
   __shared__ __attribute__((aligned(16))) double s_pq_all[CPW][TP][8];
@@ -5207,6 +5461,19 @@ __global__ __launch_bounds__(kThreads, MINW) void k_doublet_diag(PileupView pv, 
     double* o = grid + (((size_t)cell * V + j) * V + j) * A;
     o[0] = acc0; o[1] = acc1;
   }
+}
+template <int MINW, int VP = 32>                // VP: the panel — 32 samples (two barcodes per wavefront) or 16 (four)
+__global__ __launch_bounds__(kThreads, MINW) void k_doublet_diag(PileupView pv, int nrd_width, const float* __restrict__ g,
+                                                           const double* __restrict__ tabs, const int32_t* __restrict__ sched,
+                                                           double* __restrict__ grid, const double* __restrict__ pfin, const double* __restrict__ pseed) {
+  diag_body<MINW, VP, VP>(pv, nrd_width, g, tabs, sched, grid, pfin, pseed);
+}
+// ... of the samples j = 0..15 of 32 only (behind k_doublet_a2u2)
+template <int MINW>
+__global__ __launch_bounds__(kThreads, MINW) void k_doublet_diag_lo(PileupView pv, int nrd_width, const float* __restrict__ g,
+                                                           const double* __restrict__ tabs, const int32_t* __restrict__ sched,
+                                                           double* __restrict__ grid, const double* __restrict__ pfin, const double* __restrict__ pseed) {
+  diag_body<MINW, 32, 16>(pv, nrd_width, g, tabs, sched, grid, pfin, pseed);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -8725,10 +8992,23 @@ int launch_doublet(dmx_engine* e) {
   if (V == 32 && pfin_a2_grid && e->geno_safe && !e->knob("DMX_A2_SYM") && !e->knob("DMX_A2_NO_SYMU") && !e->knob("DMX_A2_NO_GD") && !e->knob("DMX_A2_MINW1")) {
     // 32 soft-field samples on the default grid (cfg3, the headline): k_doublet_a2's kernel over UNORDERED pairs — a thread owns [j][k] and [k][j] and forms
     // the products they share once — and the 64 diagonal accumulators of a barcode on one wavefront behind it (DMX_A2_NO_SYMU=1: k_doublet_a2)
+    // dense pileups (pair p of every barcode is SNP p, every barcode has the same pair count): two barcodes per workgroup share the products g_j[l] g_k[m] of
+    // a unit, one slab of the unordered pairs per workgroup (DMX_A2U_ONE_BARCODE=1: k_doublet_a2u)
     const size_t cbd = (size_t)32 * 18 * 8 + (size_t)32 * GS * 8 + 2 * 34 * 8 + 32 * (4 + 4 + 8);
+    const bool two_barcodes = e->pv.pair_snp == nullptr && !e->knob("DMX_A2U_ONE_BARCODE");
+    const bool diag16 = two_barcodes && !e->knob("DMX_A2U2_NO_DIAG") && !e->knob("DMX_A2U_DIAG_WAVE");   // the entries [j][j], j = 16..31, in k_doublet_a2u2's idle slots
+    if (diag16)
+      DMX_LAUNCH(k2_fn, (k_doublet_a2u<k_doublet_a2u2>), dim3((unsigned)((B + 1) / 2), 2), block, 0, e->stream, e->pv, e->nrd_width, e->d_g,
+                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
+    else if (two_barcodes)
+      DMX_LAUNCH(k2_fn, (k_doublet_a2u<k_doublet_a2u2_whole_diag_behind>), dim3((unsigned)((B + 1) / 2), 2), block, 0, e->stream, e->pv, e->nrd_width, e->d_g,
+                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
+    else
     DMX_LAUNCH(k2_fn, (k_doublet_a2u<4>), dim3((unsigned)B, 1), block, cbd, e->stream, e->pv, e->nrd_width, e->d_g,
                        e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
-    if (e->knob("DMX_A2U_DIAG_WAVE"))             // kernel experiments only: the diagonal on one wavefront per barcode (the first form)
+    if (diag16)
+      hipLaunchKernelGGL((k_doublet_diag_lo<5>), dim3((unsigned)((B + 15) / 16)), block, 0, e->stream, e->pv, e->nrd_width, e->d_g, e->d_lut, e->d_sched, e->d_grid, pfin_a2, pseed_a2);
+    else if (e->knob("DMX_A2U_DIAG_WAVE"))             // kernel experiments only: the diagonal on one wavefront per barcode (the first form)
       hipLaunchKernelGGL((k_doublet_a2s<4, 4, 0>), dim3((unsigned)((B + 3) / 4), 1), block, 0, e->stream, e->pv, e->nrd_width, e->d_g, e->d_gp0, e->d_lut, e->d_sched,
                          e->d_grid, e->d_l00, pfin_a2);
     else
