@@ -49,6 +49,7 @@ SYMBOLS = [
     "dmx_engine_compose", "dmx_engine_composed_pileup", "dmx_engine_get_composed", "dmx_engine_compose_info",
     "dmx_engine_census_step", "dmx_engine_census", "dmx_engine_get_census", "dmx_engine_census_info",
     "dmx_engine_census_fisher", "dmx_engine_census_fisher_info",
+    "dmx_engine_doublet_anchored", "dmx_engine_get_anchored", "dmx_engine_anchored_info",
 ]
 
 
@@ -175,6 +176,16 @@ class TripletRequest(C.Structure):     # dmx_triplet_request
 class TripletInfo(C.Structure):        # dmx_triplet_info
     _fields_ = [("kernel_ms", C.c_double), ("profile_bytes", C.c_int64), ("n_used", C.c_int64), ("n_cells", C.c_int32), ("n_base", C.c_int32),
                 ("n_shares", C.c_int32), ("n_samples", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class AnchoredRequest(C.Structure):    # dmx_anchored_request
+    _fields_ = [("n_cells", C.c_int32), ("n_anchor", C.c_int32), ("anchor_memory", C.c_int32), ("reserved0", C.c_int32), ("anchors", C.c_void_p),
+                ("reserved", C.c_int32 * 4)]
+
+
+class AnchoredInfo(C.Structure):       # dmx_anchored_info
+    _fields_ = [("col_ms", C.c_double), ("pair_ms", C.c_double), ("reduce_ms", C.c_double), ("result_bytes", C.c_int64), ("n_entries", C.c_int64),
+                ("n_cells", C.c_int32), ("n_samples", C.c_int32), ("n_alpha", C.c_int32), ("n_anchor", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class ComposeRequest(C.Structure):     # dmx_compose_request
@@ -359,6 +370,7 @@ def load() -> C.CDLL:
         "dmx_engine_cluster_mstep_window": [vp, vp], "dmx_engine_get_cluster_known": [vp, vp], "dmx_engine_cluster_known_info": [vp, vp],
         "dmx_engine_ambient": [vp, vp], "dmx_engine_get_ambient": [vp, vp, vp, vp], "dmx_engine_ambient_info": [vp, vp],
         "dmx_engine_ambient_doublet": [vp, vp], "dmx_engine_get_ambient_doublet": [vp, vp, vp, vp], "dmx_engine_ambient_doublet_info": [vp, vp],
+        "dmx_engine_doublet_anchored": [vp, vp], "dmx_engine_get_anchored": [vp, vp, vp, vp, vp, vp], "dmx_engine_anchored_info": [vp, vp],
         "dmx_engine_triplet": [vp, vp], "dmx_engine_get_triplet": [vp, vp, vp, vp], "dmx_engine_triplet_info": [vp, vp],
         "dmx_engine_compose": [vp, vp], "dmx_engine_composed_pileup": [vp, vp], "dmx_engine_get_composed": [vp, vp, vp, vp, vp, vp],
         "dmx_engine_compose_info": [vp, vp],

@@ -7518,6 +7518,336 @@ __global__ __launch_bounds__(kThreads) void k_reduce(const double* __restrict__ 
   }
 }
 
+// ---- anchored doublet search (dmx_engine_doublet_anchored) -----------------------------------------------------
+// Entries of the grid llksAB[V][V][A] without the grid: column 0 at every alpha (k_anchor_col, with llks00), the T best singlets as
+// anchors (k_anchor_select), every sample as the partner of every anchor in both orders at n >= 1 (k_anchor_pair), and K3's record over
+// what was evaluated (k_anchor_reduce).  The two entry kernels are k_doublet_generic cut down to a wavefront: one wavefront per
+// (barcode, slab of 64 NACC entries), tiles of TP = min(32, 64 / A_pad) covered pairs, and per tile
+//   phase 1  lane (pair, alpha): pair_values_open / rcp_refined / div_by, the nine finished values to LDS (and, in k_anchor_col's slab 0,
+//            the pair's llks00 term);
+//   phase 2  lane = entry: the rows of j and k as stored (float32, widened; the products are exact), the nine-term l-major sum from 0.0,
+//            dmx_log2, one add — the pairs of a tile in ascending order, so an entry is one serial sum over the barcode's pairs.
+// Entries are laid along the lanes with the SAMPLE index fastest (k_anchor_col: (n, j); k_anchor_pair: (t, order, n, k)), so a wavefront
+// reads consecutive 12-byte rows and the row of sample 0 / of the anchor is one address.  An entry's operations and operands are those of
+// k_doublet_generic's accumulator (j, k, n); nothing in them depends on T, the anchor's rank, the slab or the lane.
+// No argument-class test and no fix-up pass: the host refuses a matrix that k_check_geno did not pass.
+constexpr int kAncWaves = 4, kAncMaxT = 8, kAncTP = 32;
+constexpr uint32_t kAncNone = ~0u;
+
+template <int NACC, bool PAIR>
+__device__ __forceinline__ void anchor_body(const PileupView& pv, int nrd_width, const float* __restrict__ g, const double* __restrict__ gp0,
+                                            const double* __restrict__ tabs, const double* __restrict__ alpha, int32_t V, int32_t A,
+                                            int32_t A_pad, int32_t TP, int32_t T, const int32_t* __restrict__ anchors, int32_t n_slab,
+                                            int64_t n_units, double* __restrict__ c0, double* __restrict__ l00, double* __restrict__ pairs) {
+  __shared__ double s_tab[kTab2];
+  __shared__ double s_pGs[kAncWaves][64 * 9];
+  __shared__ double s_t00s[kAncWaves][64];
+  __shared__ int32_t s_snps[kAncWaves][kAncTP];
+  __shared__ uint32_t s_cnts[kAncWaves][kAncTP];
+  __shared__ int64_t s_offs[kAncWaves][kAncTP];
+  stage_k2_tables(s_tab, tabs, threadIdx.x, 64 * kAncWaves);
+  __syncthreads();
+  const double* s_log = s_tab + kLut2;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t unit = (int64_t)blockIdx.x * kAncWaves + wave;
+  if (unit >= n_units) return;
+  const int32_t cell = (int32_t)(unit / n_slab), slab = (int32_t)(unit % n_slab);
+  double* s_pG = s_pGs[wave]; double* s_t00 = s_t00s[wave];
+  int32_t* s_snp = s_snps[wave]; uint32_t* s_cnt = s_cnts[wave]; int64_t* s_off = s_offs[wave];
+
+  // this lane's entries: code = (j << 20) | (k << 8) | n, out = where the finished sum goes
+  const int64_t n_ent = PAIR ? (int64_t)T * 2 * (A - 1) * V : (int64_t)V * A;
+  uint32_t code[NACC];
+  int64_t out[NACC];
+  double acc[NACC];
+#pragma unroll
+  for (int i = 0; i < NACC; ++i) {
+    const int64_t en = ((int64_t)slab * NACC + i) * 64 + lane;
+    code[i] = kAncNone; out[i] = -1; acc[i] = 0.0;
+    if (en >= n_ent) continue;
+    const int32_t s = (int32_t)(en % V);
+    int32_t r = (int32_t)(en / V);
+    if (PAIR) {
+      const int32_t n = 1 + r % (A - 1); r /= (A - 1);
+      const int32_t o = r & 1, t = r >> 1;
+      const int32_t a = anchors[(size_t)cell * T + t];
+      out[i] = ((((int64_t)cell * T + t) * V + s) * 2 + o) * (A - 1) + (n - 1);
+      if (a >= 0 && a != s) code[i] = ((uint32_t)(o ? s : a) << 20) | ((uint32_t)(o ? a : s) << 8) | (uint32_t)n;
+    } else {
+      out[i] = ((int64_t)cell * V + s) * A + r;
+      code[i] = ((uint32_t)s << 20) | (uint32_t)r;
+    }
+  }
+  const bool do00 = !PAIR && slab == 0;
+  double acc00 = 0.0;
+
+  // phase-1 identity and the mixing weights of this lane's alpha (:613)
+  const int ti1 = lane / A_pad, n1 = lane % A_pad;
+  const bool lane1 = (ti1 < TP) && (n1 < A);
+  double wA[9], wR[9];
+  {
+    const double al = lane1 ? alpha[n1] : 0.0;
+#pragma unroll
+    for (int l = 0; l < 3; ++l)
+#pragma unroll
+      for (int m = 0; m < 3; ++m) {
+        const double p = 0.5 * l + (m - l) * 0.5 * al;
+        wA[l * 3 + m] = p;
+        wR[l * 3 + m] = 1.0 - p;
+      }
+  }
+  const int64_t p_beg = pv.cell_pair_off[cell];
+  const int64_t np = pv.cell_pair_off[cell + 1] - p_beg;
+  int64_t rd_base = pv.cell_read_off[cell];
+  for (int64_t tbase = 0; tbase < np; tbase += TP) {
+    const int tp = (int)min((int64_t)TP, np - tbase);
+    load_tile_headers<kAncTP>(pv, nrd_width, p_beg, tbase, tp, lane, rd_base, s_cnt, s_off, s_snp);
+    DMX_WAVE_LDS_ORDER();
+    rd_base = s_off[tp - 1] + (int64_t)s_cnt[tp - 1];
+    // ---- phase 1
+    {
+      const bool on = lane1 && ti1 < tp;
+      const uint32_t cnt = on ? s_cnt[ti1] : 0u;
+      const int64_t off = on ? s_off[ti1] : 0;
+      const uint32_t rd4 = load_rd4(pv, off, cnt);
+      double pG[9];
+      const double mx = pair_values_open<9, 0, true>(pv, cnt, off, rd4, s_tab, wA, wR, n1, pG, nullptr, on, A_pad);
+      if (on) {
+        const double y = rcp_refined(mx);
+        double* P = &s_pG[(ti1 * A + n1) * 9];
+        if (do00) {
+          (void)llks00_term(gp0, s_snp[ti1], [&](int l, int m) { const double v = div_by(pG[l * 3 + m], mx, y); P[l * 3 + m] = v; return v; },
+                            s_log, &s_t00[ti1 * A + n1]);
+        } else {
+#pragma unroll
+          for (int i = 0; i < 9; ++i) P[i] = div_by(pG[i], mx, y);                 // :656-663
+        }
+      }
+    }
+    DMX_WAVE_LDS_ORDER();
+    // ---- phase 2
+    for (int ti = 0; ti < tp; ++ti) {
+      const int32_t snp = s_snp[ti];
+      const float* __restrict__ grow = g + (size_t)snp * V * 3;
+#pragma unroll
+      for (int i = 0; i < NACC; ++i) {
+        const uint32_t cd = code[i];
+        if (cd == kAncNone) continue;
+        const int32_t j = (cd >> 20) & 0xFFF, k = (cd >> 8) & 0xFFF, n = cd & 0xFF;
+        const double a[3] = {(double)grow[j * 3], (double)grow[j * 3 + 1], (double)grow[j * 3 + 2]};
+        const double b[3] = {(double)grow[k * 3], (double)grow[k * 3 + 1], (double)grow[k * 3 + 2]};
+        const double* P = &s_pG[(ti * A + n) * 9];
+        double sum = 0.0;                                                          // :674
+#pragma unroll
+        for (int l = 0; l < 3; ++l)
+#pragma unroll
+          for (int m = 0; m < 3; ++m) sum += ((a[l] * b[m]) * P[l * 3 + m]);       // :553 then :677-679, l-major
+        acc[i] += dmx_log2_fast(sum, s_log);                                       // :683
+      }
+      if (do00 && lane < A) acc00 += s_t00[ti * A + lane];                         // :709
+    }
+    DMX_WAVE_LDS_ORDER();
+  }
+  double* __restrict__ dst = PAIR ? pairs : c0;
+#pragma unroll
+  for (int i = 0; i < NACC; ++i)
+    if (out[i] >= 0) dst[out[i]] = acc[i];
+  if (do00 && lane < A) l00[(size_t)cell * A + lane] = acc00;
+}
+
+template <int NACC>
+__global__ __launch_bounds__(64 * kAncWaves) void k_anchor_col(PileupView pv, int nrd_width, const float* __restrict__ g, const double* __restrict__ gp0,
+                                                             const double* __restrict__ tabs, const double* __restrict__ alpha, int32_t V, int32_t A,
+                                                             int32_t A_pad, int32_t TP, int32_t n_slab, int64_t n_units, double* __restrict__ c0,
+                                                             double* __restrict__ l00) {
+  anchor_body<NACC, false>(pv, nrd_width, g, gp0, tabs, alpha, V, A, A_pad, TP, 0, nullptr, n_slab, n_units, c0, l00, nullptr);
+}
+template <int NACC>
+__global__ __launch_bounds__(64 * kAncWaves) void k_anchor_pair(PileupView pv, int nrd_width, const float* __restrict__ g,
+                                                              const double* __restrict__ tabs, const double* __restrict__ alpha, int32_t V, int32_t A,
+                                                              int32_t A_pad, int32_t TP, int32_t T, const int32_t* __restrict__ anchors, int32_t n_slab,
+                                                              int64_t n_units, double* __restrict__ pairs) {
+  anchor_body<NACC, true>(pv, nrd_width, g, nullptr, tabs, alpha, V, A, A_pad, TP, T, anchors, n_slab, n_units, nullptr, nullptr, pairs);
+}
+
+__device__ __forceinline__ ArgMax wave_better(ArgMax b) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    ArgMax o;
+    o.v = __shfl_xor(b.v, d); o.i = __shfl_xor(b.i, d);
+    b = better(b, o);
+  }
+  return b;
+}
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
+  return x;
+}
+__device__ __forceinline__ double wave_max(double x) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) { const double o = __shfl_xor(x, d); x = (x < o) ? o : x; }
+  return x;
+}
+
+// The anchors of a barcode: T times the first maximum of sing[j] = c0[j][0] in ascending j among the samples not yet chosen (:746-758,
+// repeated).  One wavefront per barcode; a slot stays -1 when no sample is left that compares (NaN likelihoods).
+__global__ __launch_bounds__(64 * kAncWaves) void k_anchor_select(const double* __restrict__ c0, int32_t B, int32_t V, int32_t A, int32_t T,
+                                                                int32_t* __restrict__ anchors) {
+  const int lane = threadIdx.x & 63;
+  const int32_t cell = (int32_t)blockIdx.x * kAncWaves + (threadIdx.x >> 6);
+  if (cell >= B) return;
+  const double* S = c0 + (size_t)cell * V * A;
+  int32_t chosen[kAncMaxT];
+#pragma unroll
+  for (int t = 0; t < kAncMaxT; ++t) chosen[t] = -1;
+#pragma unroll
+  for (int t = 0; t < kAncMaxT; ++t) {
+    if (t >= T) break;
+    ArgMax b{-1e300, 0x7FFFFFFF};
+    for (int32_t j = lane; j < V; j += 64) {
+      bool taken = false;
+#pragma unroll
+      for (int u = 0; u < kAncMaxT; ++u) taken |= (u < t && chosen[u] == j);
+      if (!taken) b = better(b, ArgMax{S[(size_t)j * A], j});
+    }
+    b = wave_better(b);
+    chosen[t] = b.i == 0x7FFFFFFF ? -1 : b.i;
+    if (lane == 0) anchors[(size_t)cell * T + t] = chosen[t];
+  }
+}
+
+// Every evaluated doublet entry (j, k, n) of D_b = {n >= 1, j != k, j an anchor or k an anchor or k = 0} once, strided over the
+// wavefront's lanes: column 0 from c0, then the partner rows of every anchor in both orders — skipping (., 0, .) there (it is in c0) and,
+// in the order (k, a_t), the rows whose k is itself an anchor (they are that anchor's order (a_u, .)).
+template <class F>
+__device__ __forceinline__ void anchor_for_each(int lane, int32_t V, int32_t A, int32_t T, const int32_t* s_anc, const double* __restrict__ C0,
+                                                const double* __restrict__ PR, F&& f) {
+  const int32_t A1 = A - 1;
+  for (int32_t e = lane; e < V * A1; e += 64) {
+    const int32_t j = e / A1, n = 1 + e % A1;
+    if (j != 0) f(j, 0, n, C0[(size_t)j * A + n]);
+  }
+  const int32_t per_t = V * 2 * A1;
+  for (int32_t t = 0; t < T; ++t) {
+    const int32_t a = s_anc[t];
+    if (a < 0) continue;
+    const double* P = PR + (size_t)t * per_t;
+    for (int32_t e = lane; e < per_t; e += 64) {
+      const int32_t n = 1 + e % A1, r = e / A1, o = r & 1, s = r >> 1;
+      if (s == a) continue;
+      if (o == 0) {
+        if (s != 0) f(a, s, n, P[e]);
+      } else {
+        bool s_is_anchor = false;
+        for (int32_t u = 0; u < T; ++u) s_is_anchor |= (s_anc[u] == s);
+        if (a != 0 && !s_is_anchor) f(s, a, n, P[e]);
+      }
+    }
+  }
+}
+
+// K3's record (k_reduce) over the evaluated entries.  One wavefront per barcode.  max_llk is the maximum over sing[] and D_b;
+// sum_double runs over D_b with the reference's weights; the near-tie flags follow k_reduce's rules over D_b.  A barcode without pairs
+// gets the record K3 writes for an all-zero grid.
+__global__ __launch_bounds__(64 * kAncWaves) void k_anchor_reduce(const double* __restrict__ c0, const double* __restrict__ pairs,
+                                                                const double* __restrict__ l00, const int32_t* __restrict__ anchors,
+                                                                const int64_t* __restrict__ cell_pair_off, const double* __restrict__ alpha,
+                                                                int32_t B, int32_t V, int32_t A, int32_t T, double prior,
+                                                                dmx_cell_summary* __restrict__ out) {
+  __shared__ int32_t s_ancs[kAncWaves][kAncMaxT];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int32_t cell = (int32_t)blockIdx.x * kAncWaves + wave;
+  if (cell >= B) return;
+  int32_t* s_anc = s_ancs[wave];
+  if (lane < kAncMaxT) s_anc[lane] = lane < T ? anchors[(size_t)cell * T + lane] : -1;
+  DMX_WAVE_LDS_ORDER();
+  const double* C0 = c0 + (size_t)cell * V * A;
+  const double* PR = pairs + (size_t)cell * T * V * 2 * (A - 1);
+  const int32_t npairs = (int32_t)(cell_pair_off[cell + 1] - cell_pair_off[cell]);
+  dmx_cell_summary r;
+  r.n_pairs = npairs; r.reserved = 0; r.llk_ab = 0.0; r.llk_ba = 0.0;
+  r.llk_ab_alt = 0.0; r.llk_ba_alt = 0.0; r.ev_x_ab = 0.0; r.ev_t_ab = 0.0; r.ev_x_ba = 0.0; r.ev_t_ba = 0.0;
+  if (npairs == 0) {                               // every entry of the grid is 0: k_reduce's scans over it, in closed form
+    double ss = 0.0, sd = 0.0;
+    for (int32_t j = lane; j < V; j += 64) ss += ((1. - prior) / V);
+    for (int32_t n = 1; n < A; ++n) sd += (prior / V / (V - 1) / (A - 1) / (alpha[n] == 0.5 ? 2.0 : 1.0));
+    ss = wave_sum(ss);
+    sd *= (double)V * (double)(V - 1);
+    const int64_t others = (int64_t)V * (V - 1) * (A - 1) - 1 - (alpha[1] == 0.5 ? 1 : 0);
+    r.max_llk = 0.0; r.sum_single = ss; r.sum_double = sd;
+    r.sing_llk1 = 0.0; r.sing_llk2 = 0.0; r.llk12 = 0.0; r.llk1 = 0.0; r.llk2 = 0.0; r.llk10 = 0.0; r.llk20 = 0.0;
+    r.llk00_0 = l00[(size_t)cell * A]; r.llk00_best = l00[(size_t)cell * A + 1];
+    r.i_sing1 = 0; r.i_sing2 = 1; r.j_best = 0; r.k_best = 1; r.n_best = 1;
+    r.flags = DMX_CELL_NEAR_SINGLET | (others > 0 ? DMX_CELL_NEAR_DOUBLET : 0);
+    if (lane == 0) out[cell] = r;
+    return;
+  }
+  // (1) the maximum, the best doublet (first maximum in (j, k, n) scan order, :799-814) and the best singlet (:746-758)
+  double mx = -1e300;
+  ArgMax bd{-1e300, 0x7FFFFFFF}, b1{-1e300, 0x7FFFFFFF};
+  for (int32_t j = lane; j < V; j += 64) {
+    const double v = C0[(size_t)j * A];
+    mx = fmax(mx, v);
+    b1 = better(b1, ArgMax{v, j});
+  }
+  anchor_for_each(lane, V, A, T, s_anc, C0, PR, [&](int32_t j, int32_t k, int32_t n, double v) {
+    mx = fmax(mx, v);
+    bd = better(bd, ArgMax{v, (int32_t)(((int64_t)j * V + k) * A + n)});
+  });
+  const double max_llk = wave_max(mx);
+  bd = wave_better(bd); b1 = wave_better(b1);
+  const int32_t qbest = bd.i, i1 = b1.i;
+  ArgMax b2{-1e300, 0x7FFFFFFF};
+  for (int32_t j = lane; j < V; j += 64) if (j != i1) b2 = better(b2, ArgMax{C0[(size_t)j * A], j});
+  b2 = wave_better(b2);
+  const int32_t i2 = (b2.i == 0x7FFFFFFF) ? -1 : b2.i;
+  const bool has1 = i1 != 0x7FFFFFFF, hasb = qbest != 0x7FFFFFFF;
+  const int32_t nb = hasb ? qbest % A : 0, jkb = hasb ? qbest / A : 0, jb = jkb / V, kb = jkb % V;
+  // (2) posterior sums (:724-734) and the near-tie tests of k_reduce's step (5)
+  const double tol = 1e-7;
+  const int32_t qmir = (hasb && alpha[nb] == 0.5) ? ((kb * V + jb) * A + nb) : -1;
+  const double s2v = (i2 >= 0) ? C0[(size_t)i2 * A] : -1e300, s1v = has1 ? C0[(size_t)i1 * A] : 0.0;
+  double ss = 0.0, sd = 0.0;
+  int cnt = 0, near_d = 0;
+  for (int32_t j = lane; j < V; j += 64) {
+    const double v = C0[(size_t)j * A];
+    ss += (exp(v - max_llk) * (1. - prior) / V);
+    if (v >= s2v - tol) ++cnt;
+  }
+  anchor_for_each(lane, V, A, T, s_anc, C0, PR, [&](int32_t j, int32_t k, int32_t n, double v) {
+    sd += (exp(v - max_llk) * prior / V / (V - 1) / (A - 1) / (alpha[n] == 0.5 ? 2.0 : 1.0));
+    const int32_t q = (int32_t)(((int64_t)j * V + k) * A + n);
+    if (hasb && q != qbest && q != qmir && v >= bd.v - tol) near_d = 1;
+  });
+  ss = wave_sum(ss); sd = wave_sum(sd);
+  const int n_near_s = (int)wave_sum((double)cnt);
+  near_d = __any(near_d) ? 1 : 0;
+  int32_t flags = 0;
+  if (near_d) flags |= DMX_CELL_NEAR_DOUBLET;
+  if (i2 >= 0 && (n_near_s > 2 || s1v - s2v < tol)) flags |= DMX_CELL_NEAR_SINGLET;
+  if (lane == 0) {
+    const double kNaN = __builtin_nan("");
+    r.max_llk = max_llk; r.sum_single = ss; r.sum_double = sd;
+    r.i_sing1 = has1 ? i1 : -1; r.i_sing2 = i2;
+    r.sing_llk1 = has1 ? s1v : kNaN; r.sing_llk2 = s2v;
+    r.j_best = hasb ? jb : -1; r.k_best = hasb ? kb : -1; r.n_best = hasb ? nb : -1;
+    r.llk12 = hasb ? bd.v : kNaN;
+    r.llk1 = hasb ? C0[(size_t)jb * A] : kNaN; r.llk2 = hasb ? C0[(size_t)kb * A] : kNaN;
+    r.llk10 = hasb ? C0[(size_t)jb * A + nb] : kNaN; r.llk20 = hasb ? C0[(size_t)kb * A + nb] : kNaN;     // :824-825
+    r.llk00_0 = l00[(size_t)cell * A]; r.llk00_best = l00[(size_t)cell * A + nb];
+    if (hasb && has1 && i2 >= 0) {
+      const double s1 = r.sing_llk1, s2 = r.sing_llk2;
+      if (fabs(r.llk12 - (s1 + 2)) < tol || fabs(s1 - (s2 + 2)) < tol ||
+          ((fabs(r.llk12 - r.llk1) < tol || fabs(r.llk12 - r.llk2) < tol) && r.llk12 > s1 + 2 - tol))
+        flags |= DMX_CELL_NEAR_RULE;
+    }
+    r.flags = flags;
+    out[cell] = r;
+  }
+}
+
 // K3b — the tie-order certificate (DESIGN.md "Ties").  At alpha = 0.5 the reference's llksAB[j][k] and llksAB[k][j] are one number
 // mathematically and differ by the rounding noise of its own evaluation order; its strict-< scan then names the doublet
 // "a-b" or "b-a" by that noise.  To print the same order one has to know BOTH accumulators as the reference computes them, bit for
@@ -7774,6 +8104,7 @@ struct dmx_engine {
   DevBuf<double> d_park;                           // k_certify's per-barcode state between the launches of its SNP-blocked walk
   DevBuf<int64_t> d_blk; int32_t blk_shift = 0, blk_n = 0;   // k_snp_blocks table of the staged (sparse) pileup; blk_n = 0: none
   bool geno_safe = false;                                            // every genotype row finite, non-negative, max >= 2^-400 (k_check_geno)
+  bool geno_rows_safe = false;                                       // ... as k_check_geno found it, whatever DMX_FORCE_CHECK says (the anchored pass has no checked form to force)
   // host -> device staging of the big pileup arrays: two pinned chunks filled by host threads while the other one is in flight
   PinnedBuf h_stage[2]; Event ev_stage[2]; bool stage_busy[2] = {false, false}; int stage_cur = 0;
   // results
@@ -7889,6 +8220,13 @@ struct dmx_engine {
   int32_t trip_B = 0, trip_C = 0, trip_T = 0, trip_V = 0; bool have_trip = false;
   EventPair tev;
   dmx_triplet_info trip_info{};
+  // anchored doublet search (dmx_engine_doublet_anchored): buffers of its own; d_grid is never touched
+  DevBuf<int32_t> d_anc;                         // anchors[B][T]
+  DevBuf<double> d_ac0, d_apair, d_al00;         // c0[B][V][A], pairs[B][T][V][2][A-1], llks00[B][A]
+  DevBuf<dmx_cell_summary> d_asum;
+  bool have_anc = false;
+  EventPair anc_ev[3];                           // k_anchor_col (+ k_anchor_select), k_anchor_pair, k_anchor_reduce
+  dmx_anchored_info anc_info{};
   // pileup composer (dmx_engine_compose): the recipe, the count pass's numbers, and the composed pileup itself (grow-only, like own[])
   DevBuf<int32_t> d_cmparent; DevBuf<uint64_t> d_cmkeep;
   DevBuf<int64_t> d_cmcnt;                       // pairs[n_out] | reads[n_out] | totals[3]
@@ -8063,7 +8401,7 @@ extern "C" int dmx_engine_set_genotypes(dmx_engine* e, const float* g, int32_t n
   // genotype classes (<= 4 distinct rows per SNP: --field GT): enables the class kernels
   e->d_rows.reset(); e->d_ids.reset(); e->d_idw.reset(); e->d_idd.reset();
   e->n_classes = 0;
-  e->geno_safe = false;
+  e->geno_safe = false; e->geno_rows_safe = false;
   if (n_snps > 0) {
     DevBuf<int32_t> d_max, d_unsafe;
     if (int rc = e->d_rows.alloc((size_t)n_snps * kMaxCls * 3 * sizeof(float))) return rc;
@@ -8085,7 +8423,8 @@ extern "C" int dmx_engine_set_genotypes(dmx_engine* e, const float* g, int32_t n
     HIP_TRY(hipMemcpyAsync(&h_unsafe, d_unsafe, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     d_max.reset(); d_unsafe.reset();
-    e->geno_safe = h_unsafe == 0 && !e->knob("DMX_FORCE_CHECK");
+    e->geno_rows_safe = h_unsafe == 0;
+    e->geno_safe = e->geno_rows_safe && !e->knob("DMX_FORCE_CHECK");
     e->n_classes = (h_max >= 1 && h_max <= kMaxCls) ? h_max : 0;
     if (!e->n_classes) { e->d_rows.reset(); e->d_ids.reset(); e->d_idw.reset(); e->d_idd.reset(); }
     // canonical GT classes (see k_canon_apply): relabel when the matrix has that shape
@@ -10568,6 +10907,167 @@ extern "C" int dmx_engine_triplet_info(dmx_engine* e, dmx_triplet_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_triplet_info: null argument");
   if (!e->have_trip) return set_error(DMX_ERR_STATE, "dmx_engine_triplet_info: no profile on the staged pileup (dmx_engine_triplet first)");
   *out = e->trip_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Anchored doublet search: the arguments are checked on the host, then k_anchor_col, k_anchor_select (unless the
+// caller gave the anchors), k_anchor_pair and k_anchor_reduce on the engine's stream, each entry kernel over B x slabs wavefronts with
+// NACC = 1 / 2 / 4 entries per lane by the entry count alone.  Every buffer is the call's own.
+namespace {
+template <int NACC>
+void launch_anchor_col(dmx_engine* e, int A_pad, int TP, int32_t n_slab, int64_t n_units) {
+  hipLaunchKernelGGL((k_anchor_col<NACC>), dim3((unsigned)((n_units + kAncWaves - 1) / kAncWaves)), dim3(64 * kAncWaves), 0, e->stream, e->pv,
+                     e->nrd_width, e->d_g, (const double*)e->d_gp0, (const double*)e->d_lut, (const double*)e->d_alpha, e->V, e->A, A_pad, TP,
+                     n_slab, n_units, (double*)e->d_ac0, (double*)e->d_al00);
+}
+template <int NACC>
+void launch_anchor_pair(dmx_engine* e, int A_pad, int TP, int32_t T, int32_t n_slab, int64_t n_units) {
+  hipLaunchKernelGGL((k_anchor_pair<NACC>), dim3((unsigned)((n_units + kAncWaves - 1) / kAncWaves)), dim3(64 * kAncWaves), 0, e->stream, e->pv,
+                     e->nrd_width, e->d_g, (const double*)e->d_lut, (const double*)e->d_alpha, e->V, e->A, A_pad, TP, T,
+                     (const int32_t*)e->d_anc, n_slab, n_units, (double*)e->d_apair);
+}
+inline int anchor_nacc(int64_t n_ent) { return n_ent <= 64 ? 1 : n_ent <= 128 ? 2 : 4; }
+}  // namespace
+
+extern "C" int dmx_engine_doublet_anchored(dmx_engine* e, const dmx_anchored_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_doublet_anchored: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_doublet_anchored: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, A = e->A, T = rq->n_anchor;
+  if (e->pv.S != e->S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_doublet_anchored: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", e->S, e->pv.S);
+  if (V < 2 || A < 2) return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: %d samples x %d alphas; both must be at least 2", V, A);
+  if (A > 64 || V > 0xFFE || (int64_t)V * V * A > 0x7FFFFFFFll)
+    return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: %d samples x %d alphas exceed this build's limits (64 alphas, V*V*A < 2^31)", V, A);
+  if (T < 1 || T > kAncMaxT || T > V) return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: n_anchor %d is not in [1, min(%d, V = %d)]", T, kAncMaxT, V);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->anchors && rq->anchor_memory != DMX_MEM_HOST && rq->anchor_memory != DMX_MEM_DEVICE)
+    return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: anchor_memory %d", rq->anchor_memory);
+  if (!e->geno_rows_safe)
+    return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: the genotype matrix has a row that is not finite, non-negative and above 1e-30 somewhere; "
+                                  "run the full grid (dmx_engine_run_doublet), which has the fix-up pass for such a matrix: the anchored pass has none");
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t n_anc = (size_t)B * (size_t)T;
+  std::vector<int32_t> anc;
+  int64_t n_used = (int64_t)n_anc;
+  if (rq->anchors && n_anc > 0) {
+    anc.resize(n_anc);
+    if (rq->anchor_memory == DMX_MEM_DEVICE) {
+      HIP_TRY(hipMemcpyAsync(anc.data(), rq->anchors, sizeof(int32_t) * n_anc, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+      std::memcpy(anc.data(), rq->anchors, sizeof(int32_t) * n_anc);
+    }
+    n_used = 0;
+    for (size_t b = 0; b < (size_t)B; ++b)
+      for (int32_t t = 0; t < T; ++t) {
+        const int32_t a = anc[b * T + t];
+        if (a < -1 || a >= V) return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: anchors[%zu][%d] = %d is not -1 or a sample in [0, %d)", b, t, a, V);
+        if (a < 0) continue;
+        for (int32_t u = 0; u < t; ++u)
+          if (anc[b * T + u] == a) return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: anchors[%zu][%d] repeats anchors[%zu][%d] = %d", b, t, b, u, a);
+        ++n_used;
+      }
+  }
+  const size_t c0_b = sizeof(double) * (size_t)B * V * A, pr_b = sizeof(double) * n_anc * V * 2 * (size_t)(A - 1),
+               l00_b = sizeof(double) * (size_t)B * A, sum_b = sizeof(dmx_cell_summary) * (size_t)B, anc_b = sizeof(int32_t) * n_anc;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const size_t need = (c0_b > e->d_ac0.cap() ? c0_b + c0_b / 16 : 0) + (pr_b > e->d_apair.cap() ? pr_b + pr_b / 16 : 0) +
+                      (l00_b > e->d_al00.cap() ? l00_b : 0) + (sum_b > e->d_asum.cap() ? sum_b : 0) + (anc_b > e->d_anc.cap() ? anc_b : 0);
+  if (need > free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_doublet_anchored: the results of %d barcodes x %d samples x %d alphas x %d anchors need %zu bytes, %zu are free",
+                     B, V, A, T, c0_b + pr_b + l00_b + sum_b + anc_b, free_b);
+  if (int rc = e->d_ac0.ensure(c0_b)) return rc;
+  if (int rc = e->d_apair.ensure(pr_b)) return rc;
+  if (int rc = e->d_al00.ensure(l00_b)) return rc;
+  if (int rc = e->d_asum.ensure(sum_b)) return rc;
+  if (int rc = e->d_anc.ensure(anc_b)) return rc;
+  e->have_anc = false;
+  int A_pad = 1;
+  while (A_pad < A) A_pad <<= 1;
+  const int TP = std::min(kAncTP, 64 / A_pad);
+  const int64_t ent_c = (int64_t)V * A, ent_p = (int64_t)T * 2 * (A - 1) * V;
+  const int nacc_c = anchor_nacc(ent_c), nacc_p = anchor_nacc(ent_p);
+  const int32_t slab_c = (int32_t)((ent_c + 64 * nacc_c - 1) / (64 * nacc_c)), slab_p = (int32_t)((ent_p + 64 * nacc_p - 1) / (64 * nacc_p));
+  const int64_t units_c = (int64_t)B * slab_c, units_p = (int64_t)B * slab_p;
+  if ((units_c + kAncWaves - 1) / kAncWaves > 0x7FFFFFFFll || (units_p + kAncWaves - 1) / kAncWaves > 0x7FFFFFFFll)
+    return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: %d barcodes x %d samples need more wavefronts than one launch has", B, V);
+  const unsigned cell_blocks = (unsigned)((B + kAncWaves - 1) / kAncWaves);
+  if (int rc = e->anc_ev[0].record_start(e->stream)) return rc;
+  if (B > 0) {
+    if (nacc_c == 1) launch_anchor_col<1>(e, A_pad, TP, slab_c, units_c);
+    else if (nacc_c == 2) launch_anchor_col<2>(e, A_pad, TP, slab_c, units_c);
+    else launch_anchor_col<4>(e, A_pad, TP, slab_c, units_c);
+    HIP_TRY(hipGetLastError());
+    if (!anc.empty()) {
+      HIP_TRY(hipMemcpyAsync(e->d_anc, anc.data(), anc_b, hipMemcpyHostToDevice, e->stream));
+    } else {
+      hipLaunchKernelGGL(k_anchor_select, dim3(cell_blocks), dim3(64 * kAncWaves), 0, e->stream, (const double*)e->d_ac0, B, V, A, T, (int32_t*)e->d_anc);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (int rc = e->anc_ev[0].record_stop(e->stream)) return rc;
+  if (int rc = e->anc_ev[1].record_start(e->stream)) return rc;
+  if (B > 0) {
+    if (nacc_p == 1) launch_anchor_pair<1>(e, A_pad, TP, T, slab_p, units_p);
+    else if (nacc_p == 2) launch_anchor_pair<2>(e, A_pad, TP, T, slab_p, units_p);
+    else launch_anchor_pair<4>(e, A_pad, TP, T, slab_p, units_p);
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->anc_ev[1].record_stop(e->stream)) return rc;
+  if (int rc = e->anc_ev[2].record_start(e->stream)) return rc;
+  if (B > 0) {
+    hipLaunchKernelGGL(k_anchor_reduce, dim3(cell_blocks), dim3(64 * kAncWaves), 0, e->stream, (const double*)e->d_ac0, (const double*)e->d_apair,
+                       (const double*)e->d_al00, (const int32_t*)e->d_anc, e->pv.cell_pair_off, (const double*)e->d_alpha, B, V, A, T, e->prior,
+                       (dmx_cell_summary*)e->d_asum);
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->anc_ev[2].record_stop(e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's anchors may go away after return; anc is pageable host memory
+  if (anc.empty() && n_anc > 0) {                   // chosen on the device: a slot k_anchor_select left at -1 evaluated nothing
+    anc.resize(n_anc);
+    HIP_TRY(hipMemcpy(anc.data(), e->d_anc, anc_b, hipMemcpyDeviceToHost));
+    n_used = 0;
+    for (int32_t a : anc) n_used += a >= 0;
+  }
+  dmx_anchored_info& inf = e->anc_info;
+  std::memset(&inf, 0, sizeof inf);
+  float ms = 0.f;
+  if (int rc = e->anc_ev[0].elapsed_ms(&ms)) return rc;
+  inf.col_ms = ms;
+  if (int rc = e->anc_ev[1].elapsed_ms(&ms)) return rc;
+  inf.pair_ms = ms;
+  if (int rc = e->anc_ev[2].elapsed_ms(&ms)) return rc;
+  inf.reduce_ms = ms;
+  inf.result_bytes = (int64_t)(c0_b + pr_b + l00_b + sum_b + anc_b);
+  inf.n_entries = (int64_t)B * (ent_c + A) + n_used * (int64_t)(V - 1) * 2 * (A - 1);
+  inf.n_cells = B; inf.n_samples = V; inf.n_alpha = A; inf.n_anchor = T;
+  e->have_anc = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_anchored(dmx_engine* e, int32_t* anchors, double* c0, double* pairs, double* llks00, dmx_cell_summary* summary) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_anchored: null engine");
+  if (!e->have_anc) return set_error(DMX_ERR_STATE, "dmx_engine_get_anchored: no anchored result (dmx_engine_doublet_anchored first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const dmx_anchored_info& inf = e->anc_info;
+  const size_t B = (size_t)inf.n_cells, V = (size_t)inf.n_samples, A = (size_t)inf.n_alpha, T = (size_t)inf.n_anchor;
+  if (!B) return DMX_OK;
+  if (anchors) HIP_TRY(hipMemcpy(anchors, e->d_anc, sizeof(int32_t) * B * T, hipMemcpyDeviceToHost));
+  if (c0) HIP_TRY(hipMemcpy(c0, e->d_ac0, sizeof(double) * B * V * A, hipMemcpyDeviceToHost));
+  if (pairs) HIP_TRY(hipMemcpy(pairs, e->d_apair, sizeof(double) * B * T * V * 2 * (A - 1), hipMemcpyDeviceToHost));
+  if (llks00) HIP_TRY(hipMemcpy(llks00, e->d_al00, sizeof(double) * B * A, hipMemcpyDeviceToHost));
+  if (summary) HIP_TRY(hipMemcpy(summary, e->d_asum, sizeof(dmx_cell_summary) * B, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_anchored_info(dmx_engine* e, dmx_anchored_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_anchored_info: null argument");
+  if (!e->have_anc) return set_error(DMX_ERR_STATE, "dmx_engine_anchored_info: no anchored result (dmx_engine_doublet_anchored first)");
+  *out = e->anc_info;
   return DMX_OK;
 }
 

@@ -700,6 +700,44 @@ class Engine:
         check(self._L.dmx_engine_triplet_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.TripletInfo._fields_ if not n.startswith("reserved")}
 
+    def doublet_anchored(self, n_anchor: int = 2, anchors=None) -> None:
+        """dmx_engine_doublet_anchored over the staged pileup: column 0 of the doublet grid, the n_anchor best singlets of every barcode
+        as anchors (or the caller's `anchors`: a host array [B][T] with -1 = unused, or a device pointer (int) to B x n_anchor int32),
+        every sample as the partner of every anchor in both orders, and K3's record over those entries.  STRICT arithmetic whatever
+        the engine's mode; the full grid is never allocated.  Results: get_anchored()."""
+        if anchors is None:
+            an, mem, ptr, T = None, capi.DMX_MEM_HOST, None, int(n_anchor)
+        elif isinstance(anchors, int):
+            an, mem, ptr, T = None, capi.DMX_MEM_DEVICE, anchors, int(n_anchor)
+        else:
+            an = np.ascontiguousarray(anchors, dtype=np.int32)
+            if an.ndim != 2 or an.shape[0] != self.B:
+                raise ValueError(f"anchors must be [{self.B}][T]")
+            mem, ptr, T = capi.DMX_MEM_HOST, (an.ctypes.data if an.size else None), an.shape[1]
+            if ptr is None and self.B > 0:
+                raise ValueError("anchors must have at least one column")
+        rq = capi.AnchoredRequest(self.B, T, mem, 0, ptr)
+        check(self._L.dmx_engine_doublet_anchored(self._h, C.byref(rq)))
+
+    def get_anchored(self) -> dict:
+        """The last anchored result (dmx_engine_get_anchored): anchors[B][T] i32, c0[B][V][A] = llksAB[j][0][n], pairs[B][T][V][2][A-1]
+        with pairs[b][t][k][0][n-1] = llksAB[a_t][k][n] and pairs[b][t][k][1][n-1] = llksAB[k][a_t][n], llks00[B][A], summary[B]."""
+        inf = self.anchored_info()
+        B, V, A, T = inf["n_cells"], inf["n_samples"], inf["n_alpha"], inf["n_anchor"]
+        anchors = np.zeros((B, T), dtype=np.int32)
+        c0 = np.zeros((B, V, A))
+        pairs = np.zeros((B, T, V, 2, A - 1))
+        l00 = np.zeros((B, A))
+        summ = np.zeros(B, dtype=capi.SUMMARY_DTYPE)
+        check(self._L.dmx_engine_get_anchored(self._h, anchors.ctypes.data, c0.ctypes.data, pairs.ctypes.data, l00.ctypes.data, summ.ctypes.data))
+        return dict(anchors=anchors, c0=c0, pairs=pairs, llks00=l00, summary=summ)
+
+    def anchored_info(self) -> dict:
+        """HIP-event times (ms) of the last anchored pass's kernels, its result bytes and entry count (dmx_engine_anchored_info)."""
+        r = capi.AnchoredInfo()
+        check(self._L.dmx_engine_anchored_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.AnchoredInfo._fields_ if not n.startswith("reserved")}
+
     def compose(self, parent, keep, seed: int, index_base: int = 0) -> dict:
         """dmx_engine_compose over the staged pileup: output barcode o takes the reads of cells parent[o][0] and parent[o][1] (-1 = none),
         each read kept iff its 32-bit hash is below keep[o][slot] (0 .. 2^32; 2^32 keeps all); output o is hashed as id index_base + o,

@@ -39,7 +39,9 @@ extern "C" {
                                _triplet_info (a base pair with every sample as a third donor); dmx_engine_cluster_evidence /
                                _cluster_hard / _get_cluster_hard / _cluster_hard_device_ptr / _cluster_merge_columns / _cluster_k_info (choosing the number
                                of clusters); dmx_engine_compose / _composed_pileup / _get_composed / _compose_info (barcodes composed on
-                               the device from other barcodes' reads).  Additions only. */
+                               the device from other barcodes' reads); dmx_engine_doublet_anchored / _get_anchored / _anchored_info
+                               (the doublet search over each barcode's best singlets as anchors: wide panels without the V x V grid).
+                               Additions only. */
 
 typedef enum {
   DMX_OK = 0,
@@ -1029,6 +1031,68 @@ typedef struct {
 } dmx_census_fisher_info;
 int dmx_engine_census_fisher(dmx_engine*, const dmx_census_fisher_request*);
 int dmx_engine_census_fisher_info(dmx_engine*, dmx_census_fisher_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Anchored doublet search (appended, DMX_ABI_VERSION stays 8): the doublet stage for panels whose grid
+ * llksAB[V][V][A] does not fit or takes too long.  It evaluates the entries of that grid in which one donor is an ANCHOR (one of the
+ * barcode's T best singlets, or a sample the caller names) or the second donor is sample 0, about (2T + 1) V (A - 1) + V A entries per
+ * barcode instead of V V A, and derives K3's record from them.
+ * Arithmetic: the STRICT contract of DESIGN.md section 4, whatever the engine's mode — the reference's operation order, no contraction,
+ * IEEE division, the per-read renormalisation with one maximum across all alphas and the 1e-6 floor (cmd_cram_demuxlet.cpp:600-663),
+ * nine-term l-major sums from 0.0 (:675-681), dmx_log2, and one serial sum per entry over the barcode's pairs in ascending SNP order.
+ * Every evaluated entry is bit for bit the entry of dmx_engine_run_doublet's grid in DMX_MODE_STRICT.
+ * For barcode b, V samples, alphas alpha[0..A), A >= 2:
+ *   c0[j][n]   = llksAB[j][0][n], every j < V and n < A.  sing[j] = c0[j][0] is the singlet column that .sing2 prints, computed as the
+ *                reference computes it: the pair (j, sample 0) at alpha[0], whatever that value is (:746-770).  The entries n >= 1 are
+ *                what LLK10 / LLK20 read (:824-825); c0[0][n] is the diagonal entry.
+ *   llks00[n]  :699-709.
+ *   anchors    a_1 .. a_T: the caller's anchors[b][t] (-1 = slot not used; the used ids of a row pairwise different), or, with
+ *                anchors == NULL, chosen on the device: T times the first maximum of sing[] in ascending j among the samples not yet
+ *                chosen (the first-maximum rule of :746-758, repeated).
+ *   pairs[t][k][0][n-1] = llksAB[a_t][k][n] and pairs[t][k][1][n-1] = llksAB[k][a_t][n] for every k < V, k != a_t, and n >= 1; the
+ *                slots k = a_t and the rows of unused anchors are 0.
+ *   D_b        = {(j, k, n) : n >= 1, j != k, and (j is an anchor, or k is an anchor, or k = 0)}: the evaluated doublet entries.
+ * Record (dmx_cell_summary): n_pairs; i_sing1, i_sing2, sing_llk1, sing_llk2 from sing[] as K3 does; (j_best, k_best, n_best) the first
+ * maximum over D_b in the reference's scan order (j, then k, then n ascending, strict <, :799-814), an entry reachable through two
+ * anchors counting once; llk12; llk1 = sing[j_best], llk2 = sing[k_best], llk10 = c0[j_best][n_best], llk20 = c0[k_best][n_best];
+ * llk00_0, llk00_best; max_llk = the maximum over sing[] and D_b (the entries [j][k != 0][0] that the reference also scans are not
+ * evaluated: DMX_MODE_FAST's convention; every printed quantity is a ratio in which max_llk cancels); sum_single = :726 over all V;
+ * sum_double = :731 over D_b with the reference's weights unchanged (/ V / (V - 1) / (A - 1), and / 2 at alpha = 0.5): the omitted pairs
+ * count as 0, so PRB.DBL is a LOWER BOUND of the reference's.  DMX_CELL_NEAR_DOUBLET / _NEAR_SINGLET / _NEAR_RULE follow K3's rules over
+ * the evaluated entries; DMX_CELL_ORDER_CERTIFIED / _RESOLVABLE are never set and llk_ab .. ev_t_ba are 0.  A barcode without pairs gets
+ * the record K3 writes for it (an all-zero grid).
+ * Determinism: an entry's bits depend on b's data, (j, k, n), the alpha grid, the rows of j, k and sample 0 and V only — not on T, the
+ * anchor's rank, where `anchors` lives, nrd_width, the pileup's layout, the other barcodes, how entries are packed into wavefronts or
+ * what ran before.  No floating-point atomics.
+ * The call runs on the engine's stream and synchronises it, uses buffers of its own, never allocates the grid and leaves every other
+ * result of the engine as it was.
+ * DMX_ERR_ARG: V < 2 or A < 2 (or A > 64, V*V*A >= 2^31); n_anchor outside [1, 8] or above V; an anchor outside [-1, V); a repeated
+ * anchor in a row; n_cells that does not match the staged pileup; a genotype matrix with a row that is not finite, non-negative and
+ * somewhere above 1e-30 (run the full grid, which has the fix-up pass for such a matrix: this pass has none).
+ * DMX_ERR_STATE: no pileup or no genotypes yet; dmx_engine_get_anchored / _anchored_info before any anchored call.
+ * DMX_ERR_NOMEM: the results do not fit the free device memory (checked before anything is allocated). */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t n_anchor;            /* T, 1..8, <= V */
+  int32_t anchor_memory;       /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `anchors` lives */
+  int32_t reserved0;           /* 0 */
+  const int32_t* anchors;      /* [n_cells][T], -1 = unused; NULL = chosen on the device */
+  int32_t reserved[4];         /* 0 */
+} dmx_anchored_request;
+typedef struct {
+  double  col_ms;              /* HIP-event time of k_anchor_col and the anchor choice (k_anchor_select, or the upload of the caller's) */
+  double  pair_ms;             /* ... of k_anchor_pair */
+  double  reduce_ms;           /* ... of k_anchor_reduce */
+  int64_t result_bytes;        /* device bytes of anchors, c0, pairs, llks00 and the records */
+  int64_t n_entries;           /* entries evaluated: B (V A + A) + used anchors x (V - 1) x 2 x (A - 1) */
+  int32_t n_cells, n_samples, n_alpha, n_anchor;
+  int32_t reserved[4];
+} dmx_anchored_info;
+int dmx_engine_doublet_anchored(dmx_engine*, const dmx_anchored_request*);
+/* Device->host copies of the last result (any pointer may be NULL): anchors[B][T] i32, c0[B][V][A], pairs[B][T][V][2][A-1],
+ * llks00[B][A] f64, summary[B]. */
+int dmx_engine_get_anchored(dmx_engine*, int32_t* anchors, double* c0, double* pairs, double* llks00, dmx_cell_summary* summary);
+int dmx_engine_anchored_info(dmx_engine*, dmx_anchored_info* out);
 
 #ifdef __cplusplus
 }
