@@ -50,7 +50,10 @@ SYMBOLS = [
     "dmx_engine_census_step", "dmx_engine_census", "dmx_engine_get_census", "dmx_engine_census_info",
     "dmx_engine_census_fisher", "dmx_engine_census_fisher_info",
     "dmx_engine_doublet_anchored", "dmx_engine_get_anchored", "dmx_engine_anchored_info",
+    "dmx_engine_prior_step", "dmx_engine_get_prior_step", "dmx_engine_prior_fit", "dmx_engine_get_prior_fit",
+    "dmx_engine_prior_call", "dmx_engine_get_prior_calls", "dmx_engine_prior_info",
 ]
+DMX_PRIOR_MASKED, DMX_PRIOR_BAD = 1, 2
 
 
 class PairOverride(C.Structure):      # dmx_pair_override
@@ -197,6 +200,27 @@ class ComposeInfo(C.Structure):        # dmx_compose_info
     _fields_ = [("n_pairs", C.c_int64), ("n_reads", C.c_int64), ("bytes_read", C.c_int64), ("bytes_written", C.c_int64),
                 ("count_ms", C.c_double), ("scan_ms", C.c_double), ("fill_ms", C.c_double), ("n_out", C.c_int32), ("nrd_width", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
+
+
+class PriorRequest(C.Structure):       # dmx_prior_request
+    _fields_ = [("n_cells", C.c_int32), ("n_samples", C.c_int32), ("n_alpha", C.c_int32), ("grid_memory", C.c_int32), ("grid", C.c_void_p),
+                ("mask", C.c_void_p), ("pi0", C.c_void_p), ("d0", C.c_double), ("tol", C.c_double), ("max_iter", C.c_int32),
+                ("fix_pi", C.c_int32), ("fix_d", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class PriorCall(C.Structure):          # dmx_prior_call
+    _fields_ = [("log_e", C.c_double), ("p_sng", C.c_double), ("p_het", C.c_double), ("p_hom", C.c_double), ("p_sng1", C.c_double),
+                ("p_sng2", C.c_double), ("p_dbl1", C.c_double), ("i_sng1", C.c_int32), ("i_sng2", C.c_int32), ("j_dbl", C.c_int32),
+                ("k_dbl", C.c_int32), ("n_dbl", C.c_int32), ("flag", C.c_int32)]
+
+
+PRIOR_CALL_DTYPE = np.dtype([(n, np.float64 if t is C.c_double else np.int32) for n, t in PriorCall._fields_])
+
+
+class PriorInfo(C.Structure):          # dmx_prior_info
+    _fields_ = [("estep_ms", C.c_double), ("fold_ms", C.c_double), ("call_ms", C.c_double), ("fit_ms", C.c_double),
+                ("bytes_per_iter", C.c_int64), ("n_iter", C.c_int32), ("n_cells", C.c_int32), ("n_samples", C.c_int32), ("n_alpha", C.c_int32),
+                ("waves_per_block", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class CensusStepRequest(C.Structure):  # dmx_census_step_request
@@ -377,6 +401,9 @@ def load() -> C.CDLL:
         "dmx_engine_census_step": [vp, vp], "dmx_engine_census": [vp, vp], "dmx_engine_get_census": [vp, vp, vp, vp, vp, vp, vp, vp],
         "dmx_engine_census_info": [vp, vp],
         "dmx_engine_census_fisher": [vp, vp], "dmx_engine_census_fisher_info": [vp, vp],
+        "dmx_engine_prior_step": [vp, vp, vp, dbl], "dmx_engine_get_prior_step": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "dmx_engine_prior_fit": [vp, vp], "dmx_engine_get_prior_fit": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32],
+        "dmx_engine_prior_call": [vp, vp, vp, dbl], "dmx_engine_get_prior_calls": [vp, vp], "dmx_engine_prior_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

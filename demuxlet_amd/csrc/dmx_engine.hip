@@ -8256,6 +8256,20 @@ struct dmx_engine {
   EventPair fsev;
   dmx_census_fisher_info fis_info{};
   bool have_fis_info = false;
+  // empirical-Bayes priors (dmx_engine_prior_step / _fit / _call): a caller's host grid copied to the device, the mask, the state
+  // pi | d and its log tables, the per-barcode rows, flags and records, the included barcodes' ids and count, the chunk partials and
+  // the folded sums; the last step's and fit's results stay on the host
+  DevBuf<double> d_prgrid; DevBuf<uint8_t> d_prmask;
+  DevBuf<double> d_prst, d_prtab, d_prrows, d_prpart, d_prout;
+  DevBuf<uint8_t> d_prflag; DevBuf<dmx_prior_call> d_prcall;
+  DevBuf<int32_t> d_pridx, d_prnin;
+  EventPair prev[3];                             // k_prior_estep, the fold, k_prior_estep<call>
+  dmx_prior_info pr_info{};
+  bool have_pr_info = false, have_pr_step = false, have_pr_fit = false, have_pr_call = false;
+  int32_t pr_B = 0, pr_V = 0, pr_call_B = 0;
+  std::vector<double> pr_step_out;               // N[V] | hom | het | LL | pi'[V] | d' | B_in of the last step
+  std::vector<double> pr_fit_out, pr_fit_pi, pr_fit_ll, pr_fit_d;   // ... of the fit's final evaluation; the final pi; the traces
+  double pr_fit_dd = 0.0; int32_t pr_fit_iter = 0, pr_fit_conv = 0;
 };
 
 namespace {
@@ -12307,5 +12321,289 @@ extern "C" int dmx_demuxlet_run(const dmx_job* job) {
             tm.freeze_s, tm.setup_s, tm.stage_s, tm.wait_s, tm.write_s, tm.total_s, tm.kernel_ms, tm.n_ranges, tm.n_engines, tm.n_cells_grid_fetched,
             gpu_pair ? 1 : 0, pair_format_ms, (long long)pair_bytes, (long long)pair_patches, (long long)pair_host_cells);
   if (!doublet_ok) return set_error(DMX_ERR_ARG, "dmx_demuxlet_run: the doublet stage needs >= 2 samples and >= 2 alphas (got %d, %d)", V, A);
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Empirical-Bayes priors from the doublet grid.  prior_prepare checks the request, finds the grid (the engine's,
+// the caller's device array, or a device copy of the caller's host array), stages the mask and sizes the buffers; prior_upload puts
+// pi | d on the device and builds the log tables; prior_pass is one k_prior_estep + fold with V + 3 doubles copied back.
+#include "dmx_prior.hpp"
+
+namespace {
+
+struct PriorPlan {
+  int32_t B = 0, V = 0, A = 0, W = 4;
+  size_t lds = 0;
+  const double* grid = nullptr;
+  const uint8_t* mask = nullptr;
+};
+
+int prior_prepare(dmx_engine* e, const char* fn, const dmx_prior_request* rq, bool for_call, PriorPlan* pl) {
+  const int32_t V = e->V, A = e->A, B = rq->n_cells;
+  if (rq->n_samples != V || rq->n_alpha != A)
+    return set_error(DMX_ERR_ARG, "%s: n_samples %d, n_alpha %d; the engine has %d, %d", fn, rq->n_samples, rq->n_alpha, V, A);
+  if (V < 2 || A < 2) return set_error(DMX_ERR_ARG, "%s: needs >= 2 samples and >= 2 alphas (got %d, %d)", fn, V, A);
+  if ((int64_t)V * A > dmx_prior::kPriMaxVA) return set_error(DMX_ERR_ARG, "%s: n_samples x n_alpha = %lld, at most %d", fn, (long long)V * A, dmx_prior::kPriMaxVA);
+  if ((int64_t)V * V * A >= ((int64_t)1 << 31)) return set_error(DMX_ERR_ARG, "%s: a grid of %d x %d x %d entries per barcode", fn, V, V, A);
+  if (!rq->grid) {
+    if (!e->have_grid) return set_error(DMX_ERR_STATE, "%s: no doublet grid (dmx_engine_run_doublet first, or pass a grid)", fn);
+    if (B != e->pv.B) return set_error(DMX_ERR_ARG, "%s: n_cells %d, the staged pileup has %d", fn, B, e->pv.B);
+  } else {
+    if (B < 0) return set_error(DMX_ERR_ARG, "%s: n_cells %d", fn, B);
+    if (rq->grid_memory != DMX_MEM_HOST && rq->grid_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "%s: grid_memory %d", fn, rq->grid_memory);
+  }
+  if (B < 1) return set_error(DMX_ERR_ARG, "%s: no barcode (B_in == 0)", fn);
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t sv = (size_t)V, sb = (size_t)B, gbytes = sizeof(double) * sb * sv * sv * (size_t)A;
+  const size_t n_chunks = (sb + dmx_prior::kPriChunk - 1) / dmx_prior::kPriChunk;
+  const size_t rows_b = sizeof(double) * sb * (sv + 3), part_b = sizeof(double) * n_chunks * (sv + 3), call_b = sizeof(dmx_prior_call) * sb;
+  size_t free_b = 0, total_b = 0, need = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  auto want = [&](size_t bytes, size_t cap) { if (bytes > cap) need += bytes + bytes / 16; };
+  if (rq->grid && rq->grid_memory == DMX_MEM_HOST) want(gbytes, e->d_prgrid.cap());
+  if (for_call) want(call_b, e->d_prcall.cap()); else { want(rows_b, e->d_prrows.cap()); want(part_b, e->d_prpart.cap()); }
+  want(sb, e->d_prmask.cap());
+  if (!for_call) { want(sb, e->d_prflag.cap()); want(sizeof(int32_t) * sb, e->d_pridx.cap()); }
+  if (need > free_b) return set_error(DMX_ERR_NOMEM, "%s: %d barcodes x %d samples need %zu more device bytes, %zu are free", fn, B, V, need, free_b);
+  if (rq->grid && rq->grid_memory == DMX_MEM_HOST) {
+    if (int rc = e->d_prgrid.ensure(gbytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_prgrid, rq->grid, gbytes, hipMemcpyHostToDevice, e->stream));
+    pl->grid = e->d_prgrid;
+  } else {
+    pl->grid = rq->grid ? rq->grid : (const double*)e->d_grid;
+  }
+  if (int rc = e->d_prmask.ensure(sb)) return rc;
+  if (int rc = e->d_prnin.ensure(sizeof(int32_t))) return rc;
+  if (int rc = e->d_prst.ensure(sizeof(double) * (sv + 1))) return rc;
+  if (int rc = e->d_prtab.ensure(sizeof(double) * (3 * sv + 1))) return rc;
+  if (int rc = e->d_prout.ensure(sizeof(double) * (2 * sv + 5))) return rc;
+  if (for_call) {
+    if (int rc = e->d_prcall.ensure(call_b)) return rc;
+  } else {
+    if (int rc = e->d_prrows.ensure(rows_b)) return rc;
+    if (int rc = e->d_prpart.ensure(part_b)) return rc;
+    if (int rc = e->d_prflag.ensure(sb)) return rc;
+    if (int rc = e->d_pridx.ensure(sizeof(int32_t) * sb)) return rc;
+  }
+  if (rq->mask) {
+    HIP_TRY(hipMemcpyAsync(e->d_prmask, rq->mask, sb, hipMemcpyHostToDevice, e->stream));
+    pl->mask = e->d_prmask;
+  } else if (!rq->grid) {
+    hipLaunchKernelGGL(dmx_prior::k_prior_mask, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, e->stream, (const dmx_cell_summary*)e->d_sum, B,
+                       e->d_prmask.get());
+    HIP_TRY(hipGetLastError());
+    pl->mask = e->d_prmask;
+  } else {
+    pl->mask = nullptr;
+  }
+  HIP_TRY(hipStreamSynchronize(e->stream));         // (the caller's host grid and mask may go away on return)
+  // wavefronts per workgroup: the widest of 4, 2, 1 whose shared table, slots, rows and singlets fit 64 KiB (a barcode's bits do not depend on it)
+  const size_t va = sv * (size_t)A;
+  int32_t W = 4;
+  while (W > 1 && sizeof(double) * (va + (size_t)W * (va + 2 * sv)) > 64 * 1024) W >>= 1;
+  pl->B = B; pl->V = V; pl->A = A; pl->W = W;
+  pl->lds = sizeof(double) * (va + (size_t)W * (va + 2 * sv));
+  if (!e->have_pr_info) std::memset(&e->pr_info, 0, sizeof e->pr_info);
+  e->pr_info.bytes_per_iter = (int64_t)gbytes; e->pr_info.n_cells = B; e->pr_info.n_samples = V; e->pr_info.n_alpha = A;
+  e->pr_info.waves_per_block = W;
+  e->have_pr_info = true;
+  return DMX_OK;
+}
+
+// pi (any positive scale; NULL = uniform) and d: checked before a call touches any buffer, so that a refused call leaves the earlier results
+int prior_check_params(const char* fn, int32_t V, const double* pi, double d) {
+  if (!(d >= 0.0 && d <= 1.0)) return set_error(DMX_ERR_ARG, "%s: d = %g is not in [0, 1]", fn, d);
+  double s = 0.0;
+  for (int32_t j = 0; j < V; ++j) {
+    const double x = pi ? pi[j] : 1.0;
+    if (!(x >= 0.0 && x < INFINITY)) return set_error(DMX_ERR_ARG, "%s: pi[%d] = %g is negative or not finite", fn, j, x);
+    s += x;
+  }
+  if (!(s > 0.0 && s < INFINITY)) return set_error(DMX_ERR_ARG, "%s: pi sums to %g", fn, s);
+  return DMX_OK;
+}
+
+// pi / sum(pi) | d uploaded (the sum in ascending j), the tables built
+int prior_upload(dmx_engine* e, const PriorPlan& pl, const double* pi, double d) {
+  const int32_t V = pl.V;
+  std::vector<double> st((size_t)V + 1);
+  double s = 0.0;
+  for (int32_t j = 0; j < V; ++j) s += pi ? pi[j] : 1.0;
+  for (int32_t j = 0; j < V; ++j) st[(size_t)j] = (pi ? pi[j] : 1.0) / s;
+  st[(size_t)V] = d;
+  HIP_TRY(hipMemcpyAsync(e->d_prst, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, e->stream));
+  hipLaunchKernelGGL(dmx_prior::k_prior_tables, dim3(1), dim3(256), 0, e->stream, (const double*)e->d_prst, V, pl.A, e->d_prtab.get());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(e->stream));         // (st goes away on return)
+  return DMX_OK;
+}
+
+template <bool CALL>
+int prior_launch_estep(dmx_engine* e, const PriorPlan& pl) {
+  auto kern = &dmx_prior::k_prior_estep<CALL>;
+  if (pl.lds > 30 * 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds));
+  hipLaunchKernelGGL(kern, dim3((unsigned)((pl.B + pl.W - 1) / pl.W)), dim3(64 * pl.W), pl.lds, e->stream, pl.grid, pl.mask, pl.B, pl.V, pl.A,
+                     (const double*)e->d_prtab, e->d_prrows.get(), e->d_prflag.get(), e->d_prcall.get());
+  HIP_TRY(hipGetLastError());
+  return DMX_OK;
+}
+
+// out[V + 3] = N | hom | het | LL at the device's (pi, d); full != NULL: all 2 V + 5 doubles (then pi' | d' | B_in)
+int prior_pass(dmx_engine* e, const PriorPlan& pl, bool apply, bool fix_pi, bool fix_d, double* out, double* full) {
+  const int32_t V = pl.V;
+  if (int rc = e->prev[0].record_start(e->stream)) return rc;
+  if (int rc = prior_launch_estep<false>(e, pl)) return rc;
+  if (int rc = e->prev[0].record_stop(e->stream)) return rc;
+  if (int rc = e->prev[1].record_start(e->stream)) return rc;
+  const int32_t n_chunks = (pl.B + dmx_prior::kPriChunk - 1) / dmx_prior::kPriChunk;
+  hipLaunchKernelGGL(dmx_prior::k_prior_rank, dim3(1), dim3(1024), 0, e->stream, (const uint8_t*)e->d_prflag, pl.B, e->d_pridx.get(), e->d_prnin.get());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dmx_prior::k_prior_fold_chunk, dim3((unsigned)n_chunks, (unsigned)((V + 3 + 63) / 64)), dim3(256), 0, e->stream, (const double*)e->d_prrows,
+                     (const int32_t*)e->d_pridx, (const int32_t*)e->d_prnin, V, e->d_prpart.get());
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(dmx_prior::k_prior_fold, dim3(1), dim3(256), 0, e->stream, (const double*)e->d_prpart, (const int32_t*)e->d_prnin, V, pl.A,
+                     apply ? 1 : 0, fix_pi ? 1 : 0, fix_d ? 1 : 0, e->d_prst.get(), e->d_prout.get(), e->d_prtab.get());
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->prev[1].record_stop(e->stream)) return rc;
+  if (out) HIP_TRY(hipMemcpyAsync(out, e->d_prout, sizeof(double) * ((size_t)V + 3), hipMemcpyDeviceToHost, e->stream));
+  if (full) HIP_TRY(hipMemcpyAsync(full, e->d_prout, sizeof(double) * (2 * (size_t)V + 5), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  float ms0 = 0.f, ms1 = 0.f;
+  if (int rc = e->prev[0].elapsed_ms(&ms0)) return rc;
+  if (int rc = e->prev[1].elapsed_ms(&ms1)) return rc;
+  e->pr_info.estep_ms = ms0; e->pr_info.fold_ms = ms1;
+  return DMX_OK;
+}
+
+}  // namespace
+
+extern "C" int dmx_engine_prior_step(dmx_engine* e, const dmx_prior_request* rq, const double* pi, double d) {
+  const char* fn = "dmx_engine_prior_step";
+  if (!e || !rq || !pi) return set_error(DMX_ERR_ARG, "%s: null argument", fn);
+  PriorPlan pl;
+  if (int rc = prior_check_params(fn, e->V, pi, d)) return rc;
+  if (int rc = prior_prepare(e, fn, rq, false, &pl)) return rc;   // (a call refused up to here leaves the last step's results readable)
+  e->have_pr_step = false;
+  if (int rc = prior_upload(e, pl, pi, d)) return rc;
+  e->pr_step_out.assign(2 * (size_t)pl.V + 5, 0.0);
+  if (int rc = prior_pass(e, pl, false, false, false, nullptr, e->pr_step_out.data())) return rc;
+  if (e->pr_step_out[2 * (size_t)pl.V + 4] < 1.0) return set_error(DMX_ERR_ARG, "%s: no barcode is included (B_in == 0)", fn);
+  e->pr_B = pl.B; e->pr_V = pl.V;
+  e->have_pr_step = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_prior_step(dmx_engine* e, double* N, double* hom, double* het, double* ll, int32_t* b_in, double* pi_next,
+                                         double* d_next, double* rows, uint8_t* flags) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_prior_step: null engine");
+  if (!e->have_pr_step) return set_error(DMX_ERR_STATE, "dmx_engine_get_prior_step: no step yet (dmx_engine_prior_step first)");
+  const size_t V = (size_t)e->pr_V, B = (size_t)e->pr_B;
+  const double* o = e->pr_step_out.data();
+  if (N) std::memcpy(N, o, sizeof(double) * V);
+  if (hom) *hom = o[V];
+  if (het) *het = o[V + 1];
+  if (ll) *ll = o[V + 2];
+  if (pi_next) std::memcpy(pi_next, o + V + 3, sizeof(double) * V);
+  if (d_next) *d_next = o[2 * V + 3];
+  if (b_in) *b_in = (int32_t)o[2 * V + 4];
+  HIP_TRY(hipSetDevice(e->device));
+  if (rows) HIP_TRY(hipMemcpyAsync(rows, e->d_prrows, sizeof(double) * B * (V + 3), hipMemcpyDeviceToHost, e->stream));
+  if (flags) HIP_TRY(hipMemcpyAsync(flags, e->d_prflag, B, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_prior_fit(dmx_engine* e, const dmx_prior_request* rq) {
+  const char* fn = "dmx_engine_prior_fit";
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "%s: null argument", fn);
+  if (rq->max_iter < 1) return set_error(DMX_ERR_ARG, "%s: max_iter %d", fn, rq->max_iter);
+  PriorPlan pl;
+  if (int rc = prior_check_params(fn, e->V, rq->pi0, rq->d0)) return rc;
+  if (int rc = prior_prepare(e, fn, rq, false, &pl)) return rc;
+  e->have_pr_fit = false; e->have_pr_step = false;  // (the fit's passes overwrite the step's rows and flags)
+  if (int rc = prior_upload(e, pl, rq->pi0, rq->d0)) return rc;
+  const size_t V = (size_t)pl.V;
+  std::vector<double> out(V + 3), full(2 * V + 5);
+  e->pr_fit_ll.clear(); e->pr_fit_d.clear();
+  double d_cur = rq->d0, fit_ms = 0.0, b_in = 0.0;
+  int32_t conv = 0;
+  for (int32_t it = 0; it < rq->max_iter; ++it) {
+    // the first iteration also reads B_in and every iteration d' (the trace's next entry): V + 3 doubles decide the stop
+    if (int rc = prior_pass(e, pl, true, rq->fix_pi != 0, rq->fix_d != 0, out.data(), it == 0 ? full.data() : nullptr)) return rc;
+    fit_ms += e->pr_info.estep_ms + e->pr_info.fold_ms;
+    if (it == 0) {
+      b_in = full[2 * V + 4];
+      if (b_in < 1.0) return set_error(DMX_ERR_ARG, "%s: no barcode is included (B_in == 0)", fn);
+    }
+    e->pr_fit_ll.push_back(out[V + 2]); e->pr_fit_d.push_back(d_cur);
+    if (!rq->fix_d) d_cur = std::fmin((out[V] + out[V + 1]) / b_in, 1.0);     // (k_prior_fold's own expression)
+    if (it > 0 && rq->tol > 0.0 && e->pr_fit_ll[(size_t)it] - e->pr_fit_ll[(size_t)it - 1] < rq->tol * b_in) { conv = 1; break; }
+  }
+  e->pr_fit_out.assign(2 * V + 5, 0.0);
+  if (int rc = prior_pass(e, pl, false, true, true, nullptr, e->pr_fit_out.data())) return rc;   // the final evaluation: pi' = pi, d' = d
+  e->pr_fit_pi.assign(e->pr_fit_out.begin() + (ptrdiff_t)(V + 3), e->pr_fit_out.begin() + (ptrdiff_t)(2 * V + 3));
+  e->pr_fit_dd = e->pr_fit_out[2 * V + 3];
+  e->pr_fit_iter = (int32_t)e->pr_fit_ll.size(); e->pr_fit_conv = conv;
+  e->pr_info.n_iter = e->pr_fit_iter; e->pr_info.fit_ms = fit_ms;
+  e->pr_B = pl.B; e->pr_V = pl.V;
+  e->have_pr_fit = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_prior_fit(dmx_engine* e, double* pi, double* d, double* ll, int32_t* n_iter, int32_t* converged, int32_t* b_in,
+                                        double* N, double* hom, double* het, double* ll_trace, double* d_trace, int32_t trace_cap) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_prior_fit: null engine");
+  if (!e->have_pr_fit) return set_error(DMX_ERR_STATE, "dmx_engine_get_prior_fit: no fit yet (dmx_engine_prior_fit first)");
+  const size_t V = (size_t)e->pr_V;
+  const double* o = e->pr_fit_out.data();
+  if (pi) std::memcpy(pi, e->pr_fit_pi.data(), sizeof(double) * V);
+  if (d) *d = e->pr_fit_dd;
+  if (ll) *ll = o[V + 2];
+  if (n_iter) *n_iter = e->pr_fit_iter;
+  if (converged) *converged = e->pr_fit_conv;
+  if (b_in) *b_in = (int32_t)o[2 * V + 4];
+  if (N) std::memcpy(N, o, sizeof(double) * V);
+  if (hom) *hom = o[V];
+  if (het) *het = o[V + 1];
+  const size_t n = (size_t)std::max(0, std::min(trace_cap, e->pr_fit_iter));
+  if (ll_trace) std::memcpy(ll_trace, e->pr_fit_ll.data(), sizeof(double) * n);
+  if (d_trace) std::memcpy(d_trace, e->pr_fit_d.data(), sizeof(double) * n);
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_prior_call(dmx_engine* e, const dmx_prior_request* rq, const double* pi, double d) {
+  const char* fn = "dmx_engine_prior_call";
+  if (!e || !rq || !pi) return set_error(DMX_ERR_ARG, "%s: null argument", fn);
+  PriorPlan pl;
+  if (int rc = prior_check_params(fn, e->V, pi, d)) return rc;
+  if (int rc = prior_prepare(e, fn, rq, true, &pl)) return rc;   // (touches the records, never a step's rows or flags: a record carries its own flag)
+  e->have_pr_call = false;
+  if (int rc = prior_upload(e, pl, pi, d)) return rc;
+  if (int rc = e->prev[2].record_start(e->stream)) return rc;
+  if (int rc = prior_launch_estep<true>(e, pl)) return rc;
+  if (int rc = e->prev[2].record_stop(e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  float ms = 0.f;
+  if (int rc = e->prev[2].elapsed_ms(&ms)) return rc;
+  e->pr_info.call_ms = ms;
+  e->pr_call_B = pl.B;
+  e->have_pr_call = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_prior_calls(dmx_engine* e, dmx_prior_call* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_get_prior_calls: null argument");
+  if (!e->have_pr_call) return set_error(DMX_ERR_STATE, "dmx_engine_get_prior_calls: no records yet (dmx_engine_prior_call first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipMemcpyAsync(out, e->d_prcall, sizeof(dmx_prior_call) * (size_t)e->pr_call_B, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_prior_info(dmx_engine* e, dmx_prior_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_prior_info: null argument");
+  if (!e->have_pr_info) return set_error(DMX_ERR_STATE, "dmx_engine_prior_info: no prior pass yet (dmx_engine_prior_step, _fit or _call first)");
+  *out = e->pr_info;
   return DMX_OK;
 }

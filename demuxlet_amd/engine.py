@@ -873,6 +873,106 @@ class Engine:
         check(self._L.dmx_engine_census_fisher_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.CensusFisherInfo._fields_ if n != "reserved"}
 
+    def _prior_request(self, grid, mask, n_cells=None):
+        """(request, keep-alive list) of a prior call.  grid: None = the engine's llksAB of the last run_doublet; a host array
+        [B][V][V][A]; or a device pointer (int) to one, with n_cells=.  mask: None, or [B] (0 = leave the barcode out)."""
+        keep = []
+        if grid is None:
+            B, mem, ptr = self.B, capi.DMX_MEM_HOST, None
+        elif isinstance(grid, int):
+            if n_cells is None:
+                raise ValueError("a device grid needs n_cells=")
+            B, mem, ptr = int(n_cells), capi.DMX_MEM_DEVICE, grid
+        else:
+            gr = np.ascontiguousarray(grid, dtype=np.float64)
+            if gr.ndim != 4 or gr.shape[1:] != (self.V, self.V, self.A):
+                raise ValueError(f"grid must be [B][{self.V}][{self.V}][{self.A}]")
+            keep.append(gr)
+            B, mem, ptr = gr.shape[0], capi.DMX_MEM_HOST, (gr.ctypes.data if gr.size else None)
+            if ptr is None:
+                raise ValueError("grid has no barcode")
+        mp = None
+        if mask is not None:
+            mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            if mk.shape != (B,):
+                raise ValueError(f"mask must be [{B}]")
+            keep.append(mk)
+            mp = mk.ctypes.data if mk.size else None
+        rq = capi.PriorRequest(B, self.V, self.A, mem, ptr, mp)
+        return rq, keep
+
+    def prior_step(self, pi, d: float, grid=None, mask=None, n_cells=None, rows: bool = False) -> dict:
+        """dmx_engine_prior_step: one E + M of the empirical-Bayes prior fit at shares pi[V] (any positive scale) and doublet rate d
+        (include/dmx.h).  `grid`, `mask`, `n_cells` as in _prior_request.  Returns a dict: N[V], hom, het, ll,
+        b_in, pi_next[V], d_next, and with rows=True rows[B][V + 3] (N contributions | hom | het | log E_b) and flags[B]."""
+        rq, keep = self._prior_request(grid, mask, n_cells)
+        p = np.ascontiguousarray(pi, dtype=np.float64)
+        if p.shape != (self.V,):
+            raise ValueError(f"pi must be [{self.V}]")
+        check(self._L.dmx_engine_prior_step(self._h, C.byref(rq), p.ctypes.data, float(d)))
+        self._prior_step_B = rq.n_cells             # (a refused call leaves the last step's results, and its count, as they were)
+        return self.get_prior_step(rows=rows)
+
+    def get_prior_step(self, rows: bool = True) -> dict:
+        """The last prior_step's results (dmx_engine_get_prior_step).  They stay readable after a prior_call and after a call that was
+        refused for its arguments, the engine's state or its memory need; a prior_fit overwrites the rows, so they are gone after one."""
+        self.prior_info()                            # (DMX_ERR_STATE before any prior call)
+        B = getattr(self, "_prior_step_B", 0)       # the last step's barcodes: a later prior_call may have had another count
+        N = np.zeros(self.V); pn = np.zeros(self.V)
+        hom = C.c_double(); het = C.c_double(); ll = C.c_double(); dn = C.c_double(); b_in = C.c_int32()
+        rw = np.zeros((B, self.V + 3)) if rows else None
+        fl = np.zeros(B, dtype=np.uint8) if rows else None
+        check(self._L.dmx_engine_get_prior_step(self._h, N.ctypes.data, C.byref(hom), C.byref(het), C.byref(ll), C.byref(b_in), pn.ctypes.data,
+                                                C.byref(dn), rw.ctypes.data if rows else None, fl.ctypes.data if rows else None))
+        r = dict(N=N, hom=hom.value, het=het.value, ll=ll.value, b_in=b_in.value, pi_next=pn, d_next=dn.value)
+        if rows:
+            r.update(rows=rw, flags=fl)
+        return r
+
+    def prior_fit(self, grid=None, mask=None, n_cells=None, pi0=None, d0: float = 0.1, max_iter: int = 200, tol: float = 1e-6,
+                  fix_pi: bool = False, fix_d: bool = False) -> dict:
+        """dmx_engine_prior_fit: the EM loop inside the library from (pi0 (None = uniform), d0); it stops after the iteration whose
+        log-likelihood gain is below tol x B_in (tol <= 0: never) or after max_iter, then evaluates once more at the final (pi, d).
+        Returns a dict: pi[V], d, ll, N[V], hom, het (at the final pi, d), b_in, n_iter, converged, ll_trace[n_iter], d_trace[n_iter]
+        (iteration t's log-likelihood and the rate it was evaluated at)."""
+        rq, keep = self._prior_request(grid, mask, n_cells)
+        if pi0 is not None:
+            p0 = np.ascontiguousarray(pi0, dtype=np.float64)
+            if p0.shape != (self.V,):
+                raise ValueError(f"pi0 must be [{self.V}]")
+            keep.append(p0)
+            rq.pi0 = p0.ctypes.data
+        rq.d0, rq.tol, rq.max_iter, rq.fix_pi, rq.fix_d = float(d0), float(tol), int(max_iter), int(bool(fix_pi)), int(bool(fix_d))
+        check(self._L.dmx_engine_prior_fit(self._h, C.byref(rq)))
+        pi = np.zeros(self.V); N = np.zeros(self.V)
+        d = C.c_double(); ll = C.c_double(); hom = C.c_double(); het = C.c_double()
+        n_iter = C.c_int32(); conv = C.c_int32(); b_in = C.c_int32()
+        llt = np.zeros(int(max_iter)); dt = np.zeros(int(max_iter))
+        check(self._L.dmx_engine_get_prior_fit(self._h, pi.ctypes.data, C.byref(d), C.byref(ll), C.byref(n_iter), C.byref(conv), C.byref(b_in),
+                                               N.ctypes.data, C.byref(hom), C.byref(het), llt.ctypes.data, dt.ctypes.data, int(max_iter)))
+        n = n_iter.value
+        return dict(pi=pi, d=d.value, ll=ll.value, N=N, hom=hom.value, het=het.value, b_in=b_in.value, n_iter=n, converged=bool(conv.value),
+                    ll_trace=llt[:n].copy(), d_trace=dt[:n].copy())
+
+    def prior_call(self, pi, d: float, grid=None, mask=None, n_cells=None) -> np.ndarray:
+        """dmx_engine_prior_call + dmx_engine_get_prior_calls: the per-barcode records at (pi, d), a structured array [B] of
+        capi.PRIOR_CALL_DTYPE (log_e, p_sng, p_het, p_hom, p_sng1, p_sng2, p_dbl1, i_sng1, i_sng2, j_dbl, k_dbl, n_dbl, flag)."""
+        rq, keep = self._prior_request(grid, mask, n_cells)
+        p = np.ascontiguousarray(pi, dtype=np.float64)
+        if p.shape != (self.V,):
+            raise ValueError(f"pi must be [{self.V}]")
+        check(self._L.dmx_engine_prior_call(self._h, C.byref(rq), p.ctypes.data, float(d)))
+        out = np.zeros(rq.n_cells, dtype=capi.PRIOR_CALL_DTYPE)
+        check(self._L.dmx_engine_get_prior_calls(self._h, out.ctypes.data))
+        return out
+
+    def prior_info(self) -> dict:
+        """HIP-event times (ms) of the last prior kernels, the last fit's iterations and summed time, and the grid bytes one iteration
+        reads (dmx_engine_prior_info)."""
+        r = capi.PriorInfo()
+        check(self._L.dmx_engine_prior_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.PriorInfo._fields_ if n != "reserved"}
+
     def device_view(self) -> capi.DeviceView:
         v = capi.DeviceView()
         check(self._L.dmx_engine_device_view(self._h, C.byref(v)))

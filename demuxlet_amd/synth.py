@@ -323,6 +323,69 @@ def make_multiplet_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int,
     return sp, truth3, w
 
 
+def make_pool_pileup(rng: np.random.Generator, alleles: np.ndarray, B: int, delta: float, rbar: float, donor_shares, doublet_rate: float,
+                     alpha: float = 0.5, dense_layout: bool = False, quals: Optional[str] = None, chunk_cells: int = 256
+                     ) -> Tuple[SynthPileup, dict]:
+    """A pool loaded unevenly.  A droplet holds two cells with probability doublet_rate, otherwise one; every cell's donor is an
+    independent draw from donor_shares[V] (zeros allowed: a donor of the VCF that is not in the pool), so homotypic doublets occur at
+    their natural rate.  In a doublet a read comes from the second cell with probability alpha (ALT w.p. the dosage / 2); then sequencing
+    error as in make_pileup.  Returns (pileup, truth): pileup.truth[c] = (first, second or -1), the second equal to the first in a
+    homotypic doublet; truth = dict(first[B], second[B] (-1 in singlets), doublet[B] bool, homotypic[B] bool, cell_share[V] = the donors'
+    fractions of all drawn cells, doublet_rate = the drawn fraction of droplets with two cells, heterotypic_rate)."""
+    S, V, _ = alleles.shape
+    dosage = np.clip(alleles, 0, 1).sum(axis=2).astype(np.float64)      # [S][V]
+    p = np.asarray(donor_shares, dtype=np.float64)
+    if p.shape != (V,) or np.any(p < 0.0) or not p.sum() > 0.0:
+        raise ValueError(f"donor_shares: {V} non-negative shares with a positive sum expected")
+    p = p / p.sum()
+    if not 0.0 <= doublet_rate <= 1.0:
+        raise ValueError("doublet_rate must be in [0, 1]")
+    first = rng.choice(V, size=B, p=p).astype(np.int32)
+    dbl = rng.random(B) < doublet_rate
+    second = np.where(dbl, rng.choice(V, size=B, p=p), -1).astype(np.int32)
+    cell_pair_off = np.zeros(B + 1, dtype=np.int64)
+    cell_read_off = np.zeros(B + 1, dtype=np.int64)
+    snp_chunks, nrd_chunks, rd_chunks = [], [], []
+    totl = np.zeros(B, dtype=np.int32)
+    for c0 in range(0, B, chunk_cells):
+        c1 = min(B, c0 + chunk_cells)
+        nc = c1 - c0
+        s1, s2, isd = first[c0:c1], np.maximum(second[c0:c1], 0), dbl[c0:c1]
+        cov = np.ones((nc, S), dtype=bool) if delta >= 1.0 else rng.random((nc, S)) < delta
+        cc, ss = np.nonzero(cov)
+        npairs = len(cc)
+        nreads = 1 + rng.poisson(max(rbar - 1.0, 0.0), size=npairs)
+        pair_of_read = np.repeat(np.arange(npairs), nreads)
+        rc, rs = cc[pair_of_read], ss[pair_of_read]
+        src = np.where(isd[rc] & (rng.random(len(rc)) < alpha), s2[rc], s1[rc])
+        alt = rng.random(len(rc)) < dosage[rs, src] / 2.0
+        bq = draw_bq(rng, len(rc), quals)
+        e = rng.random(len(rc)) < ERR_OF_BQ[bq]
+        u = rng.integers(0, 3, size=len(rc))
+        allele = np.where(e, np.where(u == 0, 1 - alt.astype(np.int32), 2), alt.astype(np.int32)).astype(np.uint8)
+        keep = allele != 2
+        cell_pair_off[c0 + 1:c1 + 1] = np.bincount(cc, minlength=nc)
+        cell_read_off[c0 + 1:c1 + 1] = np.bincount(rc[keep], minlength=nc)
+        totl[c0:c1] = np.bincount(rc, minlength=nc)
+        snp_chunks.append(ss.astype(np.int32))
+        nrd_chunks.append(np.bincount(pair_of_read[keep], minlength=npairs))
+        rd_chunks.append(((allele[keep] << 7) | bq[keep]).astype(np.uint8))
+    np.cumsum(cell_pair_off, out=cell_pair_off)
+    np.cumsum(cell_read_off, out=cell_read_off)
+    nrd = np.concatenate(nrd_chunks) if nrd_chunks else np.zeros(0, dtype=np.int64)
+    nrd = nrd.astype(np.uint8 if (len(nrd) == 0 or nrd.max() <= 255) else np.uint16)
+    pair_snp = np.concatenate(snp_chunks) if snp_chunks else np.zeros(0, dtype=np.int32)
+    reads = np.concatenate(rd_chunks) if rd_chunks else np.zeros(0, dtype=np.uint8)
+    use_dense = dense_layout and delta >= 1.0
+    sp = SynthPileup(B, S, cell_pair_off, cell_read_off, None if use_dense else pair_snp, nrd, reads, totl, totl.copy(), totl.copy(),
+                     np.stack([first, second], axis=1).astype(np.int32))
+    cells = np.bincount(first, minlength=V) + np.bincount(second[dbl], minlength=V)
+    hom = dbl & (second == first)
+    truth = dict(first=first, second=second, doublet=dbl, homotypic=hom, cell_share=cells / max(int(cells.sum()), 1),
+                 doublet_rate=float(dbl.mean()) if B else 0.0, heterotypic_rate=float((dbl & ~hom).mean()) if B else 0.0)
+    return sp, truth
+
+
 def barcode_name(i: int) -> str:
     """Deterministic 16-mer barcode whose byte-wise sort order is NOT the id order (exercises the sorted-output rule)."""
     x = (i * 2654435761 + 12345) & 0xFFFFFFFF

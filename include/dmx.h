@@ -1094,6 +1094,88 @@ int dmx_engine_doublet_anchored(dmx_engine*, const dmx_anchored_request*);
 int dmx_engine_get_anchored(dmx_engine*, int32_t* anchors, double* c0, double* pairs, double* llks00, dmx_cell_summary* summary);
 int dmx_engine_anchored_info(dmx_engine*, dmx_anchored_info* out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Empirical-Bayes priors (appended, DMX_ABI_VERSION stays 8): the donor shares pi[V] of the pool's CELLS and the
+ * doublet rate d, fitted by EM from the doublet grid llksAB[B][V][V][A] that dmx_engine_run_doublet leaves on the device (either mode:
+ * DMX_MODE_FAST mirrors the alpha = 0.5 entries), and the per-barcode posteriors under those priors.
+ * Model, for barcode b with L[j][k][n] = llksAB[b][j][k][n]: the USED entries are S_j = L[j][0][0] (the singlet column .sing2 prints)
+ * and D_jkn = L[j][k][n] for j != k, n >= 1; the entries [j][k != 0][0] and the diagonal at n >= 1 are never read into a result.  A droplet
+ * holds two cells with probability d, else one; cells are independent draws from pi; a homotypic doublet has the singlet's
+ * likelihood; a doublet's alpha is uniform over the grid's A - 1 values:
+ *   w_S(j) = (1 - d) pi_j + d pi_j^2,   w_D(j,k,n) = d pi_j pi_k / (A - 1),
+ *   E_b = sum_j w_S(j) exp(S_j) + sum_{j != k, n >= 1} w_D(j,k,n) exp(D_jkn),   LL = sum_b log E_b.
+ * Responsibilities r = w exp(.) / E_b; h_j = r_S(j) d pi_j / ((1 - d) + d pi_j) is the homotypic part of a singlet-like one.  A term whose
+ * weight is exactly 0 or whose entry is -inf is exactly 0.  One step at (pi, d) gives, over the included barcodes,
+ *   N_j = sum_b [ r_S(j) + h_j + sum_{k,n} r_D(j,k,n) + sum_{k,n} r_D(k,j,n) ],  hom = sum_b sum_j h_j,  het = sum_b sum r_D,  LL,
+ * and the M-step pi'_j = N_j / sum_j N_j, d' = min(1, (hom + het) / B_in).  fix_pi / fix_d keep pi / d.
+ * A barcode is INCLUDED unless mask[b] == 0 (DMX_PRIOR_MASKED) or it is BAD (DMX_PRIOR_BAD): a NaN or +inf among its used entries, or no
+ * term above zero (every used entry -inf or of weight 0).  Flagged barcodes get rows and records of zeros and count nowhere.
+ * Per-barcode row (prior_step): N contributions [V] | homotypic mass | heterotypic mass | log E_b.
+ * Per-barcode record (prior_call): dmx_prior_call below.
+ * Sum order of the fold (section 12's convention): the included barcodes in ascending id are cut into chunks of 64; a chunk's rows are
+ * added in barcode order from 0.0, the chunk partials in ascending chunk order from 0.0.  No floating-point atomics: a barcode's row and
+ * record depend on its own grid, pi, d, V and A only; N, hom, het, LL, pi', d' on the included rows only — not on launch geometry, the
+ * stream, earlier calls, or where the grid lives.
+ * pi given by the caller is divided by its sum (ascending j) first.  Limits: V >= 2, A >= 2, V A <= 4096 (the LDS holds the column
+ * slots of a barcode: DESIGN.md section 25), V V A < 2^31; n_samples / n_alpha are the engine's.
+ * Every call runs on the engine's stream and synchronises it, uses buffers of its own and leaves every other result as it was.
+ * Among themselves: a refused call (DMX_ERR_ARG for sizes, pi or d; DMX_ERR_STATE; DMX_ERR_NOMEM) leaves the last step's, fit's and call's
+ * results readable; dmx_engine_prior_call never touches a step's rows or flags (a record carries its own flag); dmx_engine_prior_fit
+ * overwrites the step's rows, after which dmx_engine_get_prior_step is DMX_ERR_STATE, as it is after a step without an included barcode.
+ * DMX_ERR_STATE: grid == NULL before dmx_engine_run_doublet; a getter before its call.  DMX_ERR_ARG: sizes that do not match or exceed
+ * the limits; pi not finite, negative or summing to 0; d outside [0, 1]; no included barcode (B_in == 0).  DMX_ERR_NOMEM: the buffers do
+ * not fit the free device memory (checked before anything is allocated). */
+enum { DMX_PRIOR_MASKED = 1, DMX_PRIOR_BAD = 2 };
+typedef struct {
+  int32_t n_cells;             /* B: the staged pileup's with grid == NULL, else the caller's grid's */
+  int32_t n_samples, n_alpha;  /* = the engine's V and A */
+  int32_t grid_memory;         /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `grid` lives (ignored with grid == NULL) */
+  const double* grid;          /* [B][V][V][A], or NULL = the engine's llksAB of the last dmx_engine_run_doublet */
+  const uint8_t* mask;         /* host [B], 0 = leave out; NULL = barcodes with n_pairs > 0 (engine's grid) / all barcodes (caller's grid) */
+  const double* pi0;           /* fit: host [V] start, NULL = uniform */
+  double  d0;                  /* fit: start (with fix_d: the value held) */
+  double  tol;                 /* fit: stop once LL gained less than tol * B_in in an iteration; <= 0: run max_iter iterations */
+  int32_t max_iter;            /* fit: >= 1 */
+  int32_t fix_pi, fix_d;       /* fit: hold the shares / the rate */
+  int32_t reserved[5];         /* 0 */
+} dmx_prior_request;
+typedef struct {
+  double  log_e;               /* log E_b */
+  double  p_sng, p_het, p_hom; /* sum_j (r_S(j) - h_j), sum r_D, sum_j h_j: they add up to 1 */
+  double  p_sng1, p_sng2;      /* the two largest r_S(j) (first maximum wins; second = first maximum of the rest, as K3 does) */
+  double  p_dbl1;              /* responsibility of the largest doublet term */
+  int32_t i_sng1, i_sng2;
+  int32_t j_dbl, k_dbl, n_dbl; /* first maximum of w_D exp(D) in the scan order j, k, n ascending, strict <; -1 without a term above zero */
+  int32_t flag;                /* 0, DMX_PRIOR_MASKED or DMX_PRIOR_BAD */
+} dmx_prior_call;
+typedef struct {
+  double  estep_ms;            /* HIP-event time of the last k_prior_estep */
+  double  fold_ms;             /* ... of the last fold (k_prior_rank, k_prior_fold_chunk, k_prior_fold) */
+  double  call_ms;             /* ... of the last k_prior_estep<call> */
+  double  fit_ms;              /* sum of estep_ms + fold_ms over the last fit's iterations */
+  int64_t bytes_per_iter;      /* grid bytes one iteration reads from memory (B V V A 8: the second pass is counted as cache hits) */
+  int32_t n_iter;              /* iterations of the last fit (its final evaluation not counted) */
+  int32_t n_cells, n_samples, n_alpha, waves_per_block;
+  int32_t reserved[3];
+} dmx_prior_info;
+/* One E + M at (pi[V], d).  Results: dmx_engine_get_prior_step. */
+int dmx_engine_prior_step(dmx_engine*, const dmx_prior_request*, const double* pi, double d);
+/* Any pointer may be NULL: N[V], hom, het, ll, b_in, pi_next[V], d_next, rows[B][V + 3], flags[B] (uint8). */
+int dmx_engine_get_prior_step(dmx_engine*, double* N, double* hom, double* het, double* ll, int32_t* b_in, double* pi_next, double* d_next,
+                              double* rows, uint8_t* flags);
+/* The EM loop from (pi0, d0): per iteration one step and V + 3 doubles read back; iteration t's LL_t and d_t (the values it was
+ * evaluated at) are recorded; it stops after the iteration whose LL_t - LL_{t-1} < tol * B_in (converged) or after max_iter.  One more
+ * E-step at the final (pi, d) then gives the reported N, hom, het and LL.  Results: dmx_engine_get_prior_fit. */
+int dmx_engine_prior_fit(dmx_engine*, const dmx_prior_request*);
+/* Any pointer may be NULL: pi[V], d, ll (at the final pi, d), n_iter, converged, b_in, N[V], hom, het (at the final pi, d),
+ * ll_trace / d_trace [min(n_iter, trace_cap)]. */
+int dmx_engine_get_prior_fit(dmx_engine*, double* pi, double* d, double* ll, int32_t* n_iter, int32_t* converged, int32_t* b_in, double* N,
+                             double* hom, double* het, double* ll_trace, double* d_trace, int32_t trace_cap);
+/* The records at (pi[V], d).  Results: dmx_engine_get_prior_calls(out[B]). */
+int dmx_engine_prior_call(dmx_engine*, const dmx_prior_request*, const double* pi, double d);
+int dmx_engine_get_prior_calls(dmx_engine*, dmx_prior_call* out);
+int dmx_engine_prior_info(dmx_engine*, dmx_prior_info* out);
+
 #ifdef __cplusplus
 }
 #endif
