@@ -3833,7 +3833,7 @@ __global__ __launch_bounds__(kThreads) void k_doublet_generic(PileupView pv, con
 // SYMU (round 6, k_doublet_a2u below; V = 32 on 256 threads or 16 on 64, default grid): phase 2 over UNORDERED pairs — thread t owns the pairs {j, (j + d) % V} of units u = t
 // and t + TPC (d = 1 + u / V, j = u % V; d = V/2 from j < V/2 only: 496 of 512 slots at V = 32, 120 of 128 at 16) with the four accumulators [j][k][0..1],
 // [k][j][0..1] each: eight per thread, as before.
-template <int TPC, int NK, int MINW, bool GD, bool CHK, int TP, bool SYMU>
+template <int TPC, int NK, int MINW, bool GD, bool CHK, int TP, bool SYMU, int MIR = 0>
 __device__ __forceinline__ void a2_body(PileupView pv, int nrd_width, const float* __restrict__ g,
                                                          const double* __restrict__ gp0, const double* __restrict__ tabs,
                                                          const double* __restrict__ alpha,
@@ -4034,8 +4034,14 @@ __device__ __forceinline__ void a2_body(PileupView pv, int nrd_width, const floa
               s_jk1 += E[l][m];
               s_kj1 += E[m][l];
             }
-          const DmxLog2Req r_jk0 = dmx_log2_request_fast(s_jk0, s_log), r_kj0 = dmx_log2_request_fast(s_kj0, s_log),
-                           r_jk1 = dmx_log2_request_fast(s_jk1, s_log), r_kj1 = dmx_log2_request_fast(s_kj1, s_log);
+          // MIR != 0 (k_doublet_a2u16; 2: its _mirror_fallback form, every mirror whole): s_jk1 and s_kj1 are a mirrored pair (dmx_log.hpp) — three table entries
+          // per unit, [k][j]'s log from [j][k]'s entry, kd and w, settled behind the unit's guard test.  MIR == 0 (k_doublet_a2u<MINW>): four independent logs —
+          // with the mirrored form that kernel spills four more registers at its 128.
+          const DmxLog2Req r_jk0 = dmx_log2_request_fast(s_jk0, s_log), r_kj0 = dmx_log2_request_fast(s_kj0, s_log);
+          DmxLog2Req r_jk1, r_kj1;
+          DmxLog2MirrorReq r_1;
+          if constexpr (MIR != 0) r_1 = dmx_log2_request_mirror_fast(s_jk1, s_kj1, s_log);
+          else { r_jk1 = dmx_log2_request_fast(s_jk1, s_log); r_kj1 = dmx_log2_request_fast(s_kj1, s_log); }
           if (su == 0) {
             const g_t* rb = &gb[1][ti * GS];
             br[0] = rb[0]; br[1] = rb[1]; br[2] = rb[2];
@@ -4049,8 +4055,15 @@ __device__ __forceinline__ void a2_body(PileupView pv, int nrd_width, const floa
           }
           acc[2 * su][0] += dmx_log2_finish_pinned(r_jk0, lk);                 // :683
           acc[2 * su + 1][0] += dmx_log2_finish_pinned(r_kj0, lk);
-          acc[2 * su][1] += dmx_log2_finish_pinned(r_jk1, lk);
-          acc[2 * su + 1][1] += dmx_log2_finish_pinned(r_kj1, lk);
+          if constexpr (MIR != 0) {
+            double y_kj1;
+            acc[2 * su][1] += dmx_log2_finish_mirror_pinned(r_1, lk, &y_kj1);
+            if (dmx_log2_mirror_any_redo<MIR == 2>(r_1.guard)) y_kj1 = dmx_log2_mirror_settle<MIR == 2>(r_1.guard, r_1, y_kj1, s_log, lk);   // never taken in practice
+            acc[2 * su + 1][1] += y_kj1;
+          } else {
+            acc[2 * su][1] += dmx_log2_finish_pinned(r_jk1, lk);
+            acc[2 * su + 1][1] += dmx_log2_finish_pinned(r_kj1, lk);
+          }
           __builtin_amdgcn_sched_barrier(0);                                   // one unit's logs at a time (register budget; without it: no faster)
         }
       }
@@ -4144,7 +4157,16 @@ __global__ __launch_bounds__(kThreads, 3) void k_doublet_a2u16(PileupView pv, in
                                                           const int32_t* __restrict__ sched, int32_t V, int32_t GS,
                                                           double* __restrict__ grid, double* __restrict__ l00,
                                                           uint8_t* __restrict__ flagged, const double* __restrict__ pfin, const double* __restrict__ pseed) {
-  a2_body<64, 4, 1, false, false, 32, true>(pv, nrd_width, g, gp0, tabs, alpha, sched, V, GS, grid, l00, flagged, pfin, pseed);
+  a2_body<64, 4, 1, false, false, 32, true, 1>(pv, nrd_width, g, gp0, tabs, alpha, sched, V, GS, grid, l00, flagged, pfin, pseed);
+}
+// ... with every mirrored log on its slow path (tests only: DMX_EXPERIMENTS=1 DMX_A2U_MIRROR_FALLBACK=1)
+__global__ __launch_bounds__(kThreads, 3) void k_doublet_a2u16_mirror_fallback(PileupView pv, int nrd_width, const float* __restrict__ g,
+                                                          const double* __restrict__ gp0, const double* __restrict__ tabs,
+                                                          const double* __restrict__ alpha,
+                                                          const int32_t* __restrict__ sched, int32_t V, int32_t GS,
+                                                          double* __restrict__ grid, double* __restrict__ l00,
+                                                          uint8_t* __restrict__ flagged, const double* __restrict__ pfin, const double* __restrict__ pseed) {
+  a2_body<64, 4, 1, false, false, 32, true, 2>(pv, nrd_width, g, gp0, tabs, alpha, sched, V, GS, grid, l00, flagged, pfin, pseed);
 }
 
 // k_doublet_a2u for TWO barcodes per workgroup (32 samples, STRICT, default grid, provably safe rows, DENSE pileups: cfg3 — the headline).  The exact products
@@ -4152,7 +4174,7 @@ __global__ __launch_bounds__(kThreads, 3) void k_doublet_a2u16(PileupView pv, in
 // that walk their pairs in lockstep need E once.  Workgroup (x, y) owns the barcodes of schedule slots 2x and 2x + 1 and slab y of the 496 unordered pairs: thread
 // tid owns ONE unit u = tid + 256 y (k_doublet_a2u's mapping: j = u % 32, d = 1 + u / 32, k = (j + d) % 32, d = 16 from j < 16 only) for BOTH barcodes — eight
 // accumulators, as there.  Everything else stays per barcode with the reference's operands in the reference's order: 209 FP64 instructions per pair where
-// k_doublet_a2u's thread spends 218 on its two units of one barcode.
+// k_doublet_a2u's thread spends 218 on its two units of one barcode.  (207 since a barcode's two alpha-0.5 logs share one front end: the mirrored log, dmx_log.hpp.)
 // Per tile of 32 pairs: headers of both barcodes (the first wavefront: lanes 0..31 barcode 0, 32..63 barcode 1; the SNP ids are the pair indices), the 32 rows
 // staged ONCE as binary64, phase 1 on 128 lanes (wavefront = barcode, lane = (pair, alpha); the table / loop test is per wavefront) which leaves the EIGHT values
 // phase 2 reads per (barcode, pair) — alpha 0.5's q1[0..4] | alpha 0's q0[0..2], k_doublet_diag's layout; the eighteen-value layout would not fit four
@@ -4165,7 +4187,9 @@ __global__ __launch_bounds__(kThreads, 3) void k_doublet_a2u16(PileupView pv, in
 // k_doublet_a2u<k_doublet_a2u2_whole_diag_behind> are what dmx_engine_kernel_names and the profiler report.
 struct k_doublet_a2u2 { static constexpr bool diag16 = true; };
 struct k_doublet_a2u2_whole_diag_behind { static constexpr bool diag16 = false; };
-template <bool DIAG16>
+// MFB (k_doublet_a2u<k_doublet_a2u2_mirror_fallback>, tests only): the mirrored logs' guard is compile-time false, every [k][j] alpha-0.5 log takes the slow path
+struct k_doublet_a2u2_mirror_fallback { static constexpr bool diag16 = true, mirror_fallback = true; };
+template <bool DIAG16, bool MFB = false>
 __device__ __forceinline__ void a2u2_body(PileupView pv, int nrd_width, const float* __restrict__ g,
                                                          const double* __restrict__ gp0, const double* __restrict__ tabs,
                                                          const double* __restrict__ alpha, const int32_t* __restrict__ sched,
@@ -4284,6 +4308,8 @@ __device__ __forceinline__ void a2u2_body(PileupView pv, int nrd_width, const fl
     // ---- phase 2: the thread's unit, both barcodes.  E once; per barcode k_doublet_a2u's sums (a2_body, SYMU), logs and adds on its operands in its order.
     // Barcode 1's alpha-0.5 terms T' go to fresh registers, barcode 0's T replace E.  The eight logs run in two batches of four (a barcode each): four table
     // entries requested together, one wait, four second halves; the next pair's rows and q values are requested while logs are evaluated.
+    // A barcode's two alpha-0.5 sums s_jk1 and s_kj1 are a mirrored pair (dmx_log.hpp): three table entries per barcode, [k][j]'s log from [j][k]'s entry, kd and w.
+    // Its value is held until the iteration's one guard test (both barcodes' guard words, wave-uniform, never taken in practice) and added behind it.
     {
       const int tps = __builtin_amdgcn_readfirstlane(tp);
       double Q[2][3], P1[2][5], ar[3], br[3];
@@ -4337,8 +4363,8 @@ __device__ __forceinline__ void a2u2_body(PileupView pv, int nrd_width, const fl
             s_kj1[0] += E[m][l];
           }
         // barcode 0's four table entries travel while barcode 1's alpha-0.5 sums are formed
-        const DmxLog2Req a_jk0 = dmx_log2_request_fast(s_jk0[0], s_log), a_kj0 = dmx_log2_request_fast(s_kj0[0], s_log),
-                         a_jk1 = dmx_log2_request_fast(s_jk1[0], s_log), a_kj1 = dmx_log2_request_fast(s_kj1[0], s_log);
+        const DmxLog2Req a_jk0 = dmx_log2_request_fast(s_jk0[0], s_log), a_kj0 = dmx_log2_request_fast(s_kj0[0], s_log);
+        const DmxLog2MirrorReq a_1 = dmx_log2_request_mirror_fast(s_jk1[0], s_kj1[0], s_log);
         __builtin_amdgcn_sched_barrier(0);                                     // requests first: nothing of the arithmetic below moves above them
         s_jk1[1] = T1[0][0]; s_kj1[1] = T1[0][0];
 #pragma unroll
@@ -4353,22 +4379,28 @@ __device__ __forceinline__ void a2u2_body(PileupView pv, int nrd_width, const fl
         __builtin_amdgcn_s_waitcnt(0xC07F);                                    // lgkmcnt(0): ONE wait for the barcode's four entries
         __builtin_amdgcn_sched_barrier(0);                                     // (the wait has no operands: without this it sinks below the arithmetic)
         // barcode 1's entries, the next pair's q values and rows: every other LDS read of the pair travels while barcode 0's logs are evaluated
-        const DmxLog2Req b_jk0 = dmx_log2_request_fast(s_jk0[1], s_log), b_kj0 = dmx_log2_request_fast(s_kj0[1], s_log),
-                         b_jk1 = dmx_log2_request_fast(s_jk1[1], s_log), b_kj1 = dmx_log2_request_fast(s_kj1[1], s_log);
+        const DmxLog2Req b_jk0 = dmx_log2_request_fast(s_jk0[1], s_log), b_kj0 = dmx_log2_request_fast(s_kj0[1], s_log);
+        const DmxLog2MirrorReq b_1 = dmx_log2_request_mirror_fast(s_jk1[1], s_kj1[1], s_log);
+        const uint32_t mguard = a_1.guard | b_1.guard;
         load_pair(min(ti + 1, tps - 1));                                       // (the tile's last pair requests itself again: nothing reads it)
         __builtin_amdgcn_sched_barrier(0);
         acc[0][0] += dmx_log2_finish_pinned(a_jk0, lk);                        // :683
         acc[0][1] += dmx_log2_finish_pinned(a_kj0, lk);
-        acc[0][2] += dmx_log2_finish_pinned(a_jk1, lk);
-        acc[0][3] += dmx_log2_finish_pinned(a_kj1, lk);
-        asm volatile("" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(acc[0][3]));   // barcode 0's logs stay in front of the second wait
+        double ya_kj1, yb_kj1;
+        acc[0][2] += dmx_log2_finish_mirror_pinned(a_1, lk, &ya_kj1);
+        asm volatile("" : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[0][2]), "+v"(ya_kj1));      // barcode 0's logs stay in front of the second wait
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_sched_barrier(0);
         acc[1][0] += dmx_log2_finish_pinned(b_jk0, lk);
         acc[1][1] += dmx_log2_finish_pinned(b_kj0, lk);
-        acc[1][2] += dmx_log2_finish_pinned(b_jk1, lk);
-        acc[1][3] += dmx_log2_finish_pinned(b_kj1, lk);
+        acc[1][2] += dmx_log2_finish_mirror_pinned(b_1, lk, &yb_kj1);
+        if (dmx_log2_mirror_any_redo<MFB>(mguard)) {                           // out of line: the lanes whose guard failed evaluate their mirrors whole
+          ya_kj1 = dmx_log2_mirror_settle<MFB>(mguard, a_1, ya_kj1, s_log, lk);
+          yb_kj1 = dmx_log2_mirror_settle<MFB>(mguard, b_1, yb_kj1, s_log, lk);
+        }
+        acc[0][3] += ya_kj1;
+        acc[1][3] += yb_kj1;
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -4390,13 +4422,15 @@ __device__ __forceinline__ void a2u2_body(PileupView pv, int nrd_width, const fl
   if (slab0 && tid < 4 && (tid < 2 || two)) l00[(size_t)((tid >> 1) ? cell1 : cell0) * A + (tid & 1)] = acc00;
   if (!ok) flag_cell(flagged, bb ? cell1 : cell0);  // (phase-1 lanes of slab 0 only; a lone barcode's second copy flags the barcode itself)
 }
-template <class FORM>                            // FORM: k_doublet_a2u2 or k_doublet_a2u2_whole_diag_behind (k_doublet_a2u<MINW> above is the one-barcode kernel)
+template <class FORM, class = void> struct a2u2_mirror_fallback_of { static constexpr bool value = false; };
+template <class FORM> struct a2u2_mirror_fallback_of<FORM, std::enable_if_t<FORM::mirror_fallback>> { static constexpr bool value = true; };
+template <class FORM>                            // FORM: k_doublet_a2u2, k_doublet_a2u2_whole_diag_behind or k_doublet_a2u2_mirror_fallback (k_doublet_a2u<MINW> above is the one-barcode kernel)
 __global__ __launch_bounds__(kThreads, 4) void k_doublet_a2u(PileupView pv, int nrd_width, const float* __restrict__ g,
                                                          const double* __restrict__ gp0, const double* __restrict__ tabs,
                                                          const double* __restrict__ alpha, const int32_t* __restrict__ sched,
                                                          double* __restrict__ grid, double* __restrict__ l00,
                                                          uint8_t* __restrict__ flagged, const double* __restrict__ pfin, const double* __restrict__ pseed) {
-  a2u2_body<FORM::diag16>(pv, nrd_width, g, gp0, tabs, alpha, sched, grid, l00, flagged, pfin, pseed);
+  a2u2_body<FORM::diag16, a2u2_mirror_fallback_of<FORM>::value>(pv, nrd_width, g, gp0, tabs, alpha, sched, grid, l00, flagged, pfin, pseed);
 }
 
 // K2, A = 2, FAST mode (dmx_engine_config.mode = DMX_MODE_FAST): k_doublet_a2 with the bilinear factoring of SURVEY H3.  Not the
@@ -9350,7 +9384,10 @@ int launch_doublet(dmx_engine* e) {
     const size_t cbd = (size_t)32 * 18 * 8 + (size_t)32 * GS * 8 + 2 * 34 * 8 + 32 * (4 + 4 + 8);
     const bool two_barcodes = e->pv.pair_snp == nullptr && !e->knob("DMX_A2U_ONE_BARCODE");
     const bool diag16 = two_barcodes && !e->knob("DMX_A2U2_NO_DIAG") && !e->knob("DMX_A2U_DIAG_WAVE");   // the entries [j][j], j = 16..31, in k_doublet_a2u2's idle slots
-    if (diag16)
+    if (diag16 && e->knob("DMX_A2U_MIRROR_FALLBACK"))   // tests only: the two-barcode kernel with every mirrored log on its slow path
+      DMX_LAUNCH(k2_fn, (k_doublet_a2u<k_doublet_a2u2_mirror_fallback>), dim3((unsigned)((B + 1) / 2), 2), block, 0, e->stream, e->pv, e->nrd_width, e->d_g,
+                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
+    else if (diag16)
       DMX_LAUNCH(k2_fn, (k_doublet_a2u<k_doublet_a2u2>), dim3((unsigned)((B + 1) / 2), 2), block, 0, e->stream, e->pv, e->nrd_width, e->d_g,
                          e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
     else if (two_barcodes)
@@ -9383,6 +9420,10 @@ int launch_doublet(dmx_engine* e) {
   }
   else if (V == 16 && pfin_a2_grid && e->geno_safe && !e->knob("DMX_A2_NO_SYMU")) {
     // 16 soft-field samples on the default grid (cfg5): the same — unordered pairs on k_doublet_a2<64,4>'s kernel, the diagonal on 16 lanes per barcode behind it
+    if (e->knob("DMX_A2U_MIRROR_FALLBACK"))            // tests only: every mirrored log on its slow path
+      DMX_LAUNCH(k2_fn, (k_doublet_a2u16_mirror_fallback), dim3((unsigned)((B + 3) / 4), 1), block, cell_bytes * 4, e->stream, e->pv, e->nrd_width, e->d_g,
+                         e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
+    else
     DMX_LAUNCH(k2_fn, (k_doublet_a2u16), dim3((unsigned)((B + 3) / 4), 1), block, cell_bytes * 4, e->stream, e->pv, e->nrd_width, e->d_g,
                        e->d_gp0, e->d_lut, e->d_alpha, e->d_sched, V, GS, e->d_grid, e->d_l00, e->d_flag(), pfin_a2, pseed_a2);
     hipLaunchKernelGGL((k_doublet_diag<5, 16>), dim3((unsigned)((B + 15) / 16)), block, 0, e->stream, e->pv, e->nrd_width, e->d_g, e->d_lut, e->d_sched, e->d_grid, pfin_a2, pseed_a2);
@@ -11591,6 +11632,22 @@ __global__ void k_debug_log(const double* __restrict__ x, double* __restrict__ y
     y[i] = dmx_log_is_special(x[i]) ? log(x[i]) : v;
   }
 }
+// a mirrored pair per lane through the device functions the STRICT unordered-pair kernels call, their wave-uniform guard test included (normal positive arguments)
+__global__ void k_debug_log2_mirror(const double* __restrict__ x, const double* __restrict__ xm, double* __restrict__ y, double* __restrict__ ym, int64_t n,
+                                    const double* __restrict__ tab) {
+  __shared__ double s_log[DMX_LOG2_TABLE_DOUBLES];
+  for (int i = threadIdx.x; i < DMX_LOG2_TABLE_DOUBLES; i += blockDim.x) s_log[i] = tab[i];
+  __syncthreads();
+  const DmxLogPins lk = dmx_log_pins();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const DmxLog2MirrorReq m = dmx_log2_request_mirror_fast(x[i], xm[i], s_log);
+    double vm;
+    const double v = dmx_log2_finish_mirror_pinned(m, lk, &vm);
+    if (dmx_log2_mirror_any_redo<false>(m.guard)) vm = dmx_log2_mirror_settle<false>(m.guard, m, vm, s_log, lk);
+    y[i] = v;
+    ym[i] = vm;
+  }
+}
 }  // namespace
 
 namespace {
@@ -11696,6 +11753,24 @@ extern "C" int dmx_debug_device_log(const double* x, double* y, int64_t n, int32
 extern "C" int dmx_debug_device_log2(const double* x, double* y, int64_t n, int32_t device) { return debug_device_log(2, x, y, n, device); }
 extern "C" int dmx_debug_device_log2_lite(const double* x, double* y, int64_t n, int32_t device) { return debug_device_log(3, x, y, n, device); }
 extern "C" int dmx_debug_device_log2_lite32(const double* x, double* y, int64_t n, int32_t device) { return debug_device_log(4, x, y, n, device); }
+extern "C" int dmx_debug_device_log2_mirror(const double* x, const double* xm, double* y, double* ym, int64_t n, int32_t device) {
+  if (!x || !xm || !y || !ym || n < 0) return set_error(DMX_ERR_ARG, "dmx_debug_device_log2_mirror: bad arguments");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return set_error(DMX_ERR_NOGPU, "dmx_debug_device_log2_mirror: no such HIP device");
+  HIP_TRY(hipSetDevice(device));
+  DevBuf<double> dx, dxm, dy, dym, dt;
+  const size_t bytes = std::max<size_t>(sizeof(double) * (size_t)n, 16);
+  for (DevBuf<double>* d : {&dx, &dxm, &dy, &dym}) if (int rc = d->alloc(bytes)) return rc;
+  if (int rc = dt.alloc(sizeof(double) * DMX_LOG2_TABLE_DOUBLES)) return rc;
+  HIP_TRY(hipMemcpy(dx, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dxm, xm, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dt, dmx_log2_table_host, sizeof(double) * DMX_LOG2_TABLE_DOUBLES, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_debug_log2_mirror, dim3(1024), dim3(256), 0, 0, dx, dxm, dy, dym, n, dt);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(y, dy, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ym, dym, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // (ABI 8) `.pair` rows formatted on the device (csrc/dmx_format.hpp)

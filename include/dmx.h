@@ -827,6 +827,7 @@ int dmx_debug_device_log(const double* x, double* y, int64_t n, int32_t device);
 int dmx_debug_device_log2(const double* x, double* y, int64_t n, int32_t device);   /* dmx_log2: the doublet kernels' log (256 bins, ABI 6) */
 int dmx_debug_device_log2_lite32(const double* x, double* y, int64_t n, int32_t device); /* (ABI 8, appended in round 6) FAST's second phase-2 log: split 32-bin table (conflict-free LDS reads), degree-5 near-minimax tail — 8 FP64 instructions, |error| <= 1.2e-15 absolute (csrc/dmx_log.hpp) */
 int dmx_debug_device_log2_lite(const double* x, double* y, int64_t n, int32_t device);   /* (ABI 7) DMX_MODE_FAST's phase-2 log: dmx_log2's table, series cut after r^4/4 — 6 FP64 instructions, |error| <= 6e-15 absolute, unbiased (csrc/dmx_log.hpp) */
+int dmx_debug_device_log2_mirror(const double* x, const double* xm, double* y, double* ym, int64_t n, int32_t device);   /* (ABI 8, appended) dmx_log2 of the mirrored pairs (x[i], xm[i]) — two sums of the same terms in two orders — through the device functions of the STRICT unordered-pair doublet kernels: the mirror takes the primary's table entry when the high words agree from bit 11 up, its own otherwise (csrc/dmx_log.hpp); y[i], ym[i] = dmx_debug_device_log2's bits for x[i], xm[i].  Normal positive arguments. */
 /* Diagnostics: the device's log() ceiling, measured by a register-resident microkernel (no memory traffic): which = 0 the
  * kernels' dmx_log, which = 1 ocml's log().  bench.py reports both next to the kernels' achieved log rate. */
 int dmx_debug_log_rate(int32_t which, int32_t iters, int32_t device, double* logs_per_second);   /* which: 0 dmx_log, 1 ocml log(), 2 dmx_log2 */
