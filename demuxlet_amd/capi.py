@@ -52,6 +52,7 @@ SYMBOLS = [
     "dmx_engine_doublet_anchored", "dmx_engine_get_anchored", "dmx_engine_anchored_info",
     "dmx_engine_prior_step", "dmx_engine_get_prior_step", "dmx_engine_prior_fit", "dmx_engine_get_prior_fit",
     "dmx_engine_prior_call", "dmx_engine_get_prior_calls", "dmx_engine_prior_info",
+    "dmx_engine_fit", "dmx_engine_get_fit", "dmx_engine_fit_info",
 ]
 DMX_PRIOR_MASKED, DMX_PRIOR_BAD = 1, 2
 
@@ -169,6 +170,16 @@ class AmbientDoubletRequest(C.Structure):  # dmx_ambient_doublet_request
 class AmbientDoubletInfo(C.Structure):   # dmx_ambient_doublet_info
     _fields_ = [("kernel_ms", C.c_double), ("profile_bytes", C.c_int64), ("n_used", C.c_int64), ("n_cells", C.c_int32), ("n_cand", C.c_int32),
                 ("n_alpha", C.c_int32), ("n_grid", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class FitRequest(C.Structure):           # dmx_fit_request
+    _fields_ = [("n_cells", C.c_int32), ("n_snps", C.c_int32), ("hyp_memory", C.c_int32), ("max_reads", C.c_int32), ("hyp", C.c_void_p),
+                ("alpha", C.c_void_p), ("rho", C.c_void_p), ("ambient", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class FitInfo(C.Structure):              # dmx_fit_info
+    _fields_ = [("kernel_ms", C.c_double), ("bytes", C.c_int64), ("n_trunc", C.c_int64), ("n_zero", C.c_int64), ("n_cells", C.c_int32),
+                ("n_used", C.c_int32), ("n_singlet", C.c_int32), ("n_doublet", C.c_int32), ("max_reads", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class TripletRequest(C.Structure):     # dmx_triplet_request
@@ -405,6 +416,7 @@ def load() -> C.CDLL:
         "dmx_engine_prior_step": [vp, vp, vp, dbl], "dmx_engine_get_prior_step": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "dmx_engine_prior_fit": [vp, vp], "dmx_engine_get_prior_fit": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32],
         "dmx_engine_prior_call": [vp, vp, vp, dbl], "dmx_engine_get_prior_calls": [vp, vp], "dmx_engine_prior_info": [vp, vp],
+        "dmx_engine_fit": [vp, vp], "dmx_engine_get_fit": [vp, vp, vp, vp, vp, vp, vp, vp], "dmx_engine_fit_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -3448,6 +3448,193 @@ __global__ __launch_bounds__(64 * kAmbDblWaves) void k_ambient_dbl(PileupView pv
   }
 }
 
+// ---- goodness of fit (dmx_engine_fit) -----------------------------------------------------------------------------
+// For a barcode b with the hypothesis (v1, v2, alpha, rho): over b's pairs, the log-likelihood c0 = log L(x) of the first m = min(n, M)
+// stored reads' allele pattern x, and the mean and variance that log L(y) has when y is drawn from Pr(y) = L(y) / sum L(y') over the 2^m
+// patterns (include/dmx.h states the operations).  k_ambient's skeleton — the log table and the phred tables in LDS, 64 pair headers per
+// trip, read offsets by the DPP scan — but lane = pair: one wavefront per used barcode, lane l takes pairs l, l + 64, ... of the barcode
+// in ascending order and keeps its own serial sums; at the end the 64 lanes' sums are added serially in lane order by lane 0 (no
+// floating-point atomics, nothing from another barcode).  A lane holds mat / err3 of its m reads and p_c / q_c / W_c of the NC = 3
+// (singlet) or 9 (doublet) components in registers, and, where NC * MM <= 36, t_r(c, 0 / 1) as well (KEEP); the doublet kernels for
+// M > 4 form t_r from mat, err3, p_c and q_c per factor (three FP64 operations, not one; same operations, same bits).  Every array is
+// indexed by unrolled constants only, the pattern's bits select by v_cndmask: no scratch.  The pattern loop runs to 2^mmax, mmax the
+// tile's largest m (wave-uniform); lanes of smaller m sit out the rest (DESIGN.md section 26 says what that costs).
+constexpr int kFitWaves = 4;                     // wavefronts (barcodes) per workgroup; they share the log and phred tables
+constexpr int kFitMaxReads = 8;
+
+template <int NC, int MM, bool KEEP>
+__device__ __forceinline__ double fit_pattern(uint32_t y, uint32_t m, int mmax, const double (&t0)[KEEP ? MM * NC : 1],
+                                              const double (&t1)[KEEP ? MM * NC : 1], const double (&mat)[MM], const double (&e3)[MM],
+                                              const double (&pp)[NC], const double (&qq)[NC], const double (&W)[NC]) {
+  double L = 0.0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    double F = 1.0;
+#pragma unroll
+    for (int r = 0; r < MM; ++r) {
+      if (r < mmax) {                              // wave-uniform
+        const bool alt = (y >> r) & 1u;
+        double t;
+        if constexpr (KEEP) {
+          t = alt ? t1[r * NC + c] : t0[r * NC + c];   // (two arrays: one array indexed by 2 i + alt would be addressed, and live in scratch)
+        } else {
+          const double pR = alt ? e3[r] : mat[r], pA = alt ? mat[r] : e3[r];
+          t = pR * qq[c] + pA * pp[c];
+        }
+        F = r == 0 ? t : ((uint32_t)r < m ? F * t : F);
+      }
+    }
+    const double t = W[c] * F;
+    L = c == 0 ? t : L + t;
+  }
+  return L;
+}
+
+template <bool DBL, int MM>
+__global__ __launch_bounds__(64 * kFitWaves) void k_fit(PileupView pv, int nrd_width, const double* __restrict__ tabs, const float* __restrict__ g,
+                                                      int32_t V, const int32_t* __restrict__ idx, int32_t n_idx, const int32_t* __restrict__ hyp,
+                                                      const double* __restrict__ alpha, const double* __restrict__ rho,
+                                                      const double* __restrict__ amb, int32_t M, int32_t B, double* __restrict__ out,
+                                                      int32_t* __restrict__ cnt) {
+  static_assert(MM == 1 || MM == 2 || MM == 4 || MM == 8, "reads per pair the instantiation holds");
+  constexpr int NC = DBL ? 9 : 3;
+  constexpr bool KEEP = NC * MM <= 36;
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_me[128][2];                // by base quality: {mat, err / 3}
+  __shared__ double s_red[kFitWaves][64][3];
+  __shared__ int32_t s_cnt[kFitWaves][64][4];
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += 64 * kFitWaves) s_log[i] = tabs[kLut + i];
+  for (int i = threadIdx.x; i < 128; i += 64 * kFitWaves) { s_me[i][0] = tabs[i]; s_me[i][1] = tabs[128 + i]; }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int32_t unit = (int32_t)blockIdx.x * kFitWaves + wave;
+  if (unit >= n_idx) return;
+  const int32_t cell = __builtin_amdgcn_readfirstlane(idx[unit]);
+  const int32_t v1 = __builtin_amdgcn_readfirstlane(hyp[2 * (size_t)cell]);
+  const int32_t v2 = DBL ? __builtin_amdgcn_readfirstlane(hyp[2 * (size_t)cell + 1]) : -1;
+  const double rh = rho[cell], om = 1.0 - rh;
+  double cm[NC];
+  if (DBL) {
+    const double al = alpha[cell];
+#pragma unroll
+    for (int l = 0; l < 3; ++l)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) cm[l * 3 + k] = 0.5 * l + (k - l) * 0.5 * al;
+  } else {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) cm[c] = 0.5 * c;
+  }
+  const DmxLogPins lk = dmx_log_pins();
+  double obs = 0.0, mean = 0.0, var = 0.0;
+  int32_t ns = 0, nr = 0, nt = 0, nz = 0;
+  const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+  int64_t rd_base = pv.cell_read_off[cell];
+  for (int64_t p0 = p_beg; p0 < p_end; p0 += 64) {
+    const int64_t p = p0 + lane;
+    const bool in = p < p_end;
+    const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+    const uint32_t incl = seg_scan_incl<64>(n);
+    const int64_t off = rd_base + (int64_t)(incl - n);
+    rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    uint32_t m = 0, x = 0;
+    double W[NC], pp[NC], qq[NC], mat[MM], e3[MM];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { W[c] = 0.0; pp[c] = 0.0; qq[c] = 0.0; }
+#pragma unroll
+    for (int r = 0; r < MM; ++r) { mat[r] = 0.0; e3[r] = 0.0; }
+    if (n > 0) {
+      const int32_t snp = pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg);
+      const float* gs = g + (size_t)snp * V * 3;
+      const float* r1 = gs + (size_t)v1 * 3;
+      const float x0 = r1[0], x1 = r1[1], x2 = r1[2];
+      bool ok = x0 != 0.f || x1 != 0.f || x2 != 0.f;
+      if (DBL) {
+        const float* r2 = gs + (size_t)v2 * 3;
+        const float y0 = r2[0], y1 = r2[1], y2 = r2[2];
+        ok = ok && (y0 != 0.f || y1 != 0.f || y2 != 0.f);
+        const double g1[3] = {(double)x0, (double)x1, (double)x2}, g2[3] = {(double)y0, (double)y1, (double)y2};
+#pragma unroll
+        for (int c = 0; c < NC; ++c) W[c] = g1[c / 3] * g2[c % 3];    // float32 x float32: exact in float64
+      } else {
+        W[0] = x0; W[1] = x1; W[2] = x2;
+      }
+      if (ok) {
+        m = min(n, (uint32_t)M);
+        const double ra = rh * amb[snp];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) { pp[c] = om * cm[c] + ra; qq[c] = 1.0 - pp[c]; }
+        const uint32_t w0 = load_rd4(pv, off, m);
+        const uint32_t w1 = (MM > 4 && m > 4) ? load_rd4(pv, off + 4, m - 4) : 0u;
+#pragma unroll
+        for (int r = 0; r < MM; ++r) {
+          const uint32_t byte = ((r < 4 ? w0 : w1) >> (8 * (r & 3))) & 0xFF;
+          mat[r] = s_me[byte & 127][0]; e3[r] = s_me[byte & 127][1];
+          if ((uint32_t)r < m) x |= (byte >> 7) << r;
+        }
+      }
+    }
+    int mmax = 0;
+#pragma unroll
+    for (int r = 0; r < MM; ++r)
+      if (__ballot(m > (uint32_t)r)) mmax = r + 1;
+    if (mmax == 0) continue;
+    double t0[KEEP ? MM * NC : 1], t1[KEEP ? MM * NC : 1];
+    if constexpr (KEEP) {
+#pragma unroll
+      for (int r = 0; r < MM; ++r)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          t0[r * NC + c] = mat[r] * qq[c] + e3[r] * pp[c];
+          t1[r * NC + c] = e3[r] * qq[c] + mat[r] * pp[c];
+        }
+    } else {
+      t0[0] = 0.0; t1[0] = 0.0;
+    }
+    bool live = m > 0;
+    double c0 = 0.0;
+    if (live) {
+      const double Lx = fit_pattern<NC, MM, KEEP>(x, m, mmax, t0, t1, mat, e3, pp, qq, W);
+      if (Lx == 0.0) { live = false; nz += 1; }
+      else c0 = dmx_log_is_special(Lx) ? log(Lx) : dmx_log_fast_pinned(Lx, s_log, lk);
+    }
+    double S0 = 0.0, S1 = 0.0, S2 = 0.0;
+    const uint32_t npat = live ? 1u << m : 0u, nmax = 1u << mmax;
+    for (uint32_t y = 0; y < nmax; ++y) {
+      if (y < npat) {
+        const double L = fit_pattern<NC, MM, KEEP>(y, m, mmax, t0, t1, mat, e3, pp, qq, W);
+        if (L != 0.0) {
+          const double lg = dmx_log_is_special(L) ? log(L) : dmx_log_fast_pinned(L, s_log, lk);
+          const double u = lg - c0;
+          S0 += L; S1 += L * u; S2 += L * (u * u);
+        }
+      }
+    }
+    if (live) {
+      if (S0 == 0.0 || !(fabs(S0) < INFINITY)) {
+        nz += 1;
+      } else {
+        const double e1 = S1 / S0, d = S2 / S0 - e1 * e1;
+        obs += c0; mean += c0 + e1; var += d > 0.0 ? d : 0.0;
+        ns += 1; nr += (int32_t)m; nt += n > (uint32_t)M;
+      }
+    }
+  }
+  s_red[wave][lane][0] = obs; s_red[wave][lane][1] = mean; s_red[wave][lane][2] = var;
+  s_cnt[wave][lane][0] = ns; s_cnt[wave][lane][1] = nr; s_cnt[wave][lane][2] = nt; s_cnt[wave][lane][3] = nz;
+  DMX_WAVE_LDS_ORDER();
+  if (lane == 0) {
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    int32_t k0 = 0, k1 = 0, k2 = 0, k3 = 0;
+    for (int l = 0; l < 64; ++l) {
+      a0 += s_red[wave][l][0]; a1 += s_red[wave][l][1]; a2 += s_red[wave][l][2];
+      k0 += s_cnt[wave][l][0]; k1 += s_cnt[wave][l][1]; k2 += s_cnt[wave][l][2]; k3 += s_cnt[wave][l][3];
+    }
+    out[cell] = a0; out[(size_t)B + cell] = a1; out[2 * (size_t)B + cell] = a2;
+    cnt[cell] = k0; cnt[(size_t)B + cell] = k1; cnt[2 * (size_t)B + cell] = k2; cnt[3 * (size_t)B + cell] = k3;
+  }
+}
+
 // ---- triplet profile (dmx_engine_triplet) -------------------------------------------------------------------------
 // For a barcode b, a base pair (v1, v2), a share triple (w1, w2, w3) and EVERY sample c of the pool as the third donor:
 //   p_lmn = 0.5 (w1 l + w2 m + w3 n),   f_lmn = product over the pair's stored reads of pR (1 - p_lmn) + pA p_lmn,
@@ -8304,6 +8491,13 @@ struct dmx_engine {
   std::vector<double> pr_step_out;               // N[V] | hom | het | LL | pi'[V] | d' | B_in of the last step
   std::vector<double> pr_fit_out, pr_fit_pi, pr_fit_ll, pr_fit_d;   // ... of the fit's final evaluation; the final pi; the traces
   double pr_fit_dd = 0.0; int32_t pr_fit_iter = 0, pr_fit_conv = 0;
+  // goodness of fit (dmx_engine_fit): its own copies of the hypotheses, alpha[B] | rho[B] and a[S], the used barcodes' ids (singlets,
+  // then doublets), and the results obs | mean | var [3][B] and n_snp | n_read | n_trunc | n_zero [4][B]
+  DevBuf<int32_t> d_fhyp, d_fidx, d_fcnt;
+  DevBuf<double> d_fpar, d_famb, d_fout;
+  int32_t fit_B = 0; bool have_fit = false;
+  EventPair fev;
+  dmx_fit_info fit_info{};
 };
 
 namespace {
@@ -8834,6 +9028,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   e->have_sing = e->have_grid = false;
   e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_adbl = false; e->have_cdbl = false;
   e->have_trip = false;
+  e->have_fit = false;
   e->have_comp = false;
   e->have_census = false; e->have_cen_info = false; e->have_fis_info = false;
   e->have_pileup = true;
@@ -12680,5 +12875,150 @@ extern "C" int dmx_engine_prior_info(dmx_engine* e, dmx_prior_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_prior_info: null argument");
   if (!e->have_pr_info) return set_error(DMX_ERR_STATE, "dmx_engine_prior_info: no prior pass yet (dmx_engine_prior_step, _fit or _call first)");
   *out = e->pr_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Goodness of fit: the arguments are checked on the host (hyp, alpha, rho and a are small), the used barcodes'
+// ids are listed singlets first, then one launch of k_fit<false, MM> over the singlets and one of k_fit<true, MM> over the doublets, MM
+// the smallest of 1 / 2 / 4 / 8 that holds max_reads.  Every buffer is the call's own.
+namespace {
+
+template <bool DBL>
+void launch_fit(dmx_engine* e, int32_t MMsel, const int32_t* idx, int32_t n_idx, int32_t M) {
+  if (n_idx <= 0) return;
+  const dim3 grid((unsigned)((n_idx + kFitWaves - 1) / kFitWaves)), block(64 * kFitWaves);
+  const double* par = e->d_fpar;
+  const int32_t B = e->pv.B;
+#define DMX_FIT_LAUNCH(MMV)                                                                                                              \
+  hipLaunchKernelGGL((k_fit<DBL, MMV>), grid, block, 0, e->stream, e->pv, e->nrd_width, (const double*)e->d_lut, e->d_g, e->V, idx, n_idx, \
+                     (const int32_t*)e->d_fhyp, par, par + B, (const double*)e->d_famb, M, B, e->d_fout.get(), e->d_fcnt.get())
+  if (MMsel == 1) DMX_FIT_LAUNCH(1);
+  else if (MMsel == 2) DMX_FIT_LAUNCH(2);
+  else if (MMsel == 4) DMX_FIT_LAUNCH(4);
+  else DMX_FIT_LAUNCH(8);
+#undef DMX_FIT_LAUNCH
+}
+
+}  // namespace
+
+extern "C" int dmx_engine_fit(dmx_engine* e, const dmx_fit_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_fit: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_fit: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_fit: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S, M = rq->max_reads;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_fit: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_fit: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_fit: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (M < 1 || M > kFitMaxReads) return set_error(DMX_ERR_ARG, "dmx_engine_fit: max_reads %d is not in [1, %d]", M, kFitMaxReads);
+  if (B > 0 && (!rq->hyp || !rq->alpha)) return set_error(DMX_ERR_ARG, "dmx_engine_fit: missing hyp / alpha");
+  if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_fit: rho is given without ambient");
+  if (rq->hyp_memory != DMX_MEM_HOST && rq->hyp_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_fit: hyp_memory %d", rq->hyp_memory);
+  for (int32_t b = 0; b < B; ++b) {
+    const double al = rq->alpha[b], rh = rq->rho ? rq->rho[b] : 0.0;
+    if (!(al >= 0.0 && al <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_fit: alpha[%d] = %g is not in [0, 1]", b, al);
+    if (!(rh >= 0.0 && rh <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_fit: rho[%d] = %g is not in [0, 1]", b, rh);
+  }
+  if (rq->ambient)
+    for (int32_t i = 0; i < S; ++i)
+      if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_fit: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  HIP_TRY(hipSetDevice(e->device));
+  std::vector<int32_t> h((size_t)B * 2);
+  if (B > 0) {
+    if (rq->hyp_memory == DMX_MEM_DEVICE) {
+      HIP_TRY(hipMemcpyAsync(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+      std::memcpy(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B);
+    }
+  }
+  std::vector<int32_t> idx;
+  idx.reserve((size_t)B);
+  int32_t n_sng = 0;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int32_t b = 0; b < B; ++b) {
+      const int32_t v1 = h[2 * (size_t)b], v2 = h[2 * (size_t)b + 1];
+      if (pass == 0) {
+        const bool ok = v1 == -1 || (v1 >= 0 && v1 < V && (v2 == -1 || (v2 >= 0 && v2 < V && v2 != v1)));
+        if (!ok)
+          return set_error(DMX_ERR_ARG, "dmx_engine_fit: hyp[%d] = (%d, %d) is not -1, a sample in [0, %d) or two different samples", b, v1, v2, V);
+        if (v1 >= 0 && v2 < 0) { idx.push_back(b); ++n_sng; }
+      } else if (v1 >= 0 && v2 >= 0) {
+        idx.push_back(b);
+      }
+    }
+  const int32_t n_used = (int32_t)idx.size(), n_dbl = n_used - n_sng;
+  const size_t out_b = sizeof(double) * 3 * (size_t)B, cnt_b = sizeof(int32_t) * 4 * (size_t)B, par_b = sizeof(double) * 2 * (size_t)B;
+  const size_t need = out_b + cnt_b + par_b + sizeof(int32_t) * 3 * (size_t)B + sizeof(double) * (size_t)S;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (out_b > e->d_fout.cap() && need + need / 16 > free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_fit: the results of %d barcodes need %zu bytes, %zu are free", B, need, free_b);
+  if (int rc = e->d_fout.ensure(out_b)) return rc;
+  if (int rc = e->d_fcnt.ensure(cnt_b)) return rc;
+  if (int rc = e->d_fpar.ensure(par_b)) return rc;
+  if (int rc = e->d_fhyp.ensure(sizeof(int32_t) * 2 * (size_t)B)) return rc;
+  if (int rc = e->d_fidx.ensure(sizeof(int32_t) * (size_t)B)) return rc;
+  if (int rc = e->d_famb.ensure(sizeof(double) * (size_t)S)) return rc;
+  e->have_fit = false;
+  std::vector<double> par((size_t)B * 2, 0.0);
+  for (int32_t b = 0; b < B; ++b) {
+    par[(size_t)b] = rq->alpha[b];
+    if (rq->rho) par[(size_t)B + b] = rq->rho[b];
+  }
+  if (B > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_fhyp, h.data(), sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_fpar, par.data(), par_b, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_fout, 0, out_b, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_fcnt, 0, cnt_b, e->stream));
+  }
+  if (n_used > 0) HIP_TRY(hipMemcpyAsync(e->d_fidx, idx.data(), sizeof(int32_t) * (size_t)n_used, hipMemcpyHostToDevice, e->stream));
+  if (S > 0) {
+    if (rq->ambient) HIP_TRY(hipMemcpyAsync(e->d_famb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
+    else HIP_TRY(hipMemsetAsync(e->d_famb, 0, sizeof(double) * (size_t)S, e->stream));
+  }
+  const int32_t MMsel = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8;
+  if (int rc = e->fev.record_start(e->stream)) return rc;
+  launch_fit<false>(e, MMsel, e->d_fidx, n_sng, M);
+  HIP_TRY(hipGetLastError());
+  launch_fit<true>(e, MMsel, e->d_fidx + n_sng, n_dbl, M);
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->fev.record_stop(e->stream)) return rc;
+  std::vector<int32_t> tz((size_t)B * 2);
+  if (B > 0) HIP_TRY(hipMemcpyAsync(tz.data(), e->d_fcnt + 2 * (size_t)B, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return
+  float ms = 0.f;
+  if (int rc = e->fev.elapsed_ms(&ms)) return rc;
+  dmx_fit_info& inf = e->fit_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.kernel_ms = ms; inf.bytes = (int64_t)need; inf.n_cells = B; inf.n_used = n_used; inf.n_singlet = n_sng; inf.n_doublet = n_dbl;
+  inf.max_reads = M;
+  for (int32_t b = 0; b < B; ++b) { inf.n_trunc += tz[(size_t)b]; inf.n_zero += tz[(size_t)B + b]; }
+  e->fit_B = B; e->have_fit = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_fit(dmx_engine* e, double* obs, double* mean, double* var, int32_t* n_snp, int32_t* n_read, int32_t* n_trunc,
+                                  int32_t* n_zero) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_fit: null engine");
+  if (!e->have_fit) return set_error(DMX_ERR_STATE, "dmx_engine_get_fit: no result on the staged pileup (dmx_engine_fit first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t B = (size_t)e->fit_B;
+  if (!B) return DMX_OK;
+  double* const dp[3] = {obs, mean, var};
+  int32_t* const ip[4] = {n_snp, n_read, n_trunc, n_zero};
+  for (int k = 0; k < 3; ++k)
+    if (dp[k]) HIP_TRY(hipMemcpy(dp[k], e->d_fout + k * B, sizeof(double) * B, hipMemcpyDeviceToHost));
+  for (int k = 0; k < 4; ++k)
+    if (ip[k]) HIP_TRY(hipMemcpy(ip[k], e->d_fcnt + k * B, sizeof(int32_t) * B, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_fit_info(dmx_engine* e, dmx_fit_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_fit_info: null argument");
+  if (!e->have_fit) return set_error(DMX_ERR_STATE, "dmx_engine_fit_info: no result on the staged pileup (dmx_engine_fit first)");
+  *out = e->fit_info;
   return DMX_OK;
 }

@@ -668,6 +668,47 @@ class Engine:
         check(self._L.dmx_engine_ambient_doublet_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.AmbientDoubletInfo._fields_ if n != "reserved"}
 
+    def fit_profile(self, hyp, alpha, rho=None, ambient=None, max_reads: int = 4) -> dict:
+        """dmx_engine_fit over the staged pileup: the goodness of fit of one hypothesis per barcode.  hyp[b] = (v1, v2): v1 = -1 = not used,
+        v2 = -1 = a singlet of v1, otherwise a doublet with a share alpha[b] of v2's reads; rho[b] (None = 0) of the reads come from a soup
+        of ALT frequency ambient[i].  `hyp` is a host array [B][2], or a device pointer (int) to B x 2 int32.  Returns a dict of obs / mean /
+        var (f64 [B]: the log-likelihood of each pair's first max_reads reads, and its mean and variance under the hypothesis) and n_snp /
+        n_read / n_trunc / n_zero (i32 [B])."""
+        al = np.ascontiguousarray(alpha, dtype=np.float64)
+        if al.shape != (self.B,):
+            raise ValueError(f"alpha must be [{self.B}]")
+        rh = None
+        if rho is not None:
+            rh = np.ascontiguousarray(rho, dtype=np.float64)
+            if rh.shape != (self.B,):
+                raise ValueError(f"rho must be [{self.B}]")
+        amb = None
+        if ambient is not None:
+            amb = np.ascontiguousarray(ambient, dtype=np.float64)
+            if amb.ndim != 1:
+                raise ValueError("ambient must be 1-D")
+        if isinstance(hyp, int):
+            h, mem, ptr = None, capi.DMX_MEM_DEVICE, hyp
+        else:
+            h = np.ascontiguousarray(hyp, dtype=np.int32)
+            if h.shape != (self.B, 2):
+                raise ValueError(f"hyp must be [{self.B}][2]")
+            mem, ptr = capi.DMX_MEM_HOST, (h.ctypes.data if h.size else None)
+        n_snps = len(amb) if amb is not None else self.S
+        rq = capi.FitRequest(self.B, n_snps, mem, int(max_reads), ptr, al.ctypes.data if al.size else None,
+                             rh.ctypes.data if rh is not None and rh.size else None, amb.ctypes.data if amb is not None and amb.size else None)
+        check(self._L.dmx_engine_fit(self._h, C.byref(rq)))
+        out = {k: np.zeros(self.B) for k in ("obs", "mean", "var")}
+        out.update({k: np.zeros(self.B, dtype=np.int32) for k in ("n_snp", "n_read", "n_trunc", "n_zero")})
+        check(self._L.dmx_engine_get_fit(self._h, *(out[k].ctypes.data for k in ("obs", "mean", "var", "n_snp", "n_read", "n_trunc", "n_zero"))))
+        return out
+
+    def fit_info(self) -> dict:
+        """HIP-event time (ms) of the last fit_profile, its device bytes and its totals (dmx_engine_fit_info)."""
+        r = capi.FitInfo()
+        check(self._L.dmx_engine_fit_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.FitInfo._fields_ if n != "reserved"}
+
     def triplet_profile(self, base, shares, n_base=None):
         """dmx_engine_triplet over the staged pileup: LL[b][s][t][c] of barcode b as a triplet of the base pair base[b][s] = (v1, v2)
         (v1 = -1: slot not used) and the third donor c, with the read shares shares[t] = (w1, w2, w3) of v1, v2 and c.  `base` is a host

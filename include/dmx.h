@@ -40,7 +40,8 @@ extern "C" {
                                _cluster_hard / _get_cluster_hard / _cluster_hard_device_ptr / _cluster_merge_columns / _cluster_k_info (choosing the number
                                of clusters); dmx_engine_compose / _composed_pileup / _get_composed / _compose_info (barcodes composed on
                                the device from other barcodes' reads); dmx_engine_doublet_anchored / _get_anchored / _anchored_info
-                               (the doublet search over each barcode's best singlets as anchors: wide panels without the V x V grid).
+                               (the doublet search over each barcode's best singlets as anchors: wide panels without the V x V grid);
+                               dmx_engine_fit / _get_fit / _fit_info (goodness of fit of each barcode's hypothesis).
                                Additions only. */
 
 typedef enum {
@@ -1176,6 +1177,65 @@ int dmx_engine_get_prior_fit(dmx_engine*, double* pi, double* d, double* ll, int
 int dmx_engine_prior_call(dmx_engine*, const dmx_prior_request*, const double* pi, double d);
 int dmx_engine_get_prior_calls(dmx_engine*, dmx_prior_call* out);
 int dmx_engine_prior_info(dmx_engine*, dmx_prior_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Goodness of fit of a call (no counterpart in the reference; later, still ABI 8).  Every other pass ranks
+ * hypotheses against each other; this one asks whether a barcode's hypothesis explains its reads at all.  Barcode b carries ONE
+ * hypothesis hyp[b] = (v1, v2) with alpha[b] and rho[b]: v1 = -1 = not used; v2 = -1 = a singlet of v1; otherwise a doublet of two
+ * different samples, alpha the share of v2's reads; rho the fraction of reads from a soup of ALT frequencies a[n_snps].  Components c
+ * and weights W_c are the existing profiles':
+ *   singlet   c = g = 0, 1, 2:       W_c = gp[i][v1][g],                p_c = (1 - rho) g / 2 + rho a_i             (dmx_engine_ambient)
+ *   doublet   c = (l, m), l-major:   W_c = gp[i][v1][l] gp[i][v2][m],   p_c = (1 - rho) (0.5 l + (m - l) 0.5 alpha) + rho a_i
+ *             (float32 widened to float64: the product is exact)                                           (dmx_engine_ambient_doublet)
+ * A pair (b, i) with n stored reads enters with its FIRST m = min(n, M) reads in stored order, M = max_reads in [1, 8]; stored order
+ * does not depend on the alleles, so the sub-likelihood has a known law under the hypothesis.  For an allele pattern y in {0, 1}^m
+ * (an integer; bit r = the allele of read r), with mat / err the phred tables at read r's base quality:
+ *   t_r(c, 0) = mat (1 - p_c) + (err / 3) p_c,   t_r(c, 1) = (err / 3) (1 - p_c) + mat p_c     (two products, one sum; 1 - p_c rounded once)
+ *   F_c(y)    = t_0(c, y_0) t_1(c, y_1) ... in stored order;   L(y) = sum_c W_c F_c(y) in component order.
+ * Conditional on every read being stored, Pr(y) = L(y) / sum_y' L(y') (the per-read normaliser mat + err / 3 does not depend on c).
+ * With x the observed pattern, c0 = log L(x) and u(y) = log L(y) - c0 (the log is dmx_log), over y ascending
+ *   S0 = sum L(y),   S1 = sum L(y) u(y),   S2 = sum L(y) (u(y) u(y))       (a pattern with L(y) = 0 adds nothing to any of them),
+ * and the pair adds   obs += c0,   mean += c0 + S1 / S0,   var += max(0, S2 / S0 - (S1 / S0)^2).
+ * A pair with no stored read, or where a hypothesised sample's gp row is all zero, contributes nothing and is not counted.  A pair
+ * with L(x) = 0, or whose S0 is 0 or not finite, contributes nothing either and is counted in n_zero[b].  n_snp[b] / n_read[b] count the
+ * pairs / reads (m per pair) that contributed, n_trunc[b] those of them with n > M.  No rescaling is needed: the smallest non-zero
+ * term is eight factors >= err(127) / 3 times a product of two float32 subnormals, still a normal float64.  Unused barcodes get zero
+ * rows.  Without truncation obs[b] is dmx_engine_ambient's LL at (v1, rho), or dmx_engine_ambient_doublet's at (v1, v2, alpha, rho), up
+ * to rounding.
+ * Summation plan: a barcode's pairs in stored order are dealt to 64 serial sums (pair k of the barcode goes to sum k mod 64, in
+ * ascending k); the 64 sums are then added serially, sum 0 first.  No floating-point atomics: b's seven outputs depend on b's own pairs
+ * and reads, its hypothesis, M, and the gp rows and a entries it touches only — not on B, the other barcodes, what ran before, the
+ * stream, or where hyp lives.  The call runs on the engine's stream, synchronises it before returning (host inputs may be freed then),
+ * uses buffers of its own and leaves every other result of the engine as it was.
+ * DMX_ERR_ARG: max_reads outside [1, 8]; an alpha or rho outside [0, 1] or not finite; an a_i outside [0, 1]; a hypothesis that is none
+ * of unused (v1 = -1), a sample in [0, V) with v2 = -1, or two different samples in [0, V); rho without ambient; n_cells / n_snps that
+ * do not match the staged pileup / the genotype matrix.  DMX_ERR_STATE: no pileup or no genotypes yet, or a query before a call.
+ * DMX_ERR_NOMEM: the outputs do not fit the free device memory (earlier results stay readable). */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t hyp_memory;          /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `hyp` lives */
+  int32_t max_reads;           /* M, 1..8 */
+  const int32_t* hyp;          /* [n_cells][2] */
+  const double* alpha;         /* [n_cells] float64 in [0, 1], HOST (read for every barcode; used by doublets) */
+  const double* rho;           /* [n_cells] float64 in [0, 1], HOST; NULL = 0 */
+  const double* ambient;       /* [n_snps] float64 in [0, 1], HOST; NULL only when rho is NULL */
+  int32_t reserved[4];         /* 0 */
+} dmx_fit_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the last call's k_fit launches (singlets, then doublets) */
+  int64_t bytes;               /* device bytes of the call's buffers */
+  int64_t n_trunc, n_zero;     /* totals over the barcodes */
+  int32_t n_cells, n_used, n_singlet, n_doublet;
+  int32_t max_reads;
+  int32_t reserved[3];
+} dmx_fit_info;
+int dmx_engine_fit(dmx_engine*, const dmx_fit_request*);
+/* Device->host copies of the last call's results (any pointer may be NULL): obs / mean / var [B] f64, n_snp / n_read / n_trunc /
+ * n_zero [B] i32. */
+int dmx_engine_get_fit(dmx_engine*, double* obs, double* mean, double* var, int32_t* n_snp, int32_t* n_read, int32_t* n_trunc,
+                       int32_t* n_zero);
+int dmx_engine_fit_info(dmx_engine*, dmx_fit_info* out);
 
 #ifdef __cplusplus
 }
