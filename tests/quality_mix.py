@@ -109,7 +109,23 @@ FAMILIES = [
     ("k2_anf", "GP", 16, A3, "fast", {}, "k_singlet_own<", "k_doublet_anf<", False, 3),
     ("k2_a2f", "GP", 16, (0.0, 0.25), "fast", {"DMX_NO_ANF": "1"}, "k_singlet_own<", "k_doublet_a2f<", False, 3),
     ("k2_generic", "GP", 8, A2, "strict", {"DMX_K2_GENERIC": "1"}, "k_singlet<", "k_doublet_generic<", False, 3),
+    # K2 on DENSE pileups of 32 / 16 soft-field samples (family_problem: S = 131 = four tiles and three pairs, B = 11 = five two-barcode workgroups
+    # and a lone last barcode): the two-barcode kernel (the headline) and its forms, the one-barcode kernel on the same layout, k_doublet_a2u16.
+    # The K2 names are whole names (kernel_named below tells k_doublet_a2u16 from its fall-back form, which the prefix alone does not).
+    ("k2_a2u2", "GP", 32, A2, "strict", {}, "k_singlet_own<", "k_doublet_a2u<k_doublet_a2u2>", True, 3),
+    ("k2_a2u2_diag_behind", "GP", 32, A2, "strict", {"DMX_A2U2_NO_DIAG": "1"}, "k_singlet_own<", "k_doublet_a2u<k_doublet_a2u2_whole_diag_behind>", True, 3),
+    ("k2_a2u2_mirror_fallback", "GP", 32, A2, "strict", {"DMX_A2U_MIRROR_FALLBACK": "1"}, "k_singlet_own<", "k_doublet_a2u<k_doublet_a2u2_mirror_fallback>",
+     True, 3),
+    ("k2_a2u_dense_one_barcode", "GP", 32, A2, "strict", {"DMX_A2U_ONE_BARCODE": "1"}, "k_singlet_own<", "k_doublet_a2u<4>", True, 3),
+    ("k2_a2u16_dense", "GP", 16, A2, "strict", {}, "k_singlet_own<", "k_doublet_a2u16", True, 3),
+    ("k2_a2u16_mirror_fallback", "GP", 16, A2, "strict", {"DMX_A2U_MIRROR_FALLBACK": "1"}, "k_singlet_own<", "k_doublet_a2u16_mirror_fallback", True, 3),
 ]
+
+
+def kernel_named(name, want):
+    """kernel_names reported `want`: as a prefix when `want` ends inside a template argument list ("k_doublet_a2<"), as the whole name
+    otherwise (the name itself, or the name and a parameter list) — "k_doublet_a2u16" is not "k_doublet_a2u16_mirror_fallback"."""
+    return name.startswith(want) and (want.endswith("<") or name == want or name.startswith(want + "("))
 
 
 def family_problem(eng, case, field, V, dense, deep, quals):
@@ -124,7 +140,8 @@ def family_problem(eng, case, field, V, dense, deep, quals):
 
 SWITCHES = ("DMX_K1_CANP", "DMX_A2_NO_SYMU", "DMX_A2_SYM", "DMX_NO_ANF", "DMX_K2_GENERIC", "DMX_FINALS_ANY_DEPTH", "DMX_SYM_NO_FINALS",
             "DMX_A2_NO_FINALS", "DMX_SYM_NO_SEEDS", "DMX_A2_NO_SEEDS", "DMX_CERTIFY_NO_FINALS", "DMX_CERTIFY_NO_SEEDS", "DMX_NO_CLASSES",
-            "DMX_K1_NO_CANP", "DMX_K1_NO_LEAN", "DMX_K1_NO_OWN")
+            "DMX_K1_NO_CANP", "DMX_K1_NO_LEAN", "DMX_K1_NO_OWN", "DMX_A2U_ONE_BARCODE", "DMX_A2U2_NO_DIAG", "DMX_A2U_MIRROR_FALLBACK",
+            "DMX_A2U_DIAG_WAVE")
 TABLES = {
     "tables_default": {},
     "tables_off": {k: "1" for k in ("DMX_SYM_NO_FINALS", "DMX_A2_NO_FINALS", "DMX_SYM_NO_SEEDS", "DMX_A2_NO_SEEDS", "DMX_CERTIFY_NO_FINALS",
@@ -133,7 +150,9 @@ TABLES = {
 }
 
 
-def run_with_env(eng, monkeypatch, g, sp, alphas, mode, env):
+def run_with_env(eng, monkeypatch, g, sp, alphas, mode, env, stage=None, split=False):
+    """One engine run under the switches `env`.  stage(engine): the caller's own way of handing the pileup over (default: set_pileup of the host
+    arrays); what it returns is kept alive until the engine is closed.  split: run_singlet + run_doublet in place of dmx_engine_run."""
     from demuxlet_amd import capi
     monkeypatch.setenv("DMX_EXPERIMENTS", "1")
     for k in SWITCHES:
@@ -141,7 +160,13 @@ def run_with_env(eng, monkeypatch, g, sp, alphas, mode, env):
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     e = eng.Engine(g.shape[1], alphas, 0.5, mode=capi.DMX_MODE_FAST if mode == "fast" else capi.DMX_MODE_STRICT)
-    e.set_genotypes(g); e.set_pileup(host_pileup(eng, sp)); e.run(); e.sync()
+    e.set_genotypes(g)
+    keep = stage(e) if stage else e.set_pileup(host_pileup(eng, sp))
+    if split:
+        e.run_singlet(); e.run_doublet()
+    else:
+        e.run()
+    e.sync()
     names = e.kernel_names()
     llks, llk0s = e.get_singlet()
     grid, l00, summ = e.get_doublet()

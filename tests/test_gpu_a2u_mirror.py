@@ -55,7 +55,7 @@ def eng():
 
 
 def run(eng, monkeypatch, g, sp, env):
-    for k in ("DMX_A2U_ONE_BARCODE", "DMX_A2U2_NO_DIAG", "DMX_A2U_MIRROR_FALLBACK"):   # (not among the switches run_with_env clears)
+    for k in ("DMX_A2U_ONE_BARCODE", "DMX_A2U2_NO_DIAG", "DMX_A2U_MIRROR_FALLBACK"):   # (run_with_env clears them as well)
         monkeypatch.delenv(k, raising=False)
     return run_with_env(eng, monkeypatch, g, sp, A2, "strict", env)
 

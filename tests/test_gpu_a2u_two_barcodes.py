@@ -79,7 +79,7 @@ def eng():
 
 
 def run(eng, monkeypatch, g, sp, env):
-    for k in ("DMX_A2U_ONE_BARCODE", "DMX_A2U2_NO_DIAG"):         # (not among the switches run_with_env clears)
+    for k in ("DMX_A2U_ONE_BARCODE", "DMX_A2U2_NO_DIAG"):         # (run_with_env clears them as well)
         monkeypatch.delenv(k, raising=False)
     return run_with_env(eng, monkeypatch, g, sp, A2, "strict", env)
 

@@ -1163,6 +1163,56 @@ def test_demuxlet_run_from_a_device_resident_pileup(eng, oracle, tmp_path, monke
         eng.demuxlet_run(ds, g, sms, alphas, str(tmp_path / "x"), barcodes=bcs, n_gpus=2)
 
 
+@pytest.mark.parametrize("sorted_ids", [False, True], ids=["gathered", "views"])
+def test_demuxlet_run_dense_headline_over_ranges(eng, oracle, tmp_path, monkeypatch, sorted_ids):
+    """The case (32, "GP", dense, STRICT) of test_demuxlet_run_from_a_device_resident_pileup at a small shape of its own (that test's 300 barcodes x 500 SNPs
+    and its DMX_RANGE_BYTES would make 300 ranges of one barcode each): the ranges of dmx_demuxlet_run on top of k_doublet_a2u<k_doublet_a2u2> — views of the
+    caller's device arrays with a non-zero first cell (sorted ids), ranges gathered on the device from non-consecutive cells (unsorted ids), two-byte read
+    counts, the K3 records, the certificate and the writers.  Byte-identical files from the device-resident and the host pileup, and those are the oracle's."""
+    import torch
+    from demuxlet_amd import synth, capi
+    from quality_mix import genotypes, mixed_depth_pileup
+    V, S, B = 32, 70, 11
+    alphas = (0.0, 0.5)
+    rng = np.random.default_rng(4132)
+    raw = synth.make_raw_genotypes(rng, S, V)
+    g = genotypes(eng, rng, raw.alleles, "GP")
+    sp = mixed_depth_pileup(rng, raw.alleles, B, 1.0, quals="edges", dense=True, deep=2, doublet_rate=0.4)
+    assert sp.pair_snp is None and sp.pair_nrd.dtype == np.uint16
+    pl = host_pileup(eng, sp)
+    # unsorted: barcode i is the (7 i mod 11)-th in output order, so consecutive output rows are cells 8 apart (mod 11) and no range is a run of consecutive cells
+    bcs = [f"BC{i:05d}-1" for i in range(B)] if sorted_ids else [f"BC{(i * 7) % B:05d}-1" for i in range(B)]
+    sms = [f"S{j:02d}" for j in range(V)]
+    # the engine runs the two-barcode kernel on this pileup (the job itself does not report kernel names)
+    monkeypatch.setenv("DMX_EXPERIMENTS", "1")
+    e = eng.Engine(V, alphas, 0.5)
+    e.set_genotypes(g); e.set_pileup(pl); e.run(); e.sync()
+    names = e.kernel_names(); e.close()
+    assert names["doublet"] == "k_doublet_a2u<k_doublet_a2u2>", names
+    dev = torch.device("cuda", 0)
+    t = {k: torch.from_numpy(np.ascontiguousarray(getattr(pl, k))).to(dev) for k in ("cell_pair_off", "cell_read_off", "pair_nrd", "reads")}
+    hs = pl.as_struct()
+    ds = capi.Pileup(B, S, hs.n_pairs, hs.n_reads, t["cell_pair_off"].data_ptr(), t["cell_read_off"].data_ptr(), None, t["pair_nrd"].data_ptr(),
+                     pl.pair_nrd.dtype.itemsize, capi.DMX_MEM_DEVICE, t["reads"].data_ptr(), pl.rd_totl.ctypes.data, pl.rd_pass.ctypes.data,
+                     pl.rd_uniq.ctypes.data)
+    oracle_from_pileup_files(oracle, sp, g, alphas, bcs, sms, tmp_path / "orc")
+    # Ranges (dmx_demuxlet_run): a barcode's grid is 32 x 32 x 2 doubles = 16 384 bytes, and the eleven barcodes are equal work (70 pairs each).
+    #   DMX_RANGE_BYTES = 50 000: at most 3 barcodes per range, ceil(11 x 16 384 / 50 000) = 4 ranges, cut where the work passes 11 r / 4 barcodes = after 3, 6
+    #     and 9: ranges of 3, 3, 3 and 2 barcodes — the first three are odd (one full workgroup and a lone last barcode), and start at cells 0, 3, 6, 9.
+    #   DMX_RANGE_BYTES = 90 000: at most 5 per range, ceil(11 x 16 384 / 90 000) = 3 ranges, cut after 4 and 8: ranges of 4, 4 and 3 — the last one is odd.
+    for tag, rb, wp, n_ranges in (("one", None, False, 1), ("many", "50000", False, 4), ("pair", "90000", True, 3)):
+        if rb: monkeypatch.setenv("DMX_RANGE_BYTES", rb)
+        else: monkeypatch.delenv("DMX_RANGE_BYTES", raising=False)
+        th = eng.demuxlet_run(pl, g, sms, alphas, str(tmp_path / f"h_{tag}"), write_pair=wp, barcodes=bcs, timing=True)
+        td = eng.demuxlet_run(ds, g, sms, alphas, str(tmp_path / f"d_{tag}"), write_pair=wp, barcodes=bcs, timing=True)
+        assert td["n_ranges"] == th["n_ranges"] == n_ranges, (tag, td["n_ranges"], th["n_ranges"])
+        assert td["n_cells_grid_fetched"] == th["n_cells_grid_fetched"]
+        for suf in ("single", "sing2", "best") + (("pair",) if wp else ()):
+            a, b = (tmp_path / f"d_{tag}.{suf}").read_bytes(), (tmp_path / f"h_{tag}.{suf}").read_bytes()
+            assert a == b, (tag, suf)
+            assert a == (tmp_path / f"orc.{suf}").read_bytes(), (tag, suf)
+
+
 def oracle_from_pileup_files(oracle, sp, g, alphas, barcodes, sample_ids, prefix):
     al = (sp.reads >> 7).astype(np.uint32)
     words = (al << 24) | ((sp.reads & 0x7F).astype(np.uint32) << 16) | 1

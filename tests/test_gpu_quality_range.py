@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from golden_util import printed_mask
-from quality_mix import A2, FAMILIES, TABLES, family_problem, genotypes, mixed_depth_pileup, oracle_run, run_with_env
+from quality_mix import A2, FAMILIES, TABLES, family_problem, genotypes, kernel_named, mixed_depth_pileup, oracle_run, run_with_env
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-9
@@ -49,6 +49,7 @@ def test_kernel_family_against_oracle(eng, oracle, monkeypatch, case, field, V, 
         out = run_with_env(eng, monkeypatch, g, sp, alphas, mode, {**env, **tenv})
         names = out["names"]
         assert names["singlet"].startswith(k1) and names["doublet"].startswith(k2), (tname, names)
+        assert kernel_named(names["doublet"], k2), (tname, names)          # a whole K2 name is the whole name (k_doublet_a2u16 / its fall-back form)
         d = max_diffs(out, ref, alphas, mode)
         print(f"{case} {quals} {tname}: {names['singlet']} | {names['doublet']} | {names['certify']}: "
               + " ".join(f"{k} {v:.2e}" for k, v in d.items()))

@@ -49,6 +49,13 @@ UNSAFE_NAMES = {
     "k2_anf": ("k_singlet_own<16, false, true>", "k_doublet_anf<256, 1, 4, 16, 8, 3, true>"),
     "k2_a2f": ("k_singlet_own<16, false, true>", "k_doublet_a2f<64, 4>"),
     "k2_generic": ("k_singlet<1, 8, false>", "k_doublet_generic<unsigned short, 1, false>"),
+    # the dense families of the two-barcode kernel and k_doublet_a2u16: the A2U switches select nothing without a safe matrix
+    "k2_a2u2": ("k_singlet_own<32, true, true>", "k_doublet_a2<256, 4, 4, true, true, 32>"),
+    "k2_a2u2_diag_behind": ("k_singlet_own<32, true, true>", "k_doublet_a2<256, 4, 4, true, true, 32>"),
+    "k2_a2u2_mirror_fallback": ("k_singlet_own<32, true, true>", "k_doublet_a2<256, 4, 4, true, true, 32>"),
+    "k2_a2u_dense_one_barcode": ("k_singlet_own<32, true, true>", "k_doublet_a2<256, 4, 4, true, true, 32>"),
+    "k2_a2u16_dense": ("k_singlet_own<16, true, true>", "k_doublet_a2<64, 4, 1, false, true, 32>"),
+    "k2_a2u16_mirror_fallback": ("k_singlet_own<16, true, true>", "k_doublet_a2<64, 4, 1, false, true, 32>"),
 }
 BY_CASE = {f[0]: f for f in FAMILIES}
 ARRAYS = ("llks", "llk0s", "grid", "l00")
