@@ -282,6 +282,16 @@ int dmx_engine_algorithmic_bytes(dmx_engine*, dmx_kernel_bytes* out);
  *                  a row with n_cell = 0 is prior's row, bit for bit (no floor).
  * Sum order: a sample's assigned barcodes in ascending cell id are cut into chunks of 64; inside a chunk the terms are added in barcode
  * order, then the chunk sums in ascending chunk order.  No floating-point atomics: the same inputs give the same bits, whatever ran before.
+ * Operations (binary64, every product, sum and quotient rounded on its own; tests/contract_emul.cpp restates them and
+ * tests/test_gpu_contract_bits.py compares the bits):
+ *   GL        G = (1, 1, 1); per stored read in stored order, with mat / err the phred tables at its base quality, e3 = err / 3 and
+ *             h = 0.5 - err / 3 (each rounded once):  G_0 *= allele 1 ? e3 : mat,  G_1 *= h,  G_2 *= allele 1 ? mat : e3,
+ *             t = (G_0 + G_1) + G_2,  G_g = G_g / t (IEEE division);  after the last read G_g += 1e-6, t = (G_0 + G_1) + G_2, G_g = G_g / t.
+ *             A pair without stored reads is the last step alone on (1, 1, 1).  (The kernels start from tables of these values and divide
+ *             by a refined reciprocal where that is correctly rounded: the same bits.)
+ *   log       dmx_log; its arguments are >= 1e-6 / (1 + 3e-6), never outside the positive normal numbers.
+ *   sums      a chunk's sum starts at +0 and takes the logs of its barcodes' pairs at the SNP in barcode order; LL starts at +0 and takes the
+ *             chunk sums in chunk order (a chunk without a pair at the SNP adds +0).
  * The call runs on the engine's stream and synchronises it before returning (the prior may be freed then).  It leaves every other result
  * of the engine as it was. */
 typedef struct {
@@ -330,7 +340,10 @@ int dmx_engine_refine_info(dmx_engine*, dmx_refine_info* out);
  *   q's row, bit for bit.  Sum order: the slots of a SNP in ascending cell id, one after the other, as acc = fma(w, lgl, acc) from 0
  *   (W: acc += w); no floating-point atomics, so the bits depend neither on the launch geometry nor on what ran before.  gp' goes to
  *   the OTHER of two buffers when the current one is the engine's genotype matrix (dmx_engine_set_genotypes(..., DMX_MEM_DEVICE) with
- *   dmx_engine_cluster_device_ptr), so an M-step never overwrites the matrix K1 reads.
+ *   dmx_engine_cluster_device_ptr), so an M-step never overwrites the matrix K1 reads.  lgl[j][g] is dmx_log of the refinement's G_g,
+ *   operation for operation (section 12's block above); fma is the correctly rounded fused multiply-add, its first operand the weight
+ *   w[b][c] read as stored (0, 1 and 1e-300 are weights like any other); LL and W of a SNP without slots are +0
+ *   (tests/contract_emul.cpp, tests/test_gpu_contract_bits.py).
  *
  * dmx_engine_cluster_estep: from K1's llks[B][C] of the last run_singlet, C = R * K columns grouped as R restarts x K clusters, per
  *   barcode b and restart r:  a_k = (llks[b][rK + k] + log_pi[r][k]) / T,  w[b][rK + k] = exp(a_k - max a) / sum over k;  a barcode
@@ -606,7 +619,22 @@ int dmx_engine_cluster_known_info(dmx_engine*, dmx_cluster_known_info* out);
  * no stored read, or whose gp row is all zero, contributes nothing; n_snp[b] / n_read[b] count the pairs / reads that did.  f_g is kept
  * in range by exact power-of-two rescaling, the exponent carried into the log; the log is dmx_log.  Each (b, q) is one serial sum with
  * no floating-point atomics: the same inputs give the same bits whatever the grid's length or what ran before, and a grid split over
- * two calls gives the same bits at the shared points.  Unassigned barcodes get zero rows.  The call runs on the engine's stream,
+ * two calls gives the same bits at the shared points.  Unassigned barcodes get zero rows.
+ * Operations (binary64, every product and sum rounded on its own: no contraction; tests/contract_emul.cpp restates them and
+ * tests/test_gpu_contract_bits.py compares the bits):
+ *   p_g       om = 1 - rho,  ra = rho a_i;  p_0 = ra,  p_1 = 0.5 om + ra,  p_2 = om + ra;  q_g = 1 - p_g, rounded once;
+ *   factor    e3 = err[bq] / 3 rounded once;  t_g = pR q_g + pA p_g (two products, one sum);  f_g = t_g of the first stored read, then
+ *             f_g = f_g t_g read by read;
+ *   rescale   only in a pair of 8 or more stored reads.  After the first read's factor, f_g of an entry with gp[i][v][g] = 0 is set to 0,
+ *             so that the scale follows the entries that count.  After every eighth read (the pair's reads 8, 16, ...), with
+ *             mx = max(f_0, f_1, f_2): when 0 < mx < 2^-300, e = the exponent of mx as frexp gives it (mx = m 2^e, 0.5 <= m < 1), every
+ *             f_g = ldexp(f_g, -e) and E += e (E starts at 0 for every pair);
+ *   term      L = (gp_0 f_0 + gp_1 f_1) + gp_2 f_2 with the float32 entries widened;  lg = dmx_log(L), and when E != 0
+ *             lg = fma(E, DMX_LOG_LN2HI, fma(E, DMX_LOG_LN2LO, lg)), the two parts of ln 2 of csrc/dmx_log.hpp;
+ *   sum       LL[b][q] starts at +0 and takes lg pair by pair.
+ * An L that is not a positive normal number goes to the runtime's log instead of dmx_log; on these paths that is L = 0 only (every
+ * counted product is 0, which takes phred tables with a zero entry), and the term and LL[b][q] are -inf.
+ * The call runs on the engine's stream,
  * synchronises it before returning (host inputs may be freed then) and leaves every other result of the engine as it was.
  * DMX_ERR_ARG: Q outside [1, 256], a grid point outside [0, 1] or not strictly ascending, an a_i outside [0, 1], assign[b] outside
  * [-1, V), n_cells / n_snps that do not match the staged pileup / the genotype matrix.  DMX_ERR_STATE: no pileup or no genotypes yet.
@@ -649,7 +677,22 @@ int dmx_engine_ambient_info(dmx_engine*, dmx_ambient_info* out);
  * range by exact power-of-two rescaling, one exponent per entry, carried into the log: pairs of hundreds of reads give the finite value
  * of the log-space sum.  Each (b, c, n, q) is one serial sum with no floating-point atomics and no cross-lane step: its bits depend on
  * b's data, (v1, v2), alpha and rho only — not on C, A, Q, the slot, the other candidates or what ran before — and a grid (rho or alpha)
- * split over two calls gives the same bits at the shared points.  Unused slots get zero rows.  The call runs on the engine's stream,
+ * split over two calls gives the same bits at the shared points.  Unused slots get zero rows.
+ * Operations (binary64, every product and sum rounded on its own: no contraction; tests/contract_emul.cpp restates them and
+ * tests/test_gpu_contract_bits.py compares the bits), entries in the order k = 3 l + m:
+ *   p_lm      c_lm = 0.5 l + ((m - l) 0.5) alpha (the product with alpha and the sum rounded; the rest is exact);  om = 1 - rho,
+ *             ra = rho a_i;  p_lm = om c_lm + ra,  q_lm = 1 - p_lm, rounded once;
+ *   factor    as dmx_engine_ambient: e3 = err[bq] / 3,  t_lm = pR q_lm + pA p_lm,  f_lm = t_lm of the first stored read, then f_lm t_lm;
+ *   weights   w_lm = gp[i][v1][l] gp[i][v2][m], exact;
+ *   < 8 reads L = w_00 f_00, then L = L + w_lm f_lm in entry order (every product rounded);  lg = dmx_log(L);
+ *   >= 8      after every eighth read (the pair's reads 8, 16, ...) every entry with 0 < f_lm < 2^-300 takes e = its exponent as frexp
+ *             gives it, f_lm = ldexp(f_lm, -e), E_lm += e (from 0).  Per candidate E = max E_lm over the entries with w_lm != 0 and
+ *             f_lm > 0;  t_lm = w_lm ldexp(f_lm, max(E_lm - E, -1100)) where w_lm != 0, else +0;  L = t_00, then L = L + t_lm in entry
+ *             order;  lg = dmx_log(L), and when E != 0  lg = fma(E, DMX_LOG_LN2HI, fma(E, DMX_LOG_LN2LO, lg)).  A zero weight never
+ *             zeroes a product here (no entry is shared between candidates).  Without an entry to take E from, L = 0;
+ *   sum       LL[b][c][n][q] starts at +0 and takes lg pair by pair.
+ * An L that is not a positive normal number goes to the runtime's log; on these paths that is L = 0 only, and the entry is -inf.
+ * The call runs on the engine's stream,
  * synchronises it before returning (host inputs may be freed then), uses buffers of its own and leaves every other result of the
  * engine, the last dmx_engine_ambient profile included, as it was.
  * DMX_ERR_ARG: C or A outside [1, 8], Q outside [1, 256], alpha or grid outside [0, 1] or not strictly ascending, an a_i outside [0, 1],
@@ -1202,8 +1245,15 @@ int dmx_engine_prior_info(dmx_engine*, dmx_prior_info* out);
  * term is eight factors >= err(127) / 3 times a product of two float32 subnormals, still a normal float64.  Unused barcodes get zero
  * rows.  Without truncation obs[b] is dmx_engine_ambient's LL at (v1, rho), or dmx_engine_ambient_doublet's at (v1, v2, alpha, rho), up
  * to rounding.
+ * Operations (binary64, every product, sum and quotient rounded on its own: no contraction; tests/contract_emul.cpp restates them and
+ * tests/test_gpu_contract_bits.py compares the bits): om = 1 - rho, ra = rho a_i (rho = NULL: rho = 0 and ra = 0); c_g = 0.5 g for a singlet,
+ * c_lm = 0.5 l + ((m - l) 0.5) alpha for a doublet (the product with alpha and the sum rounded); p_c = om c_c + ra; err / 3 rounded once;
+ * F_c = t_0, then F_c = F_c t_r; L = W_0 F_0, then L = L + W_c F_c; S0, S1, S2 start at +0 and take L, L u and L (u u) (u u first);
+ * e1 = S1 / S0 and d = S2 / S0 - e1 e1 with IEEE divisions, mean takes c0 + e1 (that sum first), var takes d when d > 0 and +0 otherwise.
+ * L(y) != 0 is a positive normal number (below), so every log is dmx_log.
  * Summation plan: a barcode's pairs in stored order are dealt to 64 serial sums (pair k of the barcode goes to sum k mod 64, in
- * ascending k); the 64 sums are then added serially, sum 0 first.  No floating-point atomics: b's seven outputs depend on b's own pairs
+ * ascending k; k counts every pair of the barcode, whether it contributes or not; each sum starts at +0); the 64 sums are then added
+ * serially onto +0, sum 0 first.  No floating-point atomics: b's seven outputs depend on b's own pairs
  * and reads, its hypothesis, M, and the gp rows and a entries it touches only — not on B, the other barcodes, what ran before, the
  * stream, or where hyp lives.  The call runs on the engine's stream, synchronises it before returning (host inputs may be freed then),
  * uses buffers of its own and leaves every other result of the engine as it was.
