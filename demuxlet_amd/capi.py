@@ -53,6 +53,7 @@ SYMBOLS = [
     "dmx_engine_prior_step", "dmx_engine_get_prior_step", "dmx_engine_prior_fit", "dmx_engine_get_prior_fit",
     "dmx_engine_prior_call", "dmx_engine_get_prior_calls", "dmx_engine_prior_info",
     "dmx_engine_fit", "dmx_engine_get_fit", "dmx_engine_fit_info",
+    "dmx_engine_share_scan", "dmx_engine_get_share_scan", "dmx_engine_share_fit", "dmx_engine_get_share_fit", "dmx_engine_share_info",
 ]
 DMX_PRIOR_MASKED, DMX_PRIOR_BAD = 1, 2
 
@@ -180,6 +181,26 @@ class FitRequest(C.Structure):           # dmx_fit_request
 class FitInfo(C.Structure):              # dmx_fit_info
     _fields_ = [("kernel_ms", C.c_double), ("bytes", C.c_int64), ("n_trunc", C.c_int64), ("n_zero", C.c_int64), ("n_cells", C.c_int32),
                 ("n_used", C.c_int32), ("n_singlet", C.c_int32), ("n_doublet", C.c_int32), ("max_reads", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+DMX_SHARE_INTERIOR, DMX_SHARE_AT_0, DMX_SHARE_AT_1, DMX_SHARE_NOT_CONVERGED, DMX_SHARE_FLAT, DMX_SHARE_NONFINITE = 1, 2, 4, 8, 16, 32
+
+
+class ShareScanRequest(C.Structure):     # dmx_share_scan_request
+    _fields_ = [("n_cells", C.c_int32), ("n_snps", C.c_int32), ("n_anchor", C.c_int32), ("anchor_memory", C.c_int32), ("anchors", C.c_void_p),
+                ("rho", C.c_void_p), ("ambient", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class ShareFitRequest(C.Structure):      # dmx_share_fit_request
+    _fields_ = [("n_cells", C.c_int32), ("n_snps", C.c_int32), ("n_cand", C.c_int32), ("cand_memory", C.c_int32), ("cand", C.c_void_p),
+                ("rho", C.c_void_p), ("ambient", C.c_void_p), ("start", C.c_double), ("tol", C.c_double), ("probe", C.c_double),
+                ("max_iter", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+class ShareInfo(C.Structure):            # dmx_share_info
+    _fields_ = [("scan_ms", C.c_double), ("fit_ms", C.c_double), ("scan_bytes", C.c_int64), ("fit_bytes", C.c_int64), ("scan_entries", C.c_int64),
+                ("fit_used", C.c_int64), ("fit_evals", C.c_int64), ("n_cells", C.c_int32), ("n_samples", C.c_int32), ("n_anchor", C.c_int32),
+                ("n_cand", C.c_int32), ("have_scan", C.c_int32), ("have_fit", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 class TripletRequest(C.Structure):     # dmx_triplet_request
@@ -417,6 +438,8 @@ def load() -> C.CDLL:
         "dmx_engine_prior_fit": [vp, vp], "dmx_engine_get_prior_fit": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32],
         "dmx_engine_prior_call": [vp, vp, vp, dbl], "dmx_engine_get_prior_calls": [vp, vp], "dmx_engine_prior_info": [vp, vp],
         "dmx_engine_fit": [vp, vp], "dmx_engine_get_fit": [vp, vp, vp, vp, vp, vp, vp, vp], "dmx_engine_fit_info": [vp, vp],
+        "dmx_engine_share_scan": [vp, vp], "dmx_engine_get_share_scan": [vp, vp, vp], "dmx_engine_share_fit": [vp, vp],
+        "dmx_engine_get_share_fit": [vp, vp, vp], "dmx_engine_share_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -3635,6 +3635,336 @@ __global__ __launch_bounds__(64 * kFitWaves) void k_fit(PileupView pv, int nrd_w
   }
 }
 
+// ---- continuous mixing share (dmx_engine_share_scan / dmx_engine_share_fit) ---------------------------------------
+// Section 18's doublet likelihood LL(alpha) of a barcode and a pair (v1, v2) with its first and second derivative in alpha
+// (include/dmx.h states the operations).  Per entry (l, m) the read loop keeps, beside the product f_lm and its exponent, S1 = sum u and
+// S2 = sum u u of u = (pA - pR) / t over the reads; the three entries l = m have s_lm = 0 and take no quotient.  The power-of-two scale
+// of a deep pair is common to L, L' and L'' and cancels in D1 = L' / L and D2 = L'' / L - D1 D1.
+//   k_share_scan  alpha = 0, every partner of an anchor: p_lm does not depend on m there, so phase 1 (lane = pair) runs the read loop for
+//                 the three l once per pair and leaves F_l, x = s S1 and y = x x - s s S2 of the six l != m entries in LDS; phase 2
+//                 (lane = partner) folds the tile's pairs in stored order into the lane's own three sums: nine weights, two quotients, one
+//                 log.  One wavefront per (barcode, anchor slot, block of 64 partners); nothing crosses lanes.
+//   k_share_fit   one wavefront per (barcode, candidate), lane = pair as k_fit; the 64 lanes' sums are added serially in lane order by
+//                 every lane (the same bits in each), and the safeguarded Newton iteration runs on the wave-uniform result.  The reads
+//                 are read again each evaluation.
+constexpr int kShareWaves = 4;
+constexpr int kShareMaxAnchor = 4, kShareMaxCand = 8, kShareMaxSamples = 1024, kShareMaxIter = 200;
+constexpr int kShareFitDoubles = 13, kShareFitInts = 4;   // per (b, c): alpha_hat | LL, LL', LL'' at alpha_hat, 0, 1, probe;  n_eval, status, n_snp, n_read
+constexpr int32_t kShareNoExp = INT32_MIN / 2;
+
+// The read loop of one pair over NE entries: f (with section 18's rescaling into E) and, for the entries with s != 0, S1 and S2.
+template <int NE, bool DIAG>
+__device__ __forceinline__ void share_reads(const PileupView& pv, int64_t off, uint32_t n, uint32_t w, const double (&pp)[NE], const double (&qq)[NE],
+                                            const double (*s_pra)[2], double (&f)[NE], int32_t (&E)[NE], double (&S1)[NE], double (&S2)[NE]) {
+#pragma unroll
+  for (int k = 0; k < NE; ++k) { f[k] = 0.0; E[k] = 0; S1[k] = 0.0; S2[k] = 0.0; }
+  for (uint32_t r = 0; r < n; ++r) {
+    if (r > 0 && (r & 3) == 0) w = load_rd4(pv, off + r, n - r);
+    const uint32_t byte = (w >> (8 * (r & 3))) & 0xFF;
+    const double pR = s_pra[byte][0], pA = s_pra[byte][1];
+    const double dlt = pA - pR;
+#pragma unroll
+    for (int k = 0; k < NE; ++k) {
+      const double t = pR * qq[k] + pA * pp[k];
+      f[k] = r == 0 ? t : f[k] * t;
+      if (!DIAG || k % 4 != 0) {
+        const double u = t != 0.0 ? dlt / t : 0.0;              // a factor 0 zeroes f: the entry adds nothing, whatever S1 and S2 hold
+        S1[k] += u; S2[k] += u * u;
+      }
+    }
+    if ((r & 7) == 7) {
+#pragma unroll
+      for (int k = 0; k < NE; ++k)
+        if (f[k] < kAmbRescaleBelow && f[k] > 0.0) {
+          int e;
+          (void)frexp(f[k], &e);
+          f[k] = ldexp(f[k], -e);
+          E[k] += e;
+        }
+    }
+  }
+}
+
+struct ShareScanPair { double F[3], x[6], y[6]; float g1[3]; int32_t snp, E; uint32_t n; };   // n = 0: skipped
+
+__global__ __launch_bounds__(64 * kShareWaves) void k_share_scan(PileupView pv, int nrd_width, const double* __restrict__ tabs, const float* __restrict__ g,
+                                                               int32_t V, const int32_t* __restrict__ anchors, int32_t T, const double* __restrict__ rho,
+                                                               const double* __restrict__ amb, int32_t n_vblk, int64_t n_units,
+                                                               double* __restrict__ out, int32_t* __restrict__ cnt) {
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_pra[256][2];               // by read byte (allele << 7 | bq): {pR, pA}
+  __shared__ ShareScanPair s_tile[kShareWaves][64];
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += 64 * kShareWaves) s_log[i] = tabs[kLut + i];
+  for (int i = threadIdx.x; i < 256; i += 64 * kShareWaves) {
+    const double mat = tabs[i & 127], e3 = tabs[128 + (i & 127)];
+    s_pra[i][0] = (i >> 7) ? e3 : mat;
+    s_pra[i][1] = (i >> 7) ? mat : e3;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t unit = (int64_t)blockIdx.x * kShareWaves + wave;
+  if (unit >= n_units) return;
+  const int32_t vb = (int32_t)(unit % n_vblk), slot = (int32_t)(unit / n_vblk);   // slot = b T + t
+  const int32_t cell = slot / T;
+  const int32_t v1 = __builtin_amdgcn_readfirstlane(anchors[slot]);
+  if (v1 < 0) return;                              // (the call zeroed the outputs)
+  const int32_t v = vb * 64 + lane;
+  const bool active = v < V && v != v1;
+  const int32_t vv = v < V ? v : 0;
+  const double rh = amb_uniform(rho[cell]), om = 1.0 - rh;
+  const double s1 = om * 0.5;                      // s_lm = s1 (m - l): exact multiples
+  const DmxLogPins lk = dmx_log_pins();
+  ShareScanPair* tile = s_tile[wave];
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  int32_t ns = 0, nr = 0;
+  const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+  int64_t rd_base = pv.cell_read_off[cell];
+  for (int64_t p0 = p_beg; p0 < p_end; p0 += 64) {
+    const int64_t p = p0 + lane;
+    const bool in = p < p_end;
+    const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+    const uint32_t incl = seg_scan_incl<64>(n);
+    const int64_t off = rd_base + (int64_t)(incl - n);
+    rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    {                                              // phase 1: lane = pair
+      ShareScanPair h;
+      h.n = 0; h.snp = 0; h.E = 0;
+#pragma unroll
+      for (int l = 0; l < 3; ++l) { h.F[l] = 0.0; h.g1[l] = 0.f; }
+#pragma unroll
+      for (int j = 0; j < 6; ++j) { h.x[j] = 0.0; h.y[j] = 0.0; }
+      if (n > 0) {
+        const int32_t snp = pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg);
+        const float* r1 = g + ((size_t)snp * V + (size_t)v1) * 3;
+        const float x0 = r1[0], x1 = r1[1], x2 = r1[2];
+        if (x0 != 0.f || x1 != 0.f || x2 != 0.f) {
+          const double ra = rh * amb[snp];
+          double pp[3], qq[3], f[3], S1[3], S2[3];
+          int32_t E[3];
+#pragma unroll
+          for (int l = 0; l < 3; ++l) { pp[l] = om * (0.5 * l) + ra; qq[l] = 1.0 - pp[l]; }
+          share_reads<3, false>(pv, off, n, load_rd4(pv, off, n), pp, qq, s_pra, f, E, S1, S2);
+          h.g1[0] = x0; h.g1[1] = x1; h.g1[2] = x2;
+          int32_t em = kShareNoExp;
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+            if (h.g1[l] != 0.f && f[l] > 0.0) em = max(em, E[l]);
+#pragma unroll
+          for (int l = 0; l < 3; ++l) h.F[l] = (h.g1[l] != 0.f && f[l] > 0.0) ? ldexp(f[l], max(E[l] - em, -1100)) : 0.0;
+          int j = 0;
+#pragma unroll
+          for (int l = 0; l < 3; ++l)
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+              if (m == l) continue;
+              const double s = s1 * (double)(m - l);
+              const double x = s * S1[l];
+              h.x[j] = x; h.y[j] = x * x - (s * s) * S2[l];
+              ++j;
+            }
+          h.snp = snp; h.E = em; h.n = n;
+        }
+      }
+      ns += (int32_t)__builtin_popcountll(__ballot(h.n > 0));
+      nr += (int32_t)(uint32_t)__builtin_amdgcn_readlane((int)seg_scan_incl<64>(h.n), 63);
+      tile[lane] = h;
+    }
+    DMX_WAVE_LDS_ORDER();
+    const int cnt_t = (int)min<int64_t>(64, p_end - p0);
+    for (int j = 0; j < cnt_t; ++j) {                // phase 2: lane = partner
+      const ShareScanPair& h = tile[j];
+      const uint32_t nj = (uint32_t)__builtin_amdgcn_readfirstlane((int)h.n);
+      if (nj == 0) continue;
+      const float* r2 = g + ((size_t)h.snp * V + (size_t)vv) * 3;
+      const float y0 = r2[0], y1 = r2[1], y2 = r2[2];
+      if (!active || (y0 == 0.f && y1 == 0.f && y2 == 0.f)) continue;
+      const double g1[3] = {(double)h.g1[0], (double)h.g1[1], (double)h.g1[2]}, g2[3] = {(double)y0, (double)y1, (double)y2};
+      double L = 0.0, L1 = 0.0, L2 = 0.0;
+      int o = 0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        const double wk = g1[k / 3] * g2[k % 3];                   // float32 x float32: exact in float64
+        const double t = wk != 0.0 ? wk * h.F[k / 3] : 0.0;
+        L = k == 0 ? t : L + t;
+        if (k % 4 != 0) {
+          const double t1 = t * h.x[o], t2 = t * h.y[o];
+          L1 = o == 0 ? t1 : L1 + t1;
+          L2 = o == 0 ? t2 : L2 + t2;
+          ++o;
+        }
+      }
+      double lg = dmx_log_is_special(L) ? log(L) : dmx_log_fast_pinned(L, s_log, lk);
+      const int32_t em = h.E;
+      if (em != 0) lg = __builtin_fma((double)em, DMX_LOG_LN2HI, __builtin_fma((double)em, DMX_LOG_LN2LO, lg));
+      const double d1 = L1 / L;
+      a0 += lg; a1 += d1; a2 += L2 / L - d1 * d1;
+    }
+    DMX_WAVE_LDS_ORDER();
+  }
+  if (active) {
+    double* o = out + ((size_t)slot * V + (size_t)v) * 3;
+    o[0] = a0; o[1] = a1; o[2] = a2;
+  }
+  if (vb == 0 && lane == 0) { cnt[2 * (size_t)slot] = ns; cnt[2 * (size_t)slot + 1] = nr; }
+}
+
+// One evaluation of (LL, LL', LL'') at the share `al` for k_share_fit's wavefront; the results are wave-uniform.
+__device__ __forceinline__ void share_fit_eval(const PileupView& pv, int nrd_width, const float* __restrict__ g, int32_t V, int32_t cell, int32_t v1,
+                                            int32_t v2, double rh, const double* __restrict__ amb, double al, const double (*s_pra)[2],
+                                            const double* s_log, double (*red)[3], int lane, double (&res)[3], int32_t& n_snp, int32_t& n_read) {
+  const double om = 1.0 - rh, s1 = om * 0.5;
+  double cm[9];
+#pragma unroll
+  for (int l = 0; l < 3; ++l)
+#pragma unroll
+    for (int m = 0; m < 3; ++m) cm[l * 3 + m] = amb_uniform(0.5 * l + ((m - l) * 0.5) * al);
+  const DmxLogPins lk = dmx_log_pins();
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  int32_t ns = 0, nr = 0;
+  const int64_t p_beg = pv.cell_pair_off[cell], p_end = pv.cell_pair_off[cell + 1];
+  int64_t rd_base = pv.cell_read_off[cell];
+  for (int64_t p0 = p_beg; p0 < p_end; p0 += 64) {
+    const int64_t p = p0 + lane;
+    const bool in = p < p_end;
+    const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+    const uint32_t incl = seg_scan_incl<64>(n);
+    const int64_t off = rd_base + (int64_t)(incl - n);
+    rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    if (n == 0) continue;
+    const int32_t snp = pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - p_beg);
+    const float* gs = g + (size_t)snp * V * 3;
+    const float* r1 = gs + (size_t)v1 * 3;
+    const float* r2 = gs + (size_t)v2 * 3;
+    const float x0 = r1[0], x1 = r1[1], x2 = r1[2], y0 = r2[0], y1 = r2[1], y2 = r2[2];
+    if (!((x0 != 0.f || x1 != 0.f || x2 != 0.f) && (y0 != 0.f || y1 != 0.f || y2 != 0.f))) continue;
+    const double g1[3] = {(double)x0, (double)x1, (double)x2}, g2[3] = {(double)y0, (double)y1, (double)y2};
+    const double ra = rh * amb[snp];
+    double pp[9], qq[9], f[9], S1[9], S2[9];
+    int32_t E[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) { pp[k] = om * cm[k] + ra; qq[k] = 1.0 - pp[k]; }
+    share_reads<9, true>(pv, off, n, load_rd4(pv, off, n), pp, qq, s_pra, f, E, S1, S2);
+    int32_t em = kShareNoExp;
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+      if (g1[k / 3] * g2[k % 3] != 0.0 && f[k] > 0.0) em = max(em, E[k]);
+    double L = 0.0, L1 = 0.0, L2 = 0.0;
+    int o = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      const double wk = g1[k / 3] * g2[k % 3];                     // float32 x float32: exact in float64
+      const double t = wk != 0.0 ? wk * ldexp(f[k], max(E[k] - em, -1100)) : 0.0;
+      L = k == 0 ? t : L + t;
+      if (k % 4 != 0) {
+        const double s = s1 * (double)(k % 3 - k / 3);
+        const double x = s * S1[k];
+        const double y = x * x - (s * s) * S2[k];
+        const double t1 = t * x, t2 = t * y;
+        L1 = o == 0 ? t1 : L1 + t1;
+        L2 = o == 0 ? t2 : L2 + t2;
+        ++o;
+      }
+    }
+    double lg = dmx_log_is_special(L) ? log(L) : dmx_log_fast_pinned(L, s_log, lk);
+    if (em != 0) lg = __builtin_fma((double)em, DMX_LOG_LN2HI, __builtin_fma((double)em, DMX_LOG_LN2LO, lg));
+    const double d1 = L1 / L;
+    a0 += lg; a1 += d1; a2 += L2 / L - d1 * d1;
+    ns += 1; nr += (int32_t)n;
+  }
+  DMX_WAVE_LDS_ORDER();                            // (the last evaluation's sums have been read by every lane)
+  red[lane][0] = a0; red[lane][1] = a1; red[lane][2] = a2;
+  DMX_WAVE_LDS_ORDER();
+  double b0 = 0.0, b1 = 0.0, b2 = 0.0;
+  for (int l = 0; l < 64; ++l) { b0 += red[l][0]; b1 += red[l][1]; b2 += red[l][2]; }
+  res[0] = amb_uniform(b0); res[1] = amb_uniform(b1); res[2] = amb_uniform(b2);
+  n_snp = (int32_t)__builtin_amdgcn_readlane((int)seg_scan_incl<64>((uint32_t)ns), 63);
+  n_read = (int32_t)__builtin_amdgcn_readlane((int)seg_scan_incl<64>((uint32_t)nr), 63);
+}
+
+__device__ __forceinline__ bool share_finite3(const double (&r)[3]) { return fabs(r[0]) < INFINITY && fabs(r[1]) < INFINITY && fabs(r[2]) < INFINITY; }
+
+__global__ __launch_bounds__(64 * kShareWaves) void k_share_fit(PileupView pv, int nrd_width, const double* __restrict__ tabs, const float* __restrict__ g,
+                                                              int32_t V, const int32_t* __restrict__ cand, const double* __restrict__ rho,
+                                                              const double* __restrict__ amb, double start, double tol, int32_t max_iter, double probe,
+                                                              int64_t n_units, double* __restrict__ out, int32_t* __restrict__ outi) {
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_pra[256][2];               // by read byte (allele << 7 | bq): {pR, pA}
+  __shared__ double s_red[kShareWaves][64][3];
+  for (int i = threadIdx.x; i < DMX_LOG_TABLE_DOUBLES; i += 64 * kShareWaves) s_log[i] = tabs[kLut + i];
+  for (int i = threadIdx.x; i < 256; i += 64 * kShareWaves) {
+    const double mat = tabs[i & 127], e3 = tabs[128 + (i & 127)];
+    s_pra[i][0] = (i >> 7) ? e3 : mat;
+    s_pra[i][1] = (i >> 7) ? mat : e3;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t unit = (int64_t)blockIdx.x * kShareWaves + wave;   // = b C + c
+  if (unit >= n_units) return;
+  const int32_t v1 = __builtin_amdgcn_readfirstlane(cand[2 * unit]), v2 = __builtin_amdgcn_readfirstlane(cand[2 * unit + 1]);
+  if (v1 < 0) return;                              // (the call zeroed the outputs)
+  const int32_t C = (int32_t)(n_units / pv.B), cell = (int32_t)(unit / C);
+  const double rh = amb_uniform(rho[cell]);
+  double r0[3] = {0.0, 0.0, 0.0}, r1[3] = {0.0, 0.0, 0.0}, rx[3] = {0.0, 0.0, 0.0}, rp[3] = {0.0, 0.0, 0.0}, res[3];
+  double a = 0.0, ahat = 0.0, lo = 0.0, hi = 1.0;
+  int32_t state = 0, n_eval = 0, it = 0, status = 0, n_snp = 0, n_read = 0, ks = 0, kr = 0;
+  for (;;) {
+    share_fit_eval(pv, nrd_width, g, V, cell, v1, v2, rh, amb, a, s_pra, s_log, s_red[wave], lane, res, ks, kr);
+    bool done = false;
+    if (state == 0) {                              // step 1: the two ends
+      ++n_eval; n_snp = ks; n_read = kr;
+      r0[0] = res[0]; r0[1] = res[1]; r0[2] = res[2];
+      a = 1.0; state = 1;
+    } else if (state == 1) {
+      ++n_eval;
+      r1[0] = res[0]; r1[1] = res[1]; r1[2] = res[2];
+      const bool dn0 = r0[1] <= 0.0, up1 = r1[1] >= 0.0;
+      int end = -1;
+      if (!share_finite3(r0) || !share_finite3(r1)) end = 0;      // nothing to iterate on: reported at 0 with DMX_SHARE_NONFINITE
+      else if (dn0 && up1) end = r1[0] > r0[0] ? 1 : 0;           // step 2 (a tie goes to 0)
+      else if (dn0) end = 0;                                      // step 3
+      else if (up1) end = 1;                                      // step 4
+      if (end == 0) { ahat = 0.0; rx[0] = r0[0]; rx[1] = r0[1]; rx[2] = r0[2]; status = DMX_SHARE_AT_0; done = true; }
+      else if (end == 1) { ahat = 1.0; rx[0] = r1[0]; rx[1] = r1[1]; rx[2] = r1[2]; status = DMX_SHARE_AT_1; done = true; }
+      else { a = start; state = 2; }                              // step 5
+    } else if (state == 2) {                       // steps 6 to 9
+      ++n_eval; ++it;
+      if (res[1] > 0.0) lo = a; else hi = a;
+      double an = a - res[1] / res[2];
+      if (!(res[2] < 0.0 && an > lo && an < hi)) an = (lo + hi) * 0.5;
+      const bool conv = fabs(an - a) <= tol;
+      if (conv || it >= max_iter) {
+        if (!conv) status |= DMX_SHARE_NOT_CONVERGED;
+        state = 3;
+      }
+      a = an;
+    } else if (state == 3) {                       // step 10
+      ++n_eval;
+      ahat = a; rx[0] = res[0]; rx[1] = res[1]; rx[2] = res[2];
+      status |= DMX_SHARE_INTERIOR;
+      done = true;
+    } else {                                       // the probe (not counted in n_eval)
+      rp[0] = res[0]; rp[1] = res[1]; rp[2] = res[2];
+      break;
+    }
+    if (done) {
+      if (!(probe >= 0.0)) break;
+      a = probe; state = 4;
+    }
+  }
+  if (rx[2] >= 0.0) status |= DMX_SHARE_FLAT;
+  if (!share_finite3(r0) || !share_finite3(r1) || !share_finite3(rx)) status |= DMX_SHARE_NONFINITE;
+  if (lane == 0) {
+    double* o = out + (size_t)unit * kShareFitDoubles;
+    o[0] = ahat;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { o[1 + i] = rx[i]; o[4 + i] = r0[i]; o[7 + i] = r1[i]; o[10 + i] = rp[i]; }
+    int32_t* oi = outi + (size_t)unit * kShareFitInts;
+    oi[0] = n_eval; oi[1] = status; oi[2] = n_snp; oi[3] = n_read;
+  }
+}
+
 // ---- triplet profile (dmx_engine_triplet) -------------------------------------------------------------------------
 // For a barcode b, a base pair (v1, v2), a share triple (w1, w2, w3) and EVERY sample c of the pool as the third donor:
 //   p_lmn = 0.5 (w1 l + w2 m + w3 n),   f_lmn = product over the pair's stored reads of pR (1 - p_lmn) + pA p_lmn,
@@ -8498,6 +8828,13 @@ struct dmx_engine {
   int32_t fit_B = 0; bool have_fit = false;
   EventPair fev;
   dmx_fit_info fit_info{};
+  // continuous mixing share (dmx_engine_share_scan / _share_fit): each call's own copies of anchors / cand, rho[B] and a[S], and its
+  // results: the scan's (LL, LL', LL'')[B][T][V] and counts [B][T][2]; the fit's 13 doubles and 4 ints per (b, c)
+  DevBuf<int32_t> d_ssanc, d_sscnt, d_sfcand, d_sfint;
+  DevBuf<double> d_ssrho, d_ssamb, d_ssout, d_sfrho, d_sfamb, d_sfout;
+  int32_t ss_B = 0, ss_T = 0, ss_V = 0, sf_B = 0, sf_C = 0; bool have_sscan = false, have_sfit = false;
+  EventPair ssev, sfev;
+  dmx_share_info share_info{};
 };
 
 namespace {
@@ -9029,6 +9366,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_adbl = false; e->have_cdbl = false;
   e->have_trip = false;
   e->have_fit = false;
+  e->have_sscan = false; e->have_sfit = false;
   e->have_comp = false;
   e->have_census = false; e->have_cen_info = false; e->have_fis_info = false;
   e->have_pileup = true;
@@ -13020,5 +13358,215 @@ extern "C" int dmx_engine_fit_info(dmx_engine* e, dmx_fit_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_fit_info: null argument");
   if (!e->have_fit) return set_error(DMX_ERR_STATE, "dmx_engine_fit_info: no result on the staged pileup (dmx_engine_fit first)");
   *out = e->fit_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Continuous mixing share: both calls check their arguments on the host (anchors / cand, rho and a are small),
+// copy them to buffers of their own and launch one kernel.
+namespace {
+
+// rho[B] (NULL = 0) and a[S] (NULL only with rho = NULL) checked and copied to the device for a share call.
+int share_stage_soup(dmx_engine* e, const char* who, const double* rho, const double* ambient, int32_t B, int32_t S, double* d_rho, double* d_amb) {
+  if (rho)
+    for (int32_t b = 0; b < B; ++b)
+      if (!(rho[b] >= 0.0 && rho[b] <= 1.0)) return set_error(DMX_ERR_ARG, "%s: rho[%d] = %g is not in [0, 1]", who, b, rho[b]);
+  if (ambient)
+    for (int32_t i = 0; i < S; ++i)
+      if (!(ambient[i] >= 0.0 && ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "%s: ambient[%d] = %g is not in [0, 1]", who, i, ambient[i]);
+  if (!d_rho) return DMX_OK;                       // (the check alone)
+  if (B > 0) {
+    if (rho) HIP_TRY(hipMemcpyAsync(d_rho, rho, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, e->stream));
+    else HIP_TRY(hipMemsetAsync(d_rho, 0, sizeof(double) * (size_t)B, e->stream));
+  }
+  if (S > 0) {
+    if (ambient) HIP_TRY(hipMemcpyAsync(d_amb, ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
+    else HIP_TRY(hipMemsetAsync(d_amb, 0, sizeof(double) * (size_t)S, e->stream));
+  }
+  return DMX_OK;
+}
+
+int share_fetch_ids(dmx_engine* e, const int32_t* src, int32_t memory, size_t n, std::vector<int32_t>& dst) {
+  dst.resize(n);
+  if (n == 0) return DMX_OK;
+  if (memory == DMX_MEM_DEVICE) {
+    HIP_TRY(hipMemcpyAsync(dst.data(), src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  } else {
+    std::memcpy(dst.data(), src, sizeof(int32_t) * n);
+  }
+  return DMX_OK;
+}
+
+}  // namespace
+
+extern "C" int dmx_engine_share_scan(dmx_engine* e, const dmx_share_scan_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_share_scan: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_share_scan: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S, T = rq->n_anchor;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_share_scan: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (T < 1 || T > kShareMaxAnchor) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: n_anchor %d is not in [1, %d]", T, kShareMaxAnchor);
+  if (V > kShareMaxSamples) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: %d samples, at most %d", V, kShareMaxSamples);
+  if (B > 0 && !rq->anchors) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: missing anchors");
+  if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: rho is given without ambient");
+  if (rq->anchor_memory != DMX_MEM_HOST && rq->anchor_memory != DMX_MEM_DEVICE)
+    return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: anchor_memory %d", rq->anchor_memory);
+  if (int rc = share_stage_soup(e, "dmx_engine_share_scan", rq->rho, rq->ambient, B, S, nullptr, nullptr)) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t n_slot = (size_t)B * (size_t)T;
+  std::vector<int32_t> an;
+  if (int rc = share_fetch_ids(e, rq->anchors, rq->anchor_memory, n_slot, an)) return rc;
+  int64_t n_used = 0;
+  for (size_t k = 0; k < n_slot; ++k) {
+    if (an[k] == -1) continue;
+    if (an[k] < 0 || an[k] >= V)
+      return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: anchors[%zu][%zu] = %d is not -1 or a sample in [0, %d)", k / (size_t)T, k % (size_t)T, an[k], V);
+    ++n_used;
+  }
+  const size_t out_b = sizeof(double) * 3 * n_slot * (size_t)V, cnt_b = sizeof(int32_t) * 2 * n_slot;
+  const size_t need = out_b + cnt_b + sizeof(int32_t) * n_slot + sizeof(double) * ((size_t)B + (size_t)S);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (out_b > e->d_ssout.cap() && need + need / 16 > free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_share_scan: the %d x %d x %d scan needs %zu bytes, %zu are free", B, T, V, need, free_b);
+  if (int rc = e->d_ssout.ensure(out_b)) return rc;
+  if (int rc = e->d_sscnt.ensure(cnt_b)) return rc;
+  if (int rc = e->d_ssanc.ensure(sizeof(int32_t) * n_slot)) return rc;
+  if (int rc = e->d_ssrho.ensure(sizeof(double) * (size_t)B)) return rc;
+  if (int rc = e->d_ssamb.ensure(sizeof(double) * (size_t)S)) return rc;
+  e->have_sscan = false;
+  if (int rc = share_stage_soup(e, "dmx_engine_share_scan", rq->rho, rq->ambient, B, S, e->d_ssrho, e->d_ssamb)) return rc;
+  if (n_slot > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_ssanc, an.data(), sizeof(int32_t) * n_slot, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_ssout, 0, out_b, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_sscnt, 0, cnt_b, e->stream));
+  }
+  const int32_t n_vblk = (V + 63) / 64;
+  const int64_t n_units = (int64_t)n_slot * n_vblk;
+  if (int rc = e->ssev.record_start(e->stream)) return rc;
+  if (n_units > 0) {
+    hipLaunchKernelGGL(k_share_scan, dim3((unsigned)((n_units + kShareWaves - 1) / kShareWaves)), dim3(64 * kShareWaves), 0, e->stream, e->pv,
+                       e->nrd_width, (const double*)e->d_lut, e->d_g, V, (const int32_t*)e->d_ssanc, T, (const double*)e->d_ssrho,
+                       (const double*)e->d_ssamb, n_vblk, n_units, e->d_ssout.get(), e->d_sscnt.get());
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->ssev.record_stop(e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return
+  float ms = 0.f;
+  if (int rc = e->ssev.elapsed_ms(&ms)) return rc;
+  dmx_share_info& inf = e->share_info;
+  inf.scan_ms = ms; inf.scan_bytes = (int64_t)need; inf.scan_entries = n_used * (int64_t)(V - 1);
+  inf.n_cells = B; inf.n_samples = V; inf.n_anchor = T; inf.have_scan = 1;
+  e->ss_B = B; e->ss_T = T; e->ss_V = V; e->have_sscan = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_share_scan(dmx_engine* e, double* out, int32_t* n_snp_read) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_share_scan: null engine");
+  if (!e->have_sscan) return set_error(DMX_ERR_STATE, "dmx_engine_get_share_scan: no scan on the staged pileup (dmx_engine_share_scan first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t n_slot = (size_t)e->ss_B * (size_t)e->ss_T;
+  if (!n_slot) return DMX_OK;
+  if (out) HIP_TRY(hipMemcpy(out, e->d_ssout, sizeof(double) * 3 * n_slot * (size_t)e->ss_V, hipMemcpyDeviceToHost));
+  if (n_snp_read) HIP_TRY(hipMemcpy(n_snp_read, e->d_sscnt, sizeof(int32_t) * 2 * n_slot, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_share_fit(dmx_engine* e, const dmx_share_fit_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_share_fit: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_share_fit: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S, C = rq->n_cand;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_share_fit: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (C < 1 || C > kShareMaxCand) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: n_cand %d is not in [1, %d]", C, kShareMaxCand);
+  if (B > 0 && !rq->cand) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: missing cand");
+  if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: rho is given without ambient");
+  if (rq->cand_memory != DMX_MEM_HOST && rq->cand_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: cand_memory %d", rq->cand_memory);
+  if (!(rq->tol > 0.0 && rq->tol < INFINITY)) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: tol %g is not a positive number", rq->tol);
+  if (rq->max_iter < 1 || rq->max_iter > kShareMaxIter) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: max_iter %d is not in [1, %d]", rq->max_iter, kShareMaxIter);
+  if (!(rq->start > 0.0 && rq->start < 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: start %g is not in (0, 1)", rq->start);
+  if (!(rq->probe < 0.0 || (rq->probe >= 0.0 && rq->probe <= 1.0)))
+    return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: probe %g is neither negative (none) nor in [0, 1]", rq->probe);
+  if (int rc = share_stage_soup(e, "dmx_engine_share_fit", rq->rho, rq->ambient, B, S, nullptr, nullptr)) return rc;
+  HIP_TRY(hipSetDevice(e->device));
+  const size_t n_slot = (size_t)B * (size_t)C;
+  std::vector<int32_t> cd;
+  if (int rc = share_fetch_ids(e, rq->cand, rq->cand_memory, 2 * n_slot, cd)) return rc;
+  int64_t n_used = 0;
+  for (size_t k = 0; k < n_slot; ++k) {
+    const int32_t v1 = cd[2 * k], v2 = cd[2 * k + 1];
+    if (v1 == -1) continue;
+    if (v1 < 0 || v1 >= V || v2 < 0 || v2 >= V || v1 == v2)
+      return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: cand[%zu][%zu] = (%d, %d) is not -1 or two different samples in [0, %d)",
+                       k / (size_t)C, k % (size_t)C, v1, v2, V);
+    ++n_used;
+  }
+  const size_t out_b = sizeof(double) * kShareFitDoubles * n_slot, int_b = sizeof(int32_t) * kShareFitInts * n_slot;
+  const size_t need = out_b + int_b + sizeof(int32_t) * 2 * n_slot + sizeof(double) * ((size_t)B + (size_t)S);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (out_b > e->d_sfout.cap() && need + need / 16 > free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_share_fit: the results of %d x %d candidates need %zu bytes, %zu are free", B, C, need, free_b);
+  if (int rc = e->d_sfout.ensure(out_b)) return rc;
+  if (int rc = e->d_sfint.ensure(int_b)) return rc;
+  if (int rc = e->d_sfcand.ensure(sizeof(int32_t) * 2 * n_slot)) return rc;
+  if (int rc = e->d_sfrho.ensure(sizeof(double) * (size_t)B)) return rc;
+  if (int rc = e->d_sfamb.ensure(sizeof(double) * (size_t)S)) return rc;
+  e->have_sfit = false;
+  if (int rc = share_stage_soup(e, "dmx_engine_share_fit", rq->rho, rq->ambient, B, S, e->d_sfrho, e->d_sfamb)) return rc;
+  if (n_slot > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_sfcand, cd.data(), sizeof(int32_t) * 2 * n_slot, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_sfout, 0, out_b, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_sfint, 0, int_b, e->stream));
+  }
+  const int64_t n_units = (int64_t)n_slot;
+  if (int rc = e->sfev.record_start(e->stream)) return rc;
+  if (n_units > 0) {
+    hipLaunchKernelGGL(k_share_fit, dim3((unsigned)((n_units + kShareWaves - 1) / kShareWaves)), dim3(64 * kShareWaves), 0, e->stream, e->pv,
+                       e->nrd_width, (const double*)e->d_lut, e->d_g, V, (const int32_t*)e->d_sfcand, (const double*)e->d_sfrho,
+                       (const double*)e->d_sfamb, rq->start, rq->tol, rq->max_iter, rq->probe, n_units, e->d_sfout.get(), e->d_sfint.get());
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->sfev.record_stop(e->stream)) return rc;
+  std::vector<int32_t> oi(kShareFitInts * n_slot);
+  if (n_slot > 0) HIP_TRY(hipMemcpyAsync(oi.data(), e->d_sfint, int_b, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return
+  float ms = 0.f;
+  if (int rc = e->sfev.elapsed_ms(&ms)) return rc;
+  dmx_share_info& inf = e->share_info;
+  inf.fit_ms = ms; inf.fit_bytes = (int64_t)need; inf.fit_used = n_used; inf.fit_evals = 0;
+  for (size_t k = 0; k < n_slot; ++k)
+    if (cd[2 * k] >= 0) inf.fit_evals += oi[kShareFitInts * k] + (rq->probe >= 0.0 ? 1 : 0);
+  inf.n_cells = B; inf.n_samples = V; inf.n_cand = C; inf.have_fit = 1;
+  e->sf_B = B; e->sf_C = C; e->have_sfit = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_share_fit(dmx_engine* e, double* values, int32_t* counts) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_share_fit: null engine");
+  if (!e->have_sfit) return set_error(DMX_ERR_STATE, "dmx_engine_get_share_fit: no fit on the staged pileup (dmx_engine_share_fit first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t n_slot = (size_t)e->sf_B * (size_t)e->sf_C;
+  if (!n_slot) return DMX_OK;
+  if (values) HIP_TRY(hipMemcpy(values, e->d_sfout, sizeof(double) * kShareFitDoubles * n_slot, hipMemcpyDeviceToHost));
+  if (counts) HIP_TRY(hipMemcpy(counts, e->d_sfint, sizeof(int32_t) * kShareFitInts * n_slot, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_share_info(dmx_engine* e, dmx_share_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_share_info: null argument");
+  if (!e->have_sscan && !e->have_sfit)
+    return set_error(DMX_ERR_STATE, "dmx_engine_share_info: neither call has run on the staged pileup (dmx_engine_share_scan / _share_fit first)");
+  *out = e->share_info;
+  out->have_scan = e->have_sscan; out->have_fit = e->have_sfit;
   return DMX_OK;
 }

@@ -709,6 +709,75 @@ class Engine:
         check(self._L.dmx_engine_fit_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.FitInfo._fields_ if n != "reserved"}
 
+    def _share_soup(self, rho, ambient):
+        rh = amb = None
+        if rho is not None:
+            rh = np.ascontiguousarray(rho, dtype=np.float64)
+            if rh.shape != (self.B,):
+                raise ValueError(f"rho must be [{self.B}]")
+        if ambient is not None:
+            amb = np.ascontiguousarray(ambient, dtype=np.float64)
+            if amb.ndim != 1:
+                raise ValueError("ambient must be 1-D")
+        return rh, amb, (len(amb) if amb is not None else self.S)
+
+    def share_scan(self, anchors, rho=None, ambient=None, n_anchor=None):
+        """dmx_engine_share_scan over the staged pileup: for anchors[b][t] (-1 = slot not used) and every other sample v, LL, LL' and LL'' in
+        the share alpha of v's reads at alpha = 0, with a fraction rho[b] (None = 0) of the reads from a soup of ALT frequency ambient[i].
+        `anchors` is a host array [B][T], or a device pointer (int) to B x n_anchor int32.  Returns (out[B][T][V][3] f64, n_snp[B][T] i32,
+        n_read[B][T] i32)."""
+        rh, amb, n_snps = self._share_soup(rho, ambient)
+        if isinstance(anchors, int):
+            if n_anchor is None:
+                raise ValueError("device anchors need n_anchor=")
+            an, mem, ptr, T = None, capi.DMX_MEM_DEVICE, anchors, int(n_anchor)
+        else:
+            an = np.ascontiguousarray(anchors, dtype=np.int32)
+            if an.ndim != 2 or an.shape[0] != self.B:
+                raise ValueError(f"anchors must be [{self.B}][T]")
+            mem, ptr, T = capi.DMX_MEM_HOST, (an.ctypes.data if an.size else None), an.shape[1]
+        rq = capi.ShareScanRequest(self.B, n_snps, T, mem, ptr, rh.ctypes.data if rh is not None and rh.size else None,
+                                   amb.ctypes.data if amb is not None and amb.size else None)
+        check(self._L.dmx_engine_share_scan(self._h, C.byref(rq)))
+        out = np.zeros((self.B, T, self.V, 3))
+        cnt = np.zeros((self.B, T, 2), dtype=np.int32)
+        check(self._L.dmx_engine_get_share_scan(self._h, out.ctypes.data, cnt.ctypes.data))
+        return out, cnt[:, :, 0].copy(), cnt[:, :, 1].copy()
+
+    def share_fit(self, cand, rho=None, ambient=None, start: float = 0.5, tol: float = 1e-6, max_iter: int = 30, probe: float = -1.0,
+                  n_cand=None) -> dict:
+        """dmx_engine_share_fit over the staged pileup: for cand[b][c] = (v1, v2) (v1 = -1: slot not used) the share alpha_hat of v2's reads
+        that maximises the doublet log-likelihood, by the safeguarded Newton iteration include/dmx.h states.  `cand` is a host array
+        [B][C][2], or a device pointer (int) to B x n_cand x 2 int32.  Returns a dict of alpha, ll / d1 / d2 (at alpha_hat), ll0 / d10 / d20
+        (at 0), ll1 / d11 / d21 (at 1), llp / d1p / d2p (at `probe`, when it is in [0, 1]) (f64 [B][C]) and n_eval, status, n_snp, n_read
+        (i32 [B][C])."""
+        rh, amb, n_snps = self._share_soup(rho, ambient)
+        if isinstance(cand, int):
+            if n_cand is None:
+                raise ValueError("a device cand needs n_cand=")
+            cd, mem, ptr, Cn = None, capi.DMX_MEM_DEVICE, cand, int(n_cand)
+        else:
+            cd = np.ascontiguousarray(cand, dtype=np.int32)
+            if cd.ndim != 3 or cd.shape[0] != self.B or cd.shape[2] != 2:
+                raise ValueError(f"cand must be [{self.B}][C][2]")
+            mem, ptr, Cn = capi.DMX_MEM_HOST, (cd.ctypes.data if cd.size else None), cd.shape[1]
+        rq = capi.ShareFitRequest(self.B, n_snps, Cn, mem, ptr, rh.ctypes.data if rh is not None and rh.size else None,
+                                  amb.ctypes.data if amb is not None and amb.size else None, float(start), float(tol), float(probe), int(max_iter))
+        check(self._L.dmx_engine_share_fit(self._h, C.byref(rq)))
+        val = np.zeros((self.B, Cn, 13))
+        cnt = np.zeros((self.B, Cn, 4), dtype=np.int32)
+        check(self._L.dmx_engine_get_share_fit(self._h, val.ctypes.data, cnt.ctypes.data))
+        names = ("alpha", "ll", "d1", "d2", "ll0", "d10", "d20", "ll1", "d11", "d21", "llp", "d1p", "d2p")
+        out = {n: val[:, :, i].copy() for i, n in enumerate(names)}
+        out.update({n: cnt[:, :, i].copy() for i, n in enumerate(("n_eval", "status", "n_snp", "n_read"))})
+        return out
+
+    def share_info(self) -> dict:
+        """HIP-event times (ms) of the last share_scan / share_fit, their device bytes, entries and evaluations (dmx_engine_share_info)."""
+        r = capi.ShareInfo()
+        check(self._L.dmx_engine_share_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.ShareInfo._fields_ if n != "reserved"}
+
     def triplet_profile(self, base, shares, n_base=None):
         """dmx_engine_triplet over the staged pileup: LL[b][s][t][c] of barcode b as a triplet of the base pair base[b][s] = (v1, v2)
         (v1 = -1: slot not used) and the third donor c, with the read shares shares[t] = (w1, w2, w3) of v1, v2 and c.  `base` is a host

@@ -41,7 +41,9 @@ extern "C" {
                                of clusters); dmx_engine_compose / _composed_pileup / _get_composed / _compose_info (barcodes composed on
                                the device from other barcodes' reads); dmx_engine_doublet_anchored / _get_anchored / _anchored_info
                                (the doublet search over each barcode's best singlets as anchors: wide panels without the V x V grid);
-                               dmx_engine_fit / _get_fit / _fit_info (goodness of fit of each barcode's hypothesis).
+                               dmx_engine_fit / _get_fit / _fit_info (goodness of fit of each barcode's hypothesis);
+                               dmx_engine_share_scan / _get_share_scan / _share_fit / _get_share_fit / _share_info (every partner of a
+                               barcode's anchors scored at alpha = 0, and a doublet's mixing share fitted continuously).
                                Additions only. */
 
 typedef enum {
@@ -1286,6 +1288,118 @@ int dmx_engine_fit(dmx_engine*, const dmx_fit_request*);
 int dmx_engine_get_fit(dmx_engine*, double* obs, double* mean, double* var, int32_t* n_snp, int32_t* n_read, int32_t* n_trunc,
                        int32_t* n_zero);
 int dmx_engine_fit_info(dmx_engine*, dmx_fit_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Continuous mixing share of a doublet (no counterpart in the reference; later, still ABI 8).  Every pass that
+ * names a doublet scores it at listed shares; these two calls treat the share alpha of v2's reads as a parameter.  The model is
+ * dmx_engine_ambient_doublet's, with ONE contamination rho_b per barcode (rho = NULL: 0) instead of a grid, so the values compare with
+ * dmx_engine_ambient / _ambient_doublet.  For barcode b, the pair (v1, v2), entries k = 3 l + m (l of v1, m of v2):
+ *   p_lm = (1 - rho) (0.5 l + (m - l) 0.5 alpha) + rho a_i,   t_r,lm = pR_r (1 - p_lm) + pA_r p_lm,   f_lm = product over the reads of t_r,lm,
+ *   L_i = sum_lm w_lm f_lm,  w_lm = gp[i][v1][l] gp[i][v2][m],   LL(alpha) = sum_i log L_i,
+ * and its derivatives in alpha, with  s_lm = (1 - rho) 0.5 (m - l),  u_r,lm = (pA_r - pR_r) / t_r,lm,  S1_lm = sum_r u,  S2_lm = sum_r u u:
+ *   f'_lm = f_lm s_lm S1_lm,   f''_lm = f_lm ((s_lm S1_lm)^2 - s_lm^2 S2_lm),   D1_i = L'_i / L_i,   D2_i = L''_i / L_i - D1_i^2,
+ *   LL' = sum_i D1_i,   LL'' = sum_i D2_i.
+ * The three entries l = m have s = 0: they add to L only.  As for dmx_engine_ambient_doublet, a pair with no stored read, or where
+ * either sample's gp row is all zero, contributes nothing and is not counted.  With one-hot gp rows LL is concave in alpha; with soft
+ * rows it need not be, and dmx_engine_share_fit finds a LOCAL maximum.
+ * Operations (binary64, every product, sum and quotient rounded on its own: IEEE divisions, no contraction), entries in the order k:
+ *   p_lm      om = 1 - rho, ra = rho a_i;  c_lm = 0.5 l + ((m - l) 0.5) alpha;  p_lm = om c_lm + ra,  q_lm = 1 - p_lm;  s_lm = (om 0.5) (m - l);
+ *   read r    t = pR q_lm + pA p_lm;  f_lm = t of the first stored read, then f_lm t;  for l != m:  u = (pA - pR) / t,  S1 += u,  S2 += u u
+ *             (from +0).  A factor t = 0 makes f_lm = 0 and takes u = 0: the entry then adds nothing to L, L' or L''.  After every eighth
+ *             read an entry with 0 < f_lm < 2^-300 is rescaled into E_lm exactly as dmx_engine_ambient_doublet does (at every depth:
+ *             below 8 reads E_lm stays 0);
+ *   pair      E = max E_lm over the entries with w_lm != 0 and f_lm > 0;  T_lm = w_lm ldexp(f_lm, max(E_lm - E, -1100)) where w_lm != 0,
+ *             else +0;  L = T_00, then L + T_lm;  over the six l != m in entry order  x = s_lm S1_lm,  y = x x - (s_lm s_lm) S2_lm,
+ *             L' = T x of the first, then L' + T x;  L'' likewise with y;  lg = dmx_log(L), and when E != 0
+ *             lg = fma(E, DMX_LOG_LN2HI, fma(E, DMX_LOG_LN2LO, lg));  D1 = L' / L;  D2 = L'' / L - D1 D1.  The scale 2^-E is common to L, L' and
+ *             L'' and cancels in D1 and D2.  Without an entry to take E from, L = 0: lg = -inf and D1, D2 are NaN.
+ *
+ * dmx_engine_share_scan: for anchors[b][t] (t < T <= 4; -1 = slot not used) and EVERY partner v != anchor, v < V <= 1024, the three
+ * numbers LL(0), LL'(0), LL''(0) of the pair (anchor, v) — the score statistic of "v is in the droplet too" is z = LL'(0) / sqrt(-LL''(0)).
+ * At alpha = 0 p_lm does not depend on m, so the read loop runs for l = 0, 1, 2 once per pair for all partners (c_l = 0.5 l; E is the
+ * maximum over the l with gp[i][anchor][l] != 0 and f_l > 0, which is the rule above for any partner whose row is not all zero;
+ * F_l = ldexp(f_l, max(E_l - E, -1100)), +0 where gp[i][anchor][l] = 0 or f_l = 0; T_lm = w_lm F_l where w_lm != 0).  Each (b, t, v) is ONE
+ * serial sum per output over b's pairs in stored (ascending SNP) order, starting at +0.  out[b][t][v] = (LL, LL', LL''); the row of
+ * v = anchor and the rows of unused slots are zero.  n_snp / n_read [b][t] count the pairs / reads with a stored read and a non-zero
+ * anchor row (a partner whose own row is all zero at a pair skips that pair).
+ *
+ * dmx_engine_share_fit: for candidates cand[b][c] = (v1, v2) (c < C <= 8; v1 = -1 = slot not used; otherwise two different samples) the
+ * share alpha_hat in [0, 1] that maximises LL, by a safeguarded Newton iteration on the device; an "evaluation" gives LL, LL', LL'' at one
+ * alpha:
+ *    1. evaluate at 0 and at 1;
+ *    2. if LL'(0) <= 0 and LL'(1) >= 0: alpha_hat = the end with the larger LL, 0 on a tie;
+ *    3. else if LL'(0) <= 0: alpha_hat = 0;
+ *    4. else if LL'(1) >= 0: alpha_hat = 1;
+ *    5. otherwise lo = 0, hi = 1, alpha = start;
+ *    6. evaluate at alpha;
+ *    7. lo = alpha if LL' > 0, else hi = alpha;
+ *    8. alpha' = alpha - LL' / LL'' when LL'' < 0 and lo < alpha' < hi, otherwise alpha' = (lo + hi) / 2;
+ *    9. stop when |alpha' - alpha| <= tol, or when this was evaluation number max_iter of step 6 (DMX_SHARE_NOT_CONVERGED); otherwise
+ *       alpha = alpha' and back to 6;
+ *   10. one final evaluation at alpha_hat = alpha' (DMX_SHARE_INTERIOR).
+ * In cases 2 to 4 the values at alpha_hat are those of step 1.  If a value of step 1 is not finite nothing is iterated: alpha_hat = 0
+ * with DMX_SHARE_AT_0 | DMX_SHARE_NONFINITE.  DMX_SHARE_FLAT: LL''(alpha_hat) >= 0 (no standard error; a pair of samples with the same
+ * one-hot rows gives LL' = LL'' = 0 and ends in case 2 at 0).  DMX_SHARE_NONFINITE: a value at 0, 1 or alpha_hat is not finite.  With
+ * probe in [0, 1] one more evaluation at alpha = probe is returned (not counted in n_eval); probe < 0: none, zeros.
+ * Summation plan of one evaluation: as dmx_engine_fit — pair k of the barcode (k counts every pair, contributing or not) goes to serial
+ * sum k mod 64, each from +0 in ascending k; the 64 sums are added serially onto +0, sum 0 first; the same for LL, LL' and LL''.
+ * values[b][c][13] = alpha_hat | LL, LL', LL'' at alpha_hat | at 0 | at 1 | at probe;  counts[b][c][4] = n_eval (steps 1, 6, 10), status,
+ * n_snp, n_read.  Unused slots get zeros.
+ *
+ * Both calls: no floating-point atomics; a result's bits depend on b's data, the pair, rho_b, a, start / tol / max_iter / probe and V
+ * only — not on B, T or C, the slot, where anchors / cand live, nrd_width, the other barcodes or what ran before.  They run on the
+ * engine's stream, synchronise it before returning (host inputs may be freed then), use buffers of their own and leave every other result
+ * of the engine as it was.
+ * DMX_ERR_ARG: T outside [1, 4]; C outside [1, 8]; V > 1024 (scan); an id outside [-1, V); v1 = v2; a rho_b or a_i outside [0, 1] or not
+ * finite; rho without ambient; tol <= 0; max_iter outside [1, 200]; start outside (0, 1); a probe above 1 or NaN; n_cells / n_snps that do
+ * not match the staged pileup / the genotype matrix.  DMX_ERR_STATE: no pileup or no genotypes yet, or a query before a call.
+ * DMX_ERR_NOMEM: the outputs do not fit the free device memory (checked before anything is allocated; earlier results stay readable). */
+#define DMX_SHARE_INTERIOR      1
+#define DMX_SHARE_AT_0          2
+#define DMX_SHARE_AT_1          4
+#define DMX_SHARE_NOT_CONVERGED 8
+#define DMX_SHARE_FLAT          16
+#define DMX_SHARE_NONFINITE     32
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t n_anchor;            /* T, 1..4 */
+  int32_t anchor_memory;       /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `anchors` lives */
+  const int32_t* anchors;      /* [n_cells][n_anchor] */
+  const double* rho;           /* [n_cells] float64 in [0, 1], HOST; NULL = 0 */
+  const double* ambient;       /* [n_snps] float64 in [0, 1], HOST; NULL only when rho is NULL */
+  int32_t reserved[4];         /* 0 */
+} dmx_share_scan_request;
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t n_cand;              /* C, 1..8 */
+  int32_t cand_memory;         /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `cand` lives */
+  const int32_t* cand;         /* [n_cells][n_cand][2] */
+  const double* rho;           /* [n_cells] float64 in [0, 1], HOST; NULL = 0 */
+  const double* ambient;       /* [n_snps] float64 in [0, 1], HOST; NULL only when rho is NULL */
+  double  start;               /* in (0, 1); the front ends use 0.5 */
+  double  tol;                 /* > 0; the front ends use 1e-6 */
+  double  probe;               /* in [0, 1]: one more evaluation there; negative: none */
+  int32_t max_iter;            /* 1..200; the front ends use 30 */
+  int32_t reserved[5];         /* 0 */
+} dmx_share_fit_request;
+typedef struct {
+  double  scan_ms, fit_ms;     /* HIP-event times of the last k_share_scan / k_share_fit */
+  int64_t scan_bytes, fit_bytes;   /* device bytes of each call's buffers */
+  int64_t scan_entries;        /* (b, t, v) entries scored: used anchor slots x (V - 1) */
+  int64_t fit_used, fit_evals; /* candidate slots in use; evaluations run over them (the probe included) */
+  int32_t n_cells, n_samples, n_anchor, n_cand;
+  int32_t have_scan, have_fit; /* which of the two has run on the staged pileup */
+  int32_t reserved[4];
+} dmx_share_info;
+int dmx_engine_share_scan(dmx_engine*, const dmx_share_scan_request*);
+/* Device->host copies of the last scan (any pointer may be NULL): out[B][T][V][3] f64, n_snp_read[B][T][2] i32. */
+int dmx_engine_get_share_scan(dmx_engine*, double* out, int32_t* n_snp_read);
+int dmx_engine_share_fit(dmx_engine*, const dmx_share_fit_request*);
+/* Device->host copies of the last fit (any pointer may be NULL): values[B][C][13] f64, counts[B][C][4] i32. */
+int dmx_engine_get_share_fit(dmx_engine*, double* values, int32_t* counts);
+int dmx_engine_share_info(dmx_engine*, dmx_share_info* out);
 
 #ifdef __cplusplus
 }
