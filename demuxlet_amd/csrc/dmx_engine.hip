@@ -3635,6 +3635,192 @@ __global__ __launch_bounds__(64 * kFitWaves) void k_fit(PileupView pv, int nrd_w
   }
 }
 
+// ---- site audit (dmx_engine_site_fit) ----------------------------------------------------------------------------
+// k_fit's per-pair terms, summed per SNP instead of per barcode, with the pair's ALT excess k(x) - E k(y) and its variance beside them.
+// Sum order (the contract): the used barcodes as dmx_engine_fit lists them (singlets, then doublets, ascending cell id each), each list
+// cut into chunks of kSiteChunk; inside a chunk the terms are added in list order (k_site_partial), then the chunk partials in ascending
+// chunk order (k_site_fold).  No floating-point atomics.  The slab table is the refinement's (k_snp_blocks at kRefSlabShift).
+constexpr int kSiteChunk = 64;                   // used barcodes per chunk
+struct SitePartial { double v[5]; int32_t n[5]; int32_t pad; };   // obs, mean, var, exc, vexc | n_cell, n_read, n_alt, n_trunc, n_zero
+static_assert(sizeof(SitePartial) == 64, "partial rows of 64 bytes");
+
+// One wavefront per (chunk, SNP slab), the chunk's barcodes one after another as k_refine_partial walks them; per barcode lane = pair
+// over its pairs inside the slab, the per-pair body k_fit's (same operations, same bits: a pair's terms do not depend on which pairs
+// share its tile).  Each lane adds its terms into the slab's LDS accumulators at its SNP: a barcode has at most one pair per SNP, so
+// lanes never collide, and the LDS executes one wavefront's instructions in program order, so barcode b + 1 adds after barcode b.
+// `members` / `chunk_beg` are the whole plan's; this launch covers chunks c0 + blockIdx.y and writes partial rows row0 + blockIdx.y.
+template <bool DBL, int MM>
+__global__ __launch_bounds__(64) void k_site_partial(PileupView pv, int nrd_width, const double* __restrict__ tabs, const float* __restrict__ g, int32_t V,
+                                                     const int64_t* __restrict__ blk, int32_t nblk, const int32_t* __restrict__ members,
+                                                     const int32_t* __restrict__ chunk_beg, int32_t c0, int32_t row0, const int32_t* __restrict__ hyp,
+                                                     const double* __restrict__ alpha, const double* __restrict__ rho,
+                                                     const double* __restrict__ amb, int32_t M, SitePartial* __restrict__ partial) {
+  static_assert(MM == 1 || MM == 2 || MM == 4 || MM == 8, "reads per pair the instantiation holds");
+  constexpr int NC = DBL ? 9 : 3;
+  constexpr bool KEEP = NC * MM <= 36;
+  __shared__ double s_log[DMX_LOG_TABLE_DOUBLES];
+  __shared__ double s_me[128][2];                // by base quality: {mat, err / 3}
+  __shared__ double s_v[5][kRefSlab];
+  __shared__ int32_t s_n[5][kRefSlab];
+  const int lane = threadIdx.x;
+  const int32_t slab = blockIdx.x, chunk = c0 + (int32_t)blockIdx.y;
+  const int32_t s0 = slab << kRefSlabShift;
+  for (int i = lane; i < DMX_LOG_TABLE_DOUBLES; i += 64) s_log[i] = tabs[kLut + i];
+  for (int i = lane; i < 128; i += 64) { s_me[i][0] = tabs[i]; s_me[i][1] = tabs[128 + i]; }
+  for (int i = lane; i < kRefSlab; i += 64) {
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { s_v[j][i] = 0.0; s_n[j][i] = 0; }
+  }
+  __syncthreads();
+  const DmxLogPins lk = dmx_log_pins();
+  const int32_t m_end = __builtin_amdgcn_readfirstlane(chunk_beg[chunk + 1]);
+  for (int32_t mb = __builtin_amdgcn_readfirstlane(chunk_beg[chunk]); mb < m_end; ++mb) {
+    const int32_t cell = __builtin_amdgcn_readfirstlane(members[mb]);
+    const int32_t v1 = __builtin_amdgcn_readfirstlane(hyp[2 * (size_t)cell]);
+    const int32_t v2 = DBL ? __builtin_amdgcn_readfirstlane(hyp[2 * (size_t)cell + 1]) : -1;
+    const double rh = rho[cell], om = 1.0 - rh;
+    double cm[NC];
+    if (DBL) {
+      const double al = alpha[cell];
+#pragma unroll
+      for (int l = 0; l < 3; ++l)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) cm[l * 3 + k] = 0.5 * l + (k - l) * 0.5 * al;
+    } else {
+#pragma unroll
+      for (int c = 0; c < NC; ++c) cm[c] = 0.5 * c;
+    }
+    const int64_t* bt = blk + ((size_t)cell * (nblk + 1) + slab) * 2;
+    const int64_t p_end = bt[2], cell_p0 = pv.cell_pair_off[cell];
+    int64_t rd_base = bt[1];
+    for (int64_t p0 = bt[0]; p0 < p_end; p0 += 64) {
+      const int64_t p = p0 + lane;
+      const bool in = p < p_end;
+      const uint32_t n = in ? load_nrd(pv.pair_nrd, p, nrd_width) : 0u;
+      const int32_t snp = in ? (pv.pair_snp ? pv.pair_snp[p] : (int32_t)(p - cell_p0)) : 0;
+      const uint32_t incl = seg_scan_incl<64>(n);
+      const int64_t off = rd_base + (int64_t)(incl - n);
+      rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      const int k = snp - s0;                          // inside the slab by construction (pairs in ascending SNP order); checked all the same
+      uint32_t m = 0, x = 0;
+      double W[NC], pp[NC], qq[NC], mat[MM], e3[MM];
+#pragma unroll
+      for (int c = 0; c < NC; ++c) { W[c] = 0.0; pp[c] = 0.0; qq[c] = 0.0; }
+#pragma unroll
+      for (int r = 0; r < MM; ++r) { mat[r] = 0.0; e3[r] = 0.0; }
+      if (n > 0 && (unsigned)k < (unsigned)kRefSlab) {
+        const float* gs = g + (size_t)snp * V * 3;
+        const float* r1 = gs + (size_t)v1 * 3;
+        const float x0 = r1[0], x1 = r1[1], x2 = r1[2];
+        bool ok = x0 != 0.f || x1 != 0.f || x2 != 0.f;
+        if (DBL) {
+          const float* r2 = gs + (size_t)v2 * 3;
+          const float y0 = r2[0], y1 = r2[1], y2 = r2[2];
+          ok = ok && (y0 != 0.f || y1 != 0.f || y2 != 0.f);
+          const double g1[3] = {(double)x0, (double)x1, (double)x2}, g2[3] = {(double)y0, (double)y1, (double)y2};
+#pragma unroll
+          for (int c = 0; c < NC; ++c) W[c] = g1[c / 3] * g2[c % 3];    // float32 x float32: exact in float64
+        } else {
+          W[0] = x0; W[1] = x1; W[2] = x2;
+        }
+        if (ok) {
+          m = min(n, (uint32_t)M);
+          const double ra = rh * amb[snp];
+#pragma unroll
+          for (int c = 0; c < NC; ++c) { pp[c] = om * cm[c] + ra; qq[c] = 1.0 - pp[c]; }
+          const uint32_t w0 = load_rd4(pv, off, m);
+          const uint32_t w1 = (MM > 4 && m > 4) ? load_rd4(pv, off + 4, m - 4) : 0u;
+#pragma unroll
+          for (int r = 0; r < MM; ++r) {
+            const uint32_t byte = ((r < 4 ? w0 : w1) >> (8 * (r & 3))) & 0xFF;
+            mat[r] = s_me[byte & 127][0]; e3[r] = s_me[byte & 127][1];
+            if ((uint32_t)r < m) x |= (byte >> 7) << r;
+          }
+        }
+      }
+      int mmax = 0;
+#pragma unroll
+      for (int r = 0; r < MM; ++r)
+        if (__ballot(m > (uint32_t)r)) mmax = r + 1;
+      if (mmax == 0) continue;
+      double t0[KEEP ? MM * NC : 1], t1[KEEP ? MM * NC : 1];
+      if constexpr (KEEP) {
+#pragma unroll
+        for (int r = 0; r < MM; ++r)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            t0[r * NC + c] = mat[r] * qq[c] + e3[r] * pp[c];
+            t1[r * NC + c] = e3[r] * qq[c] + mat[r] * pp[c];
+          }
+      } else {
+        t0[0] = 0.0; t1[0] = 0.0;
+      }
+      bool live = m > 0, zero = false;
+      double lc0 = 0.0;
+      if (live) {
+        const double Lx = fit_pattern<NC, MM, KEEP>(x, m, mmax, t0, t1, mat, e3, pp, qq, W);
+        if (Lx == 0.0) { live = false; zero = true; }
+        else lc0 = dmx_log_is_special(Lx) ? log(Lx) : dmx_log_fast_pinned(Lx, s_log, lk);
+      }
+      double S0 = 0.0, S1 = 0.0, S2 = 0.0, A1 = 0.0, A2 = 0.0;
+      const uint32_t npat = live ? 1u << m : 0u, nmax = 1u << mmax;
+      for (uint32_t y = 0; y < nmax; ++y) {
+        if (y < npat) {
+          const double L = fit_pattern<NC, MM, KEEP>(y, m, mmax, t0, t1, mat, e3, pp, qq, W);
+          if (L != 0.0) {
+            const double lg = dmx_log_is_special(L) ? log(L) : dmx_log_fast_pinned(L, s_log, lk);
+            const double u = lg - lc0, ky = (double)__popc(y);
+            S0 += L; S1 += L * u; S2 += L * (u * u);
+            A1 += L * ky; A2 += L * (ky * ky);
+          }
+        }
+      }
+      if (live) {
+        if (S0 == 0.0 || !(fabs(S0) < INFINITY)) {
+          zero = true;
+        } else {
+          const double e1 = S1 / S0, d = S2 / S0 - e1 * e1;
+          const double a1 = A1 / S0, da = A2 / S0 - a1 * a1;
+          const int32_t kx = (int32_t)__popc(x);
+          s_v[0][k] += lc0; s_v[1][k] += lc0 + e1; s_v[2][k] += d > 0.0 ? d : 0.0;
+          s_v[3][k] += (double)kx - a1; s_v[4][k] += da > 0.0 ? da : 0.0;
+          s_n[0][k] += 1; s_n[1][k] += (int32_t)m; s_n[2][k] += kx; s_n[3][k] += n > (uint32_t)M;
+        }
+      }
+      if (zero) s_n[4][k] += 1;
+      DMX_WAVE_LDS_ORDER();
+    }
+  }
+  SitePartial* out = partial + (size_t)(row0 + (int32_t)blockIdx.y) * pv.S + s0;
+  const int lim = min(kRefSlab, pv.S - s0);
+  for (int i = lane; i < lim; i += 64) {
+    SitePartial r;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { r.v[j] = s_v[j][i]; r.n[j] = s_n[j][i]; }
+    r.pad = 0;
+    out[i] = r;
+  }
+}
+
+// One lane per SNP: adds the `nc` partial rows of this wave of chunks, in ascending chunk order, onto the running sums val[5][S] and
+// cnt[5][S] (zeroed before the first wave).
+__global__ __launch_bounds__(256) void k_site_fold(const SitePartial* __restrict__ partial, int32_t S, int32_t nc, double* __restrict__ val,
+                                                   int32_t* __restrict__ cnt) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S) return;
+  double a[5];
+  int32_t k[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) { a[j] = val[(size_t)j * S + i]; k[j] = cnt[(size_t)j * S + i]; }
+  for (int32_t c = 0; c < nc; ++c) {
+    const SitePartial& r = partial[(size_t)c * S + i];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) { a[j] += r.v[j]; k[j] += r.n[j]; }
+  }
+#pragma unroll
+  for (int j = 0; j < 5; ++j) { val[(size_t)j * S + i] = a[j]; cnt[(size_t)j * S + i] = k[j]; }
+}
+
 // ---- continuous mixing share (dmx_engine_share_scan / dmx_engine_share_fit) ---------------------------------------
 // Section 18's doublet likelihood LL(alpha) of a barcode and a pair (v1, v2) with its first and second derivative in alpha
 // (include/dmx.h states the operations).  Per entry (l, m) the read loop keeps, beside the product f_lm and its exponent, S1 = sum u and
@@ -8828,6 +9014,15 @@ struct dmx_engine {
   int32_t fit_B = 0; bool have_fit = false;
   EventPair fev;
   dmx_fit_info fit_info{};
+  // site audit (dmx_engine_site_fit): its own copies of the hypotheses, alpha[B] | rho[B] and a[S], the plan chunk_beg[n_chunks + 1] |
+  // members[n_used], the partials of one wave, and the results obs | mean | var | exc | vexc [5][S] and n_cell | n_read | n_alt |
+  // n_trunc | n_zero [5][S]; the slab table is the refinement's d_rblk
+  DevBuf<int32_t> d_shyp, d_splan, d_scnt;
+  DevBuf<double> d_spar, d_samb, d_sout;
+  DevBuf<SitePartial> d_spart;
+  int32_t site_S = 0; bool have_site = false;
+  EventPair siev;
+  dmx_site_fit_info site_info{};
   // continuous mixing share (dmx_engine_share_scan / _share_fit): each call's own copies of anchors / cand, rho[B] and a[S], and its
   // results: the scan's (LL, LL', LL'')[B][T][V] and counts [B][T][2]; the fit's 13 doubles and 4 ints per (b, c)
   DevBuf<int32_t> d_ssanc, d_sscnt, d_sfcand, d_sfint;
@@ -9366,6 +9561,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   e->rblk_valid = false; e->have_refined = false; e->have_amb = false; e->have_adbl = false; e->have_cdbl = false;
   e->have_trip = false;
   e->have_fit = false;
+  e->have_site = false;
   e->have_sscan = false; e->have_sfit = false;
   e->have_comp = false;
   e->have_census = false; e->have_cen_info = false; e->have_fis_info = false;
@@ -13358,6 +13554,194 @@ extern "C" int dmx_engine_fit_info(dmx_engine* e, dmx_fit_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_fit_info: null argument");
   if (!e->have_fit) return set_error(DMX_ERR_STATE, "dmx_engine_fit_info: no result on the staged pileup (dmx_engine_fit first)");
   *out = e->fit_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Site audit: dmx_engine_fit's checks and lists, then the refinement's scheme — the slab table of the staged
+// pileup (shared with the refinement: the same kernel at the same shift), per wave of chunks one launch of k_site_partial<false, MM>
+// over the wave's singlet chunks, one of k_site_partial<true, MM> over its doublet chunks, and k_site_fold.
+namespace {
+
+template <bool DBL>
+void launch_site_partial(dmx_engine* e, int32_t MMsel, int32_t nblk, const int32_t* d_mem, const int32_t* d_beg, int32_t c0, int32_t nc, int32_t row0,
+                         int32_t M) {
+  if (nc <= 0) return;
+  const dim3 grid((unsigned)nblk, (unsigned)nc), block(64);
+  const double* par = e->d_spar;
+  const int32_t B = e->pv.B;
+#define DMX_SITE_LAUNCH(MMV)                                                                                                                \
+  hipLaunchKernelGGL((k_site_partial<DBL, MMV>), grid, block, 0, e->stream, e->pv, e->nrd_width, (const double*)e->d_lut, e->d_g, e->V,       \
+                     (const int64_t*)e->d_rblk, nblk, d_mem, d_beg, c0, row0, (const int32_t*)e->d_shyp, par, par + B, (const double*)e->d_samb, \
+                     M, e->d_spart.get())
+  if (MMsel == 1) DMX_SITE_LAUNCH(1);
+  else if (MMsel == 2) DMX_SITE_LAUNCH(2);
+  else if (MMsel == 4) DMX_SITE_LAUNCH(4);
+  else DMX_SITE_LAUNCH(8);
+#undef DMX_SITE_LAUNCH
+}
+
+}  // namespace
+
+extern "C" int dmx_engine_site_fit(dmx_engine* e, const dmx_site_fit_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_site_fit: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_site_fit: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S, M = rq->max_reads;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_site_fit: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (M < 1 || M > kFitMaxReads) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: max_reads %d is not in [1, %d]", M, kFitMaxReads);
+  if (B > 0 && (!rq->hyp || !rq->alpha)) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: missing hyp / alpha");
+  if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: rho is given without ambient");
+  if (rq->hyp_memory != DMX_MEM_HOST && rq->hyp_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: hyp_memory %d", rq->hyp_memory);
+  const size_t per_chunk = sizeof(SitePartial) * (size_t)S;
+  if (rq->partial_bytes < 0 || (rq->partial_bytes > 0 && (uint64_t)rq->partial_bytes < per_chunk))
+    return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: partial_bytes %lld is below one chunk's %zu bytes", (long long)rq->partial_bytes, per_chunk);
+  for (int32_t b = 0; b < B; ++b) {
+    const double al = rq->alpha[b], rh = rq->rho ? rq->rho[b] : 0.0;
+    if (!(al >= 0.0 && al <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: alpha[%d] = %g is not in [0, 1]", b, al);
+    if (!(rh >= 0.0 && rh <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: rho[%d] = %g is not in [0, 1]", b, rh);
+  }
+  if (rq->ambient)
+    for (int32_t i = 0; i < S; ++i)
+      if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0))
+        return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  HIP_TRY(hipSetDevice(e->device));
+  std::vector<int32_t> h((size_t)B * 2);
+  if (B > 0) {
+    if (rq->hyp_memory == DMX_MEM_DEVICE) {
+      HIP_TRY(hipMemcpyAsync(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+    } else {
+      std::memcpy(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B);
+    }
+  }
+  std::vector<int32_t> idx;
+  idx.reserve((size_t)B);
+  int32_t n_sng = 0;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int32_t b = 0; b < B; ++b) {
+      const int32_t v1 = h[2 * (size_t)b], v2 = h[2 * (size_t)b + 1];
+      if (pass == 0) {
+        const bool ok = v1 == -1 || (v1 >= 0 && v1 < V && (v2 == -1 || (v2 >= 0 && v2 < V && v2 != v1)));
+        if (!ok)
+          return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: hyp[%d] = (%d, %d) is not -1, a sample in [0, %d) or two different samples", b, v1, v2, V);
+        if (v1 >= 0 && v2 < 0) { idx.push_back(b); ++n_sng; }
+      } else if (v1 >= 0 && v2 >= 0) {
+        idx.push_back(b);
+      }
+    }
+  const int32_t n_used = (int32_t)idx.size(), n_dbl = n_used - n_sng;
+  // ---- plan: chunk_beg[nch + 1] | members[n_used]; no chunk straddles the two lists
+  const int32_t ncs = (n_sng + kSiteChunk - 1) / kSiteChunk, ncd = (n_dbl + kSiteChunk - 1) / kSiteChunk, nch = ncs + ncd;
+  std::vector<int32_t> plan;
+  plan.reserve((size_t)nch + 1 + (size_t)n_used);
+  for (int32_t c = 0; c < ncs; ++c) plan.push_back(c * kSiteChunk);
+  for (int32_t c = 0; c < ncd; ++c) plan.push_back(n_sng + c * kSiteChunk);
+  plan.push_back(n_used);                                             // (the last singlet chunk ends at chunk_beg[ncs] = n_sng either way)
+  plan.insert(plan.end(), idx.begin(), idx.end());
+  const size_t o_mem = (size_t)nch + 1;
+
+  const int32_t nblk = (int32_t)(((int64_t)S + kRefSlab - 1) >> kRefSlabShift);
+  const size_t out_b = sizeof(double) * 5 * (size_t)S, cnt_b = sizeof(int32_t) * 5 * (size_t)S, par_b = sizeof(double) * 2 * (size_t)B;
+  const size_t blk_b = sizeof(int64_t) * 2 * (size_t)B * ((size_t)nblk + 1);
+  const bool build_blk = !e->rblk_valid || e->rblk_S != S;
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  const size_t budget = rq->partial_bytes > 0 ? (size_t)rq->partial_bytes : std::min<size_t>((size_t)4 << 30, free_b / 6);
+  const int32_t cpw = (int32_t)std::max<size_t>(1, std::min<size_t>({per_chunk ? budget / per_chunk : (size_t)65535, (size_t)65535, (size_t)std::max(nch, 1)}));
+  const size_t part_b = nch > 0 ? per_chunk * (size_t)cpw : 0;
+  const size_t need = out_b + cnt_b + par_b + sizeof(int32_t) * 2 * (size_t)B + sizeof(int32_t) * plan.size() + sizeof(double) * (size_t)S + part_b;
+  const size_t grow = (out_b > e->d_sout.cap() ? need - part_b : 0) + (part_b > e->d_spart.cap() ? part_b : 0) +
+                      (build_blk && blk_b > e->d_rblk.cap() ? blk_b : 0);
+  if (grow && grow + grow / 16 > free_b)
+    return set_error(DMX_ERR_NOMEM, "dmx_engine_site_fit: the results and partials of %d SNPs need %zu more bytes, %zu are free", S, grow, free_b);
+  if (int rc = e->d_sout.ensure(out_b)) return rc;
+  if (int rc = e->d_scnt.ensure(cnt_b)) return rc;
+  if (int rc = e->d_spar.ensure(par_b)) return rc;
+  if (int rc = e->d_shyp.ensure(sizeof(int32_t) * 2 * (size_t)B)) return rc;
+  if (int rc = e->d_splan.ensure(sizeof(int32_t) * plan.size())) return rc;
+  if (int rc = e->d_samb.ensure(sizeof(double) * (size_t)S)) return rc;
+  if (part_b) if (int rc = e->d_spart.ensure(part_b)) return rc;
+  if (build_blk && B > 0) if (int rc = e->d_rblk.ensure(blk_b)) return rc;
+  e->have_site = false;
+  std::vector<double> par((size_t)B * 2, 0.0);
+  for (int32_t b = 0; b < B; ++b) {
+    par[(size_t)b] = rq->alpha[b];
+    if (rq->rho) par[(size_t)B + b] = rq->rho[b];
+  }
+  if (B > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_shyp, h.data(), sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_spar, par.data(), par_b, hipMemcpyHostToDevice, e->stream));
+  }
+  HIP_TRY(hipMemcpyAsync(e->d_splan, plan.data(), sizeof(int32_t) * plan.size(), hipMemcpyHostToDevice, e->stream));
+  if (S > 0) {
+    HIP_TRY(hipMemsetAsync(e->d_sout, 0, out_b, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_scnt, 0, cnt_b, e->stream));
+    if (rq->ambient) HIP_TRY(hipMemcpyAsync(e->d_samb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
+    else HIP_TRY(hipMemsetAsync(e->d_samb, 0, sizeof(double) * (size_t)S, e->stream));
+  }
+  if (build_blk && B > 0) {
+    hipLaunchKernelGGL(k_snp_blocks, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, kRefSlabShift, nblk, e->d_rblk);
+    HIP_TRY(hipGetLastError());
+  }
+  e->rblk_valid = true; e->rblk_S = S;
+  const int32_t MMsel = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8;
+  int32_t n_waves = 0;
+  if (int rc = e->siev.record_start(e->stream)) return rc;
+  if (nch > 0 && S > 0) {
+    const int32_t* d_beg = e->d_splan;
+    const int32_t* d_mem = e->d_splan + o_mem;
+    for (int32_t c0 = 0; c0 < nch; c0 += cpw, ++n_waves) {
+      const int32_t c1 = std::min(c0 + cpw, nch), cs1 = std::min(c1, ncs), cd0 = std::max(c0, ncs);
+      launch_site_partial<false>(e, MMsel, nblk, d_mem, d_beg, c0, cs1 - c0, 0, M);
+      HIP_TRY(hipGetLastError());
+      launch_site_partial<true>(e, MMsel, nblk, d_mem, d_beg, cd0, c1 - cd0, cd0 - c0, M);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_site_fold, dim3((unsigned)((S + 255) / 256)), dim3(256), 0, e->stream, (const SitePartial*)e->d_spart.get(), S, c1 - c0,
+                         e->d_sout.get(), e->d_scnt.get());
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (int rc = e->siev.record_stop(e->stream)) return rc;
+  std::vector<int32_t> tz((size_t)S * 2);
+  if (S > 0) HIP_TRY(hipMemcpyAsync(tz.data(), e->d_scnt + 3 * (size_t)S, sizeof(int32_t) * 2 * (size_t)S, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return
+  float ms = 0.f;
+  if (int rc = e->siev.elapsed_ms(&ms)) return rc;
+  dmx_site_fit_info& inf = e->site_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.kernel_ms = ms; inf.bytes = (int64_t)need; inf.partial_bytes = (int64_t)part_b;
+  inf.n_chunks = nch; inf.n_waves = n_waves; inf.chunk_cells = kSiteChunk; inf.slab_snps = kRefSlab;
+  inf.n_cells = B; inf.n_snps = S; inf.n_used = n_used; inf.n_singlet = n_sng; inf.n_doublet = n_dbl; inf.max_reads = M;
+  for (int32_t i = 0; i < S; ++i) { inf.n_trunc += tz[(size_t)i]; inf.n_zero += tz[(size_t)S + i]; }
+  e->site_S = S; e->have_site = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_site_fit(dmx_engine* e, double* obs, double* mean, double* var, double* exc, double* vexc, int32_t* n_cell,
+                                       int32_t* n_read, int32_t* n_alt, int32_t* n_trunc, int32_t* n_zero) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_site_fit: null engine");
+  if (!e->have_site) return set_error(DMX_ERR_STATE, "dmx_engine_get_site_fit: no result on the staged pileup (dmx_engine_site_fit first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t S = (size_t)e->site_S;
+  if (!S) return DMX_OK;
+  double* const dp[5] = {obs, mean, var, exc, vexc};
+  int32_t* const ip[5] = {n_cell, n_read, n_alt, n_trunc, n_zero};
+  for (int k = 0; k < 5; ++k)
+    if (dp[k]) HIP_TRY(hipMemcpy(dp[k], e->d_sout + k * S, sizeof(double) * S, hipMemcpyDeviceToHost));
+  for (int k = 0; k < 5; ++k)
+    if (ip[k]) HIP_TRY(hipMemcpy(ip[k], e->d_scnt + k * S, sizeof(int32_t) * S, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_site_fit_info(dmx_engine* e, dmx_site_fit_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit_info: null argument");
+  if (!e->have_site) return set_error(DMX_ERR_STATE, "dmx_engine_site_fit_info: no result on the staged pileup (dmx_engine_site_fit first)");
+  *out = e->site_info;
   return DMX_OK;
 }
 

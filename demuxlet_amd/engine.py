@@ -709,6 +709,37 @@ class Engine:
         check(self._L.dmx_engine_fit_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.FitInfo._fields_ if n != "reserved"}
 
+    def site_fit(self, hyp, alpha, rho=None, ambient=None, max_reads: int = 4, partial_bytes: int = 0) -> dict:
+        """dmx_engine_site_fit over the staged pileup: the goodness of fit of every SNP's row under one hypothesis per barcode (fit_profile's
+        arguments).  `partial_bytes` caps the chunk-partial buffer (0 = the default budget); the results do not depend on it.  Returns a dict
+        of obs / mean / var / exc / vexc (f64 [S]: fit_profile's three sums over the barcodes at the SNP, the signed excess of ALT reads over
+        their expectation and its variance) and n_cell / n_read / n_alt / n_trunc / n_zero (i32 [S])."""
+        al = np.ascontiguousarray(alpha, dtype=np.float64)
+        if al.shape != (self.B,):
+            raise ValueError(f"alpha must be [{self.B}]")
+        rh, amb, n_snps = self._share_soup(rho, ambient)
+        if isinstance(hyp, int):
+            h, mem, ptr = None, capi.DMX_MEM_DEVICE, hyp
+        else:
+            h = np.ascontiguousarray(hyp, dtype=np.int32)
+            if h.shape != (self.B, 2):
+                raise ValueError(f"hyp must be [{self.B}][2]")
+            mem, ptr = capi.DMX_MEM_HOST, (h.ctypes.data if h.size else None)
+        rq = capi.SiteFitRequest(self.B, n_snps, mem, int(max_reads), ptr, al.ctypes.data if al.size else None,
+                                 rh.ctypes.data if rh is not None and rh.size else None, amb.ctypes.data if amb is not None and amb.size else None,
+                                 int(partial_bytes))
+        check(self._L.dmx_engine_site_fit(self._h, C.byref(rq)))
+        out = {k: np.zeros(n_snps) for k in ("obs", "mean", "var", "exc", "vexc")}
+        out.update({k: np.zeros(n_snps, dtype=np.int32) for k in ("n_cell", "n_read", "n_alt", "n_trunc", "n_zero")})
+        check(self._L.dmx_engine_get_site_fit(self._h, *(v.ctypes.data for v in out.values())))
+        return out
+
+    def site_fit_info(self) -> dict:
+        """HIP-event time (ms) of the last site_fit, its device bytes, chunks, waves and totals (dmx_engine_site_fit_info)."""
+        r = capi.SiteFitInfo()
+        check(self._L.dmx_engine_site_fit_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.SiteFitInfo._fields_ if n != "reserved"}
+
     def _share_soup(self, rho, ambient):
         rh = amb = None
         if rho is not None:

@@ -43,7 +43,8 @@ extern "C" {
                                (the doublet search over each barcode's best singlets as anchors: wide panels without the V x V grid);
                                dmx_engine_fit / _get_fit / _fit_info (goodness of fit of each barcode's hypothesis);
                                dmx_engine_share_scan / _get_share_scan / _share_fit / _get_share_fit / _share_info (every partner of a
-                               barcode's anchors scored at alpha = 0, and a doublet's mixing share fitted continuously).
+                               barcode's anchors scored at alpha = 0, and a doublet's mixing share fitted continuously);
+                               dmx_engine_site_fit / _get_site_fit / _site_fit_info (goodness of fit of each SNP's row).
                                Additions only. */
 
 typedef enum {
@@ -1400,6 +1401,67 @@ int dmx_engine_share_fit(dmx_engine*, const dmx_share_fit_request*);
 /* Device->host copies of the last fit (any pointer may be NULL): values[B][C][13] f64, counts[B][C][4] i32. */
 int dmx_engine_get_share_fit(dmx_engine*, double* values, int32_t* counts);
 int dmx_engine_share_info(dmx_engine*, dmx_share_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Site audit: goodness of fit per SNP (no counterpart in the reference; later, still ABI 8).  dmx_engine_fit asks
+ * whether a barcode's call explains that barcode's reads, summed over its SNPs; this call asks the transposed question: does SNP i's row
+ * of the genotype matrix explain the reads the pool holds there, summed over the barcodes?  The request's fields are dmx_fit_request's,
+ * with the same meaning and the same checks (one hypothesis hyp[b] = (v1, v2), alpha[b], rho[b], ambient a[n_snps], M = max_reads).
+ * Per-pair terms: exactly dmx_engine_fit's, operation for operation, as the block above states them — which pairs count (a stored read,
+ * no all-zero gp row of a hypothesised sample), the first m = min(n, M) reads in stored order, W_c, p_c, t_r, F_c, L(y), c0 = log L(x),
+ * S0, S1, S2 over y ascending, e1 = S1 / S0, d = S2 / S0 - e1 e1, and the rule for n_zero (L(x) = 0, or S0 zero or not finite: the pair
+ * contributes nothing and is counted in n_zero).  Two more sums run over y ascending from +0, a pattern with L(y) = 0 adding nothing:
+ * with k(y) the number of ALT reads in y (an exact small integer as a double),
+ *   A1 += L(y) k(y),   A2 += L(y) (k(y) k(y))   (the product of the k's first),   a1 = A1 / S0,
+ * the pair's signed ALT excess is k(x) - a1 and its variance max(0, A2 / S0 - a1 a1) (IEEE divisions, every operation rounded on its own).
+ * Outputs per SNP i, summed over the counted pairs at i:
+ *   obs += c0,  mean += c0 + e1,  var += max(0, d),  exc += k(x) - a1,  vexc += max(0, A2 / S0 - a1 a1)                   (float64)
+ *   n_cell (pairs), n_read (m per pair), n_alt (k(x) per pair: observed ALT among the reads used), n_trunc (pairs with n > M), n_zero  (int32)
+ * A SNP that no counted pair covers gets zero rows.  Z = (obs - mean) / sqrt(var) is the site's fit; exc / sqrt(vexc) tells
+ * unexplained ALT reads (> 0) from missing ones (< 0).
+ * Summation plan: the used barcodes are listed singlet hypotheses first, then doublet hypotheses, each in ascending cell id (the order
+ * in which dmx_engine_fit lists them).  Each of the two lists is cut into chunks of 64 consecutive entries; the last chunk of a list may
+ * be short and no chunk straddles the two lists.  For a SNP, the terms of a chunk's barcodes are added onto +0 in list order (a
+ * barcode has at most one pair per SNP); the chunk partials are then added onto +0 in ascending chunk order.  Slab width, launch
+ * geometry and the number of buffer waves are not part of the contract.  No floating-point atomics: a SNP's ten numbers depend only on
+ * the pairs at that SNP, their barcodes' hypotheses and list positions, M, and the gp rows and a_i touched — not on the other SNPs,
+ * partial_bytes, the stream, where hyp lives, or what ran before.  The call runs on the engine's stream, synchronises it before
+ * returning, uses buffers of its own (and the refinement's slab table of the staged pileup, which it builds when the refinement has
+ * not) and leaves every other result of the engine as it was.
+ * partial_bytes: 0 = the default budget of the chunk-partial buffer (64 bytes per chunk and SNP), 4 GiB or a sixth of the free memory
+ * as for dmx_engine_refine_genotypes; otherwise the cap on that buffer.  The chunks are processed in waves that fit it.
+ * DMX_ERR_ARG: every case of dmx_engine_fit, and a partial_bytes that is negative or below one chunk's worth (64 n_snps).
+ * DMX_ERR_STATE: no pileup or no genotypes yet, or a query before a call (dmx_engine_set_pileup clears the results).
+ * DMX_ERR_NOMEM: the buffers do not fit the free device memory (earlier results stay readable). */
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t hyp_memory;          /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `hyp` lives */
+  int32_t max_reads;           /* M, 1..8 */
+  const int32_t* hyp;          /* [n_cells][2] */
+  const double* alpha;         /* [n_cells] float64 in [0, 1], HOST */
+  const double* rho;           /* [n_cells] float64 in [0, 1], HOST; NULL = 0 */
+  const double* ambient;       /* [n_snps] float64 in [0, 1], HOST; NULL only when rho is NULL */
+  int64_t partial_bytes;       /* cap on the chunk-partial buffer; 0 = default */
+  int32_t reserved[4];         /* 0 */
+} dmx_site_fit_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the last call's k_site_partial / k_site_fold launches */
+  int64_t bytes;               /* device bytes of the call's buffers, the partials included */
+  int64_t partial_bytes;       /* ... of the chunk-partial buffer */
+  int64_t n_trunc, n_zero;     /* totals over the SNPs */
+  int32_t n_chunks, n_waves;   /* chunks of 64 barcodes; waves of chunks the partial buffer held in turn */
+  int32_t chunk_cells, slab_snps;
+  int32_t n_cells, n_snps, n_used, n_singlet, n_doublet;
+  int32_t max_reads;
+  int32_t reserved[4];
+} dmx_site_fit_info;
+int dmx_engine_site_fit(dmx_engine*, const dmx_site_fit_request*);
+/* Device->host copies of the last call's results (any pointer may be NULL): obs / mean / var / exc / vexc [S] f64, n_cell / n_read /
+ * n_alt / n_trunc / n_zero [S] i32. */
+int dmx_engine_get_site_fit(dmx_engine*, double* obs, double* mean, double* var, double* exc, double* vexc, int32_t* n_cell,
+                            int32_t* n_read, int32_t* n_alt, int32_t* n_trunc, int32_t* n_zero);
+int dmx_engine_site_fit_info(dmx_engine*, dmx_site_fit_info* out);
 
 #ifdef __cplusplus
 }
