@@ -55,6 +55,7 @@ SYMBOLS = [
     "dmx_engine_fit", "dmx_engine_get_fit", "dmx_engine_fit_info",
     "dmx_engine_share_scan", "dmx_engine_get_share_scan", "dmx_engine_share_fit", "dmx_engine_get_share_fit", "dmx_engine_share_info",
     "dmx_engine_site_fit", "dmx_engine_get_site_fit", "dmx_engine_site_fit_info",
+    "dmx_engine_redraw", "dmx_engine_redrawn_pileup", "dmx_engine_get_redrawn", "dmx_engine_redraw_info",
 ]
 DMX_PRIOR_MASKED, DMX_PRIOR_BAD = 1, 2
 
@@ -194,6 +195,22 @@ class SiteFitInfo(C.Structure):          # dmx_site_fit_info
                 ("n_chunks", C.c_int32), ("n_waves", C.c_int32), ("chunk_cells", C.c_int32), ("slab_snps", C.c_int32), ("n_cells", C.c_int32),
                 ("n_snps", C.c_int32), ("n_used", C.c_int32), ("n_singlet", C.c_int32), ("n_doublet", C.c_int32), ("max_reads", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
+
+
+DMX_REDRAW_PAIR, DMX_REDRAW_DONOR = 0, 1
+
+
+class RedrawRequest(C.Structure):        # dmx_redraw_request
+    _fields_ = [("n_cells", C.c_int32), ("n_snps", C.c_int32), ("hyp_memory", C.c_int32), ("genotype_draw", C.c_int32), ("hyp", C.c_void_p),
+                ("alpha", C.c_void_p), ("rho", C.c_void_p), ("ambient", C.c_void_p), ("seed", C.c_uint64), ("geno_seed", C.c_uint64),
+                ("index_base", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+class RedrawInfo(C.Structure):           # dmx_redraw_info
+    _fields_ = [("kernel_ms", C.c_double), ("bytes_read", C.c_int64), ("bytes_written", C.c_int64), ("n_pairs_drawn", C.c_int64),
+                ("n_pairs_skipped", C.c_int64), ("n_reads_drawn", C.c_int64), ("n_reads_kept", C.c_int64), ("n_cells", C.c_int32),
+                ("n_used", C.c_int32), ("n_singlet", C.c_int32), ("n_doublet", C.c_int32), ("genotype_draw", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
 
 
 DMX_SHARE_INTERIOR, DMX_SHARE_AT_0, DMX_SHARE_AT_1, DMX_SHARE_NOT_CONVERGED, DMX_SHARE_FLAT, DMX_SHARE_NONFINITE = 1, 2, 4, 8, 16, 32
@@ -454,6 +471,8 @@ def load() -> C.CDLL:
         "dmx_engine_share_scan": [vp, vp], "dmx_engine_get_share_scan": [vp, vp, vp], "dmx_engine_share_fit": [vp, vp],
         "dmx_engine_get_share_fit": [vp, vp, vp], "dmx_engine_share_info": [vp, vp],
         "dmx_engine_site_fit": [vp, vp], "dmx_engine_get_site_fit": [vp] * 11, "dmx_engine_site_fit_info": [vp, vp],
+        "dmx_engine_redraw": [vp, vp], "dmx_engine_redrawn_pileup": [vp, vp], "dmx_engine_get_redrawn": [vp, vp, vp],
+        "dmx_engine_redraw_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

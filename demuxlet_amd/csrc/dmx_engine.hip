@@ -9023,6 +9023,14 @@ struct dmx_engine {
   int32_t site_S = 0; bool have_site = false;
   EventPair siev;
   dmx_site_fit_info site_info{};
+  // model-drawn null pool (dmx_engine_redraw): its own copies of the hypotheses, alpha[B] | rho[B] and a[S], the used barcodes' ids,
+  // the per-barcode counts [4][B], and the results: the redrawn read bytes (grow-only, like the composed pileup) and geno[pairs][2]
+  DevBuf<int32_t> d_rwhyp, d_rwidx, d_rwcnt;
+  DevBuf<double> d_rwpar, d_rwamb;
+  DevBuf<uint8_t> d_rwreads; DevBuf<int8_t> d_rwgeno;
+  int64_t rw_pairs = 0; bool have_redraw = false;
+  EventPair rwev;
+  dmx_redraw_info redraw_info{};
   // continuous mixing share (dmx_engine_share_scan / _share_fit): each call's own copies of anchors / cand, rho[B] and a[S], and its
   // results: the scan's (LL, LL', LL'')[B][T][V] and counts [B][T][2]; the fit's 13 doubles and 4 ints per (b, c)
   DevBuf<int32_t> d_ssanc, d_sscnt, d_sfcand, d_sfint;
@@ -9562,6 +9570,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   e->have_trip = false;
   e->have_fit = false;
   e->have_site = false;
+  e->have_redraw = false;
   e->have_sscan = false; e->have_sfit = false;
   e->have_comp = false;
   e->have_census = false; e->have_cen_info = false; e->have_fis_info = false;
@@ -13742,6 +13751,158 @@ extern "C" int dmx_engine_site_fit_info(dmx_engine* e, dmx_site_fit_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit_info: null argument");
   if (!e->have_site) return set_error(DMX_ERR_STATE, "dmx_engine_site_fit_info: no result on the staged pileup (dmx_engine_site_fit first)");
   *out = e->site_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Model-drawn null pool (csrc/dmx_redraw.hpp): dmx_engine_fit's checks and list of used barcodes, a device copy of
+// the whole read array into the output, -1 into geno, and one launch of k_redraw over the used barcodes.
+#include "dmx_redraw.hpp"
+
+extern "C" int dmx_engine_redraw(dmx_engine* e, const dmx_redraw_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: null argument");
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_redraw: no pileup staged (dmx_engine_set_pileup first)");
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_redraw: no genotype matrix (dmx_engine_set_genotypes first)");
+  const int32_t B = e->pv.B, V = e->V, S = e->S;
+  if (e->pv.S != S)
+    return set_error(DMX_ERR_STATE, "dmx_engine_redraw: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
+  if ((e->d_rwreads && e->pv.reads == (const uint8_t*)e->d_rwreads.get()) || (e->d_cmpoff && e->pv.cell_pair_off == (const int64_t*)e->d_cmpoff.get()))
+    return set_error(DMX_ERR_STATE, "dmx_engine_redraw: the staged pileup is this engine's own redrawn or composed pileup (it would be overwritten)");
+  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: n_cells %d, the staged pileup has %d", rq->n_cells, B);
+  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (rq->genotype_draw != DMX_REDRAW_PAIR && rq->genotype_draw != DMX_REDRAW_DONOR)
+    return set_error(DMX_ERR_ARG, "dmx_engine_redraw: genotype_draw %d is neither DMX_REDRAW_PAIR nor DMX_REDRAW_DONOR", rq->genotype_draw);
+  if (rq->index_base < 0) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: index_base %lld is negative", (long long)rq->index_base);
+  if (B > 0 && (!rq->hyp || !rq->alpha)) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: missing hyp / alpha");
+  if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: rho is given without ambient");
+  if (rq->hyp_memory != DMX_MEM_HOST && rq->hyp_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: hyp_memory %d", rq->hyp_memory);
+  for (int32_t b = 0; b < B; ++b) {
+    const double al = rq->alpha[b], rh = rq->rho ? rq->rho[b] : 0.0;
+    if (!(al >= 0.0 && al <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: alpha[%d] = %g is not in [0, 1]", b, al);
+    if (!(rh >= 0.0 && rh <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: rho[%d] = %g is not in [0, 1]", b, rh);
+  }
+  if (rq->ambient)
+    for (int32_t i = 0; i < S; ++i)
+      if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  HIP_TRY(hipSetDevice(e->device));
+  std::vector<int32_t> h((size_t)B * 2);
+  std::vector<int64_t> h_po((size_t)B + 1, 0), h_ro((size_t)B + 1, 0);
+  if (B > 0 && rq->hyp_memory == DMX_MEM_DEVICE) HIP_TRY(hipMemcpyAsync(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyDeviceToHost, e->stream));
+  else if (B > 0) std::memcpy(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B);
+  HIP_TRY(hipMemcpyAsync(h_po.data(), e->pv.cell_pair_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipMemcpyAsync(h_ro.data(), e->pv.cell_read_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  std::vector<int32_t> idx;
+  idx.reserve((size_t)B);
+  int32_t n_sng = 0;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int32_t b = 0; b < B; ++b) {
+      const int32_t v1 = h[2 * (size_t)b], v2 = h[2 * (size_t)b + 1];
+      if (pass == 0) {
+        const bool ok = v1 == -1 || (v1 >= 0 && v1 < V && (v2 == -1 || (v2 >= 0 && v2 < V && v2 != v1)));
+        if (!ok)
+          return set_error(DMX_ERR_ARG, "dmx_engine_redraw: hyp[%d] = (%d, %d) is not -1, a sample in [0, %d) or two different samples", b, v1, v2, V);
+        if (v1 >= 0 && v2 < 0) { idx.push_back(b); ++n_sng; }
+      } else if (v1 >= 0 && v2 >= 0) {
+        idx.push_back(b);
+      }
+    }
+  const int32_t n_used = (int32_t)idx.size(), n_dbl = n_used - n_sng;
+  // the view's extent: offsets are absolute in a view of a caller's device arrays, so the arrays reach to the last cell's end
+  const int64_t P = h_po[(size_t)B], R = e->pv.R;
+  if (P < 0 || R < 0 || h_ro[(size_t)B] > R) return set_error(DMX_ERR_STATE, "dmx_engine_redraw: the staged offsets leave the read array");
+  const size_t reads_b = (size_t)R + 64, geno_b = 2 * (size_t)P + 16;   // (slack: the lean K1 reads four bytes at a time)
+  const size_t cnt_b = sizeof(int32_t) * 4 * (size_t)B, par_b = sizeof(double) * 2 * (size_t)B;
+  const size_t need = reads_b + geno_b + cnt_b + par_b + sizeof(int32_t) * 3 * (size_t)B + sizeof(double) * (size_t)S;
+  {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t have = e->d_rwreads.cap() + e->d_rwgeno.cap();
+    if ((reads_b > e->d_rwreads.cap() || geno_b > e->d_rwgeno.cap()) && need + need / 8 > free_b + have)
+      return set_error(DMX_ERR_NOMEM, "dmx_engine_redraw: %lld read bytes and %lld pairs need %zu bytes, %zu are free", (long long)R, (long long)P, need, free_b);
+  }
+  e->have_redraw = false;
+  if (int rc = e->d_rwreads.ensure(reads_b)) return rc;
+  if (int rc = e->d_rwgeno.ensure(geno_b)) return rc;
+  if (int rc = e->d_rwcnt.ensure(cnt_b)) return rc;
+  if (int rc = e->d_rwpar.ensure(par_b)) return rc;
+  if (int rc = e->d_rwhyp.ensure(sizeof(int32_t) * 2 * (size_t)B)) return rc;
+  if (int rc = e->d_rwidx.ensure(sizeof(int32_t) * (size_t)B)) return rc;
+  if (int rc = e->d_rwamb.ensure(sizeof(double) * (size_t)S)) return rc;
+  std::vector<double> par((size_t)B * 2, 0.0);
+  for (int32_t b = 0; b < B; ++b) {
+    par[(size_t)b] = rq->alpha[b];
+    if (rq->rho) par[(size_t)B + b] = rq->rho[b];
+  }
+  if (B > 0) {
+    HIP_TRY(hipMemcpyAsync(e->d_rwhyp, h.data(), sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(e->d_rwpar, par.data(), par_b, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_rwcnt, 0, cnt_b, e->stream));
+  }
+  if (n_used > 0) HIP_TRY(hipMemcpyAsync(e->d_rwidx, idx.data(), sizeof(int32_t) * (size_t)n_used, hipMemcpyHostToDevice, e->stream));
+  if (S > 0) {
+    if (rq->ambient) HIP_TRY(hipMemcpyAsync(e->d_rwamb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
+    else HIP_TRY(hipMemsetAsync(e->d_rwamb, 0, sizeof(double) * (size_t)S, e->stream));
+  }
+  // unused barcodes, pairs without stored reads, skipped pairs and kept reads: a plain copy of everything, which the kernel then overwrites
+  if (R > 0) HIP_TRY(hipMemcpyAsync(e->d_rwreads, e->pv.reads, (size_t)R, hipMemcpyDeviceToDevice, e->stream));
+  HIP_TRY(hipMemsetAsync(e->d_rwgeno, 0xFF, geno_b, e->stream));
+  dmx_rdw::Ctx c{};
+  c.pv = e->pv; c.nrd_width = e->nrd_width; c.tabs = (const double*)e->d_lut; c.g = e->d_g; c.V = V;
+  c.idx = e->d_rwidx; c.n_idx = n_used; c.hyp = e->d_rwhyp; c.alpha = e->d_rwpar; c.rho = e->d_rwpar + B; c.amb = e->d_rwamb;
+  c.seed = rq->seed; c.geno_seed = rq->geno_seed; c.index_base = rq->index_base; c.donor_draw = rq->genotype_draw == DMX_REDRAW_DONOR;
+  c.B = B; c.o_reads = e->d_rwreads; c.o_geno = e->d_rwgeno; c.cnt = e->d_rwcnt;
+  if (int rc = e->rwev.record_start(e->stream)) return rc;
+  if (n_used > 0) {
+    hipLaunchKernelGGL(dmx_rdw::k_redraw, dim3((unsigned)((n_used + dmx_rdw::kWaves - 1) / dmx_rdw::kWaves)), dim3(64 * dmx_rdw::kWaves), 0, e->stream, c);
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->rwev.record_stop(e->stream)) return rc;
+  std::vector<int32_t> cnt((size_t)B * 4);
+  if (B > 0) HIP_TRY(hipMemcpyAsync(cnt.data(), e->d_rwcnt, cnt_b, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return
+  float ms = 0.f;
+  if (int rc = e->rwev.elapsed_ms(&ms)) return rc;
+  dmx_redraw_info& inf = e->redraw_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.kernel_ms = ms; inf.n_cells = B; inf.n_used = n_used; inf.n_singlet = n_sng; inf.n_doublet = n_dbl; inf.genotype_draw = rq->genotype_draw;
+  const int64_t pair_bytes = (e->pv.pair_snp ? 4 : 0) + e->nrd_width;
+  for (int32_t k = 0; k < n_used; ++k) {
+    const size_t b = (size_t)idx[(size_t)k];
+    const int64_t drawn = cnt[b], skipped = cnt[(size_t)B + b], rd = cnt[2 * (size_t)B + b], rk = cnt[3 * (size_t)B + b];
+    inf.n_pairs_drawn += drawn; inf.n_pairs_skipped += skipped; inf.n_reads_drawn += rd; inf.n_reads_kept += rk;
+    inf.bytes_read += (h_po[b + 1] - h_po[b]) * pair_bytes + (drawn + skipped) * 12 * (k < n_sng ? 1 : 2) + rd + rk + 44;
+    inf.bytes_written += rd + 2 * drawn + 16;
+  }
+  e->rw_pairs = P; e->have_redraw = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_redrawn_pileup(dmx_engine* e, dmx_pileup* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_redrawn_pileup: null argument");
+  if (!e->have_redraw) return set_error(DMX_ERR_STATE, "dmx_engine_redrawn_pileup: nothing redrawn on the staged pileup (dmx_engine_redraw first)");
+  std::memset(out, 0, sizeof *out);
+  out->n_cells = e->pv.B; out->n_snps = e->pv.S; out->n_pairs = e->rw_pairs; out->n_reads = e->pv.R;
+  out->cell_pair_off = e->pv.cell_pair_off; out->cell_read_off = e->pv.cell_read_off;
+  out->pair_snp = e->pv.pair_snp; out->pair_nrd = e->pv.pair_nrd; out->nrd_width = e->nrd_width;
+  out->memory = DMX_MEM_DEVICE; out->reads = e->d_rwreads;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_redrawn(dmx_engine* e, uint8_t* reads, int8_t* geno) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_redrawn: null engine");
+  if (!e->have_redraw) return set_error(DMX_ERR_STATE, "dmx_engine_get_redrawn: nothing redrawn on the staged pileup (dmx_engine_redraw first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  if (reads && e->pv.R) HIP_TRY(hipMemcpy(reads, e->d_rwreads, (size_t)e->pv.R, hipMemcpyDeviceToHost));
+  if (geno && e->rw_pairs) HIP_TRY(hipMemcpy(geno, e->d_rwgeno, 2 * (size_t)e->rw_pairs, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_redraw_info(dmx_engine* e, dmx_redraw_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_redraw_info: null argument");
+  if (!e->have_redraw) return set_error(DMX_ERR_STATE, "dmx_engine_redraw_info: nothing redrawn on the staged pileup (dmx_engine_redraw first)");
+  *out = e->redraw_info;
   return DMX_OK;
 }
 

@@ -740,6 +740,54 @@ class Engine:
         check(self._L.dmx_engine_site_fit_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.SiteFitInfo._fields_ if n != "reserved"}
 
+    def redraw(self, hyp, alpha, rho=None, ambient=None, seed: int = 0, geno_seed: int = 0, genotype_draw: str = "donor",
+               index_base: int = 0) -> dict:
+        """dmx_engine_redraw over the staged pileup: every stored read of a used barcode gets a new allele drawn from fit_profile's law
+        under hyp[b] (fit_profile's arguments; `hyp` a host array [B][2] or a device pointer).  genotype_draw "donor": a donor has one
+        genotype per SNP in every barcode and replicate (keyed by geno_seed); "pair": a genotype per pair (keyed by seed), fit_profile's
+        own law.  Barcode b is hashed as id index_base + b.  Returns the info dict (redraw_info)."""
+        modes = {"pair": capi.DMX_REDRAW_PAIR, "donor": capi.DMX_REDRAW_DONOR}
+        if genotype_draw not in modes:
+            raise ValueError("genotype_draw must be 'donor' or 'pair'")
+        al = np.ascontiguousarray(alpha, dtype=np.float64)
+        if al.shape != (self.B,):
+            raise ValueError(f"alpha must be [{self.B}]")
+        rh, amb, n_snps = self._share_soup(rho, ambient)
+        if isinstance(hyp, int):
+            h, mem, ptr = None, capi.DMX_MEM_DEVICE, hyp
+        else:
+            h = np.ascontiguousarray(hyp, dtype=np.int32)
+            if h.shape != (self.B, 2):
+                raise ValueError(f"hyp must be [{self.B}][2]")
+            mem, ptr = capi.DMX_MEM_HOST, (h.ctypes.data if h.size else None)
+        rq = capi.RedrawRequest(self.B, n_snps, mem, modes[genotype_draw], ptr, al.ctypes.data if al.size else None,
+                                rh.ctypes.data if rh is not None and rh.size else None, amb.ctypes.data if amb is not None and amb.size else None,
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(geno_seed) & 0xFFFFFFFFFFFFFFFF, int(index_base))
+        check(self._L.dmx_engine_redraw(self._h, C.byref(rq)))
+        return self.redraw_info()
+
+    def redraw_info(self) -> dict:
+        """HIP-event time (ms) of the last redraw's kernel, its algorithmic bytes and its counts (dmx_engine_redraw_info)."""
+        r = capi.RedrawInfo()
+        check(self._L.dmx_engine_redraw_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.RedrawInfo._fields_ if n != "reserved"}
+
+    def redrawn_pileup(self) -> capi.Pileup:
+        """The redrawn pileup as a device-resident dmx_pileup (dmx_engine_redrawn_pileup) for another engine's set_pileup_struct or for
+        demuxlet_run: the staged source's own offsets and pair arrays with new reads; the rd_* counters are NULL (a caller that needs
+        them attaches the source's host arrays).  Owned by this engine: valid until its next redraw / set_pileup / close."""
+        st = capi.Pileup()
+        check(self._L.dmx_engine_redrawn_pileup(self._h, C.byref(st)))
+        return st
+
+    def get_redrawn(self) -> dict:
+        """The last redraw copied to the host (dmx_engine_get_redrawn): reads (uint8 [n_reads]) and geno (int8 [n_pairs][2]: the drawn
+        genotypes of v1 and v2, -1 = not drawn)."""
+        st = self.redrawn_pileup()
+        reads = np.zeros(st.n_reads, dtype=np.uint8); geno = np.zeros((st.n_pairs, 2), dtype=np.int8)
+        check(self._L.dmx_engine_get_redrawn(self._h, reads.ctypes.data if reads.size else None, geno.ctypes.data if geno.size else None))
+        return {"reads": reads, "geno": geno}
+
     def _share_soup(self, rho, ambient):
         rh = amb = None
         if rho is not None:

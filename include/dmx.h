@@ -44,7 +44,9 @@ extern "C" {
                                dmx_engine_fit / _get_fit / _fit_info (goodness of fit of each barcode's hypothesis);
                                dmx_engine_share_scan / _get_share_scan / _share_fit / _get_share_fit / _share_info (every partner of a
                                barcode's anchors scored at alpha = 0, and a doublet's mixing share fitted continuously);
-                               dmx_engine_site_fit / _get_site_fit / _site_fit_info (goodness of fit of each SNP's row).
+                               dmx_engine_site_fit / _get_site_fit / _site_fit_info (goodness of fit of each SNP's row);
+                               dmx_engine_redraw / _redrawn_pileup / _get_redrawn / _redraw_info (every read's allele drawn again
+                               from the model: the staged pool's null pool).
                                Additions only. */
 
 typedef enum {
@@ -1462,6 +1464,84 @@ int dmx_engine_site_fit(dmx_engine*, const dmx_site_fit_request*);
 int dmx_engine_get_site_fit(dmx_engine*, double* obs, double* mean, double* var, double* exc, double* vexc, int32_t* n_cell,
                             int32_t* n_read, int32_t* n_alt, int32_t* n_trunc, int32_t* n_zero);
 int dmx_engine_site_fit_info(dmx_engine*, dmx_site_fit_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Model-drawn null pool (no counterpart in the reference; later, still ABI 8).  The parametric bootstrap of the
+ * staged pileup: its structure stays — which barcode covers which SNP, with how many reads, at which base qualities — and every stored
+ * read's allele is drawn again from dmx_engine_fit's law under the barcode's hypothesis.  In the result the truth is known and the
+ * model holds exactly, so what a statistic does there is its null law at this pool's depth.  The redrawn pileup has the source's exact
+ * layout; only bit 7 (the allele) of a read byte changes, the base quality (the low 7 bits) is kept.
+ * The law is dmx_engine_fit's: hyp[b] = (v1, v2) with alpha[b], rho[b] and the soup a[n_snps] mean what they mean in dmx_fit_request,
+ * the components c, their weights W_c and ALT shares p_c are the ones stated there.  For a pair (b, i) with n >= 1 stored reads a
+ * genotype is drawn for v1, and one for v2 if the hypothesis is a doublet — independently, each from its own gp row; W_c is the product
+ * of the two rows' entries, so this IS the draw of the component.  Then EVERY stored read r = 0 .. n - 1 (not only the first M) gets a
+ * new allele in stored order.  Pairs without stored reads (allele-2-only, see dmx_pileup) and unused barcodes (v1 = -1) are copied as
+ * they are.
+ * Bits (binary64, every product, sum and quotient rounded on its own: no contraction; integers mod 2^64; mix64 is dmx_engine_compose's;
+ * GOLD = 0x9E3779B97F4A7C15; barcode b has the id = index_base + b; n_snp is the pair's SNP id):
+ *   read uniform                    u  = mix64(mix64(seed + GOLD (4 id + 1)) + (n_snp << 32 | r)) >> 32
+ *   genotype uniform, PAIR, slot s  ug = mix64(mix64(seed + GOLD (4 id + 2 + s)) + (n_snp << 32)) >> 32          (s = 0 for v1, 1 for v2)
+ *   genotype uniform, DONOR, sample v   ug = mix64(mix64(geno_seed + GOLD (4 v + 2)) + (n_snp << 32)) >> 32
+ *     DONOR depends on neither the barcode, the slot, seed nor index_base: every barcode of donor v, in every replicate, sees the same
+ *     genotype at SNP i, as in a real pool.  PAIR draws a genotype per pair, which is dmx_engine_fit's own law.  The first-level keys of
+ *     one barcode's read stream (4 id + 1) and its PAIR genotype streams (4 id + 2, 4 id + 3) are different multiples of GOLD.
+ *   genotype from a row (w0, w1, w2), float32 widened:   c01 = w0 + w1,   s = c01 + w2,   x = ((double) ug 2^-32) s,
+ *     g = 0 if x < w0, else 1 if x < c01, else 2.   A genotype of weight zero is never drawn: x >= 0 rules out g = 0 at w0 = 0; w1 = 0
+ *     makes c01 = w0, an empty interval; and x < s strictly (ug 2^-32 <= 1 - 2^-32, s a normal number whose spacing is far finer), so
+ *     with w2 = 0, where s = c01, g = 2 is never reached.
+ *   a row that skips the pair: a hypothesised sample's row is all zero, or has a negative or non-finite entry.  The pair's reads are
+ *     copied unchanged, its geno entries stay -1, and it is counted in n_pairs_skipped.
+ *   read: om = 1 - rho, ra = rho a_i, c_c and p_c = om c_c + ra exactly as dmx_engine_fit states them, for the drawn component only
+ *     (c_g = 0.5 g; c_lm = 0.5 l + ((m - l) 0.5) alpha); with mat / err the phred tables at the read's base quality, e3 = err / 3 rounded once:
+ *       q1 = 1 - p_c,   num = e3 q1 + mat p_c,   den = mat + e3,   q = num / den,   thr = (uint64) (q 4294967296.0)   (truncation);
+ *     the new allele is 1 iff (uint64) u < thr: q = 0 never draws ALT, q = 1 (thr = 2^32) always does.  If !(q >= 0 && q <= 1) the read
+ *     keeps its stored allele and is counted in n_reads_kept.  q is t_r(c, 1) / (t_r(c, 0) + t_r(c, 1)) of dmx_engine_fit: the law of
+ *     a read's allele given that the read is stored.
+ * One kernel, k_redraw, after a device copy of the read array: plain vector stores, no floating-point atomics, nothing from another
+ * barcode.  A barcode's bytes depend only on its own pairs, its hypothesis, its id, the seeds, and the gp rows and a_i it touches — not on
+ * B, the dense or sparse layout, nrd_width, what ran before, or where hyp lives.  The call runs on the engine's stream, synchronises it
+ * before returning (host inputs may be freed then), uses buffers of its own and leaves every other result of the engine as it was.
+ * DMX_ERR_ARG: every argument case of dmx_engine_fit (max_reads apart: there is none); a genotype_draw that is neither constant;
+ * index_base < 0.  DMX_ERR_STATE: no pileup or no genotypes yet; the staged pileup is this engine's own redrawn or composed pileup;
+ * a query before a call (dmx_engine_set_pileup clears the result).  DMX_ERR_NOMEM: the outputs do not fit the free device memory. */
+#define DMX_REDRAW_PAIR  0
+#define DMX_REDRAW_DONOR 1
+typedef struct {
+  int32_t n_cells;             /* = the staged pileup's n_cells */
+  int32_t n_snps;              /* = the genotype matrix's n_snps */
+  int32_t hyp_memory;          /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `hyp` lives */
+  int32_t genotype_draw;       /* DMX_REDRAW_PAIR or DMX_REDRAW_DONOR */
+  const int32_t* hyp;          /* [n_cells][2], dmx_fit_request's meaning; v1 = -1: the barcode's reads are copied unchanged */
+  const double* alpha;         /* [n_cells] float64 in [0, 1], HOST */
+  const double* rho;           /* [n_cells] float64 in [0, 1], HOST; NULL = 0 */
+  const double* ambient;       /* [n_snps] float64 in [0, 1], HOST; NULL only when rho is NULL */
+  uint64_t seed, geno_seed;
+  int64_t  index_base;         /* >= 0: barcode b is hashed as id = index_base + b */
+  int32_t  reserved[4];        /* 0 */
+} dmx_redraw_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the last call's k_redraw (the copy of the read array before it is not in it) */
+  int64_t bytes_read, bytes_written;   /* algorithmic device bytes of k_redraw alone: the used barcodes' pair headers, the gp rows and read
+                                          bytes of their pairs with stored reads, 44 bytes of parameters per barcode; the redrawn read bytes,
+                                          two geno bytes per drawn pair, 16 bytes of counts per barcode */
+  int64_t n_pairs_drawn;       /* pairs of used barcodes with a stored read and usable rows */
+  int64_t n_pairs_skipped;     /* ... with a stored read and a row that skips the pair */
+  int64_t n_reads_drawn;       /* reads of drawn pairs that got a new allele */
+  int64_t n_reads_kept;        /* reads of drawn pairs whose q was not in [0, 1] */
+  int32_t n_cells, n_used, n_singlet, n_doublet;
+  int32_t genotype_draw;
+  int32_t reserved[3];
+} dmx_redraw_info;
+int dmx_engine_redraw(dmx_engine*, const dmx_redraw_request*);
+/* The redrawn pileup as a DMX_MEM_DEVICE view (rd_* NULL: the caller attaches host counters where a consumer needs them), for
+ * dmx_engine_set_pileup of ANOTHER engine or dmx_job.pileup: the same n_*, cell_pair_off, cell_read_off, pair_snp (NULL if dense),
+ * pair_nrd and nrd_width as the staged source — the source's own arrays — and new reads[] owned by the engine.  Valid until the next
+ * redraw / set_pileup / destroy of this engine. */
+int dmx_engine_redrawn_pileup(dmx_engine*, dmx_pileup* out);
+/* Device->host copies (either pointer may be NULL): reads [the view's n_reads]; geno [the view's n_pairs][2] int8, the drawn genotypes
+ * of v1 and v2 per pair, -1 = not drawn (no stored read, a skipped pair, an unused barcode, the second slot of a singlet). */
+int dmx_engine_get_redrawn(dmx_engine*, uint8_t* reads, int8_t* geno);
+int dmx_engine_redraw_info(dmx_engine*, dmx_redraw_info* out);
 
 #ifdef __cplusplus
 }
