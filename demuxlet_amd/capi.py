@@ -56,6 +56,7 @@ SYMBOLS = [
     "dmx_engine_share_scan", "dmx_engine_get_share_scan", "dmx_engine_share_fit", "dmx_engine_get_share_fit", "dmx_engine_share_info",
     "dmx_engine_site_fit", "dmx_engine_get_site_fit", "dmx_engine_site_fit_info",
     "dmx_engine_redraw", "dmx_engine_redrawn_pileup", "dmx_engine_get_redrawn", "dmx_engine_redraw_info",
+    "dmx_engine_geno_compare", "dmx_engine_get_geno_compare", "dmx_engine_geno_compare_info",
 ]
 DMX_PRIOR_MASKED, DMX_PRIOR_BAD = 1, 2
 
@@ -211,6 +212,20 @@ class RedrawInfo(C.Structure):           # dmx_redraw_info
                 ("n_pairs_skipped", C.c_int64), ("n_reads_drawn", C.c_int64), ("n_reads_kept", C.c_int64), ("n_cells", C.c_int32),
                 ("n_used", C.c_int32), ("n_singlet", C.c_int32), ("n_doublet", C.c_int32), ("genotype_draw", C.c_int32),
                 ("reserved", C.c_int32 * 3)]
+
+
+DMX_KIN_MAX_COLUMNS = 4096
+
+
+class KinRequest(C.Structure):           # dmx_kin_request
+    _fields_ = [("n_snps", C.c_int32), ("n_a", C.c_int32), ("n_b", C.c_int32), ("ga", C.c_void_p), ("gb", C.c_void_p),
+                ("weight", C.c_void_p), ("g_memory", C.c_int32), ("reserved", C.c_int32)]
+
+
+class KinInfo(C.Structure):              # dmx_kin_info
+    _fields_ = [("rows_ms", C.c_double), ("tile_ms", C.c_double), ("flop", C.c_int64), ("bytes", C.c_int64), ("n_invalid_a", C.c_int64),
+                ("n_invalid_b", C.c_int64), ("n_snps", C.c_int32), ("n_a", C.c_int32), ("n_b", C.c_int32), ("tile_a", C.c_int32),
+                ("tile_b", C.c_int32), ("chunk_snps", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
 DMX_SHARE_INTERIOR, DMX_SHARE_AT_0, DMX_SHARE_AT_1, DMX_SHARE_NOT_CONVERGED, DMX_SHARE_FLAT, DMX_SHARE_NONFINITE = 1, 2, 4, 8, 16, 32
@@ -473,6 +488,7 @@ def load() -> C.CDLL:
         "dmx_engine_site_fit": [vp, vp], "dmx_engine_get_site_fit": [vp] * 11, "dmx_engine_site_fit_info": [vp, vp],
         "dmx_engine_redraw": [vp, vp], "dmx_engine_redrawn_pileup": [vp, vp], "dmx_engine_get_redrawn": [vp, vp, vp],
         "dmx_engine_redraw_info": [vp, vp],
+        "dmx_engine_geno_compare": [vp, vp], "dmx_engine_get_geno_compare": [vp, vp, vp, vp], "dmx_engine_geno_compare_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

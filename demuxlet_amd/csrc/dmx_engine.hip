@@ -9038,6 +9038,15 @@ struct dmx_engine {
   int32_t ss_B = 0, ss_T = 0, ss_V = 0, sf_B = 0, sf_C = 0; bool have_sscan = false, have_sfit = false;
   EventPair ssev, sfev;
   dmx_share_info share_info{};
+  // joint genotype tables (dmx_engine_geno_compare): device copies of host gp matrices and of the weight, the two [S][V][4] images,
+  // the invalid rows per column [n_a | n_b], and the table [n_a][n_b][4][4]
+  DevBuf<float> d_knga, d_kngb;
+  DevBuf<double> d_knw, d_knia, d_knib, d_knt;
+  DevBuf<int32_t> d_kncnt;
+  std::vector<int32_t> kn_invalid;                 // the host copy of d_kncnt
+  bool have_kin = false;
+  EventPair knrev, kntev;
+  dmx_kin_info kin_info{};
 };
 
 namespace {
@@ -14113,5 +14122,147 @@ extern "C" int dmx_engine_share_info(dmx_engine* e, dmx_share_info* out) {
     return set_error(DMX_ERR_STATE, "dmx_engine_share_info: neither call has run on the staged pileup (dmx_engine_share_scan / _share_fit first)");
   *out = e->share_info;
   out->have_scan = e->have_sscan; out->have_fit = e->have_sfit;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Joint genotype tables (csrc/dmx_kin.hpp): the arguments are checked on the host (the weight is small), host
+// matrices are copied to buffers of the call's own, k_kin_rows runs once per side and k_kin_tile once.
+#include "dmx_kin.hpp"
+
+extern "C" int dmx_engine_geno_compare(dmx_engine* e, const dmx_kin_request* rq) {
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare: null argument");
+  const int32_t S = rq->n_snps, VA = rq->n_a, VB = rq->n_b;
+  if (VA < 1 || VA > DMX_KIN_MAX_COLUMNS) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare: n_a %d is not in [1, %d]", VA, DMX_KIN_MAX_COLUMNS);
+  if (VB < 1 || VB > DMX_KIN_MAX_COLUMNS) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare: n_b %d is not in [1, %d]", VB, DMX_KIN_MAX_COLUMNS);
+  if (S < 0) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare: n_snps %d is negative", S);
+  if (rq->reserved != 0) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare: reserved is %d, not 0", rq->reserved);
+  if (rq->g_memory != DMX_MEM_HOST && rq->g_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare: g_memory %d", rq->g_memory);
+  if (!rq->gb && VB != VA) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare: gb is NULL (B is A) but n_b %d is not n_a %d", VB, VA);
+  if (!rq->ga) {
+    if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_geno_compare: ga is NULL and no genotype matrix is staged (dmx_engine_set_genotypes first)");
+    if (e->S != S || e->V != VA)
+      return set_error(DMX_ERR_STATE, "dmx_engine_geno_compare: ga is NULL and the staged matrix is %d x %d, the request says %d x %d", e->S, e->V, S, VA);
+  }
+  HIP_TRY(hipSetDevice(e->device));
+  const bool on_host = rq->g_memory == DMX_MEM_HOST;
+  if (rq->weight && S > 0) {
+    std::vector<double> hw;
+    const double* w = rq->weight;
+    if (!on_host) {
+      hw.resize((size_t)S);
+      HIP_TRY(hipMemcpyAsync(hw.data(), rq->weight, sizeof(double) * (size_t)S, hipMemcpyDeviceToHost, e->stream));
+      HIP_TRY(hipStreamSynchronize(e->stream));
+      w = hw.data();
+    }
+    for (int32_t i = 0; i < S; ++i)
+      if (!(w[i] >= 0.0 && w[i] < INFINITY)) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare: weight[%d] = %g is not a finite number >= 0", i, w[i]);
+  }
+  const size_t na = (size_t)S * (size_t)VA, nb = (size_t)S * (size_t)VB;
+  const size_t ga_b = rq->ga && on_host ? sizeof(float) * 3 * na : 0, gb_b = rq->gb && on_host ? sizeof(float) * 3 * nb : 0;
+  const size_t w_b = rq->weight && on_host ? sizeof(double) * (size_t)S : 0;
+  const size_t ia_b = sizeof(double) * 4 * na, ib_b = sizeof(double) * 4 * nb, tab_b = sizeof(double) * 16 * (size_t)VA * (size_t)VB;
+  const size_t cnt_b = sizeof(int32_t) * ((size_t)VA + (size_t)VB);
+  {
+    size_t free_b = 0, total_b = 0, grow = 0, freed = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    const size_t want[7] = {ga_b, gb_b, w_b, ia_b, ib_b, tab_b, cnt_b};
+    const size_t caps[7] = {e->d_knga.cap(), e->d_kngb.cap(), e->d_knw.cap(), e->d_knia.cap(), e->d_knib.cap(), e->d_knt.cap(), e->d_kncnt.cap()};
+    for (int k = 0; k < 7; ++k)
+      if (want[k] > caps[k]) { grow += want[k] + want[k] / 16 + 16; freed += caps[k]; }
+    if (grow > free_b + freed)
+      return set_error(DMX_ERR_NOMEM, "dmx_engine_geno_compare: %d SNPs x (%d + %d) columns need %zu bytes of matrices, %zu of images and %zu of table; %zu more than are held, %zu are free",
+                       S, VA, VB, ga_b + gb_b + w_b, ia_b + ib_b, tab_b, grow, free_b);
+  }
+  e->have_kin = false;
+  if (ga_b) if (int rc = e->d_knga.ensure(ga_b)) return rc;
+  if (gb_b) if (int rc = e->d_kngb.ensure(gb_b)) return rc;
+  if (w_b) if (int rc = e->d_knw.ensure(w_b)) return rc;
+  if (int rc = e->d_knia.ensure(ia_b)) return rc;
+  if (int rc = e->d_knib.ensure(ib_b)) return rc;
+  if (int rc = e->d_knt.ensure(tab_b)) return rc;
+  if (int rc = e->d_kncnt.ensure(cnt_b)) return rc;
+  const float* d_ga = e->d_g;
+  if (rq->ga) {
+    d_ga = rq->ga;
+    if (on_host) {
+      if (na > 0) HIP_TRY(hipMemcpyAsync(e->d_knga, rq->ga, ga_b, hipMemcpyHostToDevice, e->stream));
+      d_ga = e->d_knga;
+    }
+  }
+  const float* d_gb = d_ga;
+  if (rq->gb) {
+    d_gb = rq->gb;
+    if (on_host) {
+      if (nb > 0) HIP_TRY(hipMemcpyAsync(e->d_kngb, rq->gb, gb_b, hipMemcpyHostToDevice, e->stream));
+      d_gb = e->d_kngb;
+    }
+  }
+  const double* d_w = nullptr;
+  if (rq->weight && S > 0) {
+    d_w = rq->weight;
+    if (on_host) {
+      HIP_TRY(hipMemcpyAsync(e->d_knw, rq->weight, w_b, hipMemcpyHostToDevice, e->stream));
+      d_w = e->d_knw;
+    }
+  }
+  HIP_TRY(hipMemsetAsync(e->d_kncnt, 0, cnt_b, e->stream));
+  if (int rc = e->knrev.record_start(e->stream)) return rc;
+  if (na > 0) {
+    const unsigned ga_grid = (unsigned)std::min<size_t>((na + 255) / 256, (size_t)1 << 20), gb_grid = (unsigned)std::min<size_t>((nb + 255) / 256, (size_t)1 << 20);
+    hipLaunchKernelGGL(dmx_kin::k_kin_rows, dim3(ga_grid), dim3(256), 0, e->stream, d_ga, (int64_t)na, VA, d_w, e->d_knia.get(), e->d_kncnt.get());
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(dmx_kin::k_kin_rows, dim3(gb_grid), dim3(256), 0, e->stream, d_gb, (int64_t)nb, VB, (const double*)nullptr, e->d_knib.get(),
+                       e->d_kncnt.get() + VA);
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->knrev.record_stop(e->stream)) return rc;
+  // the wide block where its tiling alone fills the chip; the bits are the same either way
+  const bool wide = (int64_t)((VA + 31) / 32) * ((VB + 31) / 32) >= dmx_kin::kWideTiles;
+  const int32_t tile = wide ? 32 : 16;
+  const dim3 grid((unsigned)((VB + tile - 1) / tile), (unsigned)((VA + tile - 1) / tile));
+  const int32_t chunk = wide ? dmx_kin::kChunkWide : dmx_kin::kChunkNarrow;
+  const size_t lds_b = 2 * (size_t)(2 * chunk * 2 * tile) * 16;
+  if (int rc = e->kntev.record_start(e->stream)) return rc;
+  if (wide)
+    hipLaunchKernelGGL((dmx_kin::k_kin_tile<2, 2, dmx_kin::kChunkWide>), grid, dim3(dmx_kin::kThreads), lds_b, e->stream, (const double*)e->d_knia, (const double*)e->d_knib, S, VA, VB, e->d_knt.get());
+  else
+    hipLaunchKernelGGL((dmx_kin::k_kin_tile<1, 1, dmx_kin::kChunkNarrow>), grid, dim3(dmx_kin::kThreads), lds_b, e->stream, (const double*)e->d_knia, (const double*)e->d_knib, S, VA, VB, e->d_knt.get());
+  HIP_TRY(hipGetLastError());
+  if (int rc = e->kntev.record_stop(e->stream)) return rc;
+  e->kn_invalid.assign((size_t)VA + (size_t)VB, 0);
+  HIP_TRY(hipMemcpyAsync(e->kn_invalid.data(), e->d_kncnt, cnt_b, hipMemcpyDeviceToHost, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));        // the caller's inputs may go away after return
+  float ms_r = 0.f, ms_t = 0.f;
+  if (int rc = e->knrev.elapsed_ms(&ms_r)) return rc;
+  if (int rc = e->kntev.elapsed_ms(&ms_t)) return rc;
+  dmx_kin_info& inf = e->kin_info;
+  std::memset(&inf, 0, sizeof inf);
+  inf.rows_ms = ms_r; inf.tile_ms = ms_t;
+  inf.flop = 2 * 16 * (int64_t)VA * (int64_t)VB * (int64_t)S;
+  inf.bytes = (int64_t)(sizeof(float) * 3 * (na + nb) + (d_w ? sizeof(double) * (size_t)S : 0) + 2 * (ia_b + ib_b) + tab_b);
+  for (int32_t v = 0; v < VA; ++v) inf.n_invalid_a += e->kn_invalid[(size_t)v];
+  for (int32_t v = 0; v < VB; ++v) inf.n_invalid_b += e->kn_invalid[(size_t)VA + v];
+  inf.n_snps = S; inf.n_a = VA; inf.n_b = VB; inf.tile_a = tile; inf.tile_b = tile; inf.chunk_snps = chunk;
+  e->have_kin = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_geno_compare(dmx_engine* e, double* table, int32_t* n_valid_a, int32_t* n_valid_b) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_geno_compare: null engine");
+  if (!e->have_kin) return set_error(DMX_ERR_STATE, "dmx_engine_get_geno_compare: nothing compared yet (dmx_engine_geno_compare first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const dmx_kin_info& inf = e->kin_info;
+  if (table) HIP_TRY(hipMemcpy(table, e->d_knt, sizeof(double) * 16 * (size_t)inf.n_a * (size_t)inf.n_b, hipMemcpyDeviceToHost));
+  if (n_valid_a) for (int32_t v = 0; v < inf.n_a; ++v) n_valid_a[v] = inf.n_snps - e->kn_invalid[(size_t)v];
+  if (n_valid_b) for (int32_t v = 0; v < inf.n_b; ++v) n_valid_b[v] = inf.n_snps - e->kn_invalid[(size_t)inf.n_a + v];
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_geno_compare_info(dmx_engine* e, dmx_kin_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare_info: null argument");
+  if (!e->have_kin) return set_error(DMX_ERR_STATE, "dmx_engine_geno_compare_info: nothing compared yet (dmx_engine_geno_compare first)");
+  *out = e->kin_info;
   return DMX_OK;
 }

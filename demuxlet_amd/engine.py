@@ -189,9 +189,11 @@ class Engine:
         if g.ndim != 3 or g.shape[1] != self.V or g.shape[2] != 3:
             raise ValueError(f"g must be [S][{self.V}][3]")
         check(self._L.dmx_engine_set_genotypes(self._h, g.ctypes.data, g.shape[0], capi.DMX_MEM_HOST))
+        self._g_snps = g.shape[0]
 
     def set_genotypes_device(self, ptr: int, n_snps: int) -> None:
         check(self._L.dmx_engine_set_genotypes(self._h, C.c_void_p(ptr), n_snps, capi.DMX_MEM_DEVICE))
+        self._g_snps = int(n_snps)
 
     def set_pileup(self, pl: HostPileup) -> None:
         st = pl.as_struct()
@@ -779,6 +781,71 @@ class Engine:
         st = capi.Pileup()
         check(self._L.dmx_engine_redrawn_pileup(self._h, C.byref(st)))
         return st
+
+    def geno_compare(self, ga=None, gb=None, weight=None, memory: int = capi.DMX_MEM_HOST, n_snps: Optional[int] = None,
+                     n_a: Optional[int] = None, n_b: Optional[int] = None):
+        """dmx_engine_geno_compare: the weighted 4 x 4 joint tables of every column of ga [S][VA][3] with every column of gb [S][VB][3]
+        (float32 gp-style rows), T[a][b][x][y] = sum_i weight_i ra_i[a][x] rb_i[b][y] with r = (p0, p1, p2, valid); include/dmx.h
+        defines the bits.  ga = None: the engine's staged genotype matrix; gb = None: B is A; weight = None: ones.  With
+        memory = DMX_MEM_DEVICE ga / gb / weight are device pointers (ints) and n_snps, n_a, n_b give the shapes.  Needs no pileup.
+        Returns (table [VA][VB][4][4] float64, n_valid_a [VA] int32, n_valid_b [VB] int32)."""
+        keep = []
+
+        def side(g):
+            if g is None:
+                return None, None
+            if memory == capi.DMX_MEM_DEVICE:
+                return int(g), None
+            a = np.ascontiguousarray(g, dtype=np.float32)
+            if a.ndim != 3 or a.shape[2] != 3 or a.shape[1] < 1:
+                raise ValueError("a genotype matrix must be [S][V][3] with V >= 1")
+            keep.append(a)
+            return (a.ctypes.data if a.size else None), a.shape
+
+        pa, sa = side(ga)
+        pb, sb = side(gb)
+        if memory == capi.DMX_MEM_DEVICE:
+            if n_snps is None or (ga is not None and n_a is None) or (gb is not None and n_b is None):
+                raise ValueError("device inputs need n_snps, n_a and n_b")
+            S = int(n_snps)
+            VA = int(n_a) if ga is not None else self.V
+            VB = int(n_b) if gb is not None else VA
+            pw = int(weight) if weight is not None else None
+        else:
+            if sa is None and sb is None and n_snps is None:
+                n_snps = getattr(self, "_g_snps", None)
+                if n_snps is None:
+                    raise ValueError("ga is None and no genotype matrix was staged with set_genotypes (pass n_snps)")
+            S = sa[0] if sa is not None else sb[0] if sb is not None else int(n_snps)
+            if sa is not None and sb is not None and sa[0] != sb[0]:
+                raise ValueError(f"ga has {sa[0]} SNPs, gb has {sb[0]}")
+            VA = sa[1] if sa is not None else self.V
+            VB = sb[1] if sb is not None else VA
+            pw = None
+            if weight is not None:
+                w = np.ascontiguousarray(weight, dtype=np.float64)
+                if w.shape != (S,):
+                    raise ValueError(f"weight must be [{S}]")
+                keep.append(w)
+                pw = w.ctypes.data if w.size else None
+            # an empty host matrix has no address to give; the engine reads nothing at S = 0, but NULL would mean "the staged matrix"
+            if ga is not None and pa is None:
+                keep.append(np.zeros(4, dtype=np.float32)); pa = keep[-1].ctypes.data
+            if gb is not None and pb is None:
+                keep.append(np.zeros(4, dtype=np.float32)); pb = keep[-1].ctypes.data
+        rq = capi.KinRequest(S, VA, VB, pa, pb, pw, memory, 0)
+        check(self._L.dmx_engine_geno_compare(self._h, C.byref(rq)))
+        table = np.zeros((VA, VB, 4, 4), dtype=np.float64)
+        nva = np.zeros(VA, dtype=np.int32); nvb = np.zeros(VB, dtype=np.int32)
+        check(self._L.dmx_engine_get_geno_compare(self._h, table.ctypes.data, nva.ctypes.data, nvb.ctypes.data))
+        return table, nva, nvb
+
+    def geno_compare_info(self) -> dict:
+        """HIP-event times (ms) of the last geno_compare's two kernels, its FLOP and algorithmic bytes, the tile kernel's tile_a, tile_b
+        and chunk_snps, and the invalid-row counts (dmx_engine_geno_compare_info)."""
+        r = capi.KinInfo()
+        check(self._L.dmx_engine_geno_compare_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.KinInfo._fields_ if n != "reserved"}
 
     def get_redrawn(self) -> dict:
         """The last redraw copied to the host (dmx_engine_get_redrawn): reads (uint8 [n_reads]) and geno (int8 [n_pairs][2]: the drawn

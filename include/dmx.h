@@ -1543,6 +1543,55 @@ int dmx_engine_redrawn_pileup(dmx_engine*, dmx_pileup* out);
 int dmx_engine_get_redrawn(dmx_engine*, uint8_t* reads, int8_t* geno);
 int dmx_engine_redraw_info(dmx_engine*, dmx_redraw_info* out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Joint genotype tables (no counterpart in the reference; later, still ABI 8).  Every other pass compares reads
+ * with genotype columns; this one compares genotype columns with each other: for every pair (a, b) of columns of two gp-style matrices
+ * ga[n_snps][n_a][3] and gb[n_snps][n_b][3] (float32: VCF transforms, refined rows, cluster rows) the weighted 4 x 4 joint table of
+ * their rows over the SNPs.  Relatedness, cross-run matching and the expected separability of two donors are functions of it.
+ * Row transform, per (SNP i, column v), binary64, every operation rounded on its own (no contraction):
+ *   s = ((double) g0 + (double) g1) + (double) g2.  The row is valid (m = 1.0) when s is finite and > 0 and all three entries are >= 0
+ *   (a NaN fails that).  For a valid row p_x = (double) g_x / s (IEEE division); otherwise m = p_0 = p_1 = p_2 = 0.0.
+ *   The row's 4-vector is r = (p_0, p_1, p_2, m).
+ * Weights: the A side carries the optional weight c[n_snps] (float64): wa_i[x] = c_i ra_i[x], one rounding.  weight = NULL means every
+ * c_i = 1.0 and gives the bits of an explicit array of ones.  A non-finite or negative c_i is DMX_ERR_ARG.
+ * Table T[a][b][x][y], x, y in 0..3:  acc = +0.0, then for i = 0 .. n_snps - 1 in ascending order  acc = fma(wa_i[a][x], rb_i[b][y], acc)
+ * — one single chain of fused multiply-adds per entry; no slabs, no partial sums, no floating-point atomics.  An entry's bits depend on
+ * n_snps, the two columns and c only: not on n_a, n_b, the tile shape, the launch geometry, what else is in the call or what ran
+ * before.  All terms are >= 0: nothing cancels.  T[..][3][3] is the weight of the jointly valid SNPs, T[..][x][3] a's marginal over
+ * them, T[..][3][y] b's, and T[..][0..2][0..2] the joint genotype table.  With gb = NULL the full n_a x n_a table is computed; the
+ * weight sits on the A side, so T[a][b] and the transpose of T[b][a] need not have the same bits.
+ * Two kernels (csrc/dmx_kin.hpp): k_kin_rows (the row transform into [S][V][4] float64 images, the invalid rows counted per column)
+ * and k_kin_tile (the contraction).  The call needs no pileup, runs on the engine's stream and synchronises it before returning (host
+ * inputs may be freed then), owns its buffers and leaves every other result of the engine as it was.  n_snps = 0 gives a table of zeros.
+ * DMX_ERR_ARG: a null argument; n_a or n_b outside [1, 4096]; n_snps < 0; reserved != 0; a bad weight; gb = NULL with n_b != n_a; a
+ * g_memory that is neither constant.  DMX_ERR_STATE: ga = NULL without a staged genotype matrix, or with one of another shape; a get
+ * or info call before a compare.  DMX_ERR_NOMEM: the buffers do not fit the free device memory (the message names the sizes). */
+#define DMX_KIN_MAX_COLUMNS 4096
+typedef struct {
+  int32_t n_snps, n_a, n_b;
+  const float*  ga;            /* [n_snps][n_a][3]; NULL: the engine's staged matrix (n_snps / n_a must equal its S / V) */
+  const float*  gb;            /* [n_snps][n_b][3]; NULL: B is A (n_b must equal n_a) */
+  const double* weight;        /* [n_snps] or NULL */
+  int32_t g_memory;            /* DMX_MEM_HOST | DMX_MEM_DEVICE, for ga, gb and weight together */
+  int32_t reserved;            /* 0 */
+} dmx_kin_request;
+typedef struct {
+  double  rows_ms, tile_ms;    /* HIP-event times of the last call's k_kin_rows launches (both sides) and of its k_kin_tile */
+  int64_t flop;                /* 2 * 16 * n_a * n_b * n_snps */
+  int64_t bytes;               /* algorithmic device bytes: both gp matrices and the weight read, both images written and read once,
+                                  the table written */
+  int64_t n_invalid_a, n_invalid_b;   /* invalid rows over all columns of each side */
+  int32_t n_snps, n_a, n_b;
+  int32_t tile_a, tile_b;      /* columns of A and of B per workgroup of k_kin_tile in the last call */
+  int32_t chunk_snps;          /* SNPs staged per trip */
+  int32_t reserved[2];
+} dmx_kin_info;
+int dmx_engine_geno_compare(dmx_engine*, const dmx_kin_request*);
+/* Device->host copies of the last call's results (any pointer may be NULL): table [n_a][n_b][4][4] f64; n_valid_a [n_a] and n_valid_b
+ * [n_b] i32, the valid rows of each column. */
+int dmx_engine_get_geno_compare(dmx_engine*, double* table, int32_t* n_valid_a, int32_t* n_valid_b);
+int dmx_engine_geno_compare_info(dmx_engine*, dmx_kin_info* out);
+
 #ifdef __cplusplus
 }
 #endif
