@@ -33,7 +33,7 @@ SYMBOLS = [
     "dmx_engine_last_kernel_times", "dmx_engine_algorithmic_bytes", "dmx_write_single", "dmx_write_doublet",
     "dmx_demuxlet_run", "dmx_debug_device_log", "dmx_debug_device_log2", "dmx_debug_device_div", "dmx_debug_log_rate", "dmx_engine_get_sing", "dmx_engine_get_cell_grids", "dmx_write_doublet_summary", "dmx_debug_log_dd",
     "dmx_resolve_tie_order", "dmx_engine_mean_kernel_times", "dmx_store_add_batch", "dmx_write_doublet_summary_grids", "dmx_engine_kernel_names", "dmx_debug_device_log2_lite", "dmx_debug_device_log2_lite32", "dmx_debug_device_log2_mirror",
-    "dmx_engine_format_pair", "dmx_pair_text_get_info", "dmx_pair_text_read", "dmx_pair_text_free",
+    "dmx_engine_format_pair", "dmx_pair_text_get_info", "dmx_pair_text_get_scalars", "dmx_pair_text_read", "dmx_pair_text_free",
     "dmx_engine_refine_genotypes", "dmx_engine_get_refined", "dmx_engine_refined_device_ptr", "dmx_engine_refine_info",
     "dmx_engine_cluster_stage", "dmx_engine_cluster_mstep", "dmx_engine_cluster_estep", "dmx_engine_get_cluster", "dmx_engine_get_cluster_stage",
     "dmx_engine_cluster_device_ptr", "dmx_engine_cluster_info",
@@ -67,6 +67,10 @@ class PairOverride(C.Structure):      # dmx_pair_override
 
 class PairPatch(C.Structure):         # dmx_pair_patch
     _fields_ = [("offset", C.c_int64), ("value", C.c_double), ("out_cell", C.c_int32), ("singlet", C.c_int32)]
+
+
+class PairScalars(C.Structure):       # dmx_pair_scalars
+    _fields_ = [("max_llk", C.c_double), ("sum_single", C.c_double), ("sum_double", C.c_double)]
 
 
 class PairRequest(C.Structure):       # dmx_pair_request
@@ -454,7 +458,7 @@ def load() -> C.CDLL:
         "dmx_store_add_batch": [vp, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, i32],
         "dmx_write_doublet_summary_grids": [vp, vp, vp, vp, C.c_char_p],
         "dmx_engine_kernel_names": [vp, vp],
-        "dmx_engine_format_pair": [vp, vp, vp], "dmx_pair_text_get_info": [vp, vp], "dmx_pair_text_read": [vp, C.c_int64, C.c_int64, vp],
+        "dmx_engine_format_pair": [vp, vp, vp], "dmx_pair_text_get_info": [vp, vp], "dmx_pair_text_get_scalars": [vp, vp], "dmx_pair_text_read": [vp, C.c_int64, C.c_int64, vp],
         "dmx_engine_refine_genotypes": [vp, vp], "dmx_engine_get_refined": [vp, vp, vp, vp, vp, vp], "dmx_engine_refined_device_ptr": [vp, vp],
         "dmx_engine_refine_info": [vp, vp],
         "dmx_engine_cluster_stage": [vp], "dmx_engine_cluster_mstep": [vp, vp], "dmx_engine_cluster_estep": [vp, vp],

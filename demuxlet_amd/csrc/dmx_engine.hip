@@ -12530,8 +12530,28 @@ struct dmx_pair_text {
   std::vector<int64_t> cell_off;
   std::vector<uint8_t> cell_flag;
   std::vector<dmx_pair_patch> patches;
+  std::vector<dmx_pair_scalars> scal;
   double format_ms = 0.0;
 };
+
+// The limits of the device `.pair` path (dmx.h) in one place: the row map's fields hold 12 bits of a sample index and 8 of an alpha index, and a
+// chunk of 256 rows has to fit k_pair_write's LDS buffer.  dmx_engine_format_pair refuses what does not fit; dmx_demuxlet_run asks first and
+// leaves such a job to the host formatter.  Returns nullptr when the path applies, else what is in the way.
+static const char* pair_device_limit(int32_t V, int32_t A, size_t bc_max, size_t sm_max, size_t al_max, size_t* max_row_out) {
+  const size_t max_row = bc_max + 1 + 2 * sm_max + 1 + al_max + 20 + 1 + 12 + 1;   // "%s\t%s\t%s" "\t%.3lf\t" "%.5lf" "\t" "%.5lg" "\n"
+  if (max_row_out) *max_row_out = max_row;
+  if (V > 4095 || A > 255) return "samples x alphas exceed the row map's fields";
+  if (max_row > (size_t)150 * 1024 / dmx_fmt::kFmtThreads) return "rows do not fit the kernel's buffer";
+  return nullptr;
+}
+// "\t%.3lf\t" of one alpha, the reference's own conversion (:776,:788); false when it does not print
+static bool pair_alpha_text(double alpha, std::string* out) {
+  char buf[400];
+  const int n = std::snprintf(buf, sizeof buf, "\t%.3lf\t", alpha);
+  if (n < 0 || (size_t)n >= sizeof buf) return false;
+  out->assign(buf, (size_t)n);
+  return true;
+}
 
 extern "C" void dmx_pair_text_free(dmx_pair_text* t) {
   if (!t) return;
@@ -12543,6 +12563,12 @@ extern "C" int dmx_pair_text_get_info(const dmx_pair_text* t, dmx_pair_text_info
   if (!t || !out) return set_error(DMX_ERR_ARG, "dmx_pair_text_get_info: null argument");
   out->n_bytes = t->n_bytes; out->n_out = (int32_t)t->cell_flag.size(); out->n_patches = (int32_t)t->patches.size();
   out->cell_off = t->cell_off.data(); out->cell_flag = t->cell_flag.data(); out->patches = t->patches.data(); out->format_ms = t->format_ms;
+  return DMX_OK;
+}
+
+extern "C" int dmx_pair_text_get_scalars(const dmx_pair_text* t, const dmx_pair_scalars** out) {
+  if (!t || !out) return set_error(DMX_ERR_ARG, "dmx_pair_text_get_scalars: null argument");
+  *out = t->scal.data();
   return DMX_OK;
 }
 
@@ -12559,8 +12585,10 @@ extern "C" int dmx_engine_format_pair(dmx_engine* e, const dmx_pair_request* rq,
     return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: null argument");
   if (!e->have_grid) return set_error(DMX_ERR_STATE, "dmx_engine_format_pair: run_doublet has not been called");
   const int32_t V = e->V, A = e->A, n_out = rq->n_out;
-  if (V > 4095 || A > 255) return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: %d samples x %d alphas exceed the row map's fields", V, A);
+  if (pair_device_limit(V, A, 0, 0, 0, nullptr)) return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: %d samples x %d alphas exceed the row map's fields", V, A);
   for (int32_t i = 0; i < n_out; ++i) {
+    if (rq->ovr && rq->ovr[i].n >= 0 && (rq->ovr[i].a < 0 || rq->ovr[i].a >= V || rq->ovr[i].b < 0 || rq->ovr[i].b >= V || rq->ovr[i].n >= A))
+      return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: ovr[%d] = (%d, %d, %d) is not an entry of the grid", i, rq->ovr[i].a, rq->ovr[i].b, rq->ovr[i].n);
     if (rq->cells[i] < 0 || rq->cells[i] >= e->pv.B) return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: cell %d out of range (0..%d)", rq->cells[i], e->pv.B - 1);
     if (!rq->barcodes[i]) return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: barcodes[%d] is null", i);
   }
@@ -12594,14 +12622,14 @@ extern "C" int dmx_engine_format_pair(dmx_engine* e, const dmx_pair_request* rq,
   if (!pool_of(rq->barcodes, n_out, &bc_pool, &bc_off, &bc_max) || !pool_of(rq->sample_ids, V, &sm_pool, &sm_off, &sm_max))
     return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: more than 4 GB of barcode text");
   for (int32_t a = 0; a < A; ++a) {
-    char buf[400];
-    const int n = std::snprintf(buf, sizeof buf, "\t%.3lf\t", e->alpha[(size_t)a]);              // the reference's own conversion (:776,:788)
-    if (n < 0 || (size_t)n >= sizeof buf) return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: alpha[%d] does not print", a);
-    al_pool.append(buf, (size_t)n); al_off.push_back((uint32_t)al_pool.size()); al_max = std::max(al_max, (size_t)n);
+    std::string txt;
+    if (!pair_alpha_text(e->alpha[(size_t)a], &txt)) return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: alpha[%d] does not print", a);
+    al_pool.append(txt); al_off.push_back((uint32_t)al_pool.size()); al_max = std::max(al_max, txt.size());
   }
-  const size_t max_row = bc_max + 1 + 2 * sm_max + 1 + al_max + 20 + 1 + 12 + 1;
+  size_t max_row = 0;
+  if (pair_device_limit(V, A, bc_max, sm_max, al_max, &max_row))
+    return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: rows of up to %zu bytes do not fit the kernel's buffer", max_row);
   const size_t lds = (size_t)dmx_fmt::kFmtThreads * max_row;
-  if (lds > 150 * 1024) return set_error(DMX_ERR_ARG, "dmx_engine_format_pair: rows of up to %zu bytes do not fit the kernel's buffer", max_row);
   std::vector<double> pow10(310);
   for (int n = 0; n < 310; ++n) { char b[16]; std::snprintf(b, sizeof b, "1e%d", n); pow10[(size_t)n] = std::strtod(b, nullptr); }   // correctly rounded
   // ---- device copies (small; per call)
@@ -12630,6 +12658,9 @@ extern "C" int dmx_engine_format_pair(dmx_engine* e, const dmx_pair_request* rq,
   if (int rc = up(al_off.data(), sizeof(uint32_t) * al_off.size(), &d)) return rc; c.al_off = (const uint32_t*)d;
   if (int rc = up(pow10.data(), sizeof(double) * pow10.size(), &d)) return rc; c.pow10 = (const double*)d;
   int64_t* d_len = nullptr; uint32_t* d_np = nullptr; int64_t* d_off = nullptr; uint32_t* d_poff = nullptr; uint8_t* d_flag = nullptr;
+  dmx_pair_scalars* d_scal = nullptr;
+  if (int rc = up(nullptr, sizeof(dmx_pair_scalars) * (size_t)std::max(n_out, 1), (void**)&d_scal)) return rc;
+  c.scal = d_scal;
   if (int rc = up(nullptr, sizeof(int64_t) * (size_t)std::max(n_out, 1), (void**)&d_len)) return rc;
   if (int rc = up(nullptr, sizeof(uint32_t) * (size_t)std::max(n_out, 1), (void**)&d_np)) return rc;
   if (int rc = up(nullptr, sizeof(int64_t) * ((size_t)n_out + 1), (void**)&d_off)) return rc;
@@ -12641,6 +12672,7 @@ extern "C" int dmx_engine_format_pair(dmx_engine* e, const dmx_pair_request* rq,
   t->device = e->device;
   t->cell_off.assign((size_t)n_out + 1, 0);
   t->cell_flag.assign((size_t)n_out, 0);
+  t->scal.assign((size_t)std::max(n_out, 1), dmx_pair_scalars{0.0, 0.0, 0.0});
   EventPair ev;
   if (n_out > 0) {
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&dmx_fmt::k_pair_write), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -12664,6 +12696,7 @@ extern "C" int dmx_engine_format_pair(dmx_engine* e, const dmx_pair_request* rq,
     HIP_TRY(hipGetLastError());
     if (int rc = ev.record_stop(st)) return rc;
     if (n_patch) HIP_TRY(hipMemcpyAsync(t->patches.data(), d_patch, sizeof(dmx_pair_patch) * n_patch, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(t->scal.data(), d_scal, sizeof(dmx_pair_scalars) * (size_t)n_out, hipMemcpyDeviceToHost, st));   // (after the timed kernels, with the patches)
     HIP_TRY(hipStreamSynchronize(st));
     float ms = 0.f;
     if (int rc = ev.elapsed_ms(&ms)) return rc;
@@ -12810,7 +12843,16 @@ extern "C" int dmx_demuxlet_run(const dmx_job* job) {
   std::vector<Range> rg((size_t)R);
   struct RangeGuard { std::vector<Range>* r; ~RangeGuard() { for (Range& x : *r) if (x.ptext) { dmx_pair_text_free(x.ptext); x.ptext = nullptr; } } } range_guard{&rg};
   // `.pair` rows are formatted on the device (dmx_engine_format_pair) unless the fenced DMX_PAIR_ON_HOST=1 asks for the host formatter (tests compare the two)
-  const bool gpu_pair = job->write_pair && doublet_ok && !job_knob("DMX_PAIR_ON_HOST");
+  // or the job is beyond the device path's limits (pair_device_limit over ALL barcodes of the job, so every range decides alike): the host formatter then
+  bool gpu_pair = job->write_pair && doublet_ok && !job_knob("DMX_PAIR_ON_HOST");
+  if (gpu_pair) {
+    size_t bc_max = 0, sm_max = 0, al_max = 0;
+    bool prints = true;
+    for (int32_t c = 0; c < B; ++c) bc_max = std::max(bc_max, std::strlen(bcs[(size_t)c]));
+    for (int32_t j = 0; j < V; ++j) sm_max = std::max(sm_max, std::strlen(job->sample_ids[j]));
+    for (int32_t a = 0; a < A; ++a) { std::string txt; prints = prints && pair_alpha_text(job->alpha[a], &txt); al_max = std::max(al_max, txt.size()); }
+    if (!prints || pair_device_limit(V, A, bc_max, sm_max, al_max, nullptr)) gpu_pair = false;
+  }
   double pair_format_ms = 0; int64_t pair_bytes = 0, pair_patches = 0, pair_host_cells = 0;
   // Engines: one per GPU and wave slot.  When the job takes several waves, every GPU gets TWO engines (own stream, own buffers)
   // that alternate between waves, so that the slicing + H2D of wave w + 2 overlaps the kernels of wave w + 1 (the copy engine
@@ -12999,13 +13041,16 @@ extern "C" int dmx_demuxlet_run(const dmx_job* job) {
   const std::string pre(job->out_prefix);
   // The .pair file of a range whose rows were formatted on the device: the packed text comes over in pieces through one pinned buffer and goes to
   // write(2) as it is; where the device left a POSTPRB field to the host (dmx_pair_patch: the denormal range, a digit next to a rounding boundary) the
-  // field is computed here with the host libm — the expression of :780 / :792 on the barcode's K3 record — and spliced in; barcodes left to the host
+  // field is computed here with the host libm — the expression of :780 / :792 on the three scalars the text itself was printed from (the K3 record,
+  // or the certified grid's: dmx_pair_text_get_scalars) — and spliced in; barcodes left to the host
   // formatter (cell_flag != 0) have their rows (pair_rows, from write_doublet_core) inserted at their place.
   PinnedBuf pair_stage;
   constexpr int64_t kPairStage = (int64_t)32 << 20;
   auto stream_pair = [&](Range& x, const std::vector<std::string>& pair_rows, bool append) -> int {
     dmx_pair_text_info pi{};
     if (int rc = dmx_pair_text_get_info(x.ptext, &pi)) return rc;
+    const dmx_pair_scalars* scal = nullptr;
+    if (int rc = dmx_pair_text_get_scalars(x.ptext, &scal)) return rc;
     FILE* f = fopen((pre + ".pair").c_str(), append ? "a" : "w");
     if (!f) return set_error(DMX_ERR_IO, "Cannot create %s.single, %s.pair files", job->out_prefix, job->out_prefix);     // :535-536
     struct Closer { FILE* f; ~Closer() { if (f) fclose(f); } } closer{f};
@@ -13042,7 +13087,7 @@ extern "C" int dmx_demuxlet_run(const dmx_job* job) {
         const dmx_pair_patch& pp = pi.patches[ip++];
         if (int rc = put(run_beg, pp.offset)) return rc;
         run_beg = pp.offset;
-        const dmx_cell_summary& sm = x.summ[(size_t)x.out_cells[(size_t)pp.out_cell]];
+        const dmx_pair_scalars& sm = scal[pp.out_cell];
         const double tot = sm.sum_single + sm.sum_double, prior = job->doublet_prior;
         const double p = pp.singlet ? std::exp(pp.value - sm.max_llk) * (1. - prior) / V / tot
                                     : std::exp(pp.value - sm.max_llk) * prior / V / (V - 1) / (A - 1) / tot;

@@ -18,7 +18,14 @@
 //   * Barcodes whose grid entries the tie arbiter may replace (dmx::cell_needs != 0, a BEST-rule comparison within 1e-7) are not formatted here at
 //     all: the caller marks them (host_rows) and their rows come from the host formatter, inserted at the barcode's offset.  The two certified
 //     entries of an alpha = 0.5 best doublet (K3b; resolved on the host where one log() was left open) are passed in and printed as the host does.
-// Two passes: lengths (and patch count) per barcode, a scan, then the bytes — the text is packed, in output order, ready for write(2).
+//     The host formatter derives maxLLK and the two posterior sums from the grid WITH those two entries (dmx_host.cpp, call_cell on the scratch
+//     grid), K3's record from the grid without them: up to 7e-12 (STRICT) / 6e-11 (FAST) apart, far outside the 4e-13 margin.  So pass S
+//     (cell_scalars, at the head of k_pair_lengths) reduces the three numbers again for such a barcode — K3's per-term expression over the grid with the two entries replaced —
+//     and every POSTPRB field here, and every patch on the host, is built from pass S's numbers (reported per output barcode).
+//   * A barcode whose maxLLK or sumSingle + sumDouble is not finite, or whose sum is not positive (a nan / inf in an entry that is never printed
+//     reaches both through the whole-grid scans), is left to the host like an unprintable LLK (flag 2): "0" for x < -800 and for p == 0 hold
+//     for finite scalars only.
+// Passes: the scalars with the lengths (and patch count) per barcode, a scan, then the bytes — the text is packed, in output order, ready for write(2).
 #pragma once
 
 namespace dmx_fmt {
@@ -31,6 +38,7 @@ struct Ctx {
   const char* sm_pool; const uint32_t* sm_off;     // sample ids
   const char* al_pool; const uint32_t* al_off;     // "\t%.3lf\t" of every alpha
   const double* pow10;                             // 10^n, n = 0..309
+  dmx_pair_scalars* scal;                          // pass L out: max_llk, sum_single, sum_double of every output barcode (what passes L and W print from)
   int64_t* cell_len; uint32_t* cell_npatch;        // pass L out
   const int64_t* cell_off; const uint32_t* cell_poff;   // pass W in (exclusive scans)
   char* text; dmx_pair_patch* patches;
@@ -181,12 +189,11 @@ __device__ int format_row(const Ctx& c, const CellCtx& cc, uint32_t rm, char* ds
   return n + 1;
 }
 
-__device__ __forceinline__ bool load_cell(const Ctx& c, int32_t oc, CellCtx* cc) {
+__device__ __forceinline__ bool load_cell(const Ctx& c, int32_t oc, const dmx_pair_scalars& sc, CellCtx* cc) {
   const int32_t cell = c.cells[oc];
-  const dmx_cell_summary& sm = c.summ[cell];
   cc->G = c.grid + (size_t)cell * c.V * c.V * c.A;
-  cc->max_llk = sm.max_llk;
-  cc->tot = sm.sum_single + sm.sum_double;
+  cc->max_llk = sc.max_llk;
+  cc->tot = sc.sum_single + sc.sum_double;
   cc->oa = cc->ob = cc->on = -1; cc->v_ab = cc->v_ba = 0.0;
   if (c.ovr && c.ovr[oc].n >= 0) { cc->oa = c.ovr[oc].a; cc->ob = c.ovr[oc].b; cc->on = c.ovr[oc].n; cc->v_ab = c.ovr[oc].llk_ab; cc->v_ba = c.ovr[oc].llk_ba; }
   cc->bc = c.bc_pool + c.bc_off[oc];
@@ -196,19 +203,80 @@ __device__ __forceinline__ bool load_cell(const Ctx& c, int32_t oc, CellCtx* cc)
 
 constexpr int kFmtThreads = 256;
 
-// Pass L: bytes and patches of every output barcode (one workgroup per barcode)
+// Pass S (the head of pass L, by the barcode's workgroup): max_llk / sum_single / sum_double of an output barcode.  K3's record as it is, unless the
+// barcode carries certified entries whose bits differ from the grid's: then k_reduce's steps (1) and (2) again — whole-grid maximum (fmax: NaN
+// ignored), the same per-term expression, tree order for the sums — over the grid with llksAB[a][b][n] and llksAB[b][a][n] replaced.  Every thread
+// of the workgroup calls it and gets the result; s_d / s_e: kFmtThreads doubles of LDS each.
+__device__ dmx_pair_scalars cell_scalars(const Ctx& c, int32_t oc, double* s_d, double* s_e) {
+  const int t = threadIdx.x;
+  const int32_t V = c.V, A = c.A, cell = c.cells[oc];
+  const double* G = c.grid + (size_t)cell * V * V * A;
+  int32_t jk_ab = -1, jk_ba = -1, on = -1;
+  double v_ab = 0.0, v_ba = 0.0;
+  bool redo = false;
+  if (c.ovr && c.ovr[oc].n >= 0) {
+    const dmx_pair_override o = c.ovr[oc];                     // (indices checked by the caller)
+    jk_ab = o.a * V + o.b; jk_ba = o.b * V + o.a; on = o.n; v_ab = o.llk_ab; v_ba = o.llk_ba;
+    redo = __double_as_longlong(G[(size_t)jk_ab * A + on]) != __double_as_longlong(v_ab) ||
+           __double_as_longlong(G[(size_t)jk_ba * A + on]) != __double_as_longlong(v_ba);
+  }
+  if (!redo) { const dmx_cell_summary& sm = c.summ[cell]; return dmx_pair_scalars{sm.max_llk, sm.sum_single, sm.sum_double}; }
+  const int32_t nJK = V * V;
+  auto entry = [&](int32_t jk, int32_t n) -> double {
+    if (n == on) { if (jk == jk_ab) return v_ab; if (jk == jk_ba) return v_ba; }
+    return G[(size_t)jk * A + n];
+  };
+  double mx = -1e300;
+  for (int32_t jk = t; jk < nJK; jk += kFmtThreads) for (int32_t n = 0; n < A; ++n) mx = fmax(mx, entry(jk, n));
+  s_d[t] = mx;
+  __syncthreads();
+  for (int s = kFmtThreads / 2; s > 0; s >>= 1) {
+    if (t < s) s_d[t] = (s_d[t] < s_d[t + s]) ? s_d[t + s] : s_d[t];
+    __syncthreads();
+  }
+  const double max_llk = s_d[0];
+  __syncthreads();
+  double ss = 0.0, sd = 0.0;
+  for (int32_t jk = t; jk < nJK; jk += kFmtThreads) {
+    const int32_t j = jk / V, k = jk - j * V;
+    if (k == 0) ss += (exp(entry(jk, 0) - max_llk) * (1. - c.prior) / V);
+    if (j != k) for (int32_t n = 1; n < A; ++n) sd += (exp(entry(jk, n) - max_llk) * c.prior / V / (V - 1) / (A - 1) / (c.alpha[n] == 0.5 ? 2.0 : 1.0));
+  }
+  s_d[t] = ss; s_e[t] = sd;
+  __syncthreads();
+  for (int s = kFmtThreads / 2; s > 0; s >>= 1) {
+    if (t < s) { s_d[t] += s_d[t + s]; s_e[t] += s_e[t + s]; }
+    __syncthreads();
+  }
+  const dmx_pair_scalars r{max_llk, s_d[0], s_e[0]};
+  __syncthreads();
+  return r;
+}
+
+// Pass L: the scalars (pass S), bytes and patches of every output barcode (one workgroup per barcode)
 __global__ __launch_bounds__(kFmtThreads) void k_pair_lengths(Ctx c) {
   const int32_t oc = blockIdx.x;
   __shared__ unsigned long long s_len;
   __shared__ uint32_t s_np, s_bad;
+  __shared__ double s_d[kFmtThreads], s_e[kFmtThreads];
   if (threadIdx.x == 0) { s_len = 0ull; s_np = 0u; s_bad = 0u; }
   __syncthreads();
   if (c.host_rows && c.host_rows[oc]) {
-    if (threadIdx.x == 0) { c.cell_len[oc] = 0; c.cell_npatch[oc] = 0u; c.cell_flag[oc] = 1; }
+    if (threadIdx.x == 0) {
+      const dmx_cell_summary& sm = c.summ[c.cells[oc]];
+      c.scal[oc] = dmx_pair_scalars{sm.max_llk, sm.sum_single, sm.sum_double};
+      c.cell_len[oc] = 0; c.cell_npatch[oc] = 0u; c.cell_flag[oc] = 1;
+    }
     return;
   }
+  const dmx_pair_scalars sc = cell_scalars(c, oc, s_d, s_e);
+  if (threadIdx.x == 0) c.scal[oc] = sc;
   CellCtx cc;
-  load_cell(c, oc, &cc);
+  load_cell(c, oc, sc, &cc);
+  if (!(fabs(cc.max_llk) <= 1.7976931348623157e308) || !(cc.tot > 0.0 && cc.tot <= 1.7976931348623157e308)) {   // not finite, or no posterior mass
+    if (threadIdx.x == 0) { c.cell_len[oc] = 0; c.cell_npatch[oc] = 0u; c.cell_flag[oc] = 2; }
+    return;
+  }
   unsigned long long len = 0ull; uint32_t np = 0u; bool bad = false;
   for (int32_t r = threadIdx.x; r < c.n_rows; r += kFmtThreads) {
     int post_at; double v;
@@ -256,7 +324,7 @@ __global__ __launch_bounds__(kFmtThreads) void k_pair_write(Ctx c) {
   const int32_t oc = blockIdx.x;
   if (c.cell_flag[oc] != 0) return;
   CellCtx cc;
-  load_cell(c, oc, &cc);
+  load_cell(c, oc, c.scal[oc], &cc);
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   int64_t base = c.cell_off[oc];
   uint32_t pbase = c.cell_poff[oc];

@@ -240,10 +240,12 @@ class Engine:
         check(self._L.dmx_engine_get_cell_grids(self._h, cells.ctypes.data, len(cells), out.ctypes.data))
         return out
 
-    def format_pair(self, cells, barcodes: Sequence[str], sample_ids: Sequence[str], host_rows=None, ovr=None):
+    def format_pair(self, cells, barcodes: Sequence[str], sample_ids: Sequence[str], host_rows=None, ovr=None, scalars=False):
         """dmx_engine_format_pair: the `.pair` rows (cmd_cram_demuxlet.cpp:772-797) of the barcodes `cells` (ids of the staged pileup, output order) formatted on
         the device.  Returns (text bytes, cell_off[n+1], cell_flag[n], patches as a list of (offset, value, out_cell, singlet), format_ms): the POSTPRB fields the
-        device leaves to the host's libm are EMPTY in the text and listed in `patches`."""
+        device leaves to the host's libm are EMPTY in the text and listed in `patches`.  With scalars=True a sixth item follows: per OUTPUT barcode the
+        (max_llk, sum_single, sum_double) the text was printed from and a patch is computed from (dmx_pair_text_get_scalars: K3's record, or the
+        certified grid's where `ovr` changes the grid), a structured array [n]."""
         cells = np.ascontiguousarray(cells, dtype=np.int32)
         n = len(cells)
         bc, k1 = _cstrs(barcodes)
@@ -267,7 +269,14 @@ class Engine:
             flag = np.array([info.cell_flag[i] for i in range(n)], dtype=np.uint8)
             patches = [(int(info.patches[i].offset), float(info.patches[i].value), int(info.patches[i].out_cell), int(info.patches[i].singlet))
                        for i in range(info.n_patches)]
-            return buf.raw[:info.n_bytes], off, flag, patches, float(info.format_ms)
+            if not scalars:
+                return buf.raw[:info.n_bytes], off, flag, patches, float(info.format_ms)
+            sp = C.POINTER(capi.PairScalars)()
+            check(self._L.dmx_pair_text_get_scalars(h, C.byref(sp)))
+            sc = np.zeros(n, dtype=[("max_llk", np.float64), ("sum_single", np.float64), ("sum_double", np.float64)])
+            for i in range(n):
+                sc[i] = (sp[i].max_llk, sp[i].sum_single, sp[i].sum_double)
+            return buf.raw[:info.n_bytes], off, flag, patches, float(info.format_ms), sc
         finally:
             self._L.dmx_pair_text_free(h)
 

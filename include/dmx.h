@@ -227,10 +227,25 @@ int dmx_engine_get_cell_grids(dmx_engine*, const int32_t* cells, int32_t n, doub
  *             `patches`: the caller inserts, at byte `offset` of the text, "%.5lg" of exp(value - maxLLK) * c / (sumSingle + sumDouble) computed with ITS
  *             libm (c = (1 - prior) / V for a singlet row, prior / V / (V-1) / (A-1) else; the record of barcode cells[out_cell] has the three scalars).
  *             cell_flag[i]: 0 = rows in the text at [cell_off[i], cell_off[i+1]); 1 = left to the caller as requested; 2 = left to the caller because
- *             an entry is not printable here (nan, inf, |v| >= 2^43) — both with an empty range: the caller's rows go in at cell_off[i].
- * dmx_demuxlet_run uses this for `write_pair` jobs; the result is byte-identical to the host formatter's (tests/test_gpu_pair_text.py). */
-typedef struct { int32_t a, b, n, reserved; double llk_ab, llk_ba; } dmx_pair_override;   /* n < 0: none */
+ *             an entry is not printable here (nan, inf, |v| >= 2^43), or because the barcode's maxLLK or sumSingle + sumDouble is not finite or the sum
+ *             is not positive (a nan / inf in an entry that is never printed reaches them through the whole-grid scans) — both with an empty range:
+ *             the caller's rows go in at cell_off[i].
+ *   scalars   (appended, still ABI 8) The host formatter prints a barcode with certified entries from the grid WITH them: maxLLK and the two sums are
+ *             those of that grid, not K3's record (up to 7e-12 STRICT / 6e-11 FAST apart — enough to move a fifth digit).  For a barcode with
+ *             ovr[i].n >= 0 whose two values differ from the grid's bits the call reduces the three numbers again (K3's per-term expression over the
+ *             grid with the two entries replaced); for every other barcode they are the record's.  dmx_pair_text_get_scalars returns them per OUTPUT
+ *             barcode: they are what the text was printed from and what a patch must be computed from (not the record).
+ *   limits    n_samples <= 4095, n_alpha <= 255 and 256 * (longest row) <= 150 KiB, where the longest row is taken as (longest barcode) + 2 * (longest
+ *             sample id) + (longest "\t%.3lf\t" of an alpha) + 36 bytes; DMX_ERR_ARG otherwise.  dmx_demuxlet_run checks the same limits (over all
+ *             barcodes of the job) and gives such a job to the host formatter.
+ * Guaranteed, and tested as stated (tests/test_gpu_pair_text.py): the text with its patches filled in from the reported scalars, and the host's rows
+ * at the flagged barcodes, is byte for byte what the host formatter prints from the grid with the certified entries substituted — also when a
+ * certified entry moves a POSTPRB value across a rounding boundary, when a scalar is not finite, at any number of 256-row chunks, any output order
+ * and any host_rows mask; a dmx_demuxlet_run `write_pair` job writes the same four files with the device formatter, with the host formatter
+ * (DMX_PAIR_ON_HOST=1 behind DMX_EXPERIMENTS=1), and beyond the limits above. */
+typedef struct { int32_t a, b, n, reserved; double llk_ab, llk_ba; } dmx_pair_override;   /* n < 0: none; else 0 <= a, b < n_samples, 0 <= n < n_alpha */
 typedef struct { int64_t offset; double value; int32_t out_cell, singlet; } dmx_pair_patch;
+typedef struct { double max_llk, sum_single, sum_double; } dmx_pair_scalars;
 typedef struct {
   int32_t n_out;
   const int32_t* cells;             /* [n_out] */
@@ -249,6 +264,7 @@ typedef struct {
 } dmx_pair_text_info;
 int  dmx_engine_format_pair(dmx_engine*, const dmx_pair_request*, dmx_pair_text** out);   /* needs run_doublet's results; synchronises */
 int  dmx_pair_text_get_info(const dmx_pair_text*, dmx_pair_text_info* out);
+int  dmx_pair_text_get_scalars(const dmx_pair_text*, const dmx_pair_scalars** out);      /* [n_out], owned by the text (a new entry point: the info struct is the caller's and cannot grow) */
 int  dmx_pair_text_read(dmx_pair_text*, int64_t offset, int64_t n_bytes, void* dst);     /* device -> host copy of a piece of the text */
 void dmx_pair_text_free(dmx_pair_text*);
 
