@@ -1321,8 +1321,10 @@ int dmx_engine_fit_info(dmx_engine*, dmx_fit_info* out);
  * The three entries l = m have s = 0: they add to L only.  As for dmx_engine_ambient_doublet, a pair with no stored read, or where
  * either sample's gp row is all zero, contributes nothing and is not counted.  With one-hot gp rows LL is concave in alpha; with soft
  * rows it need not be, and dmx_engine_share_fit finds a LOCAL maximum.
- * Operations (binary64, every product, sum and quotient rounded on its own: IEEE divisions, no contraction), entries in the order k:
- *   p_lm      om = 1 - rho, ra = rho a_i;  c_lm = 0.5 l + ((m - l) 0.5) alpha;  p_lm = om c_lm + ra,  q_lm = 1 - p_lm;  s_lm = (om 0.5) (m - l);
+ * Operations (binary64, every product, sum and quotient rounded on its own: IEEE divisions, no contraction; tests/contract_emul.cpp restates
+ * them and tests/test_gpu_contract_bits.py compares the bits), entries in the order k:
+ *   p_lm      om = 1 - rho, ra = rho a_i;  c_lm = 0.5 l + ((m - l) 0.5) alpha;  p_lm = om c_lm + ra,  q_lm = 1 - p_lm;  s_lm = (om 0.5) (m - l).
+ *             c_lm is this expression at every alpha, 0 and 1 included (no special case: at 0 it is 0.5 l, at 1 it is 0.5 l + (m - l) 0.5);
  *   read r    t = pR q_lm + pA p_lm;  f_lm = t of the first stored read, then f_lm t;  for l != m:  u = (pA - pR) / t,  S1 += u,  S2 += u u
  *             (from +0).  A factor t = 0 makes f_lm = 0 and takes u = 0: the entry then adds nothing to L, L' or L''.  After every eighth
  *             read an entry with 0 < f_lm < 2^-300 is rescaled into E_lm exactly as dmx_engine_ambient_doublet does (at every depth:
@@ -1331,7 +1333,8 @@ int dmx_engine_fit_info(dmx_engine*, dmx_fit_info* out);
  *             else +0;  L = T_00, then L + T_lm;  over the six l != m in entry order  x = s_lm S1_lm,  y = x x - (s_lm s_lm) S2_lm,
  *             L' = T x of the first, then L' + T x;  L'' likewise with y;  lg = dmx_log(L), and when E != 0
  *             lg = fma(E, DMX_LOG_LN2HI, fma(E, DMX_LOG_LN2LO, lg));  D1 = L' / L;  D2 = L'' / L - D1 D1.  The scale 2^-E is common to L, L' and
- *             L'' and cancels in D1 and D2.  Without an entry to take E from, L = 0: lg = -inf and D1, D2 are NaN.
+ *             L'' and cancels in D1 and D2.  Without an entry to take E from, L = 0: lg = -inf and D1, D2 are NaN (0 / 0: that they are NaN
+ *             is the contract, their sign and payload are not).
  *
  * dmx_engine_share_scan: for anchors[b][t] (t < T <= 4; -1 = slot not used) and EVERY partner v != anchor, v < V <= 1024, the three
  * numbers LL(0), LL'(0), LL''(0) of the pair (anchor, v) — the score statistic of "v is in the droplet too" is z = LL'(0) / sqrt(-LL''(0)).
@@ -1340,7 +1343,9 @@ int dmx_engine_fit_info(dmx_engine*, dmx_fit_info* out);
  * F_l = ldexp(f_l, max(E_l - E, -1100)), +0 where gp[i][anchor][l] = 0 or f_l = 0; T_lm = w_lm F_l where w_lm != 0).  Each (b, t, v) is ONE
  * serial sum per output over b's pairs in stored (ascending SNP) order, starting at +0.  out[b][t][v] = (LL, LL', LL''); the row of
  * v = anchor and the rows of unused slots are zero.  n_snp / n_read [b][t] count the pairs / reads with a stored read and a non-zero
- * anchor row (a partner whose own row is all zero at a pair skips that pair).
+ * anchor row (a partner whose own row is all zero at a pair skips that pair): they are the anchor's counts, the same for every partner,
+ * and n_read adds ALL stored reads of each such pair.  In the read loop u, S1 and S2 are kept for each l (every l has an m != l), and
+ * the six l != m entries take x = s_lm S1_l, y = x x - (s_lm s_lm) S2_l.
  *
  * dmx_engine_share_fit: for candidates cand[b][c] = (v1, v2) (c < C <= 8; v1 = -1 = slot not used; otherwise two different samples) the
  * share alpha_hat in [0, 1] that maximises LL, by a safeguarded Newton iteration on the device; an "evaluation" gives LL, LL', LL'' at one
@@ -1359,7 +1364,9 @@ int dmx_engine_fit_info(dmx_engine*, dmx_fit_info* out);
  * In cases 2 to 4 the values at alpha_hat are those of step 1.  If a value of step 1 is not finite nothing is iterated: alpha_hat = 0
  * with DMX_SHARE_AT_0 | DMX_SHARE_NONFINITE.  DMX_SHARE_FLAT: LL''(alpha_hat) >= 0 (no standard error; a pair of samples with the same
  * one-hot rows gives LL' = LL'' = 0 and ends in case 2 at 0).  DMX_SHARE_NONFINITE: a value at 0, 1 or alpha_hat is not finite.  With
- * probe in [0, 1] one more evaluation at alpha = probe is returned (not counted in n_eval); probe < 0: none, zeros.
+ * probe in [0, 1] one more evaluation at alpha = probe is returned (not counted in n_eval); probe < 0: none, zeros.  The probe is
+ * evaluated whichever way the driver left, the non-finite exit of step 1 included, and does not enter the status.  n_snp / n_read are
+ * those of the evaluation at 0 (they do not depend on alpha).
  * Summation plan of one evaluation: as dmx_engine_fit — pair k of the barcode (k counts every pair, contributing or not) goes to serial
  * sum k mod 64, each from +0 in ascending k; the 64 sums are added serially onto +0, sum 0 first; the same for LL, LL' and LL''.
  * values[b][c][13] = alpha_hat | LL, LL', LL'' at alpha_hat | at 0 | at 1 | at probe;  counts[b][c][4] = n_eval (steps 1, 6, 10), status,
@@ -1437,6 +1444,8 @@ int dmx_engine_share_info(dmx_engine*, dmx_share_info* out);
  *   n_cell (pairs), n_read (m per pair), n_alt (k(x) per pair: observed ALT among the reads used), n_trunc (pairs with n > M), n_zero  (int32)
  * A SNP that no counted pair covers gets zero rows.  Z = (obs - mean) / sqrt(var) is the site's fit; exc / sqrt(vexc) tells
  * unexplained ALT reads (> 0) from missing ones (< 0).
+ * (tests/contract_emul.cpp restates the terms and the plan below with dmx_engine_fit's own per-pair code; tests/test_gpu_contract_bits.py
+ * compares the bits.)
  * Summation plan: the used barcodes are listed singlet hypotheses first, then doublet hypotheses, each in ascending cell id (the order
  * in which dmx_engine_fit lists them).  Each of the two lists is cut into chunks of 64 consecutive entries; the last chunk of a list may
  * be short and no chunk straddles the two lists.  For a SNP, the terms of a chunk's barcodes are added onto +0 in list order (a

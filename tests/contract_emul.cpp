@@ -8,8 +8,8 @@
 // -ffp-contract=fast -DEMU_FUSE_SHARED_PRODUCTS (g++ contracts a product into a sum only when the product has no other use, and the
 // three products of the genotype-likelihood recurrence are also divided on their own: alone, the flag changes nothing in the refinement
 // and the cluster stage, whereas a device compiler with contraction on fuses them all the same; the macro makes that sum fused too),
-// emu_set_variant(EMU_DESCENDING) (a barcode's pairs, a chunk's members, a SNP's slots and the 64 sums of the
-// goodness of fit taken last first) and emu_set_variant(EMU_LIBM_LOG) (libm's log for dmx_log).
+// emu_set_variant(EMU_DESCENDING) (a barcode's pairs, a chunk's members, a SNP's slots, the 64 sums of the goodness of fit and of the
+// share fit, and the site audit's chunk partials taken last first) and emu_set_variant(EMU_LIBM_LOG) (libm's log for dmx_log).
 //
 // Counters (int64[3], per call): log arguments that are zero, log arguments that are otherwise not positive normal numbers
 // (subnormal, negative, inf, nan — the kernels hand both kinds to the runtime's log, the emulator to libm's), and rescales taken.
@@ -208,6 +208,171 @@ void pair_gl(const Pair& pr, const double* mat, const double* err, double (&G)[3
   G[0] /= tmp; G[1] /= tmp; G[2] /= tmp;
 }
 
+// ---- the per-pair terms of dmx_engine_fit, which dmx_engine_site_fit reuses operation for operation ---------------------------------------
+// state 0: the pair does not count (no stored read, or an all-zero gp row of a hypothesised sample); 2: counted in n_zero; 1: it
+// contributes c0, c0 + e1 and max(0, d) (the goodness of fit) and, for the site audit, k(x) - a1 and max(0, da).
+struct PairFit { int state; uint32_t m, kx; double c0, e1, d, a1, da; };
+
+PairFit fit_pair(const Pair& x, const float* g, int32_t V, int32_t v1, int32_t v2, const double (&cm)[9], double om, double rh, const double* amb,
+                 int32_t M, const double* mat, const double* err) {
+  PairFit out = {0, 0u, 0u, 0.0, 0.0, 0.0, 0.0, 0.0};
+  if (x.n == 0) return out;
+  const bool dbl = v2 >= 0;
+  const int NC = dbl ? 9 : 3;
+  const float* r1 = g + ((size_t)x.snp * V + v1) * 3;
+  const float* r2 = dbl ? g + ((size_t)x.snp * V + v2) * 3 : nullptr;
+  if (!row_nonzero(r1) || (dbl && !row_nonzero(r2))) return out;
+  double W[9], p[9], q[9];
+  for (int c = 0; c < NC; ++c) W[c] = dbl ? (double)r1[c / 3] * (double)r2[c % 3] : (double)r1[c];
+  const double ra = rh * (amb ? amb[x.snp] : 0.0);
+  for (int c = 0; c < NC; ++c) { p[c] = om * cm[c] + ra; q[c] = 1.0 - p[c]; }
+  const uint32_t m = x.n < (uint32_t)M ? x.n : (uint32_t)M;
+  double t[8][9][2];
+  uint32_t xobs = 0;
+  for (uint32_t r = 0; r < m; ++r) {
+    const int bq = x.rd[r] & 127;
+    const double mt = mat[bq], e3 = err[bq] / 3.0;
+    xobs |= (uint32_t)(x.rd[r] >> 7) << r;
+    for (int c = 0; c < NC; ++c) {
+      t[r][c][0] = mt * q[c] + e3 * p[c];
+      t[r][c][1] = e3 * q[c] + mt * p[c];
+    }
+  }
+  auto likelihood = [&](uint32_t y) {
+    double L = 0.0;
+    for (int c = 0; c < NC; ++c) {
+      double F = t[0][c][y & 1u];
+      for (uint32_t r = 1; r < m; ++r) F = F * t[r][c][(y >> r) & 1u];
+      const double wf = W[c] * F;
+      L = c == 0 ? wf : L + wf;
+    }
+    return L;
+  };
+  out.m = m;
+  out.kx = (uint32_t)__builtin_popcount(xobs);
+  const double Lx = likelihood(xobs);
+  if (Lx == 0.0) { out.state = 2; return out; }
+  const double c0 = emu_log(Lx);
+  double S0 = 0.0, S1 = 0.0, S2 = 0.0, A1 = 0.0, A2 = 0.0;
+  for (uint32_t y = 0; y < (1u << m); ++y) {
+    const double L = likelihood(y);
+    if (L == 0.0) continue;
+    const double u = emu_log(L) - c0, ky = (double)__builtin_popcount(y);
+    S0 += L; S1 += L * u; S2 += L * (u * u);
+    A1 += L * ky; A2 += L * (ky * ky);
+  }
+  if (S0 == 0.0 || !(fabs(S0) < INFINITY)) { out.state = 2; return out; }
+  out.c0 = c0;
+  out.e1 = S1 / S0; out.d = S2 / S0 - out.e1 * out.e1;
+  out.a1 = A1 / S0; out.da = A2 / S0 - out.a1 * out.a1;
+  out.state = 1;
+  return out;
+}
+
+// ---- the entries of dmx_engine_share_scan (NE = 3: l at alpha = 0) and dmx_engine_share_fit (NE = 9: k = 3 l + m) ----------------------------
+// f with its exponent E and, where `diff[k]`, S1 = sum u and S2 = sum u u of u = (pA - pR) / t; rescaled after every eighth read at every depth.
+const int32_t kNoExponent = INT32_MIN / 2;
+
+struct Entries { double f[9], S1[9], S2[9]; int32_t E[9]; };
+
+Entries share_entries(const Pair& pr, int NE, const double* c, const bool* diff, double om, double ra, const double* mat, const double* err) {
+  double p[9], q[9];
+  for (int k = 0; k < NE; ++k) { p[k] = om * c[k] + ra; q[k] = 1.0 - p[k]; }
+  Entries x;
+  for (int k = 0; k < 9; ++k) { x.f[k] = 0.0; x.S1[k] = 0.0; x.S2[k] = 0.0; x.E[k] = 0; }
+  for (uint32_t r = 0; r < pr.n; ++r) {
+    double pR, pA;
+    read_factors(pr.rd[r], mat, err, pR, pA);
+    const double dlt = pA - pR;
+    for (int k = 0; k < NE; ++k) {
+      const double t = pR * q[k] + pA * p[k];
+      x.f[k] = r == 0 ? t : x.f[k] * t;
+      if (diff[k]) {
+        const double u = t != 0.0 ? dlt / t : 0.0;
+        x.S1[k] += u; x.S2[k] += u * u;
+      }
+    }
+    if ((r & 7) == 7)
+      for (int k = 0; k < NE; ++k)
+        if (x.f[k] < kRescaleBelow && x.f[k] > 0.0) {
+          int e;
+          (void)frexp(x.f[k], &e);
+          x.f[k] = ldexp(x.f[k], -e);
+          x.E[k] += e;
+          ++g_rescales;
+        }
+  }
+  return x;
+}
+
+// The pair's three terms from the nine scaled weighted entries T (entry order) and x, y of the six l != m entries: lg, D1, D2.
+void share_pair_terms(const double (&T)[9], const double (&xs)[9], const double (&ys)[9], int32_t E, double (&term)[3]) {
+  double L = 0.0, L1 = 0.0, L2 = 0.0;
+  bool first = true;
+  for (int k = 0; k < 9; ++k) {
+    L = k == 0 ? T[k] : L + T[k];
+    if (k % 4 == 0) continue;
+    const double t1 = T[k] * xs[k], t2 = T[k] * ys[k];
+    L1 = first ? t1 : L1 + t1;
+    L2 = first ? t2 : L2 + t2;
+    first = false;
+  }
+  double lg = emu_log(L);
+  if (E != 0) lg = add_exponent(E, lg);
+  const double d1 = L1 / L;
+  term[0] = lg; term[1] = d1; term[2] = L2 / L - d1 * d1;
+}
+
+// One evaluation of dmx_engine_share_fit at the share alpha: (LL, LL', LL''), and the pairs / reads that contributed.
+void share_evaluate(const std::vector<Pair>& pr, const float* g, int32_t V, int32_t v1, int32_t v2, double rh, const double* amb, double alpha,
+                    const double* mat, const double* err, double (&res)[3], int32_t& n_snp, int32_t& n_read) {
+  const double om = 1.0 - rh, s1 = om * 0.5;
+  double cm[9];
+  mix_constants(alpha, cm);
+  bool diff[9];
+  for (int k = 0; k < 9; ++k) diff[k] = k % 4 != 0;
+  double sums[64][3];
+  for (int l = 0; l < 64; ++l) sums[l][0] = sums[l][1] = sums[l][2] = 0.0;
+  n_snp = 0; n_read = 0;
+  const int64_t n = (int64_t)pr.size();
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t kp = at(i, n);
+    const Pair& x = pr[(size_t)kp];
+    if (x.n == 0) continue;
+    const float* r1 = g + ((size_t)x.snp * V + v1) * 3;
+    const float* r2 = g + ((size_t)x.snp * V + v2) * 3;
+    if (!row_nonzero(r1) || !row_nonzero(r2)) continue;
+    const double ra = rh * (amb ? amb[x.snp] : 0.0);
+    const Entries e = share_entries(x, 9, cm, diff, om, ra, mat, err);
+    double w[9], T[9], xs[9], ys[9];
+    int32_t E = kNoExponent;
+    for (int k = 0; k < 9; ++k) {
+      w[k] = (double)r1[k / 3] * (double)r2[k % 3];
+      if (w[k] != 0.0 && e.f[k] > 0.0 && e.E[k] > E) E = e.E[k];
+    }
+    for (int k = 0; k < 9; ++k) {
+      int sh = e.E[k] - E;
+      if (sh < -1100) sh = -1100;
+      T[k] = w[k] != 0.0 ? w[k] * ldexp(e.f[k], sh) : 0.0;
+      const double s = s1 * (double)(k % 3 - k / 3);
+      xs[k] = s * e.S1[k];
+      ys[k] = xs[k] * xs[k] - (s * s) * e.S2[k];
+    }
+    double term[3];
+    share_pair_terms(T, xs, ys, E, term);
+    const int l = (int)(kp % 64);
+    for (int j = 0; j < 3; ++j) sums[l][j] += term[j];
+    n_snp += 1; n_read += (int32_t)x.n;
+  }
+  res[0] = res[1] = res[2] = 0.0;
+  for (int i = 0; i < 64; ++i) {
+    const int l = (int)at(i, 64);
+    for (int j = 0; j < 3; ++j) res[j] += sums[l][j];
+  }
+}
+
+bool finite3(const double (&r)[3]) { return fabs(r[0]) < INFINITY && fabs(r[1]) < INFINITY && fabs(r[2]) < INFINITY; }
+
 }  // namespace
 
 extern "C" {
@@ -299,7 +464,6 @@ void emu_fit(const emu_pileup* pl, const float* g, int32_t V, const double* mat,
     const int32_t v1 = hyp[2 * (size_t)b], v2 = hyp[2 * (size_t)b + 1];
     if (v1 < 0) continue;
     const bool dbl = v2 >= 0;
-    const int NC = dbl ? 9 : 3;
     const double rh = rho ? rho[b] : 0.0, om = 1.0 - rh;
     double cm[9];
     if (dbl) mix_constants(alpha[b], cm);
@@ -311,48 +475,11 @@ void emu_fit(const emu_pileup* pl, const float* g, int32_t V, const double* mat,
     for (int64_t i = 0; i < n; ++i) {
       const int64_t k = at(i, n);
       const Pair& x = pr[(size_t)k];
-      if (x.n == 0) continue;
-      const float* r1 = g + ((size_t)x.snp * V + v1) * 3;
-      const float* r2 = dbl ? g + ((size_t)x.snp * V + v2) * 3 : nullptr;
-      if (!row_nonzero(r1) || (dbl && !row_nonzero(r2))) continue;
-      double W[9], p[9], q[9];
-      for (int c = 0; c < NC; ++c) W[c] = dbl ? (double)r1[c / 3] * (double)r2[c % 3] : (double)r1[c];
-      const double ra = rh * (amb ? amb[x.snp] : 0.0);
-      for (int c = 0; c < NC; ++c) { p[c] = om * cm[c] + ra; q[c] = 1.0 - p[c]; }
-      const uint32_t m = x.n < (uint32_t)M ? x.n : (uint32_t)M;
-      double t[8][9][2];
-      uint32_t xobs = 0;
-      for (uint32_t r = 0; r < m; ++r) {
-        const int bq = x.rd[r] & 127;
-        const double mt = mat[bq], e3 = err[bq] / 3.0;
-        xobs |= (uint32_t)(x.rd[r] >> 7) << r;
-        for (int c = 0; c < NC; ++c) {
-          t[r][c][0] = mt * q[c] + e3 * p[c];
-          t[r][c][1] = e3 * q[c] + mt * p[c];
-        }
-      }
-      auto likelihood = [&](uint32_t y) {
-        double L = 0.0;
-        for (int c = 0; c < NC; ++c) {
-          double F = t[0][c][y & 1u];
-          for (uint32_t r = 1; r < m; ++r) F = F * t[r][c][(y >> r) & 1u];
-          const double wf = W[c] * F;
-          L = c == 0 ? wf : L + wf;
-        }
-        return L;
-      };
-      const double Lx = likelihood(xobs);
-      if (Lx == 0.0) { n_zero[b] += 1; continue; }
-      const double c0 = emu_log(Lx);
-      double S0 = 0.0, S1 = 0.0, S2 = 0.0;
-      for (uint32_t y = 0; y < (1u << m); ++y) {
-        const double L = likelihood(y);
-        if (L == 0.0) continue;
-        const double u = emu_log(L) - c0;
-        S0 += L; S1 += L * u; S2 += L * (u * u);
-      }
-      if (S0 == 0.0 || !(fabs(S0) < INFINITY)) { n_zero[b] += 1; continue; }
-      const double e1 = S1 / S0, d = S2 / S0 - e1 * e1;
+      const PairFit f = fit_pair(x, g, V, v1, v2, cm, om, rh, amb, M, mat, err);
+      if (f.state == 2) n_zero[b] += 1;
+      if (f.state != 1) continue;
+      const double c0 = f.c0, e1 = f.e1, d = f.d;
+      const uint32_t m = f.m;
       const int l = (int)(k % 64);
       s_obs[l] += c0; s_mean[l] += c0 + e1; s_var[l] += d > 0.0 ? d : 0.0;
       n_snp[b] += 1; n_read[b] += (int32_t)m; n_trunc[b] += x.n > (uint32_t)M;
@@ -363,6 +490,189 @@ void emu_fit(const emu_pileup* pl, const float* g, int32_t V, const double* mat,
       a0 += s_obs[l]; a1 += s_mean[l]; a2 += s_var[l];
     }
     obs[b] = a0; mean[b] = a1; var[b] = a2;
+  }
+  counters_out(counters);
+}
+
+// dmx_engine_share_scan: out[B][T][V][3], n_snp_read[B][T][2]; rho / amb may be NULL (= 0)
+void emu_share_scan(const emu_pileup* pl, const float* g, int32_t V, const double* mat, const double* err, const int32_t* anchors, int32_t T,
+                    const double* rho, const double* amb, double* out, int32_t* n_snp_read, int64_t* counters) {
+  counters_reset();
+  struct ScanPair { bool used; int32_t snp, E; double g1[3], F[3], xs[9], ys[9]; };
+  const double c[3] = {0.0, 0.5, 1.0};               // c_l = 0.5 l
+  const bool diff[3] = {true, true, true};
+  for (int32_t b = 0; b < pl->n_cells; ++b) {
+    const std::vector<Pair> pr = pairs_of(*pl, b);
+    const int64_t n = (int64_t)pr.size();
+    const double rh = rho ? rho[b] : 0.0, om = 1.0 - rh, s1 = om * 0.5;
+    for (int32_t t = 0; t < T; ++t) {
+      const size_t slot = (size_t)b * T + t;
+      for (size_t i = 0; i < (size_t)V * 3; ++i) out[slot * V * 3 + i] = 0.0;
+      n_snp_read[2 * slot] = n_snp_read[2 * slot + 1] = 0;
+      const int32_t a = anchors[slot];
+      if (a < 0) continue;
+      std::vector<ScanPair> sp((size_t)n);
+      for (int64_t i = 0; i < n; ++i) {              // the read loop: once per pair for all partners
+        const Pair& x = pr[(size_t)i];
+        ScanPair& h = sp[(size_t)i];
+        h.used = false;
+        const float* r1 = g + ((size_t)x.snp * V + a) * 3;
+        if (x.n == 0 || !row_nonzero(r1)) continue;
+        h.used = true; h.snp = x.snp;
+        n_snp_read[2 * slot] += 1; n_snp_read[2 * slot + 1] += (int32_t)x.n;
+        const double ra = rh * (amb ? amb[x.snp] : 0.0);
+        const Entries e = share_entries(x, 3, c, diff, om, ra, mat, err);
+        h.E = kNoExponent;
+        for (int l = 0; l < 3; ++l) {
+          h.g1[l] = (double)r1[l];
+          if (h.g1[l] != 0.0 && e.f[l] > 0.0 && e.E[l] > h.E) h.E = e.E[l];
+        }
+        for (int l = 0; l < 3; ++l) {
+          int sh = e.E[l] - h.E;
+          if (sh < -1100) sh = -1100;
+          h.F[l] = (h.g1[l] != 0.0 && e.f[l] > 0.0) ? ldexp(e.f[l], sh) : 0.0;
+        }
+        for (int k = 0; k < 9; ++k) {
+          const int l = k / 3, m = k % 3;
+          const double s = s1 * (double)(m - l);
+          h.xs[k] = s * e.S1[l];
+          h.ys[k] = h.xs[k] * h.xs[k] - (s * s) * e.S2[l];
+        }
+      }
+      for (int32_t v = 0; v < V; ++v) {
+        if (v == a) continue;
+        double acc[3] = {0.0, 0.0, 0.0};
+        for (int64_t i = 0; i < n; ++i) {
+          const ScanPair& h = sp[(size_t)at(i, n)];
+          if (!h.used) continue;
+          const float* r2 = g + ((size_t)h.snp * V + v) * 3;
+          if (!row_nonzero(r2)) continue;
+          double T9[9];
+          for (int k = 0; k < 9; ++k) {
+            const double w = h.g1[k / 3] * (double)r2[k % 3];
+            T9[k] = w != 0.0 ? w * h.F[k / 3] : 0.0;
+          }
+          double term[3];
+          share_pair_terms(T9, h.xs, h.ys, h.E, term);
+          for (int j = 0; j < 3; ++j) acc[j] += term[j];
+        }
+        for (int j = 0; j < 3; ++j) out[(slot * V + v) * 3 + j] = acc[j];
+      }
+    }
+  }
+  counters_out(counters);
+}
+
+// dmx_engine_share_fit: values[B][C][13], counts[B][C][4]; rho / amb may be NULL (= 0).  trace[B][C][3] (may be NULL; the tests' conditions
+// on their inputs, not an output of the pass): how the driver left (1 = the non-finite exit, 2 / 3 / 4 = that step, 10 = iterated), the
+// bisection steps it took, and those of them where a Newton step had been formed (LL'' < 0) and was refused.
+void emu_share_fit(const emu_pileup* pl, const float* g, int32_t V, const double* mat, const double* err, const int32_t* cand, int32_t C,
+                   const double* rho, const double* amb, double start, double tol, int32_t max_iter, double probe, double* values,
+                   int32_t* counts, int32_t* trace, int64_t* counters) {
+  counters_reset();
+  enum { INTERIOR = 1, AT_0 = 2, AT_1 = 4, NOT_CONVERGED = 8, FLAT = 16, NONFINITE = 32 };
+  for (int32_t b = 0; b < pl->n_cells; ++b) {
+    const std::vector<Pair> pr = pairs_of(*pl, b);
+    const double rh = rho ? rho[b] : 0.0;
+    for (int32_t c = 0; c < C; ++c) {
+      const size_t slot = (size_t)b * C + c;
+      double* val = values + slot * 13;
+      int32_t* cnt = counts + slot * 4;
+      for (int i = 0; i < 13; ++i) val[i] = 0.0;
+      cnt[0] = cnt[1] = cnt[2] = cnt[3] = 0;
+      if (trace) trace[3 * slot] = trace[3 * slot + 1] = trace[3 * slot + 2] = 0;
+      const int32_t v1 = cand[2 * slot], v2 = cand[2 * slot + 1];
+      if (v1 < 0) continue;
+      auto evaluate = [&](double al, double (&res)[3], int32_t& ns, int32_t& nr) {
+        share_evaluate(pr, g, V, v1, v2, rh, amb, al, mat, err, res, ns, nr);
+      };
+      double r0[3], r1[3], rx[3], rp[3] = {0.0, 0.0, 0.0};
+      int32_t n_snp, n_read, ns, nr, n_eval = 0, status = 0, how = 10, n_bisect = 0, n_refused = 0;
+      double ahat;
+      evaluate(0.0, r0, n_snp, n_read); ++n_eval;                               // step 1
+      evaluate(1.0, r1, ns, nr); ++n_eval;
+      const bool dn0 = r0[1] <= 0.0, up1 = r1[1] >= 0.0;
+      int end = -1;
+      if (!finite3(r0) || !finite3(r1)) { end = 0; how = 1; }                   // nothing is iterated
+      else if (dn0 && up1) { end = r1[0] > r0[0] ? 1 : 0; how = 2; }            // step 2
+      else if (dn0) { end = 0; how = 3; }                                       // step 3
+      else if (up1) { end = 1; how = 4; }                                       // step 4
+      if (end == 0) { ahat = 0.0; status = AT_0; for (int j = 0; j < 3; ++j) rx[j] = r0[j]; }
+      else if (end == 1) { ahat = 1.0; status = AT_1; for (int j = 0; j < 3; ++j) rx[j] = r1[j]; }
+      else {
+        double lo = 0.0, hi = 1.0, a = start;                                   // step 5
+        for (int32_t it = 1;; ++it) {
+          double r[3];
+          evaluate(a, r, ns, nr); ++n_eval;                                     // step 6
+          if (r[1] > 0.0) lo = a; else hi = a;                                  // step 7
+          double an = a - r[1] / r[2];                                          // step 8
+          if (!(r[2] < 0.0 && lo < an && an < hi)) { an = (lo + hi) / 2.0; ++n_bisect; n_refused += r[2] < 0.0; }
+          const bool conv = fabs(an - a) <= tol;                                // step 9
+          a = an;
+          if (conv) break;
+          if (it >= max_iter) { status |= NOT_CONVERGED; break; }
+        }
+        evaluate(a, rx, ns, nr); ++n_eval;                                      // step 10
+        ahat = a; status |= INTERIOR;
+      }
+      if (probe >= 0.0) evaluate(probe, rp, ns, nr);                            // not counted in n_eval
+      if (rx[2] >= 0.0) status |= FLAT;
+      if (!finite3(r0) || !finite3(r1) || !finite3(rx)) status |= NONFINITE;
+      val[0] = ahat;
+      for (int j = 0; j < 3; ++j) { val[1 + j] = rx[j]; val[4 + j] = r0[j]; val[7 + j] = r1[j]; val[10 + j] = rp[j]; }
+      cnt[0] = n_eval; cnt[1] = status; cnt[2] = n_snp; cnt[3] = n_read;
+      if (trace) { trace[3 * slot] = how; trace[3 * slot + 1] = n_bisect; trace[3 * slot + 2] = n_refused; }
+    }
+  }
+  counters_out(counters);
+}
+
+// dmx_engine_site_fit: obs / mean / var / exc / vexc [S], n_cell / n_read / n_alt / n_trunc / n_zero [S]  (S = the genotype matrix's SNPs)
+void emu_site_fit(const emu_pileup* pl, const float* g, int32_t S, int32_t V, const double* mat, const double* err, const int32_t* hyp,
+                  const double* alpha, const double* rho, const double* amb, int32_t M, double* obs, double* mean, double* var, double* exc,
+                  double* vexc, int32_t* n_cell, int32_t* n_read, int32_t* n_alt, int32_t* n_trunc, int32_t* n_zero, int64_t* counters) {
+  counters_reset();
+  double* val[5] = {obs, mean, var, exc, vexc};
+  int32_t* cnt[5] = {n_cell, n_read, n_alt, n_trunc, n_zero};
+  for (int32_t i = 0; i < S; ++i)
+    for (int j = 0; j < 5; ++j) { val[j][i] = 0.0; cnt[j][i] = 0; }
+  std::vector<std::vector<int32_t>> chunks;         // singlets, then doublets, ascending cell id; no chunk straddles the two lists
+  for (int kind = 0; kind < 2; ++kind) {
+    std::vector<int32_t> list;
+    for (int32_t b = 0; b < pl->n_cells; ++b)
+      if (hyp[2 * (size_t)b] >= 0 && (hyp[2 * (size_t)b + 1] >= 0) == (kind == 1)) list.push_back(b);
+    for (size_t c0 = 0; c0 < list.size(); c0 += 64)
+      chunks.emplace_back(list.begin() + (int64_t)c0, list.begin() + (int64_t)(c0 + 64 < list.size() ? c0 + 64 : list.size()));
+  }
+  const int64_t nch = (int64_t)chunks.size();
+  std::vector<double> part((size_t)nch * S * 5, 0.0);
+  for (int64_t ch = 0; ch < nch; ++ch) {
+    const std::vector<int32_t>& mem = chunks[(size_t)ch];
+    const int64_t nm = (int64_t)mem.size();
+    double* pv = part.data() + (size_t)ch * S * 5;
+    for (int64_t i = 0; i < nm; ++i) {
+      const int32_t b = mem[(size_t)at(i, nm)];
+      const int32_t v1 = hyp[2 * (size_t)b], v2 = hyp[2 * (size_t)b + 1];
+      const double rh = rho ? rho[b] : 0.0, om = 1.0 - rh;
+      double cm[9];
+      if (v2 >= 0) mix_constants(alpha[b], cm);
+      else for (int c = 0; c < 3; ++c) cm[c] = 0.5 * c;
+      for (const Pair& x : pairs_of(*pl, b)) {
+        if (x.snp < 0 || x.snp >= S) continue;
+        const PairFit f = fit_pair(x, g, V, v1, v2, cm, om, rh, amb, M, mat, err);
+        if (f.state == 2) n_zero[x.snp] += 1;
+        if (f.state != 1) continue;
+        double* o = pv + (size_t)x.snp * 5;
+        o[0] += f.c0; o[1] += f.c0 + f.e1; o[2] += f.d > 0.0 ? f.d : 0.0;
+        o[3] += (double)f.kx - f.a1; o[4] += f.da > 0.0 ? f.da : 0.0;
+        n_cell[x.snp] += 1; n_read[x.snp] += (int32_t)f.m; n_alt[x.snp] += (int32_t)f.kx; n_trunc[x.snp] += x.n > (uint32_t)M;
+      }
+    }
+  }
+  for (int64_t i = 0; i < nch; ++i) {
+    const double* pv = part.data() + (size_t)at(i, nch) * S * 5;
+    for (int32_t s = 0; s < S; ++s)
+      for (int j = 0; j < 5; ++j) val[j][s] += pv[(size_t)s * 5 + j];
   }
   counters_out(counters);
 }

@@ -6,7 +6,9 @@ is the same source with -ffp-contract=fast (one of the three wrong variants; the
 
 The inputs: pileups of tests/quality_mix.mixed_depth_pileup cut to exact pair counts per barcode (0, 1, 63, 64, 65, 129: the kernels'
 trip of 64 pair headers, its tail and a second trip), dense ones of exactly those SNP counts, read counts as u8 / u16 / u32, genotype
-matrices with all-zero rows, hard zeros and a row of float32 subnormals, and hand-built pairs where a count or a path must be exact."""
+matrices with all-zero rows, hard zeros and a row of float32 subnormals, and hand-built pairs where a count or a path must be exact; for
+the share passes a panel of 66 samples and a pool of true unequal doublets, for the site audit hypotheses whose singlet and doublet lists
+have exact lengths."""
 import ctypes as C
 import subprocess
 from dataclasses import dataclass
@@ -20,6 +22,11 @@ import quality_mix as QM
 ROOT = Path(__file__).resolve().parents[1]
 DESCENDING, LIBM_LOG = 1, 2
 PAIR_COUNTS = (0, 1, 63, 64, 65, 129)
+SITE_FLOATS = ("obs", "mean", "var", "exc", "vexc")
+SITE_COUNTS = ("n_cell", "n_read", "n_alt", "n_trunc", "n_zero")
+SHARE_VALUES = ("alpha", "ll", "d1", "d2", "ll0", "d10", "d20", "ll1", "d11", "d21", "llp", "d1p", "d2p")     # Engine.share_fit's names
+SHARE_COUNTS = ("n_eval", "status", "n_snp", "n_read")
+INTERIOR, AT_0, AT_1, NOT_CONVERGED, FLAT, NONFINITE = 1, 2, 4, 8, 16, 32
 
 
 class EmuPileup(C.Structure):
@@ -35,7 +42,7 @@ class Emulator:
     def __init__(self, so):
         self.L = C.CDLL(str(so))
         for name in ("emu_set_variant", "emu_log_n", "emu_ambient", "emu_ambient_doublet", "emu_fit", "emu_refine", "emu_cluster_stage",
-                     "emu_cluster_mstep"):
+                     "emu_cluster_mstep", "emu_share_scan", "emu_share_fit", "emu_site_fit"):
             getattr(self.L, name).restype = None
         self.L.emu_set_variant.argtypes = [C.c_int]
         self.L.emu_log_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
@@ -46,6 +53,10 @@ class Emulator:
         self.L.emu_refine.argtypes = [P, I, I, V, V, V, V, V, V, V, V]
         self.L.emu_cluster_stage.argtypes = [P, V, V, V, V, V, V, V]
         self.L.emu_cluster_mstep.argtypes = [I, I, V, V, V, V, V, V]
+        D = C.c_double
+        self.L.emu_share_scan.argtypes = [P, V, I, V, V, V, I, V, V, V, V, V]
+        self.L.emu_share_fit.argtypes = [P, V, I, V, V, V, I, V, V, D, D, I, D, V, V, V, V]
+        self.L.emu_site_fit.argtypes = [P, V, I, I, V, V, V, V, V, V, I] + [V] * 11
 
     def variant(self, v):
         """0 = the contract; DESCENDING and / or LIBM_LOG = the wrong variants."""
@@ -110,6 +121,52 @@ class Emulator:
         self.L.emu_fit(C.byref(st), g.ctypes.data, g.shape[1], mat.ctypes.data, err.ctypes.data, hyp.ctypes.data, al.ctypes.data,
                        None if rh is None else rh.ctypes.data, None if amb is None else amb.ctypes.data, int(M),
                        *(out[k].ctypes.data for k in ("obs", "mean", "var", "n_snp", "n_read", "n_trunc", "n_zero")), cnt.ctypes.data)
+        return out, self._counters(cnt)
+
+    def share_scan(self, sp, g, mat, err, anchors, rho, ambient):
+        """(out[B][T][V][3], n_snp_read[B][T][2], counters) of dmx_engine_share_scan's contract."""
+        st, keep = self._pileup(sp)
+        g = np.ascontiguousarray(g, dtype=np.float32); mat, err = _f64(mat), _f64(err)
+        an = _i32(anchors)
+        rh = None if rho is None else _f64(rho)
+        amb = None if ambient is None else _f64(ambient)
+        B, T, V = sp.n_cells, an.shape[1], g.shape[1]
+        out = np.zeros((B, T, V, 3)); nsr = np.zeros((B, T, 2), dtype=np.int32); cnt = np.zeros(3, dtype=np.int64)
+        self.L.emu_share_scan(C.byref(st), g.ctypes.data, V, mat.ctypes.data, err.ctypes.data, an.ctypes.data, T,
+                              None if rh is None else rh.ctypes.data, None if amb is None else amb.ctypes.data, out.ctypes.data,
+                              nsr.ctypes.data, cnt.ctypes.data)
+        return out, nsr, self._counters(cnt)
+
+    def share_fit(self, sp, g, mat, err, cand, rho, ambient, start=0.5, tol=1e-6, max_iter=30, probe=-1.0):
+        """(values[B][C][13], counts[B][C][4], trace[B][C][3], counters) of dmx_engine_share_fit's contract; trace = how the driver left
+        (1 = the non-finite exit, 2 / 3 / 4 = that step, 10 = iterated), its bisection steps, and those taken where a Newton step was refused."""
+        st, keep = self._pileup(sp)
+        g = np.ascontiguousarray(g, dtype=np.float32); mat, err = _f64(mat), _f64(err)
+        cd = _i32(cand)
+        rh = None if rho is None else _f64(rho)
+        amb = None if ambient is None else _f64(ambient)
+        B, Cn = sp.n_cells, cd.shape[1]
+        val = np.zeros((B, Cn, 13)); cts = np.zeros((B, Cn, 4), dtype=np.int32); tr = np.zeros((B, Cn, 3), dtype=np.int32)
+        cnt = np.zeros(3, dtype=np.int64)
+        self.L.emu_share_fit(C.byref(st), g.ctypes.data, g.shape[1], mat.ctypes.data, err.ctypes.data, cd.ctypes.data, Cn,
+                             None if rh is None else rh.ctypes.data, None if amb is None else amb.ctypes.data, float(start), float(tol),
+                             int(max_iter), float(probe), val.ctypes.data, cts.ctypes.data, tr.ctypes.data, cnt.ctypes.data)
+        return val, cts, tr, self._counters(cnt)
+
+    def site_fit(self, sp, g, mat, err, hyp, alpha, rho, ambient, M):
+        """(dict of obs / mean / var / exc / vexc / n_cell / n_read / n_alt / n_trunc / n_zero [S], counters) of dmx_engine_site_fit's contract."""
+        st, keep = self._pileup(sp)
+        g = np.ascontiguousarray(g, dtype=np.float32); mat, err = _f64(mat), _f64(err)
+        hyp, al = _i32(hyp), _f64(alpha)
+        rh = None if rho is None else _f64(rho)
+        amb = None if ambient is None else _f64(ambient)
+        S = g.shape[0]
+        out = {k: np.zeros(S) for k in SITE_FLOATS}
+        out.update({k: np.zeros(S, dtype=np.int32) for k in SITE_COUNTS})
+        cnt = np.zeros(3, dtype=np.int64)
+        self.L.emu_site_fit(C.byref(st), g.ctypes.data, S, g.shape[1], mat.ctypes.data, err.ctypes.data, hyp.ctypes.data, al.ctypes.data,
+                            None if rh is None else rh.ctypes.data, None if amb is None else amb.ctypes.data, int(M),
+                            *(out[k].ctypes.data for k in SITE_FLOATS + SITE_COUNTS), cnt.ctypes.data)
         return out, self._counters(cnt)
 
     def refine(self, sp, S, V, mat, err, assign):
@@ -244,6 +301,38 @@ def spike_rows(g, rng):
 
 
 ALT127, REF127 = (1 << 7) | 127, 127
+POOL_COUNTS = (20, 40, 63, 64, 65, 100, 129)
+
+
+def doublet_pool(engine, synth):
+    """True unequal doublets for the share fit's interior maxima: 36 barcodes of synth.make_ambient_mixed_pileup over 300 SNPs and 4 donors,
+    every one a doublet with a share 0.2 of its reads from the second donor, near-hard GT rows, two reads per pair on average; cut to
+    POOL_COUNTS pairs (the first seven barcodes) and 30..130 elsewhere, so that barcodes on both sides of 64 pairs occur; in every fifth
+    barcode one pair's reads are repeated up to 280 reads (a deep pair: rescales are taken)."""
+    rng = np.random.default_rng(9150)
+    S, V, B = 300, 4, 36
+    raw = synth.make_raw_genotypes(rng, S, V)
+    g = QM.genotypes(engine, rng, raw.alleles, "GT")
+    sp = synth.make_ambient_mixed_pileup(rng, raw.alleles, B, 0.6, 2.0, 0.0, True, 0.2)[0]
+    po = np.asarray(sp.cell_pair_off, dtype=np.int64)
+    keep = np.zeros(po[-1], dtype=bool)
+    for b in range(B):
+        want = POOL_COUNTS[b] if b < len(POOL_COUNTS) else int(rng.integers(30, 131))
+        assert po[b + 1] - po[b] >= want
+        keep[po[b] + rng.permutation(po[b + 1] - po[b])[:want]] = True
+    sp = filter_pairs(synth, sp, keep)
+    po, nrd, snp, rd = np.asarray(sp.cell_pair_off), np.asarray(sp.pair_nrd).astype(np.int64), np.asarray(sp.pair_snp), np.asarray(sp.reads)
+    start = np.cumsum(nrd) - nrd
+    cells = []
+    for b in range(B):
+        prs = [(int(snp[k]), rd[start[k]:start[k] + nrd[k]]) for k in range(po[b], po[b + 1])]
+        if b % 5 == 2:
+            k = next(i for i, (_, r) in enumerate(prs) if len(r) >= 2)
+            prs[k] = (prs[k][0], np.tile(prs[k][1], 280 // len(prs[k][1]) + 1)[:280])
+        cells.append(prs)
+    deep = hand_pileup(synth, cells, S)
+    deep.truth[:] = sp.truth
+    return Problem("pool_02", deep, g, deep=True)
 
 
 def problems(engine, synth):
@@ -266,6 +355,9 @@ def problems(engine, synth):
     mixed("mix_edges", 9102, "edges", 0.3, 6, "GT")
     mixed("mix_max", 9103, "max", 0.5, 5, "PL", width=np.uint32)
     mixed("one_sample", 9104, "edges", 0.25, 0, "GT", V=1, B=9, counts=[0, 1, 63, 64, 65, 129, 17, 100, 140])
+    # the share scan's panel: V = 66 is the smallest V with a second block of 64 partners that has more than one active lane
+    mixed("panel_66", 9105, "edges", 0.3, 4, "GT", V=66, B=16)
+    out["pool_02"] = doublet_pool(engine, synth)
     assert out["mix_full"].sp.pair_nrd.dtype == np.uint8 and out["mix_edges"].sp.pair_nrd.dtype == np.uint16
     assert int(out["mix_edges"].sp.pair_nrd.max()) >= 256 and int(out["mix_max"].sp.pair_nrd.max()) >= 256
 
@@ -438,3 +530,114 @@ def mstep_weights(p, Cn, seed=6):
 
 
 MSTEP_CASES = [("slab_511", 1), ("slab_512", 3), ("slab_513", 70), ("mix_edges", 3), ("dense_65", 70), ("edge", 1)]
+
+
+# ---- the continuous mixing share (dmx_engine_share_scan / dmx_engine_share_fit) -----------------------------------------------------------------
+
+def barcode_rho(p, seed=7):
+    """rho[B] from {0, 0.05, 0.3, 1}; all zero on `zero` (its tables make a soup read certain)."""
+    B = p.sp.n_cells
+    rho = np.random.default_rng(9960 + seed + B).choice([0.0, 0.05, 0.3, 1.0], size=B)
+    if p.name == "zero":
+        rho[:] = 0.0
+    return rho
+
+
+PANEL_ANCHORS = (63, 64, 65, 3, 40, 0, 62, 17)     # both blocks of 64 partners and the three ids around the block's edge
+
+
+def anchors(p, T, seed=8):
+    """anchors[B][T]: on the panel PANEL_ANCHORS in turn, elsewhere random samples; one slot in six unused (-1)."""
+    B, V = p.sp.n_cells, p.V
+    rng = np.random.default_rng(9970 + seed + 17 * T + B)
+    if V == 66:
+        an = np.array([[PANEL_ANCHORS[(b * T + t) % len(PANEL_ANCHORS)] for t in range(T)] for b in range(B)])
+    else:
+        an = rng.integers(0, V, size=(B, T))
+    an = np.where(rng.random((B, T)) < 1 / 6, -1, an).astype(np.int32)
+    if p.name == "edge":
+        an[:] = np.array([0, 1, 2, -1][:T], dtype=np.int32)[None]
+    if p.name == "zero":
+        an[:] = np.array([0, 1, -1, 0][:T], dtype=np.int32)[None]
+    return an
+
+
+# (problem, T, rho given): the panel with every T, V = 3 and 5 on the mixed, dense and hand-built pileups, all three nrd widths, L = 0 on `zero`
+SHARE_SCAN_CASES = [("panel_66", 1, True), ("panel_66", 2, False), ("panel_66", 4, True), ("mix_full", 2, True), ("mix_edges", 4, True),
+                    ("mix_max", 1, False), ("dense_1", 2, True), ("dense_63", 1, False), ("dense_64", 4, True), ("dense_65", 2, True),
+                    ("dense_129", 1, True), ("edge", 4, True), ("edge", 2, False), ("zero", 2, False), ("mix_full", 2, False),
+                    ("pool_02", 4, False)]          # (the last two hold the sums in which libm's log changes a bit)
+
+
+def share_candidates(p, Cn, seed=9):
+    """cand[B][Cn][2]: on the doublet pool the true pair (maximum near 0.2), the true pair swapped (near 0.8; with a single slot, on the odd
+    barcodes), then random pairs, every seventh barcode's last slot unused; elsewhere `candidates`."""
+    if p.name != "pool_02":
+        return candidates(p, Cn, seed)
+    B, V = p.sp.n_cells, p.V
+    rng = np.random.default_rng(9980 + seed + 31 * Cn + B)
+    cand = np.full((B, Cn, 2), -1, dtype=np.int32)
+    for b in range(B):
+        for c in range(Cn):
+            if c < 2:
+                cand[b, c] = p.sp.truth[b][::-1] if (c + (Cn == 1 and b % 2)) % 2 else p.sp.truth[b]
+            else:
+                v1 = int(rng.integers(0, V))
+                cand[b, c] = (v1, (v1 + 1 + int(rng.integers(0, V - 1))) % V)
+        if b % 7 == 6:
+            cand[b, Cn - 1] = -1
+    return cand
+
+
+# (problem, C, start, tol, max_iter, probe, rho given)
+SHARE_FIT_CASES = [("pool_02", 3, 0.5, 1e-6, 30, 0.5, False), ("pool_02", 1, 0.2, 1e-2, 30, -1.0, True), ("pool_02", 8, 0.5, 1e-6, 2, 0.0, True),
+                   ("pool_02", 3, 0.2, 1e-6, 1, 1.0, False), ("pool_02", 8, 0.2, 1e-6, 30, -1.0, True), ("mix_full", 3, 0.5, 1e-6, 30, 0.5, True),
+                   ("mix_edges", 8, 0.2, 1e-2, 30, -1.0, True), ("mix_max", 1, 0.5, 1e-6, 30, 1.0, False), ("panel_66", 3, 0.5, 1e-6, 30, 0.0, True),
+                   ("dense_1", 1, 0.5, 1e-6, 30, -1.0, True), ("dense_64", 8, 0.2, 1e-6, 2, 0.5, False), ("dense_65", 3, 0.5, 1e-2, 30, 1.0, True),
+                   ("dense_129", 3, 0.2, 1e-6, 30, 0.0, True), ("edge", 8, 0.5, 1e-6, 30, 0.5, True), ("edge", 3, 0.2, 1e-2, 1, -1.0, False),
+                   ("zero", 1, 0.5, 1e-6, 30, 0.5, False), ("zero", 3, 0.2, 1e-6, 30, -1.0, False),
+                   ("mix_full", 3, 0.5, 1e-6, 30, 0.5, False)]     # (the last one holds a sum in which libm's log changes a bit)
+
+
+def share_fit_id(c):
+    return f"{c[0]}-C{c[1]}-s{c[2]}-t{c[3]:g}-i{c[4]}-p{c[5]:g}-{'soup' if c[6] else 'clean'}"
+
+
+# ---- the site audit (dmx_engine_site_fit) ----------------------------------------------------------------------------------------------------
+
+LIST_LENGTHS = (0, 1, 63, 64, 65, 129)
+
+
+def site_hypotheses(p, lists=None, seed=10):
+    """(hyp[B][2], alpha[B], rho[B]).  lists = None: `hypotheses`.  lists = (ns, nd): exactly ns singlet and nd doublet hypotheses on
+    barcodes drawn at random, the rest unused; a barcode's own sample (b mod V), one in eight a wrong one; the barcodes that hold the
+    pairs at the last two SNPs are used first."""
+    if lists is None:
+        return hypotheses(p)
+    ns, nd = lists
+    B, V, S = p.sp.n_cells, p.V, p.g.shape[0]
+    rng = np.random.default_rng(9990 + seed + 7 * ns + nd + B)
+    po = np.asarray(p.sp.cell_pair_off)
+    cell = np.repeat(np.arange(B), np.diff(po))
+    last = np.unique(cell[np.asarray(p.sp.pair_snp) >= S - 2])
+    order = np.concatenate([last, rng.permutation(np.setdiff1d(np.arange(B), last))])
+    kind = np.full(B, -1)
+    kind[order[:ns + nd]] = rng.permutation(np.repeat([0, 1], [ns, nd]))
+    v1 = np.where(rng.random(B) < 1 / 8, rng.integers(0, V, size=B), np.arange(B) % V)
+    v2 = (v1 + 1 + rng.integers(0, V - 1, size=B)) % V
+    hyp = np.stack([np.where(kind >= 0, v1, -1), np.where(kind == 1, v2, -1)], axis=1).astype(np.int32)
+    return hyp, rng.choice([0.0, 0.5, 0.37], size=B), rng.choice([0.0, 0.05, 0.3, 1.0], size=B)
+
+
+# (problem, M, rho given, (singlets, doublets) or None): over the slab problems both lists take every length of LIST_LENGTHS; the others
+# carry both kinds of hypothesis at every M
+SITE_CASES = [("slab_511", 1, True, (0, 129)), ("slab_511", 2, False, (129, 0)), ("slab_512", 3, True, (1, 65)), ("slab_512", 4, False, (65, 1)),
+              ("slab_513", 5, True, (63, 64)), ("slab_513", 8, True, (64, 63)), ("mix_edges", 1, True, None), ("mix_edges", 2, True, None),
+              ("mix_edges", 3, False, None), ("mix_full", 4, False, None), ("mix_full", 5, True, None), ("mix_max", 8, True, None),
+              ("dense_65", 4, True, None), ("dense_129", 8, False, None), ("one_sample", 3, True, None), ("edge", 8, True, None),
+              ("zero", 2, False, None), ("zero", 8, False, None)]
+SITE_WAVES_CASE = ("slab_513", 8, True, (64, 63))          # run again with partial_bytes at one chunk per wave
+
+
+def site_id(c):
+    return f"{c[0]}-M{c[1]}-{'soup' if c[2] else 'clean'}" + ("" if c[3] is None else f"-{c[3][0]}+{c[3][1]}")

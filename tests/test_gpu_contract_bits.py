@@ -1,7 +1,8 @@
 """GPU (-m gpu): the feature kernels against the host emulator of their stated contracts, bit for bit.
 
-include/dmx.h states, for the ambient profile, the ambient doublet profile, the goodness of fit, the genotype refinement and the cluster
-stage / M-step, every operation and the order of every sum.  tests/contract_emul.cpp restates those blocks as serial host loops (plain
+include/dmx.h states, for the ambient profile, the ambient doublet profile, the goodness of fit, the genotype refinement, the cluster
+stage / M-step, the share scan, the share fit (its Newton driver step by step) and the site audit, every operation and the order of
+every sum.  tests/contract_emul.cpp restates those blocks as serial host loops (plain
 recurrences and divisions, dmx_log's host emulation); tests/test_contract_emul_cpu.py shows, without a GPU, that the emulator computes
 the right numbers, that these inputs tell a contracted product, a reversed sum and libm's log from the contract, and that no log
 argument here is subnormal, inf or nan (those go to the runtime's log, which no host can promise to match).  Each case below runs the
@@ -44,12 +45,17 @@ def staged(m, p, V=None, g=None):
     return e
 
 
-def same_bits(what, got, want):
+def same_bits(what, got, want, nan_equal=False):
+    """Every element's bits.  nan_equal (the share passes only): elements that are NaN on both sides count as equal — 0 / 0 gives a NaN whose
+    sign and payload IEEE does not fix, and x86 and the device differ there; a NaN on one side only is a difference."""
     got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
     assert got.shape == want.shape and got.dtype == want.dtype, (what, got.shape, want.shape, got.dtype, want.dtype)
     a, b = CE.bits(got), CE.bits(want)
-    if not np.array_equal(a, b):
-        bad = np.argwhere(a != b)
+    ne = a != b
+    if nan_equal:
+        ne &= ~(np.isnan(got) & np.isnan(want))
+    if ne.any():
+        bad = np.argwhere(ne)
         i = tuple(bad[0])
         raise AssertionError(f"{what}: {len(bad)} of {a.size} elements differ; first at {i}: engine {got[i]!r} ({int(a[i]):#x}), "
                              f"emulator {want[i]!r} ({int(b[i]):#x})")
@@ -146,3 +152,100 @@ def test_cluster_mstep_bits(m, case):
     same_bits("snp_off", off, roff); same_bits("cell", cell, rcell); same_bits("lgl[P][3]", lgl, rlgl)
     RL, RW = m["emu"].cluster_mstep(roff, rcell, rlgl, w)
     same_bits("W[S][C]", W, RW); same_bits("LL[S][C][3]", LL, RL)
+
+
+def soup(p, given):
+    return (CE.barcode_rho(p), CE.amb_freq(p)) if given else (None, None)
+
+
+@pytest.mark.parametrize("case", CE.SHARE_SCAN_CASES, ids=lambda c: f"{c[0]}-T{c[1]}-{'soup' if c[2] else 'clean'}")
+def test_share_scan_bits(m, case):
+    name, T, given = case
+    p = m["P"][name]
+    an = CE.anchors(p, T)
+    rho, a = soup(p, given)
+    e = staged(m, p)
+    try:
+        out, n_snp, n_read = e.share_scan(an, rho, a)
+        info = e.share_info()
+    finally:
+        e.close()
+    assert info["have_scan"] == 1 and info["n_anchor"] == T and info["n_samples"] == p.V
+    assert info["scan_entries"] == int((an >= 0).sum()) * (p.V - 1)
+    want, nsr, cnt = m["emu"].share_scan(p.sp, p.g, *tables(m, p), an, rho, a)
+    assert cnt["log_other"] == 0 and (cnt["log_zero"] > 0) == (name == "zero")
+    same_bits("n_snp_read[B][T][2]", np.stack([n_snp, n_read], axis=2), nsr)
+    same_bits("out[B][T][V][3]", out, want, nan_equal=True)
+
+
+IDENTITY_PROBLEMS = ("pool_02", "mix_full", "mix_edges", "panel_66", "dense_64", "edge", "zero")
+
+
+def identity_scan(p, cand):
+    """(anchors[B][T], the barcodes of at most 64 pairs): slot t < min(C, 4) of the scan holds v1 of the fit's slot t."""
+    T = min(cand.shape[1], 4)
+    return np.ascontiguousarray(cand[:, :T, 0]), np.flatnonzero(np.diff(p.sp.cell_pair_off) <= 64)
+
+
+@pytest.mark.parametrize("case", CE.SHARE_FIT_CASES, ids=CE.share_fit_id)
+def test_share_fit_bits(m, case):
+    name, Cn, start, tol, max_iter, probe, given = case
+    p = m["P"][name]
+    cand = CE.share_candidates(p, Cn)
+    rho, a = soup(p, given)
+    e = staged(m, p)
+    try:
+        fit = e.share_fit(cand, rho, a, start=start, tol=tol, max_iter=max_iter, probe=probe)
+        info = e.share_info()
+        an, short = identity_scan(p, cand)
+        scan = e.share_scan(an, rho, a)[0] if name in IDENTITY_PROBLEMS else None
+    finally:
+        e.close()
+    used = cand[:, :, 0] >= 0
+    assert info["have_fit"] == 1 and info["n_cand"] == Cn and info["fit_used"] == int(used.sum())
+    assert info["fit_evals"] == int(fit["n_eval"][used].sum()) + (int(used.sum()) if probe >= 0 else 0)
+    val, cts, _, cnt = m["emu"].share_fit(p.sp, p.g, *tables(m, p), cand, rho, a, start, tol, max_iter, probe)
+    assert cnt["log_other"] == 0 and (cnt["log_zero"] > 0) == (name == "zero")
+    same_bits("counts[B][C][4]", np.stack([fit[k] for k in CE.SHARE_COUNTS], axis=2), cts)
+    same_bits("values[B][C][13]", np.stack([fit[k] for k in CE.SHARE_VALUES], axis=2), val, nan_equal=True)
+    if scan is not None:
+        # a barcode of at most 64 pairs leaves at most one term in each of the fit's 64 sums: its evaluation at 0 is the scan's serial sum
+        for b in short:
+            for t in range(an.shape[1]):
+                if an[b, t] >= 0:
+                    at0 = np.array([fit[k][b, t] for k in ("ll0", "d10", "d20")])
+                    same_bits(f"the fit at 0 against the scan, barcode {b} slot {t}", at0, scan[b, t, cand[b, t, 1]], nan_equal=True)
+
+
+def site_arguments(p, case):
+    _, M, given, lists = case
+    hyp, alpha, rho = CE.site_hypotheses(p, lists)
+    return hyp, alpha, rho if given else None, CE.amb_freq(p) if given else None, M
+
+
+@pytest.mark.parametrize("case", CE.SITE_CASES, ids=CE.site_id)
+def test_site_fit_bits(m, case):
+    p = m["P"][case[0]]
+    hyp, alpha, rho, a, M = site_arguments(p, case)
+    S = p.g.shape[0]
+    e = staged(m, p)
+    try:
+        out = e.site_fit(hyp, alpha, rho, a, M)
+        info = e.site_fit_info()
+        if case == CE.SITE_WAVES_CASE:                  # one chunk per wave of the partial buffer: the bits must not move
+            waves = e.site_fit(hyp, alpha, rho, a, M, partial_bytes=64 * S)
+            winfo = e.site_fit_info()
+    finally:
+        e.close()
+    ns, nd = int(((hyp[:, 0] >= 0) & (hyp[:, 1] < 0)).sum()), int(((hyp[:, 0] >= 0) & (hyp[:, 1] >= 0)).sum())
+    assert (info["n_singlet"], info["n_doublet"], info["n_used"], info["max_reads"]) == (ns, nd, ns + nd, M)
+    assert info["n_chunks"] == -(-ns // 64) + -(-nd // 64) and info["chunk_cells"] == 64
+    want, cnt = m["emu"].site_fit(p.sp, p.g, *tables(m, p), hyp, alpha, rho, a, M)
+    assert cnt["log_other"] == 0 and cnt["log_zero"] == 0
+    for k in CE.SITE_COUNTS + CE.SITE_FLOATS:
+        same_bits(k, out[k], want[k])
+    assert info["n_zero"] == int(want["n_zero"].sum()) and info["n_trunc"] == int(want["n_trunc"].sum())
+    if case == CE.SITE_WAVES_CASE:
+        assert winfo["n_waves"] == winfo["n_chunks"] == info["n_chunks"] and info["n_waves"] == 1
+        for k in CE.SITE_COUNTS + CE.SITE_FLOATS:
+            same_bits(k + " at one chunk per wave", waves[k], want[k])
