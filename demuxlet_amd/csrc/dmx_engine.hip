@@ -37,6 +37,7 @@
 extern char** environ;
 #include "dmx_log.hpp"
 #include "dmx_engine_state.hpp"
+#include "dmx_hyp_plan.hpp"
 
 using dmx::set_error;
 using dmx::DevBuf; using dmx::Event; using dmx::EventPair; using dmx::Stream; using dmx::PinnedBuf;
@@ -3537,7 +3538,7 @@ __global__ __launch_bounds__(64 * kFitWaves) void k_fit(PileupView pv, int nrd_w
     const uint32_t incl = seg_scan_incl<64>(n);
     const int64_t off = rd_base + (int64_t)(incl - n);
     rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    uint32_t m = 0, x = 0;
+    uint32_t m = 0, x = 0;                         // (the per-pair body from cm[] to the moments is k_site_partial's too: DESIGN.md says why it stays written twice)
     double W[NC], pp[NC], qq[NC], mat[MM], e3[MM];
 #pragma unroll
     for (int c = 0; c < NC; ++c) { W[c] = 0.0; pp[c] = 0.0; qq[c] = 0.0; }
@@ -3702,7 +3703,7 @@ __global__ __launch_bounds__(64) void k_site_partial(PileupView pv, int nrd_widt
       const int64_t off = rd_base + (int64_t)(incl - n);
       rd_base += (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
       const int k = snp - s0;                          // inside the slab by construction (pairs in ascending SNP order); checked all the same
-      uint32_t m = 0, x = 0;
+      uint32_t m = 0, x = 0;                       // (the per-pair body from cm[] to the moments is k_fit's: DESIGN.md says why it stays written twice)
       double W[NC], pp[NC], qq[NC], mat[MM], e3[MM];
 #pragma unroll
       for (int c = 0; c < NC; ++c) { W[c] = 0.0; pp[c] = 0.0; qq[c] = 0.0; }
@@ -10532,6 +10533,123 @@ extern "C" int dmx_engine_kernel_names(dmx_engine* e, dmx_kernel_names* out) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// What the feature calls' requests have in common ("Shared request helpers").  Every message names the calling entry point
+// (fn).  The checks read the engine and never change it, so a refused call leaves every earlier result readable.
+namespace {
+
+int require_staged(dmx_engine* e, const char* fn) {
+  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "%s: no pileup staged (dmx_engine_set_pileup first)", fn);
+  if (!e->d_g) return set_error(DMX_ERR_STATE, "%s: no genotype matrix (dmx_engine_set_genotypes first)", fn);
+  if (e->pv.S != e->S)
+    return set_error(DMX_ERR_STATE, "%s: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", fn, e->S, e->pv.S);
+  return DMX_OK;
+}
+
+int require_sizes(dmx_engine* e, const char* fn, int32_t n_cells, int32_t n_snps) {
+  if (n_cells != e->pv.B) return set_error(DMX_ERR_ARG, "%s: n_cells %d, the staged pileup has %d", fn, n_cells, e->pv.B);
+  if (n_snps != e->S) return set_error(DMX_ERR_ARG, "%s: n_snps %d, the genotype matrix has %d", fn, n_snps, e->S);
+  return DMX_OK;
+}
+
+// n ids from host or device memory into dst.  sync = false leaves a device copy pending on the stream, for a caller that waits for
+// it together with copies of its own.
+int fetch_ids(dmx_engine* e, const int32_t* src, int32_t memory, size_t n, std::vector<int32_t>& dst, bool sync = true) {
+  dst.resize(n);
+  if (n == 0) return DMX_OK;
+  if (memory == DMX_MEM_DEVICE) {
+    HIP_TRY(hipMemcpyAsync(dst.data(), src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
+    if (sync) HIP_TRY(hipStreamSynchronize(e->stream));
+  } else {
+    std::memcpy(dst.data(), src, sizeof(int32_t) * n);
+  }
+  return DMX_OK;
+}
+
+inline bool in_unit_interval(double x) { return x >= 0.0 && x <= 1.0; }   // (false for a NaN)
+int not_in_unit_interval(const char* fn, const char* name, int32_t i, double x) {
+  return set_error(DMX_ERR_ARG, "%s: %s[%d] = %g is not in [0, 1]", fn, name, i, x);
+}
+// p[n] (NULL = not given, nothing to check)
+int check_unit_interval(const char* fn, const char* name, const double* p, int32_t n) {
+  for (int32_t i = 0; p && i < n; ++i)
+    if (!in_unit_interval(p[i])) return not_in_unit_interval(fn, name, i, p[i]);
+  return DMX_OK;
+}
+
+// dst[n] on the device = src[n] of the host, or zeros where src is NULL (a soup that was not given)
+int stage_soup(dmx_engine* e, const double* src, int32_t n, double* dst) {
+  if (n <= 0) return DMX_OK;
+  if (src) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, e->stream));
+  else HIP_TRY(hipMemsetAsync(dst, 0, sizeof(double) * (size_t)n, e->stream));
+  return DMX_OK;
+}
+
+// ids[n_slot][2], C slots per barcode: every slot is -1 (unused; counted out of *n_used) or two different samples in [0, V)
+int check_pairs(const char* fn, const char* name, const std::vector<int32_t>& ids, size_t n_slot, int32_t C, int32_t V, int64_t* n_used) {
+  *n_used = 0;
+  for (size_t k = 0; k < n_slot; ++k) {
+    const int32_t v1 = ids[2 * k], v2 = ids[2 * k + 1];
+    if (v1 == -1) continue;
+    if (v1 < 0 || v1 >= V || v2 < 0 || v2 >= V || v1 == v2)
+      return set_error(DMX_ERR_ARG, "%s: %s[%zu][%zu] = (%d, %d) is not -1 or two different samples in [0, %d)", fn, name, k / (size_t)C, k % (size_t)C,
+                       v1, v2, V);
+    ++*n_used;
+  }
+  return DMX_OK;
+}
+
+// The hypotheses of dmx_engine_fit, dmx_engine_site_fit and dmx_engine_redraw: hyp[B][2] with alpha[B], rho[B] (NULL = 0) and the soup
+// ambient[S] (NULL only with rho = NULL).  The caller runs check_args, check_ranges, the fetch of hyp, list and upload in this order
+// with its own checks, buffers and device work between them; the plan lives until the call has synchronised (the uploads read it).
+struct HypPlan {
+  const char* fn;
+  int32_t B, V, S;
+  const int32_t* src; int32_t memory;              // the request's hyp and hyp_memory
+  const double *alpha, *rho, *ambient;
+  std::vector<int32_t> hyp, idx;                   // hyp on the host | the used barcodes, dmx::hyp_list_used's order
+  std::vector<double> par;                         // alpha[B] | rho[B]
+  int32_t n_sng = 0;
+
+  int32_t n_used() const { return (int32_t)idx.size(); }
+  int32_t n_dbl() const { return n_used() - n_sng; }
+  int check_args() const {
+    if (B > 0 && (!src || !alpha)) return set_error(DMX_ERR_ARG, "%s: missing hyp / alpha", fn);
+    if (rho && !ambient && S > 0) return set_error(DMX_ERR_ARG, "%s: rho is given without ambient", fn);
+    if (memory != DMX_MEM_HOST && memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "%s: hyp_memory %d", fn, memory);
+    return DMX_OK;
+  }
+  int check_ranges() const {                       // (alpha and rho barcode by barcode: the first bad barcode is the one reported)
+    for (int32_t b = 0; b < B; ++b) {
+      const double al = alpha[b], rh = rho ? rho[b] : 0.0;
+      if (!in_unit_interval(al)) return not_in_unit_interval(fn, "alpha", b, al);
+      if (!in_unit_interval(rh)) return not_in_unit_interval(fn, "rho", b, rh);
+    }
+    return check_unit_interval(fn, "ambient", ambient, S);
+  }
+  int fetch(dmx_engine* e, bool sync = true) { return fetch_ids(e, src, memory, 2 * (size_t)B, hyp, sync); }
+  int list() {
+    const int32_t b = dmx::hyp_list_used(hyp.data(), B, V, idx, &n_sng);
+    if (b >= 0)
+      return set_error(DMX_ERR_ARG, "%s: hyp[%d] = (%d, %d) is not -1, a sample in [0, %d) or two different samples", fn, b, hyp[2 * (size_t)b],
+                       hyp[2 * (size_t)b + 1], V);
+    return DMX_OK;
+  }
+  int upload(dmx_engine* e, int32_t* d_hyp, double* d_par) {
+    par.assign((size_t)B * 2, 0.0);
+    for (int32_t b = 0; b < B; ++b) {
+      par[(size_t)b] = alpha[b];
+      if (rho) par[(size_t)B + b] = rho[b];
+    }
+    if (B == 0) return DMX_OK;
+    HIP_TRY(hipMemcpyAsync(d_hyp, hyp.data(), sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemcpyAsync(d_par, par.data(), sizeof(double) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
+    return DMX_OK;
+  }
+};
+
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Genotype refinement from called singlets.  The chunk plan is a counting sort of `assign` on the host (B ints);
 // everything that touches the pileup runs on the device: k_snp_blocks (slab table, once per staged pileup), then per wave of chunks
 // k_refine_partial + k_refine_fold, then k_refine_finish.
@@ -10541,8 +10659,7 @@ extern "C" int dmx_engine_refine_genotypes(dmx_engine* e, const dmx_refine_reque
   const int32_t B = e->pv.B, V = e->V, S = e->S;
   if (e->pv.S != S)
     return set_error(DMX_ERR_STATE, "dmx_engine_refine_genotypes: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (int rc = require_sizes(e, "dmx_engine_refine_genotypes", rq->n_cells, rq->n_snps)) return rc;
   if ((B > 0 && !rq->assign) || (S > 0 && !rq->prior)) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: missing assign / prior");
   if (rq->assign_memory != DMX_MEM_HOST && rq->assign_memory != DMX_MEM_DEVICE)
     return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: assign_memory %d", rq->assign_memory);
@@ -10551,15 +10668,8 @@ extern "C" int dmx_engine_refine_genotypes(dmx_engine* e, const dmx_refine_reque
   for (Event& ev : e->rev) if (int rc = ev.create()) return rc;
 
   // ---- chunk plan: samp_chunk[V + 1] | chunk_beg[n_chunks + 1] | members[n_assigned] (cell ids by sample, ascending within a sample)
-  std::vector<int32_t> a((size_t)B);
-  if (B > 0) {
-    if (rq->assign_memory == DMX_MEM_DEVICE) {
-      HIP_TRY(hipMemcpyAsync(a.data(), rq->assign, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    } else {
-      std::memcpy(a.data(), rq->assign, sizeof(int32_t) * (size_t)B);
-    }
-  }
+  std::vector<int32_t> a;
+  if (int rc = fetch_ids(e, rq->assign, rq->assign_memory, (size_t)B, a)) return rc;
   std::vector<int64_t> cnt((size_t)V + 1, 0);
   for (int32_t b = 0; b < B; ++b) {
     if (a[(size_t)b] < -1 || a[(size_t)b] >= V) return set_error(DMX_ERR_ARG, "dmx_engine_refine_genotypes: assign[%d] = %d is not in [-1, %d)", b, a[(size_t)b], V);
@@ -10928,11 +11038,8 @@ extern "C" int dmx_engine_cluster_info(dmx_engine* e, dmx_cluster_info* out) {
 // k_cluster_efold with R more columns.
 extern "C" int dmx_engine_cluster_doublet(dmx_engine* e, int32_t n_restarts, int32_t n_clusters) {
   if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: null engine");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_doublet: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_cluster_doublet: no genotype matrix (dmx_engine_set_genotypes first)");
+  if (int rc = require_staged(e, "dmx_engine_cluster_doublet")) return rc;
   const int32_t B = e->pv.B, R = n_restarts, K = n_clusters, V = e->V;
-  if (e->pv.S != e->S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_cluster_doublet: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", e->S, e->pv.S);
   if (K < 2 || K > 65535) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: %d clusters; the doublet components need 2 .. 65 535", K);
   if (R < 1 || (int64_t)R * K != V) return set_error(DMX_ERR_ARG, "dmx_engine_cluster_doublet: %d restarts x %d clusters, the engine has %d columns", R, K, V);
   const int64_t P = (int64_t)K * (K - 1) / 2, ncols = (int64_t)R * P;
@@ -11394,34 +11501,23 @@ extern "C" int dmx_engine_cluster_known_info(dmx_engine* e, dmx_cluster_known_in
 // one launch of k_ambient over B x ceil(Q / 64) wavefronts.
 extern "C" int dmx_engine_ambient(dmx_engine* e, const dmx_ambient_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_ambient: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_ambient: no genotype matrix (dmx_engine_set_genotypes first)");
+  const char* fn = "dmx_engine_ambient";
+  if (int rc = require_staged(e, fn)) return rc;
   const int32_t B = e->pv.B, V = e->V, S = e->S, Q = rq->n_grid;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_ambient: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
   if (Q < 1 || Q > 256) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: n_grid %d is not in [1, 256]", Q);
   if (!rq->grid || (B > 0 && !rq->assign) || (S > 0 && !rq->ambient)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: missing assign / ambient / grid");
   if (rq->assign_memory != DMX_MEM_HOST && rq->assign_memory != DMX_MEM_DEVICE)
     return set_error(DMX_ERR_ARG, "dmx_engine_ambient: assign_memory %d", rq->assign_memory);
   for (int32_t q = 0; q < Q; ++q) {
     const double r = rq->grid[q];
-    if (!(r >= 0.0 && r <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: grid[%d] = %g is not in [0, 1]", q, r);
+    if (!in_unit_interval(r)) return not_in_unit_interval(fn, "grid", q, r);
     if (q > 0 && !(r > rq->grid[q - 1])) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: the grid is not strictly ascending at %d", q);
   }
-  for (int32_t i = 0; i < S; ++i)
-    if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  if (int rc = check_unit_interval(fn, "ambient", rq->ambient, S)) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  std::vector<int32_t> a((size_t)B);
-  if (B > 0) {
-    if (rq->assign_memory == DMX_MEM_DEVICE) {
-      HIP_TRY(hipMemcpyAsync(a.data(), rq->assign, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    } else {
-      std::memcpy(a.data(), rq->assign, sizeof(int32_t) * (size_t)B);
-    }
-  }
+  std::vector<int32_t> a;
+  if (int rc = fetch_ids(e, rq->assign, rq->assign_memory, (size_t)B, a)) return rc;
   int32_t n_asg = 0;
   for (int32_t b = 0; b < B; ++b) {
     if (a[(size_t)b] < -1 || a[(size_t)b] >= V) return set_error(DMX_ERR_ARG, "dmx_engine_ambient: assign[%d] = %d is not in [-1, %d)", b, a[(size_t)b], V);
@@ -11438,7 +11534,7 @@ extern "C" int dmx_engine_ambient(dmx_engine* e, const dmx_ambient_request* rq) 
   if (int rc = e->d_aamb.ensure(sizeof(double) * (size_t)S)) return rc;
   if (int rc = e->d_agrid.ensure(sizeof(double) * (size_t)Q)) return rc;
   if (B > 0) HIP_TRY(hipMemcpyAsync(e->d_aasg, a.data(), sizeof(int32_t) * (size_t)B, hipMemcpyHostToDevice, e->stream));
-  if (S > 0) HIP_TRY(hipMemcpyAsync(e->d_aamb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
+  if (int rc = stage_soup(e, rq->ambient, S, e->d_aamb)) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_agrid, rq->grid, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, e->stream));
   const int32_t n_qblk = (Q + 63) / 64;
   const int64_t n_units = (int64_t)B * n_qblk;
@@ -11496,13 +11592,10 @@ void launch_ambient_dbl(dmx_engine* e, int32_t C, int32_t A, int32_t Q, int32_t 
 
 extern "C" int dmx_engine_ambient_doublet(dmx_engine* e, const dmx_ambient_doublet_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_ambient_doublet: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_ambient_doublet: no genotype matrix (dmx_engine_set_genotypes first)");
+  const char* fn = "dmx_engine_ambient_doublet";
+  if (int rc = require_staged(e, fn)) return rc;
   const int32_t B = e->pv.B, V = e->V, S = e->S, C = rq->n_cand, A = rq->n_alpha, Q = rq->n_grid;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_ambient_doublet: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
   if (C < 1 || C > kAmbDblMaxCand) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_cand %d is not in [1, %d]", C, kAmbDblMaxCand);
   if (A < 1 || A > kAmbDblMaxAlpha) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_alpha %d is not in [1, %d]", A, kAmbDblMaxAlpha);
   if (Q < 1 || Q > 256) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: n_grid %d is not in [1, 256]", Q);
@@ -11512,37 +11605,21 @@ extern "C" int dmx_engine_ambient_doublet(dmx_engine* e, const dmx_ambient_doubl
     return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: cand_memory %d", rq->cand_memory);
   for (int32_t n = 0; n < A; ++n) {
     const double x = rq->alpha[n];
-    if (!(x >= 0.0 && x <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: alpha[%d] = %g is not in [0, 1]", n, x);
+    if (!in_unit_interval(x)) return not_in_unit_interval(fn, "alpha", n, x);
     if (n > 0 && !(x > rq->alpha[n - 1])) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: alpha is not strictly ascending at %d", n);
   }
   for (int32_t q = 0; q < Q; ++q) {
     const double r = rq->grid[q];
-    if (!(r >= 0.0 && r <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: grid[%d] = %g is not in [0, 1]", q, r);
+    if (!in_unit_interval(r)) return not_in_unit_interval(fn, "grid", q, r);
     if (q > 0 && !(r > rq->grid[q - 1])) return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: the grid is not strictly ascending at %d", q);
   }
-  for (int32_t i = 0; i < S; ++i)
-    if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0))
-      return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  if (int rc = check_unit_interval(fn, "ambient", rq->ambient, S)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   const size_t n_slot = (size_t)B * (size_t)C;
-  std::vector<int32_t> cd(n_slot * 2);
-  if (n_slot > 0) {
-    if (rq->cand_memory == DMX_MEM_DEVICE) {
-      HIP_TRY(hipMemcpyAsync(cd.data(), rq->cand, sizeof(int32_t) * 2 * n_slot, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    } else {
-      std::memcpy(cd.data(), rq->cand, sizeof(int32_t) * 2 * n_slot);
-    }
-  }
+  std::vector<int32_t> cd;
   int64_t n_used = 0;
-  for (size_t k = 0; k < n_slot; ++k) {
-    const int32_t v1 = cd[2 * k], v2 = cd[2 * k + 1];
-    if (v1 == -1) continue;
-    if (v1 < 0 || v1 >= V || v2 < 0 || v2 >= V || v1 == v2)
-      return set_error(DMX_ERR_ARG, "dmx_engine_ambient_doublet: cand[%zu][%zu] = (%d, %d) is not -1 or two different samples in [0, %d)",
-                       k / (size_t)C, k % (size_t)C, v1, v2, V);
-    ++n_used;
-  }
+  if (int rc = fetch_ids(e, rq->cand, rq->cand_memory, 2 * n_slot, cd)) return rc;
+  if (int rc = check_pairs(fn, "cand", cd, n_slot, C, V, &n_used)) return rc;
   const size_t prof = sizeof(double) * n_slot * (size_t)A * (size_t)Q;
   size_t free_b = 0, total_b = 0;
   HIP_TRY(hipMemGetInfo(&free_b, &total_b));
@@ -11554,7 +11631,7 @@ extern "C" int dmx_engine_ambient_doublet(dmx_engine* e, const dmx_ambient_doubl
   if (int rc = e->d_damb.ensure(sizeof(double) * (size_t)S)) return rc;
   if (int rc = e->d_dgrid.ensure(sizeof(double) * (size_t)(Q + A))) return rc;
   if (n_slot > 0) HIP_TRY(hipMemcpyAsync(e->d_dcand, cd.data(), sizeof(int32_t) * 2 * n_slot, hipMemcpyHostToDevice, e->stream));
-  if (S > 0) HIP_TRY(hipMemcpyAsync(e->d_damb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
+  if (int rc = stage_soup(e, rq->ambient, S, e->d_damb)) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_dgrid, rq->grid, sizeof(double) * (size_t)Q, hipMemcpyHostToDevice, e->stream));
   HIP_TRY(hipMemcpyAsync(e->d_dgrid + Q, rq->alpha, sizeof(double) * (size_t)A, hipMemcpyHostToDevice, e->stream));
   const int32_t n_qblk = (Q + 63) / 64;
@@ -11614,13 +11691,10 @@ void launch_triplet(dmx_engine* e, int32_t C, int32_t T, int32_t n_vblk, int64_t
 
 extern "C" int dmx_engine_triplet(dmx_engine* e, const dmx_triplet_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_triplet: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_triplet: no genotype matrix (dmx_engine_set_genotypes first)");
-  const int32_t B = e->pv.B, V = e->V, S = e->S, C = rq->n_base, T = rq->n_shares;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_triplet: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  const char* fn = "dmx_engine_triplet";
+  if (int rc = require_staged(e, fn)) return rc;
+  const int32_t B = e->pv.B, V = e->V, C = rq->n_base, T = rq->n_shares;
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
   if (C < 1 || C > kTripMaxSlot) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: n_base %d is not in [1, %d]", C, kTripMaxSlot);
   if (T < 1 || T > kTripMaxShare) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: n_shares %d is not in [1, %d]", T, kTripMaxShare);
   if (!rq->shares || (B > 0 && !rq->base)) return set_error(DMX_ERR_ARG, "dmx_engine_triplet: missing base / shares");
@@ -11639,24 +11713,10 @@ extern "C" int dmx_engine_triplet(dmx_engine* e, const dmx_triplet_request* rq) 
   }
   HIP_TRY(hipSetDevice(e->device));
   const size_t n_slot = (size_t)B * (size_t)C;
-  std::vector<int32_t> bs(n_slot * 2);
-  if (n_slot > 0) {
-    if (rq->base_memory == DMX_MEM_DEVICE) {
-      HIP_TRY(hipMemcpyAsync(bs.data(), rq->base, sizeof(int32_t) * 2 * n_slot, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    } else {
-      std::memcpy(bs.data(), rq->base, sizeof(int32_t) * 2 * n_slot);
-    }
-  }
+  std::vector<int32_t> bs;
   int64_t n_used = 0;
-  for (size_t k = 0; k < n_slot; ++k) {
-    const int32_t v1 = bs[2 * k], v2 = bs[2 * k + 1];
-    if (v1 == -1) continue;
-    if (v1 < 0 || v1 >= V || v2 < 0 || v2 >= V || v1 == v2)
-      return set_error(DMX_ERR_ARG, "dmx_engine_triplet: base[%zu][%zu] = (%d, %d) is not -1 or two different samples in [0, %d)",
-                       k / (size_t)C, k % (size_t)C, v1, v2, V);
-    ++n_used;
-  }
+  if (int rc = fetch_ids(e, rq->base, rq->base_memory, 2 * n_slot, bs)) return rc;
+  if (int rc = check_pairs(fn, "base", bs, n_slot, C, V, &n_used)) return rc;
   const size_t n_col = n_slot * (size_t)V;
   const size_t prof = sizeof(double) * n_col * (size_t)T, cnts = sizeof(int32_t) * 2 * n_col;
   size_t free_b = 0, total_b = 0;
@@ -11734,11 +11794,8 @@ inline int anchor_nacc(int64_t n_ent) { return n_ent <= 64 ? 1 : n_ent <= 128 ? 
 
 extern "C" int dmx_engine_doublet_anchored(dmx_engine* e, const dmx_anchored_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_doublet_anchored: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_doublet_anchored: no genotype matrix (dmx_engine_set_genotypes first)");
+  if (int rc = require_staged(e, "dmx_engine_doublet_anchored")) return rc;
   const int32_t B = e->pv.B, V = e->V, A = e->A, T = rq->n_anchor;
-  if (e->pv.S != e->S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_doublet_anchored: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", e->S, e->pv.S);
   if (V < 2 || A < 2) return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: %d samples x %d alphas; both must be at least 2", V, A);
   if (A > 64 || V > 0xFFE || (int64_t)V * V * A > 0x7FFFFFFFll)
     return set_error(DMX_ERR_ARG, "dmx_engine_doublet_anchored: %d samples x %d alphas exceed this build's limits (64 alphas, V*V*A < 2^31)", V, A);
@@ -11754,13 +11811,7 @@ extern "C" int dmx_engine_doublet_anchored(dmx_engine* e, const dmx_anchored_req
   std::vector<int32_t> anc;
   int64_t n_used = (int64_t)n_anc;
   if (rq->anchors && n_anc > 0) {
-    anc.resize(n_anc);
-    if (rq->anchor_memory == DMX_MEM_DEVICE) {
-      HIP_TRY(hipMemcpyAsync(anc.data(), rq->anchors, sizeof(int32_t) * n_anc, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    } else {
-      std::memcpy(anc.data(), rq->anchors, sizeof(int32_t) * n_anc);
-    }
+    if (int rc = fetch_ids(e, rq->anchors, rq->anchor_memory, n_anc, anc)) return rc;
     n_used = 0;
     for (size_t b = 0; b < (size_t)B; ++b)
       for (int32_t t = 0; t < T; ++t) {
@@ -12017,11 +12068,8 @@ struct CensusPlan {
 
 int census_prepare(dmx_engine* e, const char* fn, int32_t n_cells, int32_t group_memory, const int32_t* group, int32_t G, int32_t n_samples,
                    CensusPlan* plan) {
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "%s: no pileup staged (dmx_engine_set_pileup first)", fn);
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "%s: no genotype matrix (dmx_engine_set_genotypes first)", fn);
+  if (int rc = require_staged(e, fn)) return rc;
   const int32_t B = e->pv.B, V = e->V, S = e->S;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "%s: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", fn, S, e->pv.S);
   if (n_cells != B) return set_error(DMX_ERR_ARG, "%s: n_cells %d, the staged pileup has %d", fn, n_cells, B);
   if (n_samples != V) return set_error(DMX_ERR_ARG, "%s: n_samples %d, the engine has %d", fn, n_samples, V);
   if (V > kCenMaxV) return set_error(DMX_ERR_ARG, "%s: %d samples, at most %d", fn, V, kCenMaxV);
@@ -12029,15 +12077,8 @@ int census_prepare(dmx_engine* e, const char* fn, int32_t n_cells, int32_t group
   if (B > 0 && !group) return set_error(DMX_ERR_ARG, "%s: missing group", fn);
   if (group_memory != DMX_MEM_HOST && group_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "%s: group_memory %d", fn, group_memory);
   HIP_TRY(hipSetDevice(e->device));
-  std::vector<int32_t> grp((size_t)B);
-  if (B > 0) {
-    if (group_memory == DMX_MEM_DEVICE) {
-      HIP_TRY(hipMemcpyAsync(grp.data(), group, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    } else {
-      std::memcpy(grp.data(), group, sizeof(int32_t) * (size_t)B);
-    }
-  }
+  std::vector<int32_t> grp;
+  if (int rc = fetch_ids(e, group, group_memory, (size_t)B, grp)) return rc;
   std::vector<int32_t> n_in((size_t)G + 1, 0);
   for (int32_t b = 0; b < B; ++b) {
     if (grp[(size_t)b] < -1 || grp[(size_t)b] >= G) return set_error(DMX_ERR_ARG, "%s: group[%d] = %d is not in [-1, %d)", fn, b, grp[(size_t)b], G);
@@ -13501,51 +13542,19 @@ void launch_fit(dmx_engine* e, int32_t MMsel, const int32_t* idx, int32_t n_idx,
 
 extern "C" int dmx_engine_fit(dmx_engine* e, const dmx_fit_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_fit: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_fit: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_fit: no genotype matrix (dmx_engine_set_genotypes first)");
+  const char* fn = "dmx_engine_fit";
+  if (int rc = require_staged(e, fn)) return rc;
   const int32_t B = e->pv.B, V = e->V, S = e->S, M = rq->max_reads;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_fit: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_fit: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_fit: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
   if (M < 1 || M > kFitMaxReads) return set_error(DMX_ERR_ARG, "dmx_engine_fit: max_reads %d is not in [1, %d]", M, kFitMaxReads);
-  if (B > 0 && (!rq->hyp || !rq->alpha)) return set_error(DMX_ERR_ARG, "dmx_engine_fit: missing hyp / alpha");
-  if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_fit: rho is given without ambient");
-  if (rq->hyp_memory != DMX_MEM_HOST && rq->hyp_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_fit: hyp_memory %d", rq->hyp_memory);
-  for (int32_t b = 0; b < B; ++b) {
-    const double al = rq->alpha[b], rh = rq->rho ? rq->rho[b] : 0.0;
-    if (!(al >= 0.0 && al <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_fit: alpha[%d] = %g is not in [0, 1]", b, al);
-    if (!(rh >= 0.0 && rh <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_fit: rho[%d] = %g is not in [0, 1]", b, rh);
-  }
-  if (rq->ambient)
-    for (int32_t i = 0; i < S; ++i)
-      if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_fit: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  HypPlan pl{fn, B, V, S, rq->hyp, rq->hyp_memory, rq->alpha, rq->rho, rq->ambient};
+  if (int rc = pl.check_args()) return rc;
+  if (int rc = pl.check_ranges()) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  std::vector<int32_t> h((size_t)B * 2);
-  if (B > 0) {
-    if (rq->hyp_memory == DMX_MEM_DEVICE) {
-      HIP_TRY(hipMemcpyAsync(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    } else {
-      std::memcpy(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B);
-    }
-  }
-  std::vector<int32_t> idx;
-  idx.reserve((size_t)B);
-  int32_t n_sng = 0;
-  for (int pass = 0; pass < 2; ++pass)
-    for (int32_t b = 0; b < B; ++b) {
-      const int32_t v1 = h[2 * (size_t)b], v2 = h[2 * (size_t)b + 1];
-      if (pass == 0) {
-        const bool ok = v1 == -1 || (v1 >= 0 && v1 < V && (v2 == -1 || (v2 >= 0 && v2 < V && v2 != v1)));
-        if (!ok)
-          return set_error(DMX_ERR_ARG, "dmx_engine_fit: hyp[%d] = (%d, %d) is not -1, a sample in [0, %d) or two different samples", b, v1, v2, V);
-        if (v1 >= 0 && v2 < 0) { idx.push_back(b); ++n_sng; }
-      } else if (v1 >= 0 && v2 >= 0) {
-        idx.push_back(b);
-      }
-    }
-  const int32_t n_used = (int32_t)idx.size(), n_dbl = n_used - n_sng;
+  if (int rc = pl.fetch(e)) return rc;
+  if (int rc = pl.list()) return rc;
+  const std::vector<int32_t>& idx = pl.idx;
+  const int32_t n_sng = pl.n_sng, n_used = pl.n_used(), n_dbl = pl.n_dbl();
   const size_t out_b = sizeof(double) * 3 * (size_t)B, cnt_b = sizeof(int32_t) * 4 * (size_t)B, par_b = sizeof(double) * 2 * (size_t)B;
   const size_t need = out_b + cnt_b + par_b + sizeof(int32_t) * 3 * (size_t)B + sizeof(double) * (size_t)S;
   size_t free_b = 0, total_b = 0;
@@ -13559,22 +13568,13 @@ extern "C" int dmx_engine_fit(dmx_engine* e, const dmx_fit_request* rq) {
   if (int rc = e->d_fidx.ensure(sizeof(int32_t) * (size_t)B)) return rc;
   if (int rc = e->d_famb.ensure(sizeof(double) * (size_t)S)) return rc;
   e->have_fit = false;
-  std::vector<double> par((size_t)B * 2, 0.0);
-  for (int32_t b = 0; b < B; ++b) {
-    par[(size_t)b] = rq->alpha[b];
-    if (rq->rho) par[(size_t)B + b] = rq->rho[b];
-  }
+  if (int rc = pl.upload(e, e->d_fhyp, e->d_fpar)) return rc;
   if (B > 0) {
-    HIP_TRY(hipMemcpyAsync(e->d_fhyp, h.data(), sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_fpar, par.data(), par_b, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemsetAsync(e->d_fout, 0, out_b, e->stream));
     HIP_TRY(hipMemsetAsync(e->d_fcnt, 0, cnt_b, e->stream));
   }
   if (n_used > 0) HIP_TRY(hipMemcpyAsync(e->d_fidx, idx.data(), sizeof(int32_t) * (size_t)n_used, hipMemcpyHostToDevice, e->stream));
-  if (S > 0) {
-    if (rq->ambient) HIP_TRY(hipMemcpyAsync(e->d_famb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
-    else HIP_TRY(hipMemsetAsync(e->d_famb, 0, sizeof(double) * (size_t)S, e->stream));
-  }
+  if (int rc = stage_soup(e, rq->ambient, S, e->d_famb)) return rc;
   const int32_t MMsel = M <= 1 ? 1 : M <= 2 ? 2 : M <= 4 ? 4 : 8;
   if (int rc = e->fev.record_start(e->stream)) return rc;
   launch_fit<false>(e, MMsel, e->d_fidx, n_sng, M);
@@ -13648,55 +13648,22 @@ void launch_site_partial(dmx_engine* e, int32_t MMsel, int32_t nblk, const int32
 
 extern "C" int dmx_engine_site_fit(dmx_engine* e, const dmx_site_fit_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_site_fit: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_site_fit: no genotype matrix (dmx_engine_set_genotypes first)");
+  const char* fn = "dmx_engine_site_fit";
+  if (int rc = require_staged(e, fn)) return rc;
   const int32_t B = e->pv.B, V = e->V, S = e->S, M = rq->max_reads;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_site_fit: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
   if (M < 1 || M > kFitMaxReads) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: max_reads %d is not in [1, %d]", M, kFitMaxReads);
-  if (B > 0 && (!rq->hyp || !rq->alpha)) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: missing hyp / alpha");
-  if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: rho is given without ambient");
-  if (rq->hyp_memory != DMX_MEM_HOST && rq->hyp_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: hyp_memory %d", rq->hyp_memory);
+  HypPlan pl{fn, B, V, S, rq->hyp, rq->hyp_memory, rq->alpha, rq->rho, rq->ambient};
+  if (int rc = pl.check_args()) return rc;
   const size_t per_chunk = sizeof(SitePartial) * (size_t)S;
   if (rq->partial_bytes < 0 || (rq->partial_bytes > 0 && (uint64_t)rq->partial_bytes < per_chunk))
     return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: partial_bytes %lld is below one chunk's %zu bytes", (long long)rq->partial_bytes, per_chunk);
-  for (int32_t b = 0; b < B; ++b) {
-    const double al = rq->alpha[b], rh = rq->rho ? rq->rho[b] : 0.0;
-    if (!(al >= 0.0 && al <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: alpha[%d] = %g is not in [0, 1]", b, al);
-    if (!(rh >= 0.0 && rh <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: rho[%d] = %g is not in [0, 1]", b, rh);
-  }
-  if (rq->ambient)
-    for (int32_t i = 0; i < S; ++i)
-      if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0))
-        return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  if (int rc = pl.check_ranges()) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  std::vector<int32_t> h((size_t)B * 2);
-  if (B > 0) {
-    if (rq->hyp_memory == DMX_MEM_DEVICE) {
-      HIP_TRY(hipMemcpyAsync(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyDeviceToHost, e->stream));
-      HIP_TRY(hipStreamSynchronize(e->stream));
-    } else {
-      std::memcpy(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B);
-    }
-  }
-  std::vector<int32_t> idx;
-  idx.reserve((size_t)B);
-  int32_t n_sng = 0;
-  for (int pass = 0; pass < 2; ++pass)
-    for (int32_t b = 0; b < B; ++b) {
-      const int32_t v1 = h[2 * (size_t)b], v2 = h[2 * (size_t)b + 1];
-      if (pass == 0) {
-        const bool ok = v1 == -1 || (v1 >= 0 && v1 < V && (v2 == -1 || (v2 >= 0 && v2 < V && v2 != v1)));
-        if (!ok)
-          return set_error(DMX_ERR_ARG, "dmx_engine_site_fit: hyp[%d] = (%d, %d) is not -1, a sample in [0, %d) or two different samples", b, v1, v2, V);
-        if (v1 >= 0 && v2 < 0) { idx.push_back(b); ++n_sng; }
-      } else if (v1 >= 0 && v2 >= 0) {
-        idx.push_back(b);
-      }
-    }
-  const int32_t n_used = (int32_t)idx.size(), n_dbl = n_used - n_sng;
+  if (int rc = pl.fetch(e)) return rc;
+  if (int rc = pl.list()) return rc;
+  const std::vector<int32_t>& idx = pl.idx;
+  const int32_t n_sng = pl.n_sng, n_used = pl.n_used(), n_dbl = pl.n_dbl();
   // ---- plan: chunk_beg[nch + 1] | members[n_used]; no chunk straddles the two lists
   const int32_t ncs = (n_sng + kSiteChunk - 1) / kSiteChunk, ncd = (n_dbl + kSiteChunk - 1) / kSiteChunk, nch = ncs + ncd;
   std::vector<int32_t> plan;
@@ -13730,22 +13697,13 @@ extern "C" int dmx_engine_site_fit(dmx_engine* e, const dmx_site_fit_request* rq
   if (part_b) if (int rc = e->d_spart.ensure(part_b)) return rc;
   if (build_blk && B > 0) if (int rc = e->d_rblk.ensure(blk_b)) return rc;
   e->have_site = false;
-  std::vector<double> par((size_t)B * 2, 0.0);
-  for (int32_t b = 0; b < B; ++b) {
-    par[(size_t)b] = rq->alpha[b];
-    if (rq->rho) par[(size_t)B + b] = rq->rho[b];
-  }
-  if (B > 0) {
-    HIP_TRY(hipMemcpyAsync(e->d_shyp, h.data(), sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_spar, par.data(), par_b, hipMemcpyHostToDevice, e->stream));
-  }
+  if (int rc = pl.upload(e, e->d_shyp, e->d_spar)) return rc;
   HIP_TRY(hipMemcpyAsync(e->d_splan, plan.data(), sizeof(int32_t) * plan.size(), hipMemcpyHostToDevice, e->stream));
   if (S > 0) {
     HIP_TRY(hipMemsetAsync(e->d_sout, 0, out_b, e->stream));
     HIP_TRY(hipMemsetAsync(e->d_scnt, 0, cnt_b, e->stream));
-    if (rq->ambient) HIP_TRY(hipMemcpyAsync(e->d_samb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
-    else HIP_TRY(hipMemsetAsync(e->d_samb, 0, sizeof(double) * (size_t)S, e->stream));
   }
+  if (int rc = stage_soup(e, rq->ambient, S, e->d_samb)) return rc;
   if (build_blk && B > 0) {
     hipLaunchKernelGGL(k_snp_blocks, dim3((unsigned)((B + 3) / 4)), dim3(kThreads), 0, e->stream, e->pv, e->nrd_width, kRefSlabShift, nblk, e->d_rblk);
     HIP_TRY(hipGetLastError());
@@ -13815,53 +13773,27 @@ extern "C" int dmx_engine_site_fit_info(dmx_engine* e, dmx_site_fit_info* out) {
 
 extern "C" int dmx_engine_redraw(dmx_engine* e, const dmx_redraw_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_redraw: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_redraw: no genotype matrix (dmx_engine_set_genotypes first)");
+  const char* fn = "dmx_engine_redraw";
+  if (int rc = require_staged(e, fn)) return rc;
   const int32_t B = e->pv.B, V = e->V, S = e->S;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_redraw: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
   if ((e->d_rwreads && e->pv.reads == (const uint8_t*)e->d_rwreads.get()) || (e->d_cmpoff && e->pv.cell_pair_off == (const int64_t*)e->d_cmpoff.get()))
     return set_error(DMX_ERR_STATE, "dmx_engine_redraw: the staged pileup is this engine's own redrawn or composed pileup (it would be overwritten)");
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
   if (rq->genotype_draw != DMX_REDRAW_PAIR && rq->genotype_draw != DMX_REDRAW_DONOR)
     return set_error(DMX_ERR_ARG, "dmx_engine_redraw: genotype_draw %d is neither DMX_REDRAW_PAIR nor DMX_REDRAW_DONOR", rq->genotype_draw);
   if (rq->index_base < 0) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: index_base %lld is negative", (long long)rq->index_base);
-  if (B > 0 && (!rq->hyp || !rq->alpha)) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: missing hyp / alpha");
-  if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: rho is given without ambient");
-  if (rq->hyp_memory != DMX_MEM_HOST && rq->hyp_memory != DMX_MEM_DEVICE) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: hyp_memory %d", rq->hyp_memory);
-  for (int32_t b = 0; b < B; ++b) {
-    const double al = rq->alpha[b], rh = rq->rho ? rq->rho[b] : 0.0;
-    if (!(al >= 0.0 && al <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: alpha[%d] = %g is not in [0, 1]", b, al);
-    if (!(rh >= 0.0 && rh <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: rho[%d] = %g is not in [0, 1]", b, rh);
-  }
-  if (rq->ambient)
-    for (int32_t i = 0; i < S; ++i)
-      if (!(rq->ambient[i] >= 0.0 && rq->ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_redraw: ambient[%d] = %g is not in [0, 1]", i, rq->ambient[i]);
+  HypPlan pl{fn, B, V, S, rq->hyp, rq->hyp_memory, rq->alpha, rq->rho, rq->ambient};
+  if (int rc = pl.check_args()) return rc;
+  if (int rc = pl.check_ranges()) return rc;
   HIP_TRY(hipSetDevice(e->device));
-  std::vector<int32_t> h((size_t)B * 2);
   std::vector<int64_t> h_po((size_t)B + 1, 0), h_ro((size_t)B + 1, 0);
-  if (B > 0 && rq->hyp_memory == DMX_MEM_DEVICE) HIP_TRY(hipMemcpyAsync(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B, hipMemcpyDeviceToHost, e->stream));
-  else if (B > 0) std::memcpy(h.data(), rq->hyp, sizeof(int32_t) * 2 * (size_t)B);
+  if (int rc = pl.fetch(e, /*sync=*/false)) return rc;   // (one synchronise for hyp and the two offset arrays)
   HIP_TRY(hipMemcpyAsync(h_po.data(), e->pv.cell_pair_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipMemcpyAsync(h_ro.data(), e->pv.cell_read_off, sizeof(int64_t) * ((size_t)B + 1), hipMemcpyDeviceToHost, e->stream));
   HIP_TRY(hipStreamSynchronize(e->stream));
-  std::vector<int32_t> idx;
-  idx.reserve((size_t)B);
-  int32_t n_sng = 0;
-  for (int pass = 0; pass < 2; ++pass)
-    for (int32_t b = 0; b < B; ++b) {
-      const int32_t v1 = h[2 * (size_t)b], v2 = h[2 * (size_t)b + 1];
-      if (pass == 0) {
-        const bool ok = v1 == -1 || (v1 >= 0 && v1 < V && (v2 == -1 || (v2 >= 0 && v2 < V && v2 != v1)));
-        if (!ok)
-          return set_error(DMX_ERR_ARG, "dmx_engine_redraw: hyp[%d] = (%d, %d) is not -1, a sample in [0, %d) or two different samples", b, v1, v2, V);
-        if (v1 >= 0 && v2 < 0) { idx.push_back(b); ++n_sng; }
-      } else if (v1 >= 0 && v2 >= 0) {
-        idx.push_back(b);
-      }
-    }
-  const int32_t n_used = (int32_t)idx.size(), n_dbl = n_used - n_sng;
+  if (int rc = pl.list()) return rc;
+  const std::vector<int32_t>& idx = pl.idx;
+  const int32_t n_sng = pl.n_sng, n_used = pl.n_used(), n_dbl = pl.n_dbl();
   // the view's extent: offsets are absolute in a view of a caller's device arrays, so the arrays reach to the last cell's end
   const int64_t P = h_po[(size_t)B], R = e->pv.R;
   if (P < 0 || R < 0 || h_ro[(size_t)B] > R) return set_error(DMX_ERR_STATE, "dmx_engine_redraw: the staged offsets leave the read array");
@@ -13883,21 +13815,10 @@ extern "C" int dmx_engine_redraw(dmx_engine* e, const dmx_redraw_request* rq) {
   if (int rc = e->d_rwhyp.ensure(sizeof(int32_t) * 2 * (size_t)B)) return rc;
   if (int rc = e->d_rwidx.ensure(sizeof(int32_t) * (size_t)B)) return rc;
   if (int rc = e->d_rwamb.ensure(sizeof(double) * (size_t)S)) return rc;
-  std::vector<double> par((size_t)B * 2, 0.0);
-  for (int32_t b = 0; b < B; ++b) {
-    par[(size_t)b] = rq->alpha[b];
-    if (rq->rho) par[(size_t)B + b] = rq->rho[b];
-  }
-  if (B > 0) {
-    HIP_TRY(hipMemcpyAsync(e->d_rwhyp, h.data(), sizeof(int32_t) * 2 * (size_t)B, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemcpyAsync(e->d_rwpar, par.data(), par_b, hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_rwcnt, 0, cnt_b, e->stream));
-  }
+  if (int rc = pl.upload(e, e->d_rwhyp, e->d_rwpar)) return rc;
+  if (B > 0) HIP_TRY(hipMemsetAsync(e->d_rwcnt, 0, cnt_b, e->stream));
   if (n_used > 0) HIP_TRY(hipMemcpyAsync(e->d_rwidx, idx.data(), sizeof(int32_t) * (size_t)n_used, hipMemcpyHostToDevice, e->stream));
-  if (S > 0) {
-    if (rq->ambient) HIP_TRY(hipMemcpyAsync(e->d_rwamb, rq->ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
-    else HIP_TRY(hipMemsetAsync(e->d_rwamb, 0, sizeof(double) * (size_t)S, e->stream));
-  }
+  if (int rc = stage_soup(e, rq->ambient, S, e->d_rwamb)) return rc;
   // unused barcodes, pairs without stored reads, skipped pairs and kept reads: a plain copy of everything, which the kernel then overwrites
   if (R > 0) HIP_TRY(hipMemcpyAsync(e->d_rwreads, e->pv.reads, (size_t)R, hipMemcpyDeviceToDevice, e->stream));
   HIP_TRY(hipMemsetAsync(e->d_rwgeno, 0xFF, geno_b, e->stream));
@@ -13963,62 +13884,24 @@ extern "C" int dmx_engine_redraw_info(dmx_engine* e, dmx_redraw_info* out) {
 // ---------------------------------------------------------------------------------------------------------------------
 // Continuous mixing share: both calls check their arguments on the host (anchors / cand, rho and a are small),
 // copy them to buffers of their own and launch one kernel.
-namespace {
-
-// rho[B] (NULL = 0) and a[S] (NULL only with rho = NULL) checked and copied to the device for a share call.
-int share_stage_soup(dmx_engine* e, const char* who, const double* rho, const double* ambient, int32_t B, int32_t S, double* d_rho, double* d_amb) {
-  if (rho)
-    for (int32_t b = 0; b < B; ++b)
-      if (!(rho[b] >= 0.0 && rho[b] <= 1.0)) return set_error(DMX_ERR_ARG, "%s: rho[%d] = %g is not in [0, 1]", who, b, rho[b]);
-  if (ambient)
-    for (int32_t i = 0; i < S; ++i)
-      if (!(ambient[i] >= 0.0 && ambient[i] <= 1.0)) return set_error(DMX_ERR_ARG, "%s: ambient[%d] = %g is not in [0, 1]", who, i, ambient[i]);
-  if (!d_rho) return DMX_OK;                       // (the check alone)
-  if (B > 0) {
-    if (rho) HIP_TRY(hipMemcpyAsync(d_rho, rho, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, e->stream));
-    else HIP_TRY(hipMemsetAsync(d_rho, 0, sizeof(double) * (size_t)B, e->stream));
-  }
-  if (S > 0) {
-    if (ambient) HIP_TRY(hipMemcpyAsync(d_amb, ambient, sizeof(double) * (size_t)S, hipMemcpyHostToDevice, e->stream));
-    else HIP_TRY(hipMemsetAsync(d_amb, 0, sizeof(double) * (size_t)S, e->stream));
-  }
-  return DMX_OK;
-}
-
-int share_fetch_ids(dmx_engine* e, const int32_t* src, int32_t memory, size_t n, std::vector<int32_t>& dst) {
-  dst.resize(n);
-  if (n == 0) return DMX_OK;
-  if (memory == DMX_MEM_DEVICE) {
-    HIP_TRY(hipMemcpyAsync(dst.data(), src, sizeof(int32_t) * n, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-  } else {
-    std::memcpy(dst.data(), src, sizeof(int32_t) * n);
-  }
-  return DMX_OK;
-}
-
-}  // namespace
-
 extern "C" int dmx_engine_share_scan(dmx_engine* e, const dmx_share_scan_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_share_scan: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_share_scan: no genotype matrix (dmx_engine_set_genotypes first)");
+  const char* fn = "dmx_engine_share_scan";
+  if (int rc = require_staged(e, fn)) return rc;
   const int32_t B = e->pv.B, V = e->V, S = e->S, T = rq->n_anchor;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_share_scan: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
   if (T < 1 || T > kShareMaxAnchor) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: n_anchor %d is not in [1, %d]", T, kShareMaxAnchor);
   if (V > kShareMaxSamples) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: %d samples, at most %d", V, kShareMaxSamples);
   if (B > 0 && !rq->anchors) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: missing anchors");
   if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: rho is given without ambient");
   if (rq->anchor_memory != DMX_MEM_HOST && rq->anchor_memory != DMX_MEM_DEVICE)
     return set_error(DMX_ERR_ARG, "dmx_engine_share_scan: anchor_memory %d", rq->anchor_memory);
-  if (int rc = share_stage_soup(e, "dmx_engine_share_scan", rq->rho, rq->ambient, B, S, nullptr, nullptr)) return rc;
+  if (int rc = check_unit_interval(fn, "rho", rq->rho, B)) return rc;
+  if (int rc = check_unit_interval(fn, "ambient", rq->ambient, S)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   const size_t n_slot = (size_t)B * (size_t)T;
   std::vector<int32_t> an;
-  if (int rc = share_fetch_ids(e, rq->anchors, rq->anchor_memory, n_slot, an)) return rc;
+  if (int rc = fetch_ids(e, rq->anchors, rq->anchor_memory, n_slot, an)) return rc;
   int64_t n_used = 0;
   for (size_t k = 0; k < n_slot; ++k) {
     if (an[k] == -1) continue;
@@ -14038,7 +13921,8 @@ extern "C" int dmx_engine_share_scan(dmx_engine* e, const dmx_share_scan_request
   if (int rc = e->d_ssrho.ensure(sizeof(double) * (size_t)B)) return rc;
   if (int rc = e->d_ssamb.ensure(sizeof(double) * (size_t)S)) return rc;
   e->have_sscan = false;
-  if (int rc = share_stage_soup(e, "dmx_engine_share_scan", rq->rho, rq->ambient, B, S, e->d_ssrho, e->d_ssamb)) return rc;
+  if (int rc = stage_soup(e, rq->rho, B, e->d_ssrho)) return rc;
+  if (int rc = stage_soup(e, rq->ambient, S, e->d_ssamb)) return rc;
   if (n_slot > 0) {
     HIP_TRY(hipMemcpyAsync(e->d_ssanc, an.data(), sizeof(int32_t) * n_slot, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemsetAsync(e->d_ssout, 0, out_b, e->stream));
@@ -14078,13 +13962,10 @@ extern "C" int dmx_engine_get_share_scan(dmx_engine* e, double* out, int32_t* n_
 
 extern "C" int dmx_engine_share_fit(dmx_engine* e, const dmx_share_fit_request* rq) {
   if (!e || !rq) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: null argument");
-  if (!e->have_pileup) return set_error(DMX_ERR_STATE, "dmx_engine_share_fit: no pileup staged (dmx_engine_set_pileup first)");
-  if (!e->d_g) return set_error(DMX_ERR_STATE, "dmx_engine_share_fit: no genotype matrix (dmx_engine_set_genotypes first)");
+  const char* fn = "dmx_engine_share_fit";
+  if (int rc = require_staged(e, fn)) return rc;
   const int32_t B = e->pv.B, V = e->V, S = e->S, C = rq->n_cand;
-  if (e->pv.S != S)
-    return set_error(DMX_ERR_STATE, "dmx_engine_share_fit: the genotype matrix has %d SNPs, the staged pileup was checked against %d (stage it again)", S, e->pv.S);
-  if (rq->n_cells != B) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: n_cells %d, the staged pileup has %d", rq->n_cells, B);
-  if (rq->n_snps != S) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: n_snps %d, the genotype matrix has %d", rq->n_snps, S);
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
   if (C < 1 || C > kShareMaxCand) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: n_cand %d is not in [1, %d]", C, kShareMaxCand);
   if (B > 0 && !rq->cand) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: missing cand");
   if (rq->rho && !rq->ambient && S > 0) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: rho is given without ambient");
@@ -14094,20 +13975,14 @@ extern "C" int dmx_engine_share_fit(dmx_engine* e, const dmx_share_fit_request* 
   if (!(rq->start > 0.0 && rq->start < 1.0)) return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: start %g is not in (0, 1)", rq->start);
   if (!(rq->probe < 0.0 || (rq->probe >= 0.0 && rq->probe <= 1.0)))
     return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: probe %g is neither negative (none) nor in [0, 1]", rq->probe);
-  if (int rc = share_stage_soup(e, "dmx_engine_share_fit", rq->rho, rq->ambient, B, S, nullptr, nullptr)) return rc;
+  if (int rc = check_unit_interval(fn, "rho", rq->rho, B)) return rc;
+  if (int rc = check_unit_interval(fn, "ambient", rq->ambient, S)) return rc;
   HIP_TRY(hipSetDevice(e->device));
   const size_t n_slot = (size_t)B * (size_t)C;
   std::vector<int32_t> cd;
-  if (int rc = share_fetch_ids(e, rq->cand, rq->cand_memory, 2 * n_slot, cd)) return rc;
+  if (int rc = fetch_ids(e, rq->cand, rq->cand_memory, 2 * n_slot, cd)) return rc;
   int64_t n_used = 0;
-  for (size_t k = 0; k < n_slot; ++k) {
-    const int32_t v1 = cd[2 * k], v2 = cd[2 * k + 1];
-    if (v1 == -1) continue;
-    if (v1 < 0 || v1 >= V || v2 < 0 || v2 >= V || v1 == v2)
-      return set_error(DMX_ERR_ARG, "dmx_engine_share_fit: cand[%zu][%zu] = (%d, %d) is not -1 or two different samples in [0, %d)",
-                       k / (size_t)C, k % (size_t)C, v1, v2, V);
-    ++n_used;
-  }
+  if (int rc = check_pairs(fn, "cand", cd, n_slot, C, V, &n_used)) return rc;
   const size_t out_b = sizeof(double) * kShareFitDoubles * n_slot, int_b = sizeof(int32_t) * kShareFitInts * n_slot;
   const size_t need = out_b + int_b + sizeof(int32_t) * 2 * n_slot + sizeof(double) * ((size_t)B + (size_t)S);
   size_t free_b = 0, total_b = 0;
@@ -14120,7 +13995,8 @@ extern "C" int dmx_engine_share_fit(dmx_engine* e, const dmx_share_fit_request* 
   if (int rc = e->d_sfrho.ensure(sizeof(double) * (size_t)B)) return rc;
   if (int rc = e->d_sfamb.ensure(sizeof(double) * (size_t)S)) return rc;
   e->have_sfit = false;
-  if (int rc = share_stage_soup(e, "dmx_engine_share_fit", rq->rho, rq->ambient, B, S, e->d_sfrho, e->d_sfamb)) return rc;
+  if (int rc = stage_soup(e, rq->rho, B, e->d_sfrho)) return rc;
+  if (int rc = stage_soup(e, rq->ambient, S, e->d_sfamb)) return rc;
   if (n_slot > 0) {
     HIP_TRY(hipMemcpyAsync(e->d_sfcand, cd.data(), sizeof(int32_t) * 2 * n_slot, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemsetAsync(e->d_sfout, 0, out_b, e->stream));

@@ -19,6 +19,7 @@
 
 #include <vector>
 
+#include "dmx_hyp_plan.hpp"
 #include "dmx_log.hpp"
 
 extern "C" {
@@ -636,11 +637,12 @@ void emu_site_fit(const emu_pileup* pl, const float* g, int32_t S, int32_t V, co
   int32_t* cnt[5] = {n_cell, n_read, n_alt, n_trunc, n_zero};
   for (int32_t i = 0; i < S; ++i)
     for (int j = 0; j < 5; ++j) { val[j][i] = 0.0; cnt[j][i] = 0; }
-  std::vector<std::vector<int32_t>> chunks;         // singlets, then doublets, ascending cell id; no chunk straddles the two lists
+  std::vector<std::vector<int32_t>> chunks;         // the engine's own list (singlets, then doublets); no chunk straddles the two kinds
+  std::vector<int32_t> used;
+  int32_t n_sng = 0;
+  if (dmx::hyp_list_used(hyp, pl->n_cells, V, used, &n_sng) >= 0) { counters_out(counters); return; }   // (a table that the engine refuses)
   for (int kind = 0; kind < 2; ++kind) {
-    std::vector<int32_t> list;
-    for (int32_t b = 0; b < pl->n_cells; ++b)
-      if (hyp[2 * (size_t)b] >= 0 && (hyp[2 * (size_t)b + 1] >= 0) == (kind == 1)) list.push_back(b);
+    const std::vector<int32_t> list(kind == 0 ? used.begin() : used.begin() + n_sng, kind == 0 ? used.begin() + n_sng : used.end());
     for (size_t c0 = 0; c0 < list.size(); c0 += 64)
       chunks.emplace_back(list.begin() + (int64_t)c0, list.begin() + (int64_t)(c0 + 64 < list.size() ? c0 + 64 : list.size()));
   }

@@ -361,10 +361,14 @@ def test_fit_argument_and_state_errors(m):
     hyp = np.stack([np.arange(B) % V, np.full(B, -1)], axis=1).astype(np.int32)
     al, rho = np.zeros(B), np.full(B, 0.1)
 
-    def fails(e, code, *args):
+    def fails(e, code, *args, field=None):
         with pytest.raises(capi.DmxError) as ei:
             e.fit_profile(*args)
         assert ei.value.code == code, (ei.value.code, args)
+        named(ei, field)
+
+    def named(ei, field=None):                                                  # the message names the entry point and the bad field
+        assert "dmx_engine_fit: " in str(ei.value) and (field is None or field in str(ei.value)), (str(ei.value), field)
 
     e = eng.Engine(V, (0.0, 0.5), 0.5)
     try:
@@ -381,15 +385,15 @@ def test_fit_argument_and_state_errors(m):
             fails(e, capi.DMX_ERR_ARG, hyp, al, rho, a, M)
         for bad in (-0.1, 1.5, np.nan, np.inf):
             x = al.copy(); x[3] = bad
-            fails(e, capi.DMX_ERR_ARG, hyp, x, rho, a, 4)
+            fails(e, capi.DMX_ERR_ARG, hyp, x, rho, a, 4, field="alpha[3]")
             x = rho.copy(); x[B - 1] = bad
-            fails(e, capi.DMX_ERR_ARG, hyp, al, x, a, 4)
-        for bad_a in (np.full(S, 1.2), np.full(S, np.nan), a[:-1]):
-            fails(e, capi.DMX_ERR_ARG, hyp, al, rho, bad_a, 4)
+            fails(e, capi.DMX_ERR_ARG, hyp, al, x, a, 4, field=f"rho[{B - 1}]")
+        for bad_a, field in ((np.full(S, 1.2), "ambient[0]"), (np.full(S, np.nan), "ambient[0]"), (a[:-1], "n_snps")):
+            fails(e, capi.DMX_ERR_ARG, hyp, al, rho, bad_a, 4, field=field)
         for bad_h in ((V, -1), (-2, -1), (0, V), (1, 1), (0, -2)):
             h = hyp.copy(); h[5] = bad_h
-            fails(e, capi.DMX_ERR_ARG, h, al, rho, a, 4)
-        fails(e, capi.DMX_ERR_ARG, hyp, al, rho, None, 4)                       # rho without ambient
+            fails(e, capi.DMX_ERR_ARG, h, al, rho, a, 4, field="hyp[5]")
+        fails(e, capi.DMX_ERR_ARG, hyp, al, rho, None, 4, field="rho")          # rho without ambient
         with pytest.raises(ValueError):
             e.fit_profile(hyp[:-1], al, rho, a, 4)
         with pytest.raises(ValueError):
@@ -401,6 +405,7 @@ def test_fit_argument_and_state_errors(m):
             with pytest.raises(capi.DmxError) as ei:
                 capi.check(e._L.dmx_engine_fit(e._h, C_byref(rq)))
             assert ei.value.code == capi.DMX_ERR_ARG
+            named(ei)
         with pytest.raises(capi.DmxError) as ei:                               # still nothing computed
             capi.check(e._L.dmx_engine_get_fit(e._h, *([None] * 7)))
         assert ei.value.code == capi.DMX_ERR_STATE

@@ -363,10 +363,14 @@ def test_argument_and_state_errors(m):
     hyp = np.stack([np.arange(B) % V, np.full(B, -1)], axis=1).astype(np.int32)
     al, rho = np.zeros(B), np.full(B, 0.1)
 
-    def fails(e, code, *args, **kw):
+    def fails(e, code, *args, field=None, **kw):
         with pytest.raises(capi.DmxError) as ei:
             e.redraw(*args, **kw)
         assert ei.value.code == code, (ei.value.code, args, kw)
+        named(str(ei.value), field)
+
+    def named(msg, field=None):                                                 # the message names the entry point and the bad field
+        assert "dmx_engine_redraw: " in msg and (field is None or field in msg), (msg, field)
 
     def queries_fail(e):
         for call in (e.redraw_info, e.redrawn_pileup, e.get_redrawn):
@@ -385,15 +389,15 @@ def test_argument_and_state_errors(m):
         queries_fail(e)                                                         # a query before a call
         for bad in (-0.1, 1.5, np.nan, np.inf):
             x = al.copy(); x[3] = bad
-            fails(e, capi.DMX_ERR_ARG, hyp, x, rho, a)
+            fails(e, capi.DMX_ERR_ARG, hyp, x, rho, a, field="alpha[3]")
             x = rho.copy(); x[B - 1] = bad
-            fails(e, capi.DMX_ERR_ARG, hyp, al, x, a)
-        for bad_a in (np.full(S, 1.2), np.full(S, np.nan), a[:-1]):
-            fails(e, capi.DMX_ERR_ARG, hyp, al, rho, bad_a)
+            fails(e, capi.DMX_ERR_ARG, hyp, al, x, a, field=f"rho[{B - 1}]")
+        for bad_a, field in ((np.full(S, 1.2), "ambient[0]"), (np.full(S, np.nan), "ambient[0]"), (a[:-1], "n_snps")):
+            fails(e, capi.DMX_ERR_ARG, hyp, al, rho, bad_a, field=field)
         for bad_h in ((V, -1), (-2, -1), (0, V), (1, 1), (0, -2)):
             h = hyp.copy(); h[5] = bad_h
-            fails(e, capi.DMX_ERR_ARG, h, al, rho, a)
-        fails(e, capi.DMX_ERR_ARG, hyp, al, rho, None)                          # rho without ambient
+            fails(e, capi.DMX_ERR_ARG, h, al, rho, a, field="hyp[5]")
+        fails(e, capi.DMX_ERR_ARG, hyp, al, rho, None, field="rho")             # rho without ambient
         fails(e, capi.DMX_ERR_ARG, hyp, al, rho, a, index_base=-1)
         with pytest.raises(ValueError):
             e.redraw(hyp, al, rho, a, genotype_draw="cell")
@@ -405,7 +409,10 @@ def test_argument_and_state_errors(m):
             for k, v in fix.items():
                 setattr(rq, k, v)
             assert e._L.dmx_engine_redraw(e._h, C.byref(rq)) == capi.DMX_ERR_ARG, fix
-        assert e._L.dmx_engine_redraw(e._h, None) == capi.DMX_ERR_ARG and e._L.dmx_engine_redraw_info(e._h, None) == capi.DMX_ERR_ARG
+            named(e._L.dmx_last_error().decode())
+        assert e._L.dmx_engine_redraw(e._h, None) == capi.DMX_ERR_ARG
+        named(e._L.dmx_last_error().decode())
+        assert e._L.dmx_engine_redraw_info(e._h, None) == capi.DMX_ERR_ARG
         queries_fail(e)                                                         # still nothing drawn
         info = e.redraw(hyp, al, rho, a)                                        # the defaults: donor draw, seeds 0
         assert info["genotype_draw"] == 1 and info["n_used"] == B and info["n_reads_drawn"] == len(pl.reads) - int(info["n_reads_kept"])

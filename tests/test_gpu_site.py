@@ -300,10 +300,14 @@ def test_site_argument_and_state_errors(m):
     hyp = np.stack([np.arange(B) % V, np.full(B, -1)], axis=1).astype(np.int32)
     al, rho = np.zeros(B), np.full(B, 0.1)
 
-    def fails(e, code, *args, **kw):
+    def fails(e, code, *args, field=None, **kw):
         with pytest.raises(capi.DmxError) as ei:
             e.site_fit(*args, **kw)
         assert ei.value.code == code, (ei.value.code, args)
+        named(ei, field)
+
+    def named(ei, field=None):                                                  # the message names the entry point and the bad field
+        assert "dmx_engine_site_fit: " in str(ei.value) and (field is None or field in str(ei.value)), (str(ei.value), field)
 
     def query_fails(e):
         for fn, args in (("dmx_engine_get_site_fit", [None] * GETTERS), ("dmx_engine_site_fit_info", [ctypes.byref(capi.SiteFitInfo())])):
@@ -323,15 +327,15 @@ def test_site_argument_and_state_errors(m):
             fails(e, capi.DMX_ERR_ARG, hyp, al, rho, a, M)
         for bad in (-0.1, 1.5, np.nan, np.inf):
             x = al.copy(); x[3] = bad
-            fails(e, capi.DMX_ERR_ARG, hyp, x, rho, a, 4)
+            fails(e, capi.DMX_ERR_ARG, hyp, x, rho, a, 4, field="alpha[3]")
             x = rho.copy(); x[B - 1] = bad
-            fails(e, capi.DMX_ERR_ARG, hyp, al, x, a, 4)
-        for bad_a in (np.full(S, 1.2), np.full(S, np.nan), a[:-1]):
-            fails(e, capi.DMX_ERR_ARG, hyp, al, rho, bad_a, 4)
+            fails(e, capi.DMX_ERR_ARG, hyp, al, x, a, 4, field=f"rho[{B - 1}]")
+        for bad_a, field in ((np.full(S, 1.2), "ambient[0]"), (np.full(S, np.nan), "ambient[0]"), (a[:-1], "n_snps")):
+            fails(e, capi.DMX_ERR_ARG, hyp, al, rho, bad_a, 4, field=field)
         for bad_h in ((V, -1), (-2, -1), (0, V), (1, 1), (0, -2)):
             h = hyp.copy(); h[5] = bad_h
-            fails(e, capi.DMX_ERR_ARG, h, al, rho, a, 4)
-        fails(e, capi.DMX_ERR_ARG, hyp, al, rho, None, 4)                       # rho without ambient
+            fails(e, capi.DMX_ERR_ARG, h, al, rho, a, 4, field="hyp[5]")
+        fails(e, capi.DMX_ERR_ARG, hyp, al, rho, None, 4, field="rho")          # rho without ambient
         for pb in (64 * S - 1, 1, -1, -64 * S):                                 # a budget below one chunk's worth
             fails(e, capi.DMX_ERR_ARG, hyp, al, rho, a, 4, partial_bytes=pb)
         with pytest.raises(ValueError):
@@ -345,9 +349,11 @@ def test_site_argument_and_state_errors(m):
             with pytest.raises(capi.DmxError) as ei:
                 capi.check(e._L.dmx_engine_site_fit(e._h, ctypes.byref(rq)))
             assert ei.value.code == capi.DMX_ERR_ARG
+            named(ei)
         with pytest.raises(capi.DmxError) as ei:
             capi.check(e._L.dmx_engine_site_fit(e._h, None))
         assert ei.value.code == capi.DMX_ERR_ARG
+        named(ei)
         query_fails(e)                                                          # still nothing computed
         good = e.site_fit(hyp, al, rho, a, 4, partial_bytes=64 * S)             # exactly one chunk's worth is enough
         zero = e.site_fit(hyp, al, None, a, 4)                                  # ambient without rho is fine: rho = 0
