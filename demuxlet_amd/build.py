@@ -17,7 +17,7 @@ CSRC = PKG / "csrc"
 LIB = PKG / "libdmx.so"
 SOURCES = [CSRC / "dmx_host.cpp", CSRC / "dmx_engine.hip"]
 HEADERS = [ROOT / "include" / "dmx.h", CSRC / "dmx_internal.hpp", CSRC / "dmx_log.hpp", CSRC / "dmx_engine_state.hpp", CSRC / "dmx_hyp_plan.hpp",
-           CSRC / "dmx_format.hpp", CSRC / "dmx_compose.hpp", CSRC / "dmx_redraw.hpp", CSRC / "dmx_kin.hpp", CSRC / "dmx_prior.hpp", CSRC / "dmx_log_table.inc"]
+           CSRC / "dmx_format.hpp", CSRC / "dmx_compose.hpp", CSRC / "dmx_redraw.hpp", CSRC / "dmx_kin.hpp", CSRC / "dmx_blocks.hpp", CSRC / "dmx_prior.hpp", CSRC / "dmx_log_table.inc"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=default",
          "-Wall", "-Wno-unused-function", f"-I{ROOT / 'include'}", f"-I{CSRC}"]
 

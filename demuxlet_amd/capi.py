@@ -57,6 +57,7 @@ SYMBOLS = [
     "dmx_engine_site_fit", "dmx_engine_get_site_fit", "dmx_engine_site_fit_info",
     "dmx_engine_redraw", "dmx_engine_redrawn_pileup", "dmx_engine_get_redrawn", "dmx_engine_redraw_info",
     "dmx_engine_geno_compare", "dmx_engine_get_geno_compare", "dmx_engine_geno_compare_info",
+    "dmx_engine_block_llk", "dmx_engine_get_block_llk", "dmx_engine_block_llk_info",
 ]
 DMX_PRIOR_MASKED, DMX_PRIOR_BAD = 1, 2
 
@@ -230,6 +231,19 @@ class KinInfo(C.Structure):              # dmx_kin_info
     _fields_ = [("rows_ms", C.c_double), ("tile_ms", C.c_double), ("flop", C.c_int64), ("bytes", C.c_int64), ("n_invalid_a", C.c_int64),
                 ("n_invalid_b", C.c_int64), ("n_snps", C.c_int32), ("n_a", C.c_int32), ("n_b", C.c_int32), ("tile_a", C.c_int32),
                 ("tile_b", C.c_int32), ("chunk_snps", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+DMX_BLOCK_MAX_EXTRA = 8
+
+
+class BlockLlkRequest(C.Structure):      # dmx_block_llk_request
+    _fields_ = [("n_cells", C.c_int32), ("n_snps", C.c_int32), ("n_blocks", C.c_int32), ("n_extra", C.c_int32), ("block", C.c_void_p),
+                ("extra", C.c_void_p), ("extra_memory", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class BlockLlkInfo(C.Structure):         # dmx_block_llk_info
+    _fields_ = [("kernel_ms", C.c_double), ("zero_ms", C.c_double), ("result_bytes", C.c_int64), ("n_entries", C.c_int64), ("n_cells", C.c_int32),
+                ("n_samples", C.c_int32), ("n_alpha", C.c_int32), ("n_blocks", C.c_int32), ("n_extra", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 DMX_SHARE_INTERIOR, DMX_SHARE_AT_0, DMX_SHARE_AT_1, DMX_SHARE_NOT_CONVERGED, DMX_SHARE_FLAT, DMX_SHARE_NONFINITE = 1, 2, 4, 8, 16, 32
@@ -493,6 +507,7 @@ def load() -> C.CDLL:
         "dmx_engine_redraw": [vp, vp], "dmx_engine_redrawn_pileup": [vp, vp], "dmx_engine_get_redrawn": [vp, vp, vp],
         "dmx_engine_redraw_info": [vp, vp],
         "dmx_engine_geno_compare": [vp, vp], "dmx_engine_get_geno_compare": [vp, vp, vp, vp], "dmx_engine_geno_compare_info": [vp, vp],
+        "dmx_engine_block_llk": [vp, vp], "dmx_engine_get_block_llk": [vp, vp, vp, vp, vp], "dmx_engine_block_llk_info": [vp, vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

@@ -9048,6 +9048,13 @@ struct dmx_engine {
   bool have_kin = false;
   EventPair knrev, kntev;
   dmx_kin_info kin_info{};
+  // block-resolved likelihoods (dmx_engine_block_llk): the call's own copies of block[S] and extra[B][E][3], and its results
+  // col[B][G][V], l00[B][G][A], ext[B][G][E] and n_snp[B][G]
+  DevBuf<int32_t> d_bkblock, d_bkextra, d_bkn;
+  DevBuf<double> d_bkcol, d_bkl00, d_bkext;
+  bool have_blk = false;
+  EventPair bkev, bkzev;                         // k_block_col; the zeroing before it
+  dmx_block_llk_info blk_info{};
 };
 
 namespace {
@@ -9582,6 +9589,7 @@ int dmx::engine_set_pileup_cells(dmx_engine* e, const dmx_pileup* pl, const int3
   e->have_site = false;
   e->have_redraw = false;
   e->have_sscan = false; e->have_sfit = false;
+  e->have_blk = false;
   e->have_comp = false;
   e->have_census = false; e->have_cen_info = false; e->have_fis_info = false;
   e->have_pileup = true;
@@ -14185,5 +14193,133 @@ extern "C" int dmx_engine_geno_compare_info(dmx_engine* e, dmx_kin_info* out) {
   if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_geno_compare_info: null argument");
   if (!e->have_kin) return set_error(DMX_ERR_STATE, "dmx_engine_geno_compare_info: nothing compared yet (dmx_engine_geno_compare first)");
   *out = e->kin_info;
+  return DMX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Block-resolved likelihoods (csrc/dmx_blocks.hpp): block[] and extra[] are checked on the host and copied to
+// buffers of the call's own, the results are zeroed, and k_block_col runs once over B x slabs wavefronts on the engine's stream.
+#include "dmx_blocks.hpp"
+
+extern "C" int dmx_engine_block_llk(dmx_engine* e, const dmx_block_llk_request* rq) {
+  const char* fn = "dmx_engine_block_llk";
+  if (!e || !rq) return set_error(DMX_ERR_ARG, "%s: null argument", fn);
+  if (int rc = require_staged(e, fn)) return rc;
+  if (int rc = require_sizes(e, fn, rq->n_cells, rq->n_snps)) return rc;
+  const int32_t B = e->pv.B, S = e->S, V = e->V, A = e->A, G = rq->n_blocks, E = rq->n_extra;
+  if (A > 64 || V > 0xFFE) return set_error(DMX_ERR_ARG, "%s: %d samples x %d alphas exceed this build's limits (4094 samples, 64 alphas)", fn, V, A);
+  if (G < 1) return set_error(DMX_ERR_ARG, "%s: n_blocks %d is not at least 1", fn, G);
+  if (E < 0 || E > dmx_blk::kMaxExtra) return set_error(DMX_ERR_ARG, "%s: n_extra %d is not in [0, %d]", fn, E, dmx_blk::kMaxExtra);
+  for (int i = 0; i < 4; ++i)
+    if (rq->reserved[i] != 0) return set_error(DMX_ERR_ARG, "%s: reserved[%d] = %d is not 0", fn, i, rq->reserved[i]);
+  if (S > 0 && !rq->block) return set_error(DMX_ERR_ARG, "%s: block is null", fn);
+  const size_t n_ex = (size_t)B * (size_t)E * 3;
+  if (n_ex > 0 && !rq->extra) return set_error(DMX_ERR_ARG, "%s: extra is null with n_extra %d", fn, E);
+  if (n_ex > 0 && rq->extra_memory != DMX_MEM_HOST && rq->extra_memory != DMX_MEM_DEVICE)
+    return set_error(DMX_ERR_ARG, "%s: extra_memory %d", fn, rq->extra_memory);
+  for (int32_t i = 0; i < S; ++i) {
+    const int32_t g = rq->block[i];
+    if (g < 0 || g >= G) return set_error(DMX_ERR_ARG, "%s: block[%d] = %d is not in [0, %d)", fn, i, g, G);
+    if (i > 0 && g < rq->block[i - 1]) return set_error(DMX_ERR_ARG, "%s: block[%d] = %d decreases (block[%d] = %d)", fn, i, g, i - 1, rq->block[i - 1]);
+  }
+  if (!e->geno_rows_safe)
+    return set_error(DMX_ERR_ARG, "%s: the genotype matrix has a row that is not finite, non-negative and above 1e-30 somewhere; the block pass has "
+                                  "no fix-up pass for such a matrix (nor has the anchored search): repair or drop those rows first", fn);
+  HIP_TRY(hipSetDevice(e->device));
+  std::vector<int32_t> ex;
+  int64_t n_used = 0;
+  if (n_ex > 0) {
+    if (int rc = fetch_ids(e, rq->extra, rq->extra_memory, n_ex, ex)) return rc;
+    for (size_t b = 0; b < (size_t)B; ++b)
+      for (int32_t s = 0; s < E; ++s) {
+        const int32_t* x = &ex[(b * E + s) * 3];
+        if (x[0] == -1) continue;
+        if (x[0] < 0 || x[0] >= V || x[1] < 0 || x[1] >= V || x[2] < 0 || x[2] >= A)
+          return set_error(DMX_ERR_ARG, "%s: extra[%zu][%d] = (%d, %d, %d) is not unused (j = -1) or an entry of [0, %d) x [0, %d) x [0, %d)", fn, b, s,
+                           x[0], x[1], x[2], V, V, A);
+        ++n_used;
+      }
+  }
+  // the results: B G (V + A + E) doubles and B G counts
+  const double want = (double)B * (double)G * ((double)(V + A + E) * sizeof(double) + sizeof(int32_t));
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  if (want > 0x1p60)
+    return set_error(DMX_ERR_NOMEM, "%s: the results of %d barcodes x %d blocks x (%d + %d + %d) entries need %.3g bytes, %zu are free", fn, B, G, V, A,
+                     E, want, free_b);
+  const size_t BG = (size_t)B * (size_t)G;
+  const size_t col_b = sizeof(double) * BG * V, l00_b = sizeof(double) * BG * A, ext_b = sizeof(double) * BG * E, n_b = sizeof(int32_t) * BG,
+               blk_b = sizeof(int32_t) * (size_t)S, ex_b = sizeof(int32_t) * n_ex;
+  const size_t need = (col_b > e->d_bkcol.cap() ? col_b + col_b / 16 : 0) + (l00_b > e->d_bkl00.cap() ? l00_b + l00_b / 16 : 0) +
+                      (ext_b > e->d_bkext.cap() ? ext_b + ext_b / 16 : 0) + (n_b > e->d_bkn.cap() ? n_b + n_b / 16 : 0) +
+                      (blk_b > e->d_bkblock.cap() ? blk_b + blk_b / 16 : 0) + (ex_b > e->d_bkextra.cap() ? ex_b + ex_b / 16 : 0);
+  if (need > free_b)
+    return set_error(DMX_ERR_NOMEM, "%s: the results of %d barcodes x %d blocks x (%d + %d + %d) entries need %zu bytes, %zu are free", fn, B, G, V, A, E,
+                     col_b + l00_b + ext_b + n_b, free_b);
+  e->have_blk = false;
+  if (int rc = e->d_bkcol.ensure(col_b)) return rc;
+  if (int rc = e->d_bkl00.ensure(l00_b)) return rc;
+  if (int rc = e->d_bkext.ensure(ext_b)) return rc;
+  if (int rc = e->d_bkn.ensure(n_b)) return rc;
+  if (int rc = e->d_bkblock.ensure(blk_b)) return rc;
+  if (int rc = e->d_bkextra.ensure(ex_b)) return rc;
+  int A_pad = 1;
+  while (A_pad < A) A_pad <<= 1;
+  const int TP = std::min(dmx_blk::kTP, 64 / A_pad);
+  const int32_t n_slab = (int32_t)((V + E + 63) / 64);
+  const int64_t n_units = (int64_t)B * n_slab;
+  if (S > 0) HIP_TRY(hipMemcpyAsync(e->d_bkblock, rq->block, blk_b, hipMemcpyHostToDevice, e->stream));
+  if (n_ex > 0) HIP_TRY(hipMemcpyAsync(e->d_bkextra, ex.data(), ex_b, hipMemcpyHostToDevice, e->stream));
+  if (int rc = e->bkzev.record_start(e->stream)) return rc;
+  if (BG > 0) {
+    HIP_TRY(hipMemsetAsync(e->d_bkcol, 0, col_b, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_bkl00, 0, l00_b, e->stream));
+    if (ext_b > 0) HIP_TRY(hipMemsetAsync(e->d_bkext, 0, ext_b, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_bkn, 0, n_b, e->stream));
+  }
+  if (int rc = e->bkzev.record_stop(e->stream)) return rc;
+  if (int rc = e->bkev.record_start(e->stream)) return rc;
+  if (BG > 0) {
+    hipLaunchKernelGGL(dmx_blk::k_block_col, dim3((unsigned)((n_units + dmx_blk::kWaves - 1) / dmx_blk::kWaves)), dim3(64 * dmx_blk::kWaves), 0, e->stream,
+                       e->pv, e->nrd_width, e->d_g, (const double*)e->d_gp0, (const double*)e->d_lut, (const double*)e->d_alpha, V, A, A_pad, TP,
+                       (const int32_t*)e->d_bkblock, G, (const int32_t*)e->d_bkextra, E, n_slab, n_units, e->d_bkcol.get(), e->d_bkl00.get(),
+                       e->d_bkext.get(), e->d_bkn.get());
+    HIP_TRY(hipGetLastError());
+  }
+  if (int rc = e->bkev.record_stop(e->stream)) return rc;
+  HIP_TRY(hipStreamSynchronize(e->stream));        // block[] and ex are pageable host memory that may go away after return
+  dmx_block_llk_info& inf = e->blk_info;
+  std::memset(&inf, 0, sizeof inf);
+  float ms = 0.f;
+  if (int rc = e->bkev.elapsed_ms(&ms)) return rc;
+  inf.kernel_ms = ms;
+  if (int rc = e->bkzev.elapsed_ms(&ms)) return rc;
+  inf.zero_ms = ms;
+  inf.result_bytes = (int64_t)(col_b + l00_b + ext_b + n_b);
+  inf.n_entries = (int64_t)B * (V + A) + n_used;
+  inf.n_cells = B; inf.n_samples = V; inf.n_alpha = A; inf.n_blocks = G; inf.n_extra = E;
+  e->have_blk = true;
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_get_block_llk(dmx_engine* e, double* col, double* l00, double* ext, int32_t* n_snp) {
+  if (!e) return set_error(DMX_ERR_ARG, "dmx_engine_get_block_llk: null engine");
+  if (!e->have_blk) return set_error(DMX_ERR_STATE, "dmx_engine_get_block_llk: no block result on the staged pileup (dmx_engine_block_llk first)");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const dmx_block_llk_info& inf = e->blk_info;
+  const size_t BG = (size_t)inf.n_cells * (size_t)inf.n_blocks;
+  if (!BG) return DMX_OK;
+  if (col) HIP_TRY(hipMemcpy(col, e->d_bkcol, sizeof(double) * BG * (size_t)inf.n_samples, hipMemcpyDeviceToHost));
+  if (l00) HIP_TRY(hipMemcpy(l00, e->d_bkl00, sizeof(double) * BG * (size_t)inf.n_alpha, hipMemcpyDeviceToHost));
+  if (ext && inf.n_extra > 0) HIP_TRY(hipMemcpy(ext, e->d_bkext, sizeof(double) * BG * (size_t)inf.n_extra, hipMemcpyDeviceToHost));
+  if (n_snp) HIP_TRY(hipMemcpy(n_snp, e->d_bkn, sizeof(int32_t) * BG, hipMemcpyDeviceToHost));
+  return DMX_OK;
+}
+
+extern "C" int dmx_engine_block_llk_info(dmx_engine* e, dmx_block_llk_info* out) {
+  if (!e || !out) return set_error(DMX_ERR_ARG, "dmx_engine_block_llk_info: null argument");
+  if (!e->have_blk) return set_error(DMX_ERR_STATE, "dmx_engine_block_llk_info: no block result on the staged pileup (dmx_engine_block_llk first)");
+  *out = e->blk_info;
   return DMX_OK;
 }

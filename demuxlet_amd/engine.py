@@ -856,6 +856,40 @@ class Engine:
         check(self._L.dmx_engine_geno_compare_info(self._h, C.byref(r)))
         return {n: getattr(r, n) for n, _ in capi.KinInfo._fields_ if n != "reserved"}
 
+    def block_llk(self, block, n_blocks: int, extra=None, n_extra: Optional[int] = None) -> dict:
+        """dmx_engine_block_llk over the staged pileup: every barcode's singlet column, llks00 and up to 8 chosen grid entries summed per
+        genomic block.  block: int32 [S], non-decreasing, in [0, n_blocks).  extra: None, a host array [B][E][3] of (j, k, n) with
+        j = -1 = unused, or a device pointer (int) to B x n_extra x 3 int32.  STRICT terms whatever the engine's mode; include/dmx.h
+        defines the bits.  Returns col[B][G][V], l00[B][G][A], ext[B][G][E] (float64) and n_snp[B][G] (int32)."""
+        blk = np.ascontiguousarray(block, dtype=np.int32)
+        if blk.ndim != 1:
+            raise ValueError("block must be one id per SNP")
+        if extra is None:
+            ex, mem, ptr, E = None, capi.DMX_MEM_HOST, None, 0
+        elif isinstance(extra, int):
+            if n_extra is None:
+                raise ValueError("a device `extra` needs n_extra")
+            ex, mem, ptr, E = None, capi.DMX_MEM_DEVICE, extra, int(n_extra)
+        else:
+            ex = np.ascontiguousarray(extra, dtype=np.int32)
+            if ex.ndim != 3 or ex.shape[0] != self.B or ex.shape[2] != 3:
+                raise ValueError(f"extra must be [{self.B}][E][3]")
+            mem, ptr, E = capi.DMX_MEM_HOST, (ex.ctypes.data if ex.size else None), ex.shape[1]
+        rq = capi.BlockLlkRequest(self.B, blk.shape[0], int(n_blocks), E, blk.ctypes.data if blk.size else None, ptr, mem)
+        check(self._L.dmx_engine_block_llk(self._h, C.byref(rq)))
+        inf = self.block_llk_info()
+        B, G = inf["n_cells"], inf["n_blocks"]
+        col = np.zeros((B, G, inf["n_samples"])); l00 = np.zeros((B, G, inf["n_alpha"])); ext = np.zeros((B, G, inf["n_extra"]))
+        n_snp = np.zeros((B, G), dtype=np.int32)
+        check(self._L.dmx_engine_get_block_llk(self._h, col.ctypes.data, l00.ctypes.data, ext.ctypes.data, n_snp.ctypes.data))
+        return dict(col=col, l00=l00, ext=ext, n_snp=n_snp)
+
+    def block_llk_info(self) -> dict:
+        """HIP-event time (ms) of the last block_llk's kernel, its result bytes, entry count and shape (dmx_engine_block_llk_info)."""
+        r = capi.BlockLlkInfo()
+        check(self._L.dmx_engine_block_llk_info(self._h, C.byref(r)))
+        return {n: getattr(r, n) for n, _ in capi.BlockLlkInfo._fields_ if n != "reserved"}
+
     def get_redrawn(self) -> dict:
         """The last redraw copied to the host (dmx_engine_get_redrawn): reads (uint8 [n_reads]) and geno (int8 [n_pairs][2]: the drawn
         genotypes of v1 and v2, -1 = not drawn)."""

@@ -46,7 +46,8 @@ extern "C" {
                                barcode's anchors scored at alpha = 0, and a doublet's mixing share fitted continuously);
                                dmx_engine_site_fit / _get_site_fit / _site_fit_info (goodness of fit of each SNP's row);
                                dmx_engine_redraw / _redrawn_pileup / _get_redrawn / _redraw_info (every read's allele drawn again
-                               from the model: the staged pool's null pool).
+                               from the model: the staged pool's null pool); dmx_engine_block_llk / _get_block_llk /
+                               _block_llk_info (singlet column, llks00 and chosen grid entries summed per genomic block).
                                Additions only. */
 
 typedef enum {
@@ -1616,6 +1617,56 @@ int dmx_engine_geno_compare(dmx_engine*, const dmx_kin_request*);
  * [n_b] i32, the valid rows of each column. */
 int dmx_engine_get_geno_compare(dmx_engine*, double* table, int32_t* n_valid_a, int32_t* n_valid_b);
 int dmx_engine_geno_compare_info(dmx_engine*, dmx_kin_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Block-resolved likelihoods (no counterpart in the reference; later, still ABI 8).  Every call is a sum of
+ * per-SNP terms over the whole genome; this pass gives the same sums per genomic BLOCK: with block[i] in [0, G) the block of SNP i,
+ * for every barcode b and block g
+ *   col[b][g][j]   the part of llksAB[j][0][0] — the singlet column that .best / .sing2 print — from b's pairs in block g, every j < V;
+ *   l00[b][g][n]   the part of llks00[n], every n < A;
+ *   ext[b][g][s]   the part of llksAB[j][k][n] for the caller's entry extra[b][s] = (j, k, n), s < E; an unused slot (j = -1) is +0;
+ *   n_snp[b][g]    b's stored pairs whose SNP lies in block g.
+ * Arithmetic: a value is ONE serial sum from +0 over the barcode's stored pairs whose SNP lies in block g, in stored order, of the
+ * STRICT grid's own term for that entry, operation for operation: phase 1 with the one maximum shared by all
+ * alphas, the refined division, + 1e-6 and the renormalisation (cmd_cram_demuxlet.cpp:600-663), the nine-term l-major sum from 0.0
+ * (:675-681), dmx_log2, one add.  The same terms whether the engine is DMX_MODE_STRICT or DMX_MODE_FAST.  No partial sums, no
+ * floating-point atomics, no contraction.  Hence: with G = 1 every value is the entry of dmx_engine_run_doublet's STRICT grid, bit for
+ * bit; and for any G, block g's values are the STRICT grid of an engine that holds only block g's pairs.
+ * Determinism: a barcode's values depend on its own pairs, the rows it touches, the alpha grid and block[] at its own SNPs only —
+ * not on B, the other barcodes, E, what ran before, the stream or where `extra` lives.  Blocks that a barcode does not cover are +0
+ * with n_snp 0.
+ * The call runs on the engine's stream and synchronises it before returning (block[] and extra[] may be freed then), uses buffers of
+ * its own and leaves every other result of the engine readable and unchanged.
+ * DMX_ERR_ARG: a null argument; n_blocks < 1; a block[] that decreases or leaves [0, G); n_extra outside [0, 8]; an extra entry
+ * whose j is not -1 and whose (j, k, n) is outside [0, V) x [0, V) x [0, A); an extra_memory that is neither constant; reserved != 0;
+ * n_cells / n_snps that do not match the staged pileup / the genotype matrix; more than 4094 samples or 64 alphas (the anchored search's limits); a
+ * genotype matrix that k_check_geno did not pass (a row that is not finite, non-negative and somewhere above 1e-30): refused as the
+ * anchored search refuses it, since this pass has no fix-up either.
+ * DMX_ERR_STATE: no pileup or no genotypes yet; dmx_engine_get_block_llk / _block_llk_info before a call (or after a new pileup).
+ * DMX_ERR_NOMEM: the B G (V + A + E) doubles do not fit the free device memory (checked before anything is allocated; earlier
+ * results stay readable). */
+#define DMX_BLOCK_MAX_EXTRA 8
+typedef struct {
+  int32_t n_cells, n_snps;     /* = the staged pileup's n_cells, the genotype matrix's n_snps */
+  int32_t n_blocks;            /* G >= 1 */
+  int32_t n_extra;             /* E, 0..8 */
+  const int32_t* block;        /* [n_snps], HOST: non-decreasing, every value in [0, G); ids that no SNP has are allowed */
+  const int32_t* extra;        /* [n_cells][E][3] = (j, k, n); j = -1: slot unused; j = k allowed.  NULL when E = 0 */
+  int32_t extra_memory;        /* DMX_MEM_HOST or DMX_MEM_DEVICE: where `extra` lives */
+  int32_t reserved[4];         /* 0 */
+} dmx_block_llk_request;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the last call's k_block_col */
+  double  zero_ms;             /* ... of zeroing col, l00, ext and n_snp before it */
+  int64_t result_bytes;        /* device bytes of col, l00, ext and n_snp */
+  int64_t n_entries;           /* entries evaluated: B (V + A) + used extra slots */
+  int32_t n_cells, n_samples, n_alpha, n_blocks, n_extra;
+  int32_t reserved[3];
+} dmx_block_llk_info;
+int dmx_engine_block_llk(dmx_engine*, const dmx_block_llk_request*);
+/* Device->host copies of the last result (any pointer may be NULL): col[B][G][V], l00[B][G][A], ext[B][G][E] f64, n_snp[B][G] i32. */
+int dmx_engine_get_block_llk(dmx_engine*, double* col, double* l00, double* ext, int32_t* n_snp);
+int dmx_engine_block_llk_info(dmx_engine*, dmx_block_llk_info* out);
 
 #ifdef __cplusplus
 }
