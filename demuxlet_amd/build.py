@@ -17,7 +17,8 @@ CSRC = PKG / "csrc"
 LIB = PKG / "libdmx.so"
 SOURCES = [CSRC / "dmx_host.cpp", CSRC / "dmx_engine.hip"]
 HEADERS = [ROOT / "include" / "dmx.h", CSRC / "dmx_internal.hpp", CSRC / "dmx_log.hpp", CSRC / "dmx_engine_state.hpp", CSRC / "dmx_hyp_plan.hpp",
-           CSRC / "dmx_format.hpp", CSRC / "dmx_compose.hpp", CSRC / "dmx_redraw.hpp", CSRC / "dmx_kin.hpp", CSRC / "dmx_blocks.hpp", CSRC / "dmx_prior.hpp", CSRC / "dmx_log_table.inc"]
+           CSRC / "dmx_format.hpp", CSRC / "dmx_compose.hpp", CSRC / "dmx_redraw.hpp", CSRC / "dmx_kin.hpp", CSRC / "dmx_blocks.hpp", CSRC / "dmx_prior.hpp", CSRC / "dmx_log_table.inc",
+           CSRC / "dmx_gpu_inflate.hpp", CSRC / "dmx_inflate_core.hpp"]
 FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=off", "-fPIC", "-shared", "-fvisibility=default",
          "-Wall", "-Wno-unused-function", f"-I{ROOT / 'include'}", f"-I{CSRC}"]
 
@@ -42,7 +43,7 @@ CLI_SRC = CSRC / "dmx_cli.cpp"
 
 def build_cli(force: bool = False, verbose: bool = False) -> Path:
     """The `demuxlet` command-line front end (host C++ only; links libdmx.so and zlib)."""
-    deps = [CLI_SRC, CSRC / "dmx_inflate.hpp", ROOT / "include" / "dmx.h", LIB]
+    deps = [CLI_SRC, CSRC / "dmx_inflate.hpp", CSRC / "dmx_gpu_inflate.hpp", CSRC / "dmx_inflate_core.hpp", ROOT / "include" / "dmx.h", LIB]
     if not force and CLI.exists() and CLI.stat().st_mtime >= max(p.stat().st_mtime for p in deps):
         return CLI
     cmd = [hipcc(), "-O2", "-std=c++17", "-Wall", "-x", "c++", f"-I{ROOT / 'include'}", str(CLI_SRC), "-o", str(CLI),

@@ -58,6 +58,8 @@ SYMBOLS = [
     "dmx_engine_redraw", "dmx_engine_redrawn_pileup", "dmx_engine_get_redrawn", "dmx_engine_redraw_info",
     "dmx_engine_geno_compare", "dmx_engine_get_geno_compare", "dmx_engine_geno_compare_info",
     "dmx_engine_block_llk", "dmx_engine_get_block_llk", "dmx_engine_block_llk_info",
+    "dmx_inflater_create", "dmx_inflater_free", "dmx_inflater_submit", "dmx_inflater_wait", "dmx_inflater_run",
+    "dmx_inflater_pin", "dmx_inflater_unpin",
 ]
 DMX_PRIOR_MASKED, DMX_PRIOR_BAD = 1, 2
 
@@ -239,6 +241,11 @@ DMX_BLOCK_MAX_EXTRA = 8
 class BlockLlkRequest(C.Structure):      # dmx_block_llk_request
     _fields_ = [("n_cells", C.c_int32), ("n_snps", C.c_int32), ("n_blocks", C.c_int32), ("n_extra", C.c_int32), ("block", C.c_void_p),
                 ("extra", C.c_void_p), ("extra_memory", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+class InflaterInfo(C.Structure):         # dmx_inflater_info
+    _fields_ = [("kernel_ms", C.c_double), ("h2d_ms", C.c_double), ("d2h_ms", C.c_double), ("h2d_bytes", C.c_int64), ("d2h_bytes", C.c_int64),
+                ("n_members", C.c_int32), ("n_accepted", C.c_int32), ("n_refused", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class BlockLlkInfo(C.Structure):         # dmx_block_llk_info
@@ -445,7 +452,7 @@ def load() -> C.CDLL:
     if not LIB_PATH.exists():
         raise DmxError(-100, f"{LIB_PATH} is missing — build it with `python -m demuxlet_amd.build` (hipcc, gfx950)")
     L = C.CDLL(str(LIB_PATH))
-    vp, i32, dbl = C.c_void_p, C.c_int32, C.c_double
+    vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
     L.dmx_abi_version.restype = C.c_int
     L.dmx_last_error.restype = C.c_char_p
     sig = {
@@ -508,6 +515,9 @@ def load() -> C.CDLL:
         "dmx_engine_redraw_info": [vp, vp],
         "dmx_engine_geno_compare": [vp, vp], "dmx_engine_get_geno_compare": [vp, vp, vp, vp], "dmx_engine_geno_compare_info": [vp, vp],
         "dmx_engine_block_llk": [vp, vp], "dmx_engine_get_block_llk": [vp, vp, vp, vp, vp], "dmx_engine_block_llk_info": [vp, vp],
+        "dmx_inflater_create": [i32, i32, i64, i64, vp], "dmx_inflater_free": [vp],
+        "dmx_inflater_submit": [vp, i32, i32, vp, vp, vp, vp, vp, vp], "dmx_inflater_wait": [vp, i32, vp, vp],
+        "dmx_inflater_run": [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp], "dmx_inflater_pin": [vp, i64], "dmx_inflater_unpin": [vp],
     }
     for name, args in sig.items():
         f = getattr(L, name)

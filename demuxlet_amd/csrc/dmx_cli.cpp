@@ -296,6 +296,26 @@ int cli_threads() {
   return std::min(n, 32);
 }
 
+// DMX_GPU_INFLATE (the opt-in device stage of the BGZF reader): 0 = off; 1 = members go to the device once its
+// inflater is up and to the host's threads until then; 2 = as 1, but a reader waits for its inflater before its first batch.
+static const int g_gpu_inflate = [] { const char* e = getenv("DMX_GPU_INFLATE"); return !e || !*e || !strcmp(e, "0") ? 0 : (!strcmp(e, "2") ? 2 : 1); }();
+int g_gpu_device = 0;                                // --gpu (main sets it before the first file is opened)
+// Batches that the device writes into (and only those) are page-locked before their first submit, so that the device-to-host copy lands in them directly and
+// runs beside the host's work; a buffer is released before its memory is freed.  Nothing here runs unless an inflater came up.
+std::atomic<bool> g_pin_on{false};
+struct PinSet { std::mutex mu; std::set<const void*> s; };
+PinSet& pins() { static PinSet* p = new PinSet; return *p; }
+void pin_buffer(uint8_t* p, size_t bytes) {
+  PinSet& q = pins();
+  std::lock_guard<std::mutex> lk(q.mu);
+  if (!q.s.count(p) && dmx_inflater_pin(p, (int64_t)bytes) == DMX_OK) q.s.insert(p);
+}
+void unpin_buffer(uint8_t* p) {
+  PinSet& q = pins();
+  std::lock_guard<std::mutex> lk(q.mu);
+  if (q.s.erase(p)) dmx_inflater_unpin(p);
+}
+
 // A run of decompressed bytes.  Readers hand out views into it (BAM records are parsed where the inflater wrote them), so it is
 // shared: it lives until the last window of reads that points into it has been through the store.
 struct Chunk {
@@ -319,6 +339,7 @@ struct Chunk {
   }
   ~Chunk() {
     if (p && cap == kPooled) { Pool& q = pool(); std::lock_guard<std::mutex> lk(q.mu); if (q.free.size() < 16) q.free.push_back(std::move(p)); }
+    if (p && cap == kPooled && g_pin_on.load(std::memory_order_relaxed)) unpin_buffer(p.get());
   }
 };
 using ChunkP = std::shared_ptr<Chunk>;
@@ -386,6 +407,86 @@ struct BgzfPipe {
 
   struct Block { std::vector<uint8_t> raw; size_t data_off = 0, data_len = 0; uint32_t crc = 0, isize = 0; std::string err; };
 
+  // ---- DMX_GPU_INFLATE: this reader's inflater (two slots), created on a thread of its own while the first batches go to the host
+  static constexpr size_t kStageSlot = 65536 + 80;                  // a member's deflate data (< 64 KiB) + 8 zero bytes, rounded up to 16
+  struct Dev {
+    std::mutex mu; std::condition_variable cv;
+    int state = 0;                                                  // 0 off, 1 coming up, 2 ready, 3 unavailable
+    dmx_inflater* h = nullptr;
+    std::thread th;
+    std::unique_ptr<uint8_t[]> stage[2];                            // packed deflate data of the batch in each slot (page-locked)
+    std::vector<int64_t> in_off[2], out_off[2];
+    std::vector<int32_t> in_len[2], out_len[2];
+    bool inflight[2] = {false, false};
+  } dev;
+  struct DevCounters { std::atomic<int64_t> on_dev{0}, on_host{0}, refused{0}, busy_us{0}, h2d{0}, d2h{0}; };
+  static DevCounters& counters() { static DevCounters* c = new DevCounters; return *c; }
+  static void dev_unavailable(const char* reason) {                 // one notice per process, whichever reader meets it first
+    static std::atomic<bool> said{false};
+    if (!said.exchange(true)) notice("GPU inflate unavailable (%s): BGZF members are inflated on the host", reason);
+  }
+  void dev_start() {
+    dev.state = 1;
+    dev.th = std::thread([this] {
+      dmx_inflater* h = nullptr;
+      const int rc = dmx_inflater_create(g_gpu_device, (int32_t)kBatchBlocks, (int64_t)(kBatchBlocks * kStageSlot), (int64_t)Chunk::kPooled, &h);
+      if (rc == DMX_OK) {
+        for (auto& st : dev.stage) { st.reset(new uint8_t[kBatchBlocks * kStageSlot]); dmx_inflater_pin(st.get(), (int64_t)(kBatchBlocks * kStageSlot)); }
+        g_pin_on = true;
+      } else dev_unavailable(dmx_last_error());
+      { std::lock_guard<std::mutex> lk(dev.mu); dev.h = h; dev.state = rc == DMX_OK ? 2 : 3; }
+      dev.cv.notify_all();
+    });
+  }
+  int dev_state(bool wait) {
+    std::unique_lock<std::mutex> lk(dev.mu);
+    if (wait) dev.cv.wait(lk, [&] { return dev.state != 1; });
+    return dev.state;
+  }
+  void dev_failed() { dev_unavailable(dmx_last_error()); std::lock_guard<std::mutex> lk(dev.mu); dev.state = 3; }
+  // packs the batch's deflate data into the slot's staging buffer and submits it; false = this batch goes to the host
+  bool dev_submit(int slot, std::vector<Block>& blocks, size_t n, const std::vector<size_t>& off, uint8_t* out) {
+    auto &io = dev.in_off[slot], &oo = dev.out_off[slot]; auto &il = dev.in_len[slot], &ol = dev.out_len[slot];
+    io.resize(n); oo.resize(n); il.resize(n); ol.resize(n);
+    uint8_t* st = dev.stage[slot].get();
+    size_t at = 0;
+    for (size_t i = 0; i < n; ++i) {
+      const Block& b = blocks[i];
+      const size_t len = std::min(b.data_len, (size_t)65536 + 64), room = (len + 8 + 15) & ~(size_t)15;   // (a BGZF block is < 64 KiB in all)
+      memcpy(st + at, b.raw.data() + b.data_off, len);
+      memset(st + at + len, 0, room - len);
+      io[i] = (int64_t)at; il[i] = (int32_t)len; oo[i] = (int64_t)off[i]; ol[i] = (int32_t)b.isize;
+      at += room;
+    }
+    if (dmx_inflater_submit(dev.h, slot, (int32_t)n, st, io.data(), il.data(), out, oo.data(), ol.data()) != DMX_OK) { dev_failed(); return false; }
+    dev.inflight[slot] = true;
+    return true;
+  }
+  // waits for the slot's batch: a member the device accepted has its CRC checked here; every other one goes through inflate_block
+  void dev_complete(int slot, std::vector<Block>& blocks, size_t n, const std::vector<size_t>& off, uint8_t* out, int nthreads) {
+    std::vector<int32_t> status(n, -1);
+    dmx_inflater_info info;
+    memset(&info, 0, sizeof info);
+    const int rc = dmx_inflater_wait(dev.h, slot, status.data(), &info);
+    dev.inflight[slot] = false;
+    if (rc != DMX_OK) { dev_failed(); std::fill(status.begin(), status.end(), -1); }
+    DevCounters& c = counters();
+    c.busy_us += (int64_t)(1e3 * (info.h2d_ms + info.kernel_ms + info.d2h_ms)); c.h2d += info.h2d_bytes; c.d2h += info.d2h_bytes;
+    const int nt = (int)std::min<size_t>((size_t)nthreads, n);
+    std::atomic<size_t> next{0};
+    WorkerPool::get().run(nt - 1, [&](int) {
+      CpuScope cs(0);
+      int64_t a = 0, h = 0, r = 0;
+      for (size_t i; (i = next.fetch_add(1)) < n;) {
+        Block& b = blocks[i];
+        if (status[i] == 0 && dmxz::crc32_of(out + off[i], b.isize) == b.crc) { ++a; continue; }
+        ++r; ++h;
+        inflate_block(b, out + off[i]);
+      }
+      c.on_dev += a; c.on_host += h; c.refused += r;
+    });
+  }
+
   // one BGZF member into b.raw; false at a clean EOF
   bool read_block(Block& b) {
     uint8_t h[12];
@@ -446,6 +547,7 @@ struct BgzfPipe {
       }
     });
     struct IoGuard { std::mutex& mu; std::condition_variable& cv; bool& stop; std::thread& th; ~IoGuard() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); if (th.joinable()) th.join(); } } io_guard{io_mu, io_cv, io_stop, io};
+    if (g_gpu_inflate) { run_dev(nthreads, rb, io_mu, io_cv); return; }
     for (int bi = 0;; bi ^= 1) {
       { std::unique_lock<std::mutex> lk(io_mu); io_cv.wait(lk, [&] { return rb[bi].state == 1; }); }
       std::vector<Block>& blocks = rb[bi].blocks;
@@ -477,7 +579,91 @@ struct BgzfPipe {
       }
     }
   }
-  void start(FILE* f, int nthreads) { fp = f; producer = std::thread([this, nthreads] { run(nthreads); }); }
+  // DMX_GPU_INFLATE: the same loop with the device as a stage.  Batch i is packed and submitted to a slot, then batch i - 1 — in the
+  // other slot — is waited for, checked and handed on, so the device works on one batch while the file thread reads the next and
+  // the host's threads check the previous one.  A batch met before the inflater is up (or after it failed) takes the host path above.
+  // Batches are handed on in file order and a batch's bytes do not depend on where they were inflated.
+  template <class RawBatch>
+  void run_dev(int nthreads, RawBatch* rb, std::mutex& io_mu, std::condition_variable& io_cv) {
+    struct Pending { bool live = false; int bi = 0, slot = 0; size_t n = 0; ChunkP batch; std::vector<size_t> off; std::string err; } pend;
+    struct Drain {                                 // no way out of this function leaves a batch in flight or the inflater's thread running
+      BgzfPipe& p;
+      void now() {
+        p.dev_state(true);
+        std::vector<int32_t> st(kBatchBlocks);
+        for (int s = 0; s < 2; ++s) if (p.dev.inflight[s]) { dmx_inflater_wait(p.dev.h, s, st.data(), nullptr); p.dev.inflight[s] = false; }
+      }
+      ~Drain() { now(); }
+    } drain{*this};
+    auto release = [&](int bi) { { std::lock_guard<std::mutex> lk(io_mu); rb[bi].state = 0; } io_cv.notify_all(); };
+    auto publish = [&](ChunkP& batch) {
+      std::unique_lock<std::mutex> lk(mu);
+      cv_put.wait(lk, [&] { return queue.size() < kQueueDepth || stop; });
+      if (stop) return false;
+      queue.push_back(std::move(batch));
+      cv_get.notify_one();
+      return true;
+    };
+    auto finish = [&](const std::string& err) { std::lock_guard<std::mutex> lk(mu); error = err; done = true; cv_get.notify_one(); };
+    auto first_error = [&](std::vector<Block>& blocks, size_t n, std::string err) {
+      for (size_t i = 0; i < n; ++i) if (!blocks[i].err.empty()) { if (err.empty()) err = blocks[i].err; blocks[i].err.clear(); }
+      return err;
+    };
+    // the batch in `pend`: wait, check, hand on.  1 = go on, 0 = the reader was stopped, -1 = it ended the file (an error or its last batch)
+    auto complete = [&]() {
+      std::vector<Block>& blocks = rb[pend.bi].blocks;
+      dev_complete(pend.slot, blocks, pend.n, pend.off, pend.batch->p.get(), nthreads);
+      const std::string err = first_error(blocks, pend.n, pend.err);
+      const bool ends = pend.n < kBatchBlocks || !err.empty();
+      release(pend.bi);
+      pend.live = false;
+      if (!publish(pend.batch)) return 0;
+      if (ends) { finish(err); return -1; }
+      return 1;
+    };
+    if (g_gpu_inflate == 2) dev_state(true);
+    int slot = 0;
+    for (int bi = 0;; bi ^= 1) {
+      { std::unique_lock<std::mutex> lk(io_mu); io_cv.wait(lk, [&] { return rb[bi].state == 1; }); }
+      std::vector<Block>& blocks = rb[bi].blocks;
+      const size_t n = rb[bi].n;
+      std::string err = rb[bi].err;
+      ChunkP batch;
+      std::vector<size_t> off(n + 1, 0);
+      bool on_dev = false;
+      if (n) {
+        for (size_t i = 0; i < n; ++i) off[i + 1] = off[i] + blocks[i].isize;
+        const bool ready = dev_state(false) == 2;
+        batch = std::make_shared<Chunk>();
+        batch->alloc(off[n]);
+        batch->n = off[n];
+        if (ready && batch->cap == Chunk::kPooled) pin_buffer(batch->p.get(), Chunk::kPooled);   // only what the device writes into; it stays so in the pool
+        on_dev = ready && off[n] <= Chunk::kPooled && dev_submit(slot, blocks, n, off, batch->p.get());
+      }
+      if (pend.live) { const int rc = complete(); if (rc <= 0) { drain.now(); return; } }   // (the batch submitted above is waited for while its buffer lives)
+      if (on_dev) {
+        pend.live = true; pend.bi = bi; pend.slot = slot; pend.n = n; pend.batch = std::move(batch); pend.off = std::move(off); pend.err = err;
+        slot ^= 1;
+        if (n < kBatchBlocks || !err.empty()) { complete(); return; }
+        continue;
+      }
+      if (n) {
+        const int nt = (int)std::min<size_t>((size_t)nthreads, n);
+        std::atomic<size_t> next{0};
+        WorkerPool::get().run(nt - 1, [&](int) { CpuScope cs(0); for (size_t i; (i = next.fetch_add(1)) < n;) inflate_block(blocks[i], batch->p.get() + off[i]); });
+        counters().on_host += (int64_t)n;
+        err = first_error(blocks, n, err);
+        release(bi);
+        if (!publish(batch)) return;
+      }
+      if (n < kBatchBlocks || !err.empty()) { finish(err); return; }
+    }
+  }
+  void start(FILE* f, int nthreads) {
+    fp = f;
+    if (g_gpu_inflate) dev_start();
+    producer = std::thread([this, nthreads] { run(nthreads); });
+  }
   // next inflated batch; false at EOF (or error: see `error`)
   bool next(ChunkP& out) {
     std::unique_lock<std::mutex> lk(mu);
@@ -492,6 +678,9 @@ struct BgzfPipe {
     { std::lock_guard<std::mutex> lk(mu); stop = true; }
     cv_put.notify_all();
     if (producer.joinable()) producer.join();
+    if (dev.th.joinable()) dev.th.join();
+    if (dev.h) dmx_inflater_free(dev.h);
+    for (auto& st : dev.stage) if (st) dmx_inflater_unpin(st.get());
     if (fp) fclose(fp);
   }
 };
@@ -1216,6 +1405,7 @@ struct Stopwatch {             // DMX_CLI_TIMING=1: where the scan's wall-clock 
 int main(int argc, char** argv) {
   Options o;
   parse_options(argc, argv, o);
+  g_gpu_device = o.gpu;
   if (o.alpha.empty()) { o.alpha.push_back(0); o.alpha.push_back(0.5); }                                   // cmd_cram_demuxlet.cpp:78-90
 
   std::set<std::string> bcd_set;
@@ -1663,8 +1853,14 @@ int main(int argc, char** argv) {
     notice("process CPU so far: %.3f s user + %.3f s system; inside the parallel sections: inflate %.3f s, record parsing %.3f s, overlap %.3f s", ru.ru_utime.tv_sec + 1e-6 * ru.ru_utime.tv_usec, ru.ru_stime.tv_sec + 1e-6 * ru.ru_stime.tv_usec,
            1e-9 * g_cpu_ns[0].load(), 1e-9 * g_cpu_ns[1].load(), 1e-9 * g_cpu_ns[2].load());
   }
-  if (sw.on) notice("scan timing (%d threads, %s): total %.3f s = %.3g reads/s; alignment reader %.3f s, record parsing %.3f s, lock-step bookkeeping %.3f s, VCF reader (wait) %.3f s, overlap%s %.3f s, store batches %.3f s",
-                    n_threads, windowed ? "windowed" : "read by read", scan_s, (double)sr.n_read / scan_s, sw.acc[0], sw.acc[3], sw.acc[4], sw.acc[1], windowed ? "" : " + store", sw.acc[2], sw.acc[5]);
+  char gz_fields[256] = "";                     // DMX_GPU_INFLATE: where the BGZF members of both files went, so far
+  if (sw.on && g_gpu_inflate) {
+    BgzfPipe::DevCounters& c = BgzfPipe::counters();
+    snprintf(gz_fields, sizeof gz_fields, "; GPU inflate: members on device %lld, on host %lld, refused %lld, device busy %.3f s, H2D %lld bytes, D2H %lld bytes",
+             (long long)c.on_dev.load(), (long long)c.on_host.load(), (long long)c.refused.load(), 1e-6 * c.busy_us.load(), (long long)c.h2d.load(), (long long)c.d2h.load());
+  }
+  if (sw.on) notice("scan timing (%d threads, %s): total %.3f s = %.3g reads/s; alignment reader %.3f s, record parsing %.3f s, lock-step bookkeeping %.3f s, VCF reader (wait) %.3f s, overlap%s %.3f s, store batches %.3f s%s",
+                    n_threads, windowed ? "windowed" : "read by read", scan_s, (double)sr.n_read / scan_s, sw.acc[0], sw.acc[3], sw.acc[4], sw.acc[1], windowed ? "" : " + store", sw.acc[2], sw.acc[5], gz_fields);
   notice("Finished reading %d markers from the VCF file", (int)snps.size());
   notice("Total number input reads : %lld", (long long)sr.n_read);
   notice("Total number valid droplets observed : %d", dmx_store_n_cells(scl));

@@ -14323,3 +14323,8 @@ extern "C" int dmx_engine_block_llk_info(dmx_engine* e, dmx_block_llk_info* out)
   *out = e->blk_info;
   return DMX_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// BGZF members inflated on the device (csrc/dmx_gpu_inflate.hpp): k_bgzf_inflate and the dmx_inflater_* calls,
+// independent of any engine.
+#include "dmx_gpu_inflate.hpp"

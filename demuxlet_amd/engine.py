@@ -1303,6 +1303,69 @@ class Engine:
         return b
 
 
+class Inflater:
+    """BGZF members inflated on one MI355X (dmx_inflater_*): raw DEFLATE streams in, bytes and one status per
+    member out.  status 0 = accepted with zlib's bytes; anything else = refused, to be inflated by the caller (no checksum is computed)."""
+
+    PAD = 64          # bytes between two members' slots in the buffers this class packs (guards; the contract needs 8 zero bytes after an input)
+
+    def __init__(self, device: int = 0, max_members: int = 1024, max_in_bytes: int = 1 << 26, max_out_bytes: int = 1 << 26):
+        self._L = capi.load()
+        h = C.c_void_p()
+        check(self._L.dmx_inflater_create(device, max_members, max_in_bytes, max_out_bytes, C.byref(h)))
+        self._h = h
+        self._keep = {}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.dmx_inflater_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    @staticmethod
+    def pack(streams: Sequence[bytes]):
+        """The members' deflate data in one buffer: each at a multiple of 16, followed by at least PAD zero bytes.  -> (buf u8, off i64, len i32)"""
+        ln = np.array([len(z) for z in streams], dtype=np.int32)
+        slot = (ln.astype(np.int64) + Inflater.PAD + 15) // 16 * 16
+        off = np.concatenate([[0], np.cumsum(slot)[:-1]]).astype(np.int64) if len(streams) else np.zeros(0, np.int64)
+        buf = np.zeros(int(slot.sum()) + 16, dtype=np.uint8)
+        for z, o in zip(streams, off):
+            buf[o:o + len(z)] = np.frombuffer(z, dtype=np.uint8)
+        return buf, off, ln
+
+    def submit(self, slot: int, buf: np.ndarray, in_off, in_len, out: np.ndarray, out_off, out_len) -> None:
+        """dmx_inflater_submit; the arrays are kept alive until wait(slot)."""
+        a = [np.ascontiguousarray(buf, np.uint8), np.ascontiguousarray(in_off, np.int64), np.ascontiguousarray(in_len, np.int32),
+             out, np.ascontiguousarray(out_off, np.int64), np.ascontiguousarray(out_len, np.int32)]
+        assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"]
+        n = len(a[2])
+        assert len(a[1]) == n and len(a[4]) == n and len(a[5]) == n
+        check(self._L.dmx_inflater_submit(self._h, slot, n, *(x.ctypes.data for x in a)))
+        self._keep[slot] = (a, n)
+
+    def wait(self, slot: int):
+        """dmx_inflater_wait -> (status i32 [n], info dict)"""
+        a, n = self._keep.get(slot, (None, 0))
+        status = np.full(max(n, 1), -1, dtype=np.int32)
+        info = capi.InflaterInfo()
+        check(self._L.dmx_inflater_wait(self._h, slot, status.ctypes.data, C.byref(info)))
+        self._keep.pop(slot, None)
+        return status[:n], {k: getattr(info, k) for k, _ in capi.InflaterInfo._fields_ if k != "reserved"}
+
+    def run(self, streams: Sequence[bytes], out_lens: Sequence[int], guard: int = 0, fill: int = 0):
+        """Every stream i inflated into out_lens[i] bytes -> (list of bytes, status, info, out buffer, out offsets).  With guard > 0 the
+        output slots are separated (and preceded and followed) by `guard` bytes of `fill`, for the caller to look at afterwards."""
+        buf, off, ln = self.pack(streams)
+        ol = np.asarray(out_lens, dtype=np.int32)
+        ooff = (guard + np.concatenate([[0], np.cumsum(ol.astype(np.int64) + guard)[:-1]])).astype(np.int64) if len(ol) else np.zeros(0, np.int64)
+        out = np.full(int(ol.astype(np.int64).sum()) + guard * (len(ol) + 1) + 1, fill, dtype=np.uint8)
+        self.submit(0, buf, off, ln, out, ooff, ol)
+        status, info = self.wait(0)
+        return [out[o:o + n].tobytes() for o, n in zip(ooff, ol)], status, info, out, ooff
+
+
 def _cstrs(strs: Sequence[str]):
     keep = [s.encode() for s in strs]
     arr = (C.c_char_p * max(1, len(keep)))(*keep) if keep else (C.c_char_p * 1)()

@@ -47,7 +47,9 @@ extern "C" {
                                dmx_engine_site_fit / _get_site_fit / _site_fit_info (goodness of fit of each SNP's row);
                                dmx_engine_redraw / _redrawn_pileup / _get_redrawn / _redraw_info (every read's allele drawn again
                                from the model: the staged pool's null pool); dmx_engine_block_llk / _get_block_llk /
-                               _block_llk_info (singlet column, llks00 and chosen grid entries summed per genomic block).
+                               _block_llk_info (singlet column, llks00 and chosen grid entries summed per genomic block);
+                               dmx_inflater_create / _free / _submit / _wait / _run / _pin / _unpin (BGZF members inflated on the
+                               device, for the scanner's opt-in DMX_GPU_INFLATE stage).
                                Additions only. */
 
 typedef enum {
@@ -1667,6 +1669,51 @@ int dmx_engine_block_llk(dmx_engine*, const dmx_block_llk_request*);
 /* Device->host copies of the last result (any pointer may be NULL): col[B][G][V], l00[B][G][A], ext[B][G][E] f64, n_snp[B][G] i32. */
 int dmx_engine_get_block_llk(dmx_engine*, double* col, double* l00, double* ext, int32_t* n_snp);
 int dmx_engine_block_llk_info(dmx_engine*, dmx_block_llk_info* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * BGZF members inflated on the device (no counterpart in the reference; later, still ABI 8).  An inflater owns
+ * two SLOTS, each with a stream and device buffers of its own, so that the host-to-device copy, the kernel (k_bgzf_inflate: one
+ * wavefront per member) and the device-to-host copy of consecutive batches overlap: submit(slot 0), submit(slot 1), wait(slot 0),
+ * submit(slot 0), wait(slot 1), ...  It is independent of any dmx_engine and leaves GPU_MAX_HW_QUEUES alone.
+ * Contract.  Member i is a raw DEFLATE stream (RFC 1951) of in_len[i] bytes at in + in_off[i], to be inflated into out_len[i]
+ * bytes at out + out_off[i].  in_off[i] is a multiple of 4 and the host buffer is readable for in_len[i] + 8 bytes, rounded up to
+ * a multiple of 4, from there (the scanner leaves 8 zero bytes after every member; what those bytes hold never matters: the decoder reads
+ * bytes at or past in_len as zero).  The members' padded inputs must lie within max_in_bytes of one another and their outputs within
+ * max_out_bytes; output ranges must not overlap.
+ *   status[i] == 0  the stream's final block ended exactly at out_len[i] bytes, no more than in_len[i] bytes were consumed, and the
+ *                   bytes are the ones zlib's inflate gives;
+ *   status[i] != 0  refused (the value says why, see dmx_inflate_core.hpp): the member's output bytes are unspecified, but nothing
+ *                   outside out + [out_off[i], out_off[i] + out_len[i]) was written.
+ * out_len[i] == 0 is legal (the BGZF end-of-file member) and writes nothing.  A member with out_len > 65 536 or in_len > 65 536 + 64
+ * is refused (a status, not an error) and none of its bytes are touched.  A member's status and bytes do not depend on n, on the
+ * other members, on its position or on the slot.  No checksum is computed: CRC-32 is the caller's, over the bytes after the copy.
+ * The device-to-host copies land at `out` itself (one copy per run of members whose ranges follow one another), so `in`, `out`
+ * and the offset arrays must stay valid, and `out` untouched, until dmx_inflater_wait returns; page-locked buffers
+ * (dmx_inflater_pin) let the copies run beside the host's work, pageable ones are correct but serialise.
+ * Errors: DMX_ERR_NOGPU without a usable gfx950 device; DMX_ERR_ARG for a null argument, a slot that is not 0 or 1, n outside
+ * [0, max_members], a negative or misaligned offset, spans above the inflater's sizes; DMX_ERR_STATE for a submit into a slot in
+ * flight or a wait on an idle one; DMX_ERR_NOMEM when the buffers do not fit; DMX_ERR_HIP.  A submit that fails after it has queued
+ * work synchronises the slot's stream before it returns: the caller's buffers are its own again and the slot is idle. */
+typedef struct dmx_inflater dmx_inflater;
+typedef struct {
+  double  kernel_ms;           /* HIP-event time of the batch's k_bgzf_inflate */
+  double  h2d_ms, d2h_ms;      /* ... of its host-to-device and device-to-host copies */
+  int64_t h2d_bytes, d2h_bytes;
+  int32_t n_members, n_accepted, n_refused;
+  int32_t reserved[3];
+} dmx_inflater_info;
+int dmx_inflater_create(int32_t device, int32_t max_members, int64_t max_in_bytes, int64_t max_out_bytes, dmx_inflater** out);
+int dmx_inflater_free(dmx_inflater*);
+int dmx_inflater_submit(dmx_inflater*, int32_t slot, int32_t n, const uint8_t* in, const int64_t* in_off, const int32_t* in_len,
+                        uint8_t* out, const int64_t* out_off, const int32_t* out_len);
+/* Blocks until the slot's batch is done; status[n] of that batch; info may be NULL. */
+int dmx_inflater_wait(dmx_inflater*, int32_t slot, int32_t* status, dmx_inflater_info* info);
+/* submit into slot 0 + wait */
+int dmx_inflater_run(dmx_inflater*, int32_t n, const uint8_t* in, const int64_t* in_off, const int32_t* in_len,
+                     uint8_t* out, const int64_t* out_off, const int32_t* out_len, int32_t* status, dmx_inflater_info* info);
+/* Page-locks / releases a host buffer of the caller's (hipHostRegister / hipHostUnregister); unpin before the memory is freed. */
+int dmx_inflater_pin(void* ptr, int64_t bytes);
+int dmx_inflater_unpin(void* ptr);
 
 #ifdef __cplusplus
 }
